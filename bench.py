@@ -23,6 +23,13 @@ Prints ONE JSON line on rank 0:
                         eval forward + get_model_inference), C2 (fp32 forward + set loss, batch 8, 800x1333), and C2's bf16 twin.
   cpu_baseline          the CPU restatement of the TF reference (oracle/, kind "port": TF is not installable) on this box's
                         host cores, bounded samples: a batch-1 train step (same unit as `value`), the C1 forward, the C2 forward+loss.
+
+  --dump-outputs DIR    after the timed steps, rank 0 writes what the LAST timed step returned to its caller, as DIR/<name>.npy:
+                        pred_logits / pred_boxes [B,Q,*], aux_pred_logits / aux_pred_boxes [levels-1,B,Q,*] (float32), loss (the
+                        total, float64) and losses (the loss dict's values, main level then aux levels, float64), and params: the
+                        trainable parameters after that step's update (float32).  An array over DUMP_MAX_ELEMS elements is
+                        replaced by a fixed, seeded sample of its flattened values: 64 MB at most in all.
+                        Inputs, weights and dropout masks are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -44,6 +51,7 @@ STEP_GFLOP_PER_IMAGE = 610.0         # fwd + dgrad + wgrad
 PEAK_F32_MFMA_TFLOPS = 157.3         # MI355X_MICROARCH.md (v_mfma_f32_32x32x2_f32, exact f32)
 PEAK_BF16_MFMA_TFLOPS = 2500.0       # dense bf16 MFMA
 PEAK_HBM_GBS = 8000.0                # spec; ~6300 GB/s achievable by a copy kernel
+DUMP_MAX_ELEMS = 2 << 20             # --dump-outputs: per array (8 MB of float32); the five large arrays stay under 64 MB
 
 
 def make_targets(B, rng, rows=100):
@@ -59,6 +67,29 @@ def make_targets(B, rng, rows=100):
         t_bbox[b, 1:1 + n, 2:4] = rng.uniform(0.05, 0.4, (n, 2))
         t_class[b, 1:1 + n, 0] = rng.integers(1, 91, n)
     return t_bbox, t_class
+
+
+def _dump_sample(a, seed):
+    """`a` itself when it has at most DUMP_MAX_ELEMS elements, else a fixed seeded sample of its flattened values (sorted indices)."""
+    if a.size <= DUMP_MAX_ELEMS:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(out_dir, m_outputs, total, log, params_flat):
+    """--dump-outputs: what one step returned to its caller (model outputs, total loss, loss dict) and the parameters it left."""
+    os.makedirs(out_dir, exist_ok=True)
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    arrays = {"pred_logits": f32(m_outputs["pred_logits"]), "pred_boxes": f32(m_outputs["pred_boxes"]),
+              "loss": np.array(float(total), np.float64),
+              "losses": np.array([float(v) for k, v in log.items() if not k.endswith("_lr")], np.float64),
+              "params": f32(params_flat)}
+    if m_outputs.get("aux"):
+        arrays["aux_pred_logits"] = np.stack([f32(a["pred_logits"]) for a in m_outputs["aux"]])
+        arrays["aux_pred_boxes"] = np.stack([f32(a["pred_boxes"]) for a in m_outputs["aux"]])
+    for seed, name in enumerate(sorted(arrays)):
+        np.save(os.path.join(out_dir, name + ".npy"), _dump_sample(arrays[name], seed))
 
 
 def _pick_threads(requested):
@@ -249,6 +280,8 @@ def main():
     ap.add_argument("--dist-backend", type=str, default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--event-steps", type=int, default=1, help="timed steps (the last ones) whose launches carry HIP events")
     ap.add_argument("--dump-shapes", type=str, default=None, help="write the per-shape GEMM timing table (JSON) here")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed (outputs, losses, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0 = auto)")
     ap.add_argument("--grad-buckets", choices=("fp32", "bf16"), default="fp32",
                     help="N > 1: dtype of the gradient buckets on the wire (bf16 = half the bytes over xGMI, fp32 master update; parallel.DataParallel)")
@@ -257,6 +290,8 @@ def main():
     ap.add_argument("--phase-events", action="store_true", help="after the timed region: 5 eager steps with HIP events at the phase "
                     "boundaries of the launch sequence (backbone / encoder / decoder / heads / set loss, forward and backward, optimiser)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks (one process per GPU) ourselves and relay rank 0's line
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -324,16 +359,20 @@ def main():
     tb, tc = torch.from_numpy(tb).to(dev), torch.from_numpy(tc).to(dev)
     model, opt, stepper = build(args.precision)
 
-    def step(i, single=False):
+    def step_outputs(i, single=False):
+        """One step; returns what its caller receives: (model outputs, total loss, loss dict)."""
         # HIP events around single launches: that step runs on ONE stream, so that a kernel's duration is its own (on two
         # streams the events of co-running kernels overlap and every duration is stretched by its neighbour)
         engine_mod.WGRAD_STREAM = wgrad_stream_default and _hip.PROFILER is None and not single
         if args.mode == "train":
             if _hip.PROFILER is None and not single:   # (HIP events around single launches need the single-stream eager step)
-                return stepper(images, tb, tc, i)[1]
-            return training.train_step(model, images, tb, tc, opt, cfg, i)[1]
+                return stepper(images, tb, tc, i)
+            return training.train_step(model, images, tb, tc, opt, cfg, i)
         out = model(images, training=False)
-        return get_losses(out, tb, tc, cfg)[0]
+        return (out,) + tuple(get_losses(out, tb, tc, cfg))
+
+    def step(i, single=False):
+        return step_outputs(i, single)[1]
 
     def barrier(phase="barrier"):
         if world > 1:
@@ -375,12 +414,16 @@ def main():
     for i in range(args.steps):
         if prof is not None and i == args.steps - ev_steps:
             _hip.PROFILER = prof
-        last = step(args.warmup + i)
+        last_outputs = step_outputs(args.warmup + i)
         wd.feed(f"timed step {i}")
     barrier("timed region end")
     dt = time.perf_counter() - t0
     _hip.PROFILER = None
+    last = last_outputs[1]
     loss_val = float(last)
+    if args.dump_outputs and rank == 0:       # before any later step overwrites the (graph-static) output buffers
+        dump_outputs(args.dump_outputs, *last_outputs, model.engine.P.flat)
+    last_outputs = None
     dp_timing = model.dp.timing_summary() if model.dp is not None else None
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:

@@ -312,7 +312,7 @@ def test_host_side_of_the_c_abi_under_address_sanitizer():
     import subprocess
     pkg = os.path.join(ROOT, "detr-tensorflow_amd")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1")
-    r = subprocess.run(["make", "-C", pkg, "-j", str(os.cpu_count() or 2), "asan-check"], capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run(["make", "-C", pkg, "-j", os.environ.get("MAX_JOBS") or str(min(16, os.cpu_count() or 2)), "asan-check"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "host_abi_check: 0 failed expectation(s)" in r.stdout
 
