@@ -25,6 +25,8 @@ struct AttnArgs {
     float drop_scale;       // 1/(1-p) or 0
     uint32_t drop_thresh, drop_seed;      // drop_seed = dropout SITE id
     const uint32_t *drop_step;            // per-step seed in device memory (may be null), see common.h drop_key
+    const uint32_t *key_valid;            // masked kernels only: [B][kv_words] key-validity words, bit j of word t = key 32 t + j
+    int kv_words;                         // ceil(S / 32)
 };
 
 __device__ __forceinline__ int krow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
@@ -175,7 +177,7 @@ static int attn_waves(int rows, int bh) {
 
 int attn_fwd_bf16_launch(const AttnArgs &a, hipStream_t s);      // attention_bf16.hip
 int attn_bwd_bf16_launch(const AttnArgs &a, hipStream_t s);
-int attn2_fwd_from_desc(const detr_attn_desc *d, hipStream_t s);    // attention_dma.hip (io_dtype = 1)
-int attn2_bwd_from_desc(const detr_attn_desc *d, hipStream_t s);
+int attn2_fwd_from_desc(const detr_attn_desc *d, hipStream_t s, const uint32_t *key_valid = nullptr);    // attention_dma.hip (io_dtype = 1)
+int attn2_bwd_from_desc(const detr_attn_desc *d, hipStream_t s, const uint32_t *key_valid = nullptr);
 
 }  // namespace detr

@@ -41,7 +41,8 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int A2_TILE = 2048;            // one 32-row x 64-byte head tile image
 constexpr int A2_AUX = 256;              // one 64-lane x 4-byte piece (flag words / row statistics)
 constexpr int A2_RING = 3;
-constexpr float A2_SUM_LIMIT = 4096.0f;  // a lane's 16-key sum of exp2(score - reference) above this moves the reference (forward kernel)
+constexpr float A2_SUM_LIMIT = 4096.0f;
+constexpr float A2_M_EMPTY = -1.0e30f;   // masked forward: the reference of a run without a valid key (see attn2_fwd_kernel)  // a lane's 16-key sum of exp2(score - reference) above this moves the reference (forward kernel)
 // timing experiments only (scripts/experiments/attn2_ablate.sh; results are WRONG with any bit set): 1 = no DMA requests inside the key loop,
 // 2 = no fragment reads / MFMAs / softmax inside the key loop, 4 = no softmax arithmetic (the scores go straight into the PV product)
 #ifndef A2_ABLATE
@@ -65,6 +66,8 @@ struct Attn2Args {
     const uint32_t *drop_step;
     int parts;                           // waves per workgroup = contiguous runs of the streamed dimension
     int xcd_map;                         // 1: workgroup id -> (row block, problem) keeps a (batch, head) problem on one XCD
+    const uint32_t *key_valid;           // masked kernels only: [B][kv_words] key-validity words, bit j of word t = key 32 t + j
+    int kv_words;                        // ceil(S / 32)
 };
 
 #define A2_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16((A), (B), (C), 0, 0, 0)
@@ -171,6 +174,31 @@ __device__ __forceinline__ void a2_keep16(float (&p)[16], unsigned w) { a2_keep1
 template <int S>
 using a2_ic = std::integral_constant<int, S>;
 
+// key padding mask (the MASK instantiations): a tile's validity word is wave-uniform (one batch entry per wave).  A partial word
+// sets the scores of its invalid keys to -inf (register r holds key 4 hi + (r & 3) + 8 (r >> 2) of the tile, as in the ragged tail)
+// (v_bfe_i32 + v_bfi_b32 per score: the flag as an all-ones / zero word selects the score or -inf bitwise, as a2_keep does for dropout)
+template <int R, typename V>
+__device__ __forceinline__ void a2_mask_one(V &s, unsigned kw) {
+    int m;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(kw), "n"((R & 3) + 8 * (R >> 2)));
+    unsigned x;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(x) : "v"(m), "v"(__builtin_bit_cast(unsigned, (float)s[R])), "v"(0xFF800000u));
+    s[R] = __builtin_bit_cast(float, x);
+}
+template <typename V, int... R>
+__device__ __forceinline__ void a2_mask_scores(V &s, unsigned kv, int hi, std::integer_sequence<int, R...>) {
+    const unsigned kw = kv >> (4 * hi);
+    (a2_mask_one<R>(s, kw), ...);
+}
+template <typename V>
+__device__ __forceinline__ void a2_mask_scores(V &s, unsigned kv, int hi) { a2_mask_scores(s, kv, hi, std::make_integer_sequence<int, 16>{}); }
+// the validity words of a wave's first 64 key tiles, one per lane (fetched once with the prologue operands); tile i's word is then
+// v_readlane of lane i -- no memory access and no wait inside the key loop (runs longer than 64 tiles read the rest directly)
+__device__ __forceinline__ unsigned a2_kv_lanes(const uint32_t *w, int n, int lane) { return lane < n ? w[lane] : 0u; }
+__device__ __forceinline__ unsigned a2_kv_tile(unsigned lanes, const uint32_t *w, int i) {
+    return i < 64 ? (unsigned)__builtin_amdgcn_readlane((int)lanes, i) : w[i];
+}
+
 // workgroup id -> (row block x, problem bh).  Blocks are dispatched round-robin over the 8 XCDs: with xcd_map the blocks of one
 // (batch, head) problem share an XCD (its K / V stay in that XCD's L2), otherwise plain row-major order.
 __device__ __forceinline__ void a2_block(const Attn2Args &a, int nblk, int &x, int &bh) {
@@ -202,7 +230,11 @@ extern __shared__ __attribute__((aligned(16))) char a2_smem[];
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <bool DROP>
+// MASK: key padding mask (a.key_valid).  A tile without a valid key is skipped after its DMA wait (the ring's counted waits are
+// unchanged); the reference is set by the first tile with a valid key (`fresh`), and a run with none merges as l = o = 0 with
+// m = A2_M_EMPTY, a finite stand-in for -inf: exp2(A2_M_EMPTY - m') = 0 against any real run, and two empty runs merge without
+// the NaN of -inf - -inf -- the merge itself is the unmasked kernel's, operation for operation.
+template <bool DROP, bool MASK = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn2_fwd_kernel(Attn2Args a) {
     constexpr int NP = 4 + (DROP ? 1 : 0);                   // DMA requests per tile and wave
     constexpr int STAGE = 2 * A2_TILE + (DROP ? A2_AUX : 0);
@@ -256,17 +288,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { o[c][r] = 0.0f; negm[c][r] = lg2scale; }
+    const uint32_t *kvw = MASK ? a.key_valid + (long long)b * a.kv_words + t0 : nullptr;
+    const unsigned kvl = MASK ? a2_kv_lanes(kvw, nt, lane) : 0u;
+    bool fresh = true;                                   // MASK: no tile with a valid key seen yet (wave-uniform)
 
     auto tile = [&](auto stg_c, int i) {
         constexpr int STG = decltype(stg_c)::value;
+        unsigned kv = ~0u;
+        if constexpr (MASK) kv = a2_kv_tile(kvl, kvw, i);
         if constexpr ((A2_ABLATE & 1) == 0) {
             issue((STG + 2) % A2_RING, t0 + i + 2);     // (the stage of tile i - 1: its reads were drained at the end of that tile)
             ring_wait_vmcnt<2 * NP>();                  // tile i has landed
         }
         if constexpr ((A2_ABLATE & 2) != 0) return;
+        if constexpr (MASK) {
+            if (kv == 0u) return;                       // no valid key: contributes nothing (no LDS read was issued)
+        }
         const char *st = ring + STG * STAGE;
         const int kbase = (t0 + i) * 32;
-        const bool first = (STG == 0) && i == 0;        // wave-uniform
+        bool first;                                     // wave-uniform
+        if constexpr (MASK) first = fresh;
+        else first = (STG == 0) && i == 0;
         const bf16x8 k0 = a2_frag_row(st, fr, 0), k1 = a2_frag_row(st, fr, 1);
         f32x16 s[2];
 #pragma unroll
@@ -289,6 +331,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if ((r & 3) + 8 * (r >> 2) >= nv) s[c][r] = -INFINITY;
+            }
+            if constexpr (MASK) {
+                if (kv != ~0u) {
+                    A2_NO_IFCVT();
+                    a2_mask_scores(s[c], kv, hi);
+                }
             }
             if constexpr ((A2_ABLATE & 4) != 0) {
                 float pa[16];
@@ -325,6 +373,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     for (int r = 0; r < 16; ++r)
                         if ((r & 3) + 8 * (r >> 2) >= nv) s2[r] = -INFINITY;
                 }
+                if constexpr (MASK) {
+                    if (kv != ~0u) a2_mask_scores(s2, kv, hi);
+                }
                 const float d = fmaxf(halves_max(tree_max16(s2)) - lg2scale, 0.0f);
                 const float corr = a2_exp2(-d);
                 lsum[c] *= corr;
@@ -341,6 +392,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             o[c] = A2_MFMA(v0, a2_pack8(p), o[c]);
             o[c] = A2_MFMA(v1, a2_pack8(p + 8), o[c]);
         }
+        if constexpr (MASK) fresh = false;
         a2_lds_drained();
     };
     A2_TILE_LOOP(nt, tile)
@@ -349,7 +401,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         l[c] = halves_sum(lsum[c]);
-        m[c] = (nt > 0) ? lg2scale - negm[c][0] : -INFINITY;
+        if constexpr (MASK) m[c] = (nt > 0 && !fresh) ? lg2scale - negm[c][0] : A2_M_EMPTY;
+        else m[c] = (nt > 0) ? lg2scale - negm[c][0] : -INFINITY;
     }
     if (a.parts > 1) {
         // merge the partial softmaxes: (m, l, o) of runs 1 .. parts-1 travel through their own ring memory (component-major:
@@ -399,7 +452,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // ------------------------------------------------------------------------------------------------
 // backward 1/2: dQ per query block (streams the keys) + the row statistics for the dK / dV kernel
 // ------------------------------------------------------------------------------------------------
-template <bool DROP>
+template <bool DROP, bool MASK = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn2_bwd_dq_kernel(Attn2Args a) {
     constexpr int NP = 4 + (DROP ? 1 : 0);
     constexpr int STAGE = 2 * A2_TILE + (DROP ? A2_AUX : 0);
@@ -470,11 +523,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dq[c][r] = 0.0f; negL[c][r] = -Lq[c]; }
+    const uint32_t *kvw = MASK ? a.key_valid + (long long)b * a.kv_words + t0 : nullptr;
+    const unsigned kvl = MASK ? a2_kv_lanes(kvw, nt, lane) : 0u;
 
     auto tile = [&](auto stg_c, int i) {
         constexpr int STG = decltype(stg_c)::value;
+        unsigned kv = ~0u;
+        if constexpr (MASK) kv = a2_kv_tile(kvl, kvw, i);
         issue((STG + 2) % A2_RING, t0 + i + 2);
         ring_wait_vmcnt<2 * NP>();
+        if constexpr (MASK) {
+            if (kv == 0u) return;                       // no valid key: dS = 0 for the whole tile
+        }
         const char *st = ring + STG * STAGE;
         const int kbase = (t0 + i) * 32;
         const bf16x8 k0 = a2_frag_row(st, fr, 0), k1 = a2_frag_row(st, fr, 1);
@@ -511,6 +571,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if ((r & 3) + 8 * (r >> 2) >= nv) ds[r] = 0.0f;
+            }
+            if constexpr (MASK) {                       // (masked keys: P = 0, so dS = 0 -- selected, exp2 of a garbage score may be inf)
+                if (kv != ~0u) {
+                    A2_NO_IFCVT();
+                    a2_keep16(ds, kv >> (4 * hi));      // (the dropout flag select: invalid keys -> exact 0)
+                }
             }
             dq[c] = A2_MFMA(kc0, a2_pack8(ds), dq[c]);
             dq[c] = A2_MFMA(kc1, a2_pack8(ds + 8), dq[c]);
@@ -553,7 +619,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ------------------------------------------------------------------------------------------------
 // backward 2/2: dK, dV per key block (streams the queries): lane l holds key (l & 31) of a chain and 16 queries krow(r, hi)
 // ------------------------------------------------------------------------------------------------
-template <bool DROP>
+// MASK: a lane whose key is masked stores exact zeros (its column of P / dS never mixes with other keys' columns in the MFMAs)
+template <bool DROP, bool MASK = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn2_bwd_dkv_kernel(Attn2Args a) {
     constexpr int NP = 5 + (DROP ? 1 : 0);
     constexpr int STAGE = 2 * A2_TILE + A2_AUX + (DROP ? A2_AUX : 0);
@@ -703,10 +770,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         if (qp > 0) return;
     }
+    bool kval[2] = {true, true};
+    if constexpr (MASK) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int sk = key0 + 32 * c + l31;
+            kval[c] = sk < a.S && ((a.key_valid[(long long)b * a.kv_words + (sk >> 5)] >> (sk & 31)) & 1u);
+        }
+    }
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const int sk = key0 + 32 * c + l31;
         if (sk < a.S) {
+            if constexpr (MASK) {
+                if (!kval[c]) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { dk[c][r] = 0.0f; dv[c][r] = 0.0f; }
+                }
+            }
             unsigned short *dkp = a.dK + ((long long)b * a.S + sk) * a.lddk + h * 32 + 4 * hi;
             unsigned short *dvp = a.dV + ((long long)b * a.S + sk) * a.lddv + h * 32 + 4 * hi;
 #pragma unroll
@@ -803,7 +884,10 @@ int attn2_fwd_launch(Attn2Args a, hipStream_t s) {
     const bool drop = a.drop_scale != 0.0f;
     a.parts = a2_parts(blocks, cdiv(a.S, 32));
     const int lds = a.parts * A2_RING * a2_stage_bytes(0, drop);
-    if (drop) { if (a2_launch(attn2_fwd_kernel<true>, a, blocks, lds, s, "attention fwd (bf16 io)")) return -1; }
+    if (a.key_valid) {
+        if (drop) { if (a2_launch(attn2_fwd_kernel<true, true>, a, blocks, lds, s, "attention fwd masked (bf16 io)")) return -1; }
+        else if (a2_launch(attn2_fwd_kernel<false, true>, a, blocks, lds, s, "attention fwd masked (bf16 io)")) return -1;
+    } else if (drop) { if (a2_launch(attn2_fwd_kernel<true>, a, blocks, lds, s, "attention fwd (bf16 io)")) return -1; }
     else if (a2_launch(attn2_fwd_kernel<false>, a, blocks, lds, s, "attention fwd (bf16 io)")) return -1;
     DETR_LAUNCH_CHECK("attention fwd (bf16 io)");
     return 0;
@@ -815,13 +899,19 @@ int attn2_bwd_launch(Attn2Args a, hipStream_t s) {
     a2_grid(a, a.T, nblk, blocks);
     a.parts = a2_parts(blocks, cdiv(a.S, 32));
     int lds = a.parts * A2_RING * a2_stage_bytes(0, drop);
-    if (drop) { if (a2_launch(attn2_bwd_dq_kernel<true>, a, blocks, lds, s, "attention bwd dq (bf16 io)")) return -1; }
+    if (a.key_valid) {
+        if (drop) { if (a2_launch(attn2_bwd_dq_kernel<true, true>, a, blocks, lds, s, "attention bwd dq masked (bf16 io)")) return -1; }
+        else if (a2_launch(attn2_bwd_dq_kernel<false, true>, a, blocks, lds, s, "attention bwd dq masked (bf16 io)")) return -1;
+    } else if (drop) { if (a2_launch(attn2_bwd_dq_kernel<true>, a, blocks, lds, s, "attention bwd dq (bf16 io)")) return -1; }
     else if (a2_launch(attn2_bwd_dq_kernel<false>, a, blocks, lds, s, "attention bwd dq (bf16 io)")) return -1;
     DETR_LAUNCH_CHECK("attention bwd dq (bf16 io)");
     a2_grid(a, a.S, nblk, blocks);
     a.parts = a2_parts(blocks, cdiv(a.T, 32));
     lds = a.parts * A2_RING * a2_stage_bytes(1, drop);
-    if (drop) { if (a2_launch(attn2_bwd_dkv_kernel<true>, a, blocks, lds, s, "attention bwd dkv (bf16 io)")) return -1; }
+    if (a.key_valid) {
+        if (drop) { if (a2_launch(attn2_bwd_dkv_kernel<true, true>, a, blocks, lds, s, "attention bwd dkv masked (bf16 io)")) return -1; }
+        else if (a2_launch(attn2_bwd_dkv_kernel<false, true>, a, blocks, lds, s, "attention bwd dkv masked (bf16 io)")) return -1;
+    } else if (drop) { if (a2_launch(attn2_bwd_dkv_kernel<true>, a, blocks, lds, s, "attention bwd dkv (bf16 io)")) return -1; }
     else if (a2_launch(attn2_bwd_dkv_kernel<false>, a, blocks, lds, s, "attention bwd dkv (bf16 io)")) return -1;
     DETR_LAUNCH_CHECK("attention bwd dkv (bf16 io)");
     return 0;
@@ -877,14 +967,18 @@ static int a2_from_desc(const detr_attn_desc *d, int bwd, Attn2Args &a) {
     return 0;
 }
 
-int attn2_fwd_from_desc(const detr_attn_desc *d, hipStream_t s) {
+int attn2_fwd_from_desc(const detr_attn_desc *d, hipStream_t s, const uint32_t *key_valid) {
     Attn2Args a;
     if (a2_from_desc(d, 0, a)) return -1;
+    a.key_valid = key_valid;
+    a.kv_words = cdiv(d->S, 32);
     return attn2_fwd_launch(a, s);
 }
-int attn2_bwd_from_desc(const detr_attn_desc *d, hipStream_t s) {
+int attn2_bwd_from_desc(const detr_attn_desc *d, hipStream_t s, const uint32_t *key_valid) {
     Attn2Args a;
     if (a2_from_desc(d, 1, a)) return -1;
+    a.key_valid = key_valid;
+    a.kv_words = cdiv(d->S, 32);
     return attn2_bwd_launch(a, s);
 }
 

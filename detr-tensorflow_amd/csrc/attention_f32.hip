@@ -71,7 +71,9 @@ struct Tile {
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <int NW>
+// MASK: key padding mask (a.key_valid, one word per 32-key tile and batch entry: workgroup-uniform).  A tile without a valid key
+// skips its arithmetic (the running maximum is never taken from it: -inf - -inf), a partial one sets its invalid scores to -inf.
+template <int NW, bool MASK = false>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
     __shared__ float Ks[2][AT_KEYS][AT_LD];
     __shared__ float Vs[2][AT_KEYS][AT_LD];
@@ -98,6 +100,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
     const unsigned long long rowbase = ((unsigned long long)bh * a.T + tq) * (unsigned long long)((a.S + 1) & ~1);
 
     const int ntiles = (a.S + AT_KEYS - 1) / AT_KEYS;
+    // MASK: the validity words of the first 64 key tiles, one per lane (tile it's word = v_readlane of lane it: no load in the loop)
+    const uint32_t *kvw = MASK ? a.key_valid + (long long)b * a.kv_words : nullptr;
+    const unsigned kvl = (MASK && lane < ntiles) ? kvw[lane] : 0u;
     Tile<NW> rk, rv;
     rk.load(Kb, a.ldk, 0, a.S, tid);
     rv.load(Vb, a.ldv, 0, a.S, tid);
@@ -111,6 +116,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
             rk.load(Kb, a.ldk, (it + 1) * AT_KEYS, a.S, tid);
             rv.load(Vb, a.ldv, (it + 1) * AT_KEYS, a.S, tid);
         }
+        unsigned kv = ~0u;
+        if constexpr (MASK) kv = it < 64 ? (unsigned)__builtin_amdgcn_readlane((int)kvl, it) : kvw[it];
+        if (!MASK || kv != 0u) {
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.0f;
@@ -122,6 +130,13 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (kbase + krow(r, hi) >= a.S) s[r] = -INFINITY;
+        }
+        if constexpr (MASK) {
+            if (kv != ~0u) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (((kv >> krow(r, hi)) & 1u) == 0u) s[r] = -INFINITY;
+            }
         }
         const float mx = halves_max(tree_max16(s));
         const float mn = fmaxf(m, mx);              // finite: every tile holds at least one valid key
@@ -144,6 +159,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             o = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[cur][krow(r, hi)][l31], p[r], o, 0, 0, 0);
+        }
         if (more) {
             rk.store(Ks[cur ^ 1], tid);
             rv.store(Vs[cur ^ 1], tid);
@@ -163,7 +179,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs a) {
 // ------------------------------------------------------------------------------------------------
 // backward 1/2: dQ (per query tile, streams the keys) and delta = rowsum(dO * O)
 // ------------------------------------------------------------------------------------------------
-template <int NW>
+template <int NW, bool MASK = false>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(AttnArgs a) {
     __shared__ float Ks[2][AT_KEYS][AT_LD];
     __shared__ float Vs[2][AT_KEYS][AT_LD];
@@ -201,6 +217,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(AttnArgs a) {
     for (int r = 0; r < 16; ++r) dq[r] = 0.0f;
 
     const int ntiles = (a.S + AT_KEYS - 1) / AT_KEYS;
+    // MASK: the validity words of the first 64 key tiles, one per lane (tile it's word = v_readlane of lane it: no load in the loop)
+    const uint32_t *kvw = MASK ? a.key_valid + (long long)b * a.kv_words : nullptr;
+    const unsigned kvl = (MASK && lane < ntiles) ? kvw[lane] : 0u;
     Tile<NW> rk, rv;
     rk.load(Kb, a.ldk, 0, a.S, tid);
     rv.load(Vb, a.ldv, 0, a.S, tid);
@@ -214,6 +233,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(AttnArgs a) {
             rk.load(Kb, a.ldk, (it + 1) * AT_KEYS, a.S, tid);
             rv.load(Vb, a.ldv, (it + 1) * AT_KEYS, a.S, tid);
         }
+        unsigned kv = ~0u;
+        if constexpr (MASK) kv = it < 64 ? (unsigned)__builtin_amdgcn_readlane((int)kvl, it) : kvw[it];
+        if (!MASK || kv != 0u) {
         f32x16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.0f; dp[r] = 0.0f; }
@@ -234,9 +256,17 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(AttnArgs a) {
             for (int r = 0; r < 16; ++r)
                 if (kbase + krow(r, hi) >= a.S) ds[r] = 0.0f;
         }
+        if constexpr (MASK) {                       // masked keys: P = 0 (selected: exp2 of a garbage score may be inf)
+            if (kv != ~0u) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (((kv >> krow(r, hi)) & 1u) == 0u) ds[r] = 0.0f;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             dq = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[cur][krow(r, hi)][l31], ds[r], dq, 0, 0, 0);
+        }
         if (more) {
             rk.store(Ks[cur ^ 1], tid);
             rv.store(Vs[cur ^ 1], tid);
@@ -254,7 +284,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(AttnArgs a) {
 // backward 2/2: dK, dV (per key tile, streams the queries; needs LSE and delta)
 // here the natural orientation is S[query][key]: lane l holds key (l&31) and 16 queries.
 // ------------------------------------------------------------------------------------------------
-template <int NW>
+// MASK: a lane whose key is masked stores exact zeros (its P / dS column only reaches its own dK / dV column)
+template <int NW, bool MASK = false>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_dkv_kernel(AttnArgs a) {
     __shared__ float Qs[2][AT_KEYS][AT_LD];
     __shared__ float Ds[2][AT_KEYS][AT_LD];
@@ -345,6 +376,12 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dkv_kernel(AttnArgs a) {
         cur ^= 1;
     }
     if (kok) {
+        if constexpr (MASK) {
+            if (((a.key_valid[(long long)b * a.kv_words + (sk >> 5)] >> (sk & 31)) & 1u) == 0u) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { dk[r] = 0.0f; dv[r] = 0.0f; }
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             a.dK[dkoff + krow(r, hi)] = dk[r] * a.qscale;     // the staged Q is unscaled (K carries qscale * log2 e)
@@ -358,34 +395,89 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dkv_kernel(AttnArgs a) {
 using namespace detr;
 
 /* one entry point per direction; detr_attn_desc.compute selects the exact-fp32 kernels above or the bf16-MFMA kernels of
- * attention_bf16.hip */
-extern "C" int detr_hip_attention_fwd(const detr_attn_desc *d, void *stream) {
-    DETR_REQUIRE(d, "attention: null descriptor");
-    if (d->io_dtype == 1) return attn2_fwd_from_desc(d, (hipStream_t)stream);      // all-bf16 operands: attention_dma.hip
+ * attention_bf16.hip.  key_valid != null: the key-padding-masked instantiations (exact fp32 and all-bf16 operands only) */
+static int attn_fwd_impl(const detr_attn_desc *d, const uint32_t *key_valid, hipStream_t s) {
+    if (d->io_dtype == 1) return attn2_fwd_from_desc(d, s, key_valid);      // all-bf16 operands: attention_dma.hip
     DETR_REQUIRE(d->io_dtype == 0, "attention: io_dtype must be 0 (fp32 tensors) or 1 (bf16 tensors)");
     AttnArgs a;
     if (attn_from_desc(d, 0, a)) return -1;
-    hipStream_t s = (hipStream_t)stream;
     if (d->compute == 1) return attn_fwd_bf16_launch(a, s);
-    if (attn_waves(a.T, a.B * a.H) == 2) hipLaunchKernelGGL(attn_fwd_kernel<2>, dim3((unsigned)cdiv(a.T, 64), (unsigned)(a.B * a.H)), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3((unsigned)cdiv(a.T, 128), (unsigned)(a.B * a.H)), dim3(256), 0, s, a);
+    a.key_valid = key_valid;
+    a.kv_words = cdiv(a.S, 32);
+    const bool two = attn_waves(a.T, a.B * a.H) == 2;
+    const dim3 grid((unsigned)cdiv(a.T, two ? 64 : 128), (unsigned)(a.B * a.H)), block(two ? 128 : 256);
+    if (key_valid) {
+        if (two) hipLaunchKernelGGL((attn_fwd_kernel<2, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((attn_fwd_kernel<4, true>), grid, block, 0, s, a);
+    } else if (two) hipLaunchKernelGGL(attn_fwd_kernel<2>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(attn_fwd_kernel<4>, grid, block, 0, s, a);
     DETR_LAUNCH_CHECK("attention fwd");
     return 0;
 }
 
-extern "C" int detr_hip_attention_bwd(const detr_attn_desc *d, void *stream) {
-    DETR_REQUIRE(d, "attention: null descriptor");
-    if (d->io_dtype == 1) return attn2_bwd_from_desc(d, (hipStream_t)stream);
+static int attn_bwd_impl(const detr_attn_desc *d, const uint32_t *key_valid, hipStream_t s) {
+    if (d->io_dtype == 1) return attn2_bwd_from_desc(d, s, key_valid);
     DETR_REQUIRE(d->io_dtype == 0, "attention: io_dtype must be 0 (fp32 tensors) or 1 (bf16 tensors)");
     AttnArgs a;
     if (attn_from_desc(d, 1, a)) return -1;
-    hipStream_t s = (hipStream_t)stream;
     if (d->compute == 1) return attn_bwd_bf16_launch(a, s);
-    if (attn_waves(a.T, a.B * a.H) == 2) hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, dim3((unsigned)cdiv(a.T, 64), (unsigned)(a.B * a.H)), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<4>, dim3((unsigned)cdiv(a.T, 128), (unsigned)(a.B * a.H)), dim3(256), 0, s, a);
+    a.key_valid = key_valid;
+    a.kv_words = cdiv(a.S, 32);
+    bool two = attn_waves(a.T, a.B * a.H) == 2;
+    dim3 grid((unsigned)cdiv(a.T, two ? 64 : 128), (unsigned)(a.B * a.H)), block(two ? 128 : 256);
+    if (key_valid) {
+        if (two) hipLaunchKernelGGL((attn_bwd_dq_kernel<2, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((attn_bwd_dq_kernel<4, true>), grid, block, 0, s, a);
+    } else if (two) hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(attn_bwd_dq_kernel<4>, grid, block, 0, s, a);
     DETR_LAUNCH_CHECK("attention bwd dq");
-    if (attn_waves(a.S, a.B * a.H) == 2) hipLaunchKernelGGL(attn_bwd_dkv_kernel<2>, dim3((unsigned)cdiv(a.S, 64), (unsigned)(a.B * a.H)), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(attn_bwd_dkv_kernel<4>, dim3((unsigned)cdiv(a.S, 128), (unsigned)(a.B * a.H)), dim3(256), 0, s, a);
+    two = attn_waves(a.S, a.B * a.H) == 2;
+    grid = dim3((unsigned)cdiv(a.S, two ? 64 : 128), (unsigned)(a.B * a.H));
+    block = dim3(two ? 128 : 256);
+    if (key_valid) {
+        if (two) hipLaunchKernelGGL((attn_bwd_dkv_kernel<2, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<4, true>), grid, block, 0, s, a);
+    } else if (two) hipLaunchKernelGGL(attn_bwd_dkv_kernel<2>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(attn_bwd_dkv_kernel<4>, grid, block, 0, s, a);
     DETR_LAUNCH_CHECK("attention bwd dkv");
     return 0;
+}
+
+extern "C" int detr_hip_attention_fwd(const detr_attn_desc *d, void *stream) {
+    DETR_REQUIRE(d, "attention: null descriptor");
+    return attn_fwd_impl(d, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int detr_hip_attention_bwd(const detr_attn_desc *d, void *stream) {
+    DETR_REQUIRE(d, "attention: null descriptor");
+    return attn_bwd_impl(d, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int64_t detr_hip_attention_keymask_words(int32_t B, int32_t S) {
+    if (B <= 0 || S <= 0) return -1;
+    return (int64_t)B * cdiv(S, 32);
+}
+
+// shared argument checks of the masked entry points (nothing is launched or written when they fail)
+static int attn_masked_check(const detr_attn_desc *d, const uint32_t *key_valid) {
+    DETR_REQUIRE(d, "attention masked: null descriptor");
+    DETR_REQUIRE(key_valid, "attention masked: null key_valid words");
+    DETR_REQUIRE(d->io_dtype == 0 || d->io_dtype == 1, "attention masked: io_dtype must be 0 (fp32 tensors) or 1 (bf16 tensors)");
+    DETR_REQUIRE(!(d->io_dtype == 0 && d->compute == 1),
+                 "attention masked: no key-padding-masked form of the bf16-compute kernels on fp32 tensors (io_dtype = 0, compute = 1); "
+                 "use compute = 0 or bf16 operands (io_dtype = 1)");
+    DETR_REQUIRE(d->io_dtype == 0 || d->compute == 1, "attention masked: bf16 operands (io_dtype = 1) need compute = 1");
+    DETR_REQUIRE(d->B > 0 && d->S > 0, "attention masked: bad shape B=%d S=%d", d->B, d->S);
+    DETR_REQUIRE(((uintptr_t)key_valid & 3) == 0, "attention masked: key_valid must be 4-byte aligned");
+    return 0;
+}
+
+extern "C" int detr_hip_attention_fwd_masked(const detr_attn_desc *d, const uint32_t *key_valid, void *stream) {
+    if (attn_masked_check(d, key_valid)) return -1;
+    return attn_fwd_impl(d, key_valid, (hipStream_t)stream);
+}
+
+extern "C" int detr_hip_attention_bwd_masked(const detr_attn_desc *d, const uint32_t *key_valid, void *stream) {
+    if (attn_masked_check(d, key_valid)) return -1;
+    return attn_bwd_impl(d, key_valid, (hipStream_t)stream);
 }

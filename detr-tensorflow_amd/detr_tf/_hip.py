@@ -139,6 +139,10 @@ _SIGNATURES = {
     "detr_hip_attention_bwd": [POINTER(AttnDesc), c_void_p],
     "detr_hip_attention_dropmask": [POINTER(AttnDesc), c_void_p],
     "detr_hip_attention_dropmask_many": [POINTER(AttnDesc), c_int32, c_void_p],
+    "detr_hip_attention_fwd_masked": [POINTER(AttnDesc), c_void_p, c_void_p],
+    "detr_hip_attention_bwd_masked": [POINTER(AttnDesc), c_void_p, c_void_p],
+    "detr_hip_padding_mask_prepare": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, f32p, f32p, c_void_p, f32p, c_void_p, c_void_p],
+    "detr_hip_input_stage_padded": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, f32p, c_void_p, f32p, c_void_p, c_void_p],
     "detr_hip_dropout_f32": [f32p, f32p, c_int64, c_float, ctypes.c_uint32, c_void_p, c_void_p],
     "detr_hip_multi_copy": [c_void_p, c_int32, c_int32, c_void_p],
     "detr_hip_colsum_scaled": [c_void_p, c_int32, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p],
@@ -171,6 +175,7 @@ _SIGNATURES = {
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
     "detr_hip_attention_dropmask_words": [c_int32, c_int32, c_int32, c_int32],
+    "detr_hip_attention_keymask_words": [c_int32, c_int32],
     "detr_hip_colsum_det_scratch_floats": [c_int64, c_int32],
     "detr_hip_conv1x1_bwd_fused_workspace_floats": [c_int64],
     "detr_hip_workspace_bytes_gemm": [POINTER(GemmDesc)],
@@ -746,6 +751,38 @@ def attention_dropmask_words(B, H, T, S):
     return int(load().detr_hip_attention_dropmask_words(B, H, T, S))
 
 
+def attention_keymask_words(B, S):
+    """uint32 words of the key-validity buffer of a masked attention call (detr_hip_attention_keymask_words)."""
+    return int(load().detr_hip_attention_keymask_words(B, S))
+
+
+def keymask_words_from_valid(valid):
+    """Host helper: bool [B, S] key validity -> int32 [B, ceil(S/32)] words (bit j of word t = key 32 t + j), NumPy."""
+    import numpy as np
+    valid = np.asarray(valid, dtype=bool)
+    B, S = valid.shape
+    nw = (S + 31) // 32
+    bits = np.zeros((B, nw * 32), dtype=np.uint64)
+    bits[:, :S] = valid
+    w = (bits.reshape(B, nw, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2)
+    return w.astype(np.uint32).view(np.int32)
+
+
+def padding_mask_prepare(mask, Hf, Wf, tab_y, tab_x, key_valid, pos, status):
+    """mask: device uint8 / bool [B, H, W] (True = padding) -> key_valid words [B, ceil(Hf*Wf/32)], per-image positional encoding
+    pos [B*Hf*Wf, 256] and status [B] (1 = no valid feature position), one launch (detr_hip_padding_mask_prepare)."""
+    if mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 3 or not mask.is_cuda:
+        raise TypeError("padding_mask_prepare: mask must be a device uint8 / bool tensor [B, H, W]")
+    mask = mask.contiguous()
+    B, H, W = mask.shape
+    if key_valid.numel() < attention_keymask_words(B, Hf * Wf) or pos.numel() < B * Hf * Wf * 256 or status.numel() < B:
+        raise ValueError("padding_mask_prepare: output buffers too small")
+    if tab_y.numel() != (Hf + 1) ** 2 * 128 or tab_x.numel() != (Wf + 1) ** 2 * 128:
+        raise ValueError("padding_mask_prepare: sine tables do not match the feature size")
+    _check(load().detr_hip_padding_mask_prepare(mask.data_ptr(), B, H, W, Hf, Wf, tab_y.data_ptr(), tab_x.data_ptr(), key_valid.data_ptr(),
+                                                pos.data_ptr(), status.data_ptr(), _stream()), "detr_hip_padding_mask_prepare")
+
+
 def attention_dropmask(mask, B, H, T, S, *, dropout_p, dropout_site=0, dropout_step=None):
     """Fills `mask` (int32 / uint32 tensor of attention_dropmask_words(...) words) with the keep bits of the attention-probability
     dropout of (site, *step): what the all-bf16 attention kernels read instead of hashing (detr_hip_attention_dropmask)."""
@@ -772,12 +809,18 @@ def attention_dropmask_many(sites, B, H, *, dropout_p, dropout_step=None):
 
 
 def attention(q, k, v, o, lse, B, H, T, S, *, scale=1.0, dropout_p=0.0, dropout_site=0, dropout_step=None, compute=None,
-              d_o=None, dq=None, dk=None, dv=None, delta=None, dropmask=None):
+              d_o=None, dq=None, dk=None, dv=None, delta=None, dropmask=None, key_valid=None):
     """Fused attention core (include/detr_hip.h detr_attn_desc).  q / k / v / o (and the gradients) are 2-D views
     [rows, >= H*32] whose row stride is taken from the tensor, so they may be column blocks of a packed projection buffer.
     Forward when d_o is None, otherwise the backward (dq / dk / dv / delta written).
     All-bf16 operands (io_dtype = 1, csrc/attention_dma.hip): every tensor bf16, q pre-multiplied by scale * log2(e), delta with
-    2*B*H*T floats, and -- with dropout -- the keep bits of attention_dropmask() in `dropmask`."""
+    2*B*H*T floats, and -- with dropout -- the keep bits of attention_dropmask() in `dropmask`.
+    key_valid: int32 / uint32 tensor of attention_keymask_words(B, S) key-validity words (the key padding mask, see
+    detr_hip_attention_fwd_masked); not with bf16 compute on fp32 tensors."""
+    if key_valid is not None:
+        if not key_valid.is_cuda or key_valid.element_size() != 4 or key_valid.numel() < attention_keymask_words(B, S):
+            raise ValueError("attention: key_valid must be a device tensor of attention_keymask_words(B, S) 32-bit words")
+        kv = key_valid.data_ptr()
     d = AttnDesc()
     d.B, d.H, d.T, d.S = B, H, T, S
     io16 = q.dtype == torch.bfloat16
@@ -803,7 +846,10 @@ def attention(q, k, v, o, lse, B, H, T, S, *, scale=1.0, dropout_p=0.0, dropout_
     io = esz * 256 * (2 * B * T + 2 * B * S)           # q, o + k, v rows, once each
     bits = (B * H * T * S / 8.0) if (io16 and dropout_p > 0.0) else 0.0      # keep bits, one layout per kernel
     if d_o is None:
-        _check(load().detr_hip_attention_fwd(byref(d), _stream()), "detr_hip_attention_fwd")
+        if key_valid is not None:
+            _check(load().detr_hip_attention_fwd_masked(byref(d), kv, _stream()), "detr_hip_attention_fwd_masked")
+        else:
+            _check(load().detr_hip_attention_fwd(byref(d), _stream()), "detr_hip_attention_fwd")
         if ev0 is not None:
             PROFILER.end("attention_fwd", 2 * prods, ev0, f"B{B} H{H} T{T} S{S}", io + bits)
         return
@@ -815,7 +861,10 @@ def attention(q, k, v, o, lse, B, H, T, S, *, scale=1.0, dropout_p=0.0, dropout_
     if io16 and delta.numel() < 2 * B * H * T:
         raise ValueError("attention: bf16 operands need 2*B*H*T floats of `delta` scratch")
     d.delta = delta.data_ptr()
-    _check(load().detr_hip_attention_bwd(byref(d), _stream()), "detr_hip_attention_bwd")
+    if key_valid is not None:
+        _check(load().detr_hip_attention_bwd_masked(byref(d), kv, _stream()), "detr_hip_attention_bwd_masked")
+    else:
+        _check(load().detr_hip_attention_bwd(byref(d), _stream()), "detr_hip_attention_bwd")
     if ev0 is not None:      # dQ kernel: S, dP, dQ; dK/dV kernel: S, dP, dV, dK (the probabilities are recomputed twice)
         PROFILER.end("attention_bwd", 7 * prods, ev0, f"B{B} H{H} T{T} S{S}", 2.5 * io + 2 * bits)
 

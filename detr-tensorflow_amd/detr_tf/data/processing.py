@@ -7,6 +7,7 @@ PCIe (a quarter of the bytes), resize + normalisation write the fp32 NHWC tensor
 tensors with their in-band header row are built from the ragged box lists.  `normalized_images` / `pad_labels` keep the
 reference's host-side signatures for callers that still want NumPy.
 """
+import ctypes
 from ctypes import byref
 
 import numpy as np
@@ -90,6 +91,33 @@ class DeviceInputStage:
         d.interpolation = self.interpolation
         hip._check(hip.load().detr_hip_input_stage(byref(d), hip._stream()), "detr_hip_input_stage")
         return dst
+
+    def images_padded(self, images_uint8, canvas=None):
+        """Padded mixed-size batch: a list of uint8 images [h_i, w_i, 3] (NumPy or torch, each already at its final size: no
+        resize here) -> (images float32 [B, H, W, 3], masks bool [B, H, W]) on the device, H / W the largest h_i / w_i (or
+        `canvas` = (H, W)).  Image i sits at the top-left; its pixels are normalised exactly as images() does, the padding is 0.0
+        and masks is True there -- the reference's (images, masks) input (detr.py:65-72).  One launch."""
+        srcs = [torch.as_tensor(im) for im in images_uint8]
+        if not srcs or any(s.dtype != torch.uint8 or s.dim() != 3 or s.shape[-1] != 3 for s in srcs):
+            raise TypeError("DeviceInputStage.images_padded expects a non-empty list of uint8 images [h, w, 3]")
+        hw = np.array([[s.shape[0], s.shape[1]] for s in srcs], np.int32)
+        H, W = (int(hw[:, 0].max()), int(hw[:, 1].max())) if canvas is None else (int(canvas[0]), int(canvas[1]))
+        if (hw[:, 0] > H).any() or (hw[:, 1] > W).any():
+            raise ValueError(f"images_padded: an image is larger than the {H} x {W} canvas")
+        sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+        offsets = np.zeros(len(srcs), np.int64)
+        offsets[1:] = np.cumsum(sizes)[:-1]
+        packed = torch.cat([s.reshape(-1) for s in srcs]).to(self.device, non_blocking=True)
+        off_d = torch.from_numpy(offsets).to(self.device)
+        hw_d = torch.from_numpy(hw.reshape(-1)).to(self.device)
+        B = len(srcs)
+        dst = torch.empty(B, H, W, 3, dtype=torch.float32, device=self.device)
+        mask = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        perm = (ctypes.c_int32 * 3)(*self.perm)
+        hip._check(hip.load().detr_hip_input_stage_padded(packed.data_ptr(), off_d.data_ptr(), hw_d.data_ptr(), B, H, W, self.lut.data_ptr(),
+                                                          ctypes.cast(perm, ctypes.c_void_p), dst.data_ptr(), mask.data_ptr(), hip._stream()),
+                   "detr_hip_input_stage_padded")
+        return dst, mask.view(torch.bool)
 
     def targets(self, boxes_per_image, classes_per_image):
         """lists (one entry per image) of [n_i, 4] cx,cy,w,h boxes and [n_i] class ids -> (t_bbox [B,100,4] float32,

@@ -90,6 +90,39 @@ def position_embedding_sine_host(H, W, num_pos_features=128, temperature=10000.0
     return np.ascontiguousarray(pos.reshape(H * W, 2 * num_pos_features), dtype=np.float32)
 
 
+def position_embedding_sine_table(n_max, num_pos_features=128, temperature=10000.0, eps=1e-6):
+    """Per-axis sine table of the masked positional encoding (position_embeddings.py:23-50, normalize=True): entry [n][c] is the
+    encoding of cumulative count c on an axis with n valid positions, c / (n + eps) * 2 pi, through the float32 NumPy expressions
+    of position_embedding_sine_host -- so an all-valid gather reproduces it bit for bit.  [n_max + 1, n_max + 1, 128] fp32
+    (entries with c > n are never read)."""
+    k = np.arange(num_pos_features, dtype=np.float32)
+    dim_t = np.power(np.float32(temperature), (2 * np.floor(k / 2) / np.float32(num_pos_features)).astype(np.float32)).astype(np.float32)
+    tab = np.zeros((n_max + 1, n_max + 1, num_pos_features), np.float32)
+    c = np.arange(0, n_max + 1, dtype=np.float32)
+    for n in range(n_max + 1):
+        y = (c / np.float32(n + eps) * np.float32(2 * math.pi)).astype(np.float32)
+        py = (y[:, None] / dim_t[None, :]).astype(np.float32)
+        tab[n, :, 0::2], tab[n, :, 1::2] = np.sin(py[:, 0::2]), np.cos(py[:, 1::2])
+    return tab
+
+
+def downsample_mask_nearest(mask, Hf, Wf):
+    """detr.py:57-63 downsample_masks: TF-legacy nearest neighbour (align_corners = half_pixel_centers = False),
+    src = min(floor(dst * in / out), in - 1) per axis.  mask [B, H, W] bool (NumPy) -> [B, Hf, Wf]."""
+    mask = np.asarray(mask)
+    H, W = mask.shape[1:]
+    sy = np.minimum((np.arange(Hf) * H) // Hf, H - 1)
+    sx = np.minimum((np.arange(Wf) * W) // Wf, W - 1)
+    return mask[:, sy][:, :, sx]
+
+
+def feature_size(H, W):
+    """Feature-map size of an H x W input: stem conv, max-pool, layer2..4 each take ceil(n / 2)."""
+    for _ in range(5):
+        H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return H, W
+
+
 class DetrEngine:
     def __init__(self, device="cuda:0", blocks=RESNET50_BLOCKS, num_enc=6, num_dec=6, num_queries=100,
                  num_classes=92, nb_class=None, seed=0, tf_backbone=False):
@@ -112,6 +145,8 @@ class DetrEngine:
         self._bufs = {}
         self._buf_gen = 0                # bumped whenever buf() replaces (frees) a buffer: recorded graphs of older generations are invalid
         self._pos_cache = {}
+        self._pos_tables = {}
+        self.key_valid = None        # key-validity words of the current masked pass (None: unmasked)
         self._shape = None
         self.bn_scale, self.bn_shift = {}, {}
         self._weights_version, self._built = 0, {}
@@ -457,7 +492,7 @@ class DetrEngine:
             torch.cuda.current_stream().wait_stream(self._mask_stream)
             self._mask_pending = False
 
-    def _self_attn_fwd(self, tag, pfx, qk_in, v_in, B, T, out, site, ln=None):
+    def _self_attn_fwd(self, tag, pfx, qk_in, v_in, B, T, out, site, ln=None, key_valid=None):
         W, bias = self._w(f"{pfx}/in_proj_kernel"), self.P.views[f"{pfx}/in_proj_bias"]
         dp, _ = self._drop
         lse = self.buf(f"{tag}:lse", (B * HEADS, T))
@@ -470,18 +505,19 @@ class DetrEngine:
             O = self.buf(f"{tag}:O16", (B * T, D), torch.bfloat16)
             self._join_dropmasks()
             hip.attention(QKV[:, 0:D], QKV[:, D:2 * D], QKV[:, 2 * D:], O, lse, B, HEADS, T, T, scale=float(HD) ** -0.5, dropout_p=dp,
-                          dropout_site=site, dropout_step=self._seed_dev, dropmask=self._dropmask(site, B, T, T) if dp > 0.0 else None)
+                          dropout_site=site, dropout_step=self._seed_dev, dropmask=self._dropmask(site, B, T, T) if dp > 0.0 else None,
+                          key_valid=key_valid)
         else:
             QKV = self.buf(f"{tag}:QKV", (B * T, 3 * D))
             hip.gemm_group([hip.linear_fwd_call(qk_in, W[0:2 * D], bias[0:2 * D], QKV[:, 0:2 * D]),        # :294-300
                             hip.linear_fwd_call(v_in, W[2 * D:], bias[2 * D:], QKV[:, 2 * D:])])          # :302-304
             O = self.buf(f"{tag}:O", (B * T, D))
             hip.attention(QKV[:, 0:D], QKV[:, D:2 * D], QKV[:, 2 * D:], O, lse, B, HEADS, T, T, scale=float(HD) ** -0.5,
-                          dropout_p=dp, dropout_site=site, dropout_step=self._seed_dev)                    # :307-345
+                          dropout_p=dp, dropout_site=site, dropout_step=self._seed_dev, key_valid=key_valid)     # :307-345
         hip.linear_fwd(O, self._w(f"{pfx}/out_proj_kernel"), self.P.views[f"{pfx}/out_proj_bias"], out, residual=v_in,
                        dropout_p=dp, dropout_seed=site + 1, dropout_step=self._seed_dev, ln=ln)        # :346-347 + :169 (+ the LayerNorm behind it)
 
-    def _self_attn_bwd(self, tag, pfx, d_out, d_res, qk_in, v_in, B, T, d_x, site, acc_qk=None):
+    def _self_attn_bwd(self, tag, pfx, d_out, d_res, qk_in, v_in, B, T, d_x, site, acc_qk=None, key_valid=None):
         """d_out: gradient of the out-projection output (dropout backward already applied), d_res: gradient of the
         block output (residual path).  Writes d_x = gradient w.r.t. v_in, including the q / k branch when qk_in is
         v_in + const (d_x = None: not needed).  acc_qk: buffer that ACCUMULATES the gradient of the q / k input alone
@@ -499,7 +535,7 @@ class DetrEngine:
         hip.attention(QKV[:, 0:D], QKV[:, D:2 * D], QKV[:, 2 * D:], O, self._bufs[f"{tag}:lse"], B, HEADS, T, T,
                       scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=site, dropout_step=self._seed_dev,
                       d_o=dO, dq=dQKV[:, 0:D], dk=dQKV[:, D:2 * D], dv=dQKV[:, 2 * D:], delta=delta,
-                      dropmask=self._dropmask(site, B, T, T) if (a16 and dp > 0.0) else None)
+                      dropmask=self._dropmask(site, B, T, T) if (a16 and dp > 0.0) else None, key_valid=key_valid)
         # weight gradients (bias gradients fused: row sums of dy^T), one grouped launch (bf16 operands: the out-projection's pair has
         # other storage types than the in-projections' and is a launch of its own)
         wg_out = hip.linear_wgrad_call(d_out, O, G[f"{pfx}/out_proj_kernel"], bias_grad=G[f"{pfx}/out_proj_bias"])
@@ -582,16 +618,21 @@ class DetrEngine:
         return self._cross[key]
 
     # ---- forward ----------------------------------------------------------------------------------
-    def forward(self, images, training=False):
-        """See _forward_impl.  GEMM / conv compute mode: self.compute (0 = exact fp32, 1 = bf16 MFMA)."""
+    def forward(self, images, training=False, masks=None):
+        """See _forward_impl.  GEMM / conv compute mode: self.compute (0 = exact fp32, 1 = bf16 MFMA).
+        masks: optional padding mask [B, H, W] (True = padding, detr.py:65-72) as a device uint8 / bool tensor or a host array
+        (validated on the host: an image without a valid feature position raises ValueError).  A device mask is validated on
+        the device: check_mask_status() reads the result where the caller synchronises anyway."""
         hip.COMPUTE_BF16 = self.gemm_mode
         if self.compute == 1 and (self._stale("shadow16") or self.P.views16 is None):
             self._refresh_shadow()
         if self.tf_backbone and self._stale("bias_shift"):
             self._refresh_bias_shift()
+        if masks is not None and not (torch.is_tensor(masks) and masks.is_cuda):
+            masks = self._host_masks(masks, tuple(images.shape[:3]))        # validated before any launch
         self._side_begin(WGRAD_STREAM and images.is_cuda)
         try:
-            return self._forward_impl(images, training)
+            return self._forward_impl(images, training, masks)
         finally:
             try:
                 self._side_join()
@@ -627,7 +668,46 @@ class DetrEngine:
             finally:
                 hip.COMPUTE_BF16 = 0
 
-    def _forward_impl(self, images, training=False):
+    def _prepare_masks(self, masks, B, H, W, Hf, Wf):
+        """Padding mask -> self.key_valid words, per-image pos [B*L, 256] and the status words, one launch
+        (detr_hip_padding_mask_prepare).  Returns pos."""
+        L = Hf * Wf
+        if tuple(masks.shape) != (B, H, W) or masks.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"masks: expected a uint8 / bool tensor of shape {(B, H, W)}, got {masks.dtype} {tuple(masks.shape)}")
+        key = (Hf, Wf)
+        if key not in self._pos_tables:
+            self._pos_tables[key] = (torch.from_numpy(position_embedding_sine_table(Hf)).to(self.device),
+                                     torch.from_numpy(position_embedding_sine_table(Wf)).to(self.device))
+        tab_y, tab_x = self._pos_tables[key]
+        kv = self.buf("mask:key_valid", (B * ((L + 31) // 32),), torch.int32)
+        pos = self.buf("mask:pos", (B * L, D))
+        status = self.buf("mask:status", (B,), torch.int32)
+        hip.padding_mask_prepare(masks, Hf, Wf, tab_y, tab_x, kv, pos, status)
+        self.key_valid = kv
+        return pos
+
+    def _host_masks(self, masks, shape):
+        """A host mask (NumPy / CPU tensor, True = padding): validated on the host, then copied to the device as uint8."""
+        host = np.asarray(masks.cpu() if torch.is_tensor(masks) else masks).astype(bool)
+        if host.shape != shape:
+            raise ValueError(f"masks: expected shape {shape}, got {host.shape}")
+        Hf, Wf = feature_size(shape[1], shape[2])
+        empty = [b for b in range(shape[0]) if downsample_mask_nearest(host[b:b + 1], Hf, Wf).all()]
+        if empty:
+            raise ValueError(f"masks: image(s) {empty} have no valid (unpadded) position on the {Hf} x {Wf} feature map")
+        return torch.from_numpy(host.view(np.uint8)).to(self.device)
+
+    def check_mask_status(self):
+        """Raise ValueError when an image of the last masked pass had no valid feature position (reads the device status
+        words: call it where the step synchronises anyway).  No-op after an unmasked pass."""
+        if self.key_valid is None:
+            return
+        st = self._bufs["mask:status"].cpu()
+        bad = [int(b) for b in torch.nonzero(st).flatten()]
+        if bad:
+            raise ValueError(f"masks: image(s) {bad} have no valid (unpadded) position on the feature map")
+
+    def _forward_impl(self, images, training=False, masks=None):
         """images: CUDA fp32 NHWC [B,H,W,3] (already normalised, processing.py:12-16).
         Returns (logits [Lv,B,Q,C], boxes [Lv,B,Q,4]) views of engine buffers."""
         assert images.is_cuda and images.dtype == torch.float32 and images.dim() == 4 and images.shape[3] == 3
@@ -721,9 +801,15 @@ class DetrEngine:
         src = self.buf("enc:src0", (B * L, D))
         hip.gemm(B * L, D, 2048, feat, 2048, 1, self._w("input_proj/kernel"), D, 0, src, D, bias=V["input_proj/bias"])
         key = (Hf, Wf)
-        if key not in self._pos_cache:
-            self._pos_cache[key] = torch.from_numpy(position_embedding_sine_host(Hf, Wf)).to(self.device)
-        pos = self._pos_cache[key]
+        if masks is None:
+            self.key_valid = None
+            if key not in self._pos_cache:
+                self._pos_cache[key] = torch.from_numpy(position_embedding_sine_host(Hf, Wf)).to(self.device)
+            pos = self._pos_cache[key]
+        else:
+            # padded batch: per-image encoding [B*L, 256] (add_bcast / the LayerNorm's add[r % rows] take it as they take the
+            # [L, 256] constant) and the key padding mask of the encoder self-attention and every decoder cross-attention
+            pos = self._prepare_masks(masks, B, H, W, Hf, Wf)
         self.pos = pos
         # ---------------- encoder (transformer.py:157-179) ----------------
         x = src
@@ -735,7 +821,7 @@ class DetrEngine:
             x1 = self.buf(f"{tag}:x1", (B * L, D))
             x1h = self.buf(f"{tag}:x1h", (B * L, D), torch.bfloat16) if self.ffn16 else None
             ln1 = self._ln_spec(B * L, f"{pfx}/norm1", x1, f"{tag}:ln1", y16=x1h)
-            self._self_attn_fwd(f"{tag}:sa", f"{pfx}/self_attn", qk, x, B, L, a, site=16 * i, ln=ln1)
+            self._self_attn_fwd(f"{tag}:sa", f"{pfx}/self_attn", qk, x, B, L, a, site=16 * i, ln=ln1, key_valid=self.key_valid)
             if ln1 is None:
                 self._ln_fwd(a, f"{pfx}/norm1", x1, f"{tag}:ln1", y16=x1h)
             f = self.buf(f"{tag}:f", (B * L, D))
@@ -793,7 +879,7 @@ class DetrEngine:
             lse = self.buf(f"{tag}:ca:lse", (B * HEADS, Q))
             hip.attention(Qc, KV[:, i * D:(i + 1) * D], KV[:, (nd + i) * D:(nd + i + 1) * D], Oc, lse, B, HEADS, Q, L,
                           scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=ds + 2, dropout_step=self._seed_dev,
-                          dropmask=self._dropmask(ds + 2, B, Q, L) if (a16 and dp > 0.0) else None)
+                          dropmask=self._dropmask(ds + 2, B, Q, L) if (a16 and dp > 0.0) else None, key_valid=self.key_valid)
             a2 = self.buf(f"{tag}:a2", (B * Q, D))
             t2 = self.buf(f"{tag}:t2", (B * Q, D))
             t2h = self.buf(f"{tag}:t2h", (B * Q, D), torch.bfloat16) if self.ffn16 else None
@@ -931,7 +1017,7 @@ class DetrEngine:
             hip.attention(Qc, KV[:, i * D:(i + 1) * D], KV[:, (nd + i) * D:(nd + i + 1) * D], Oc, self._bufs[f"{tag}:ca:lse"],
                           B, HEADS, Q, L, scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=ds + 2, dropout_step=self._seed_dev,
                           d_o=dO, dq=dQc, dk=dKV[:, i * D:(i + 1) * D], dv=dKV[:, (nd + i) * D:(nd + i + 1) * D], delta=delta,
-                          dropmask=self._dropmask(ds + 2, B, Q, L) if (a16 and dp > 0.0) else None)
+                          dropmask=self._dropmask(ds + 2, B, Q, L) if (a16 and dp > 0.0) else None, key_valid=self.key_valid)
             self._side(lambda d_out=d_out, Oc=Oc, dQc=dQc, q2=q2, cp=cp: hip.gemm_group([
                 hip.linear_wgrad_call(d_out, Oc, G[f"{cp}/out_proj_kernel"], bias_grad=G[f"{cp}/out_proj_bias"]),
                 hip.linear_wgrad_call(dQc, q2, G[f"{cp}/in_proj_kernel"][0:D], bias_grad=G[f"{cp}/in_proj_bias"][0:D])]))
@@ -971,7 +1057,7 @@ class DetrEngine:
             d_a = self.buf(f"scratch:e_d_a{self._sx(tag)}", (B * L, D))
             d_out = self._ln_bwd(d_x1, a, f"{pfx}/norm1", d_a, f"{tag}:ln1", drop_site=16 * i + 1)
             d_xn = self.buf(f"scratch:e_d_x{i & 1}", (B * L, D))
-            self._self_attn_bwd(f"{tag}:sa", f"{pfx}/self_attn", d_out, d_a, qk, x_in, B, L, d_xn, site=16 * i)
+            self._self_attn_bwd(f"{tag}:sa", f"{pfx}/self_attn", d_out, d_a, qk, x_in, B, L, d_xn, site=16 * i, key_valid=self.key_valid)
             d_x = d_xn
         if on_bucket:
             on_bucket(0)

@@ -14,6 +14,8 @@ def eval_model(model, config, class_names, valid_dt, max_batches=None, print_res
     for it, (images, target_bbox, target_class) in enumerate(valid_dt):
         m_outputs = model(images, training=False)
         dets = get_model_inference_batched(m_outputs, config.background_class, bbox_format="yxyx")
+        if getattr(model, "engine", None) is not None:
+            model.engine.check_mask_status()      # (padded batches with a device mask; the detections are read on the host anyway)
         tb = torch.as_tensor(np.asarray(target_bbox) if not torch.is_tensor(target_bbox) else target_bbox).float().cpu()
         tc = torch.as_tensor(np.asarray(target_class) if not torch.is_tensor(target_class) else target_class).cpu()
         for b, (p_bbox, p_labels, p_scores) in enumerate(dets):

@@ -118,6 +118,9 @@ def get_losses(m_outputs, t_bbox, t_class, config):
         # (hungarian_matching.py:29); the device matcher records a status per problem instead of stopping the step
         if bool((sl.matcher.status != 0).any()):
             raise ValueError("cost matrix is infeasible or contains invalid numeric entries")
+        model = getattr(m_outputs, "model", None)
+        if model is not None:
+            model.engine.check_mask_status()    # a padded batch's device mask: an image without a valid feature position
     log = log_from_losses(losses.clone())
     total_loss = total.clone()[0]
     if hasattr(m_outputs, "set_loss"):

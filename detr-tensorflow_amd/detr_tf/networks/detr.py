@@ -123,43 +123,62 @@ class DetrModel:
         self.engine.P.save(self._npz(path))
 
     # ---- forward ----------------------------------------------------------------------------
-    def _eval_forward(self, images):
+    def _eval_forward(self, images, masks=None):
         """Eval-mode forward.  The launch sequence of a fixed input shape is static, so the second call with the same shape
         (and the same weights version) records it as a hipGraph and later calls replay it: a single 480x640 image is ~300
         launches whose host cost (ctypes, ~10 us each) exceeds their GPU time.  DETR_HIP_GRAPH=0 / model.eval_graph = False:
         always eager.  Outputs are views of the engine's buffers either way (the caller clones)."""
         eng = self.engine
+        if masks is not None and not (torch.is_tensor(masks) and masks.is_cuda):
+            masks = eng._host_masks(masks, tuple(images.shape[:3]))      # validated on the host, then a device input like any other
         if not (self.eval_graph and os.environ.get("DETR_HIP_GRAPH", "1") != "0" and images.is_cuda):
-            return eng.forward(images, training=False)
-        key = (tuple(images.shape), eng._weights_version, eng.compute)
+            return eng.forward(images, training=False, masks=masks)
+        key = (tuple(images.shape), eng._weights_version, eng.compute, masks is not None)
         g = self._eval_graph
         # a graph addresses the engine's buffers as they were at capture: any later re-allocation (a forward of another
         # shape in between) makes it unusable -- engine.buf_generation tells
         if g is not None and g["key"] == key and g["gen"] == eng.buf_generation:
             g["static"].copy_(images)
+            if masks is not None:
+                g["static_mask"].copy_(masks)
             g["graph"].replay()
             return g["out"]
         if g is not None and g["gen"] != eng.buf_generation:
             self._eval_graph = g = None
         if self._eval_seen != (key, eng.buf_generation):
             # first sighting of this shape with these buffers: eager (allocates the buffers, refreshes derived weight copies)
-            out = eng.forward(images, training=False)
-            self._eval_seen = ((tuple(images.shape), eng._weights_version, eng.compute), eng.buf_generation)
+            out = eng.forward(images, training=False, masks=masks)
+            self._eval_seen = (key, eng.buf_generation)
             return out
         static = g["static"] if g is not None and g["static"].shape == images.shape else torch.empty_like(images)
         static.copy_(images)
+        static_mask = None
+        if masks is not None:          # the mask is a static input like the images: copied in before every replay
+            static_mask = torch.empty_like(masks)
+            static_mask.copy_(masks)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):       # (see training._Segments.begin)
-            out = eng.forward(static, training=False)
-        self._eval_graph = dict(key=key, static=static, graph=graph, out=out, gen=eng.buf_generation)
+            out = eng.forward(static, training=False, masks=static_mask)
+        self._eval_graph = dict(key=key, static=static, static_mask=static_mask, graph=graph, out=out, gen=eng.buf_generation)
         graph.replay()
         return out
 
-    def __call__(self, images, training=False):
+    def __call__(self, images, training=False, masks=None):
+        """images: [B, H, W, 3] float32, or the reference's `(images, masks)` pair (detr.py:65-72); masks: [B, H, W] bool, True =
+        padding (a padded mixed-size batch).  Host masks are validated here (ValueError for an image without a
+        valid feature position); device masks on the device (engine.check_mask_status)."""
+        if isinstance(images, (tuple, list)):
+            if masks is not None or len(images) != 2:
+                raise TypeError("model((images, masks)): pass the mask once, either in the tuple or as masks=")
+            images, masks = images
         if isinstance(images, np.ndarray):
             images = torch.from_numpy(images)
         images = images.to(device=self.device, dtype=torch.float32)
-        logits, boxes = self.engine.forward(images, training=True) if training else self._eval_forward(images)
+        if masks is not None and torch.is_tensor(masks) and masks.is_cuda:
+            if masks.dtype not in (torch.bool, torch.uint8):
+                masks = masks != 0
+            masks = masks.contiguous()
+        logits, boxes = self.engine.forward(images, training=True, masks=masks) if training else self._eval_forward(images, masks)
         if self.headless:
             hs = self.engine._bufs["dec:hs"].view(self.engine.num_dec, images.shape[0], self.engine.Q, 256)
             return hs if training else hs.clone()

@@ -9,9 +9,11 @@ sizes -- lives in device memory that is refreshed before each replay.
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import _hip as hip
+from .engine import downsample_mask_nearest, feature_size
 from .loss import hungarian_matching as _matching
 from .loss.loss import get_losses, log_from_losses
 from .optimizers import GROUPS, aggregate_grad_and_apply, gather_gradient
@@ -43,10 +45,21 @@ def run_train_step(model, images, t_bbox, t_class, optimizers, config):
 
 
 def run_val_step(model, images, t_bbox, t_class, config):
-    """training.py:28-32."""
+    """training.py:28-32.  images: a tensor or the (images, masks) pair of a padded batch."""
     m_outputs = model(images, training=False)
     total_loss, log = get_losses(m_outputs, t_bbox, t_class, config)
+    if getattr(model, "engine", None) is not None:
+        model.engine.check_mask_status()      # (a device mask: after the loss, whose log the caller reads anyway)
     return m_outputs, total_loss, log
+
+
+def split_images(images):
+    """images or the reference's (images, masks) pair -> (images, masks or None)."""
+    if isinstance(images, (tuple, list)):
+        if len(images) != 2:
+            raise TypeError("expected images or an (images, masks) pair")
+        return images[0], images[1]
+    return images, None
 
 
 def train_step(model, images, t_bbox, t_class, optimizers, config, epoch_step):
@@ -139,17 +152,21 @@ class GraphedTrainStep:
 
     def _signature(self, images, t_bbox, t_class):
         c = self.config
-        return (tuple(images.shape), tuple(t_bbox.shape), bool(c.train_backbone), bool(c.train_transformers),
+        images, masks = split_images(images)
+        return (tuple(images.shape), masks is not None, tuple(t_bbox.shape), bool(c.train_backbone), bool(c.train_transformers),
                 bool(c.train_nlayers), int(c.background_class), self.model.engine.compute, float(self.model.engine.dropout_p),
                 bool(getattr(c, "check_matching", False)))
 
     def _capture(self, images, t_bbox, t_class):
         model, opts, cfg = self.model, self.optimizers, self.config
         eng, dev = model.engine, model.device
-        st_img = torch.empty(tuple(images.shape), dtype=torch.float32, device=dev)
+        img, masks = split_images(images)
+        st_img = torch.empty(tuple(img.shape), dtype=torch.float32, device=dev)
         st_tb = torch.empty(tuple(t_bbox.shape), dtype=torch.float32, device=dev)
         st_tc = torch.empty((t_bbox.shape[0], t_bbox.shape[1]), dtype=torch.int64, device=dev)
-        self.static = (st_img, st_tb, st_tc)
+        # padded batch: the mask is a static input like the images (the recorded mask-preparation launch re-reads it)
+        st_mask = torch.empty(tuple(masks.shape), dtype=torch.uint8, device=dev) if masks is not None else None
+        self.static = (st_img, st_tb, st_tc, st_mask)
         self._load_inputs(images, t_bbox, t_class)
         dp = model.dp
         seg = _Segments()
@@ -166,7 +183,8 @@ class GraphedTrainStep:
                     dp.reduce_sums = lambda sums, f=prev_hooks[1]: seg.cut(lambda: f(sums))
                     dp.finish = lambda: None
                 seg.begin()
-                m_outputs, total_loss, log, gradient_steps = run_train_step(model, st_img, st_tb, st_tc, opts, cfg)
+                m_outputs, total_loss, log, gradient_steps = run_train_step(model, st_img if st_mask is None else (st_img, st_mask),
+                                                                            st_tb, st_tc, opts, cfg)
                 seg.end()
                 if prev_hooks is not None:
                     dp.on_bucket, dp.reduce_sums, dp.finish = prev_hooks
@@ -190,7 +208,19 @@ class GraphedTrainStep:
         self._gen = eng.buf_generation
 
     def _load_inputs(self, images, t_bbox, t_class):
-        st_img, st_tb, st_tc = self.static
+        st_img, st_tb, st_tc, st_mask = self.static
+        images, masks = split_images(images)
+        if st_mask is not None:
+            if not (torch.is_tensor(masks) and masks.is_cuda):
+                # host masks are validated on the host, as in an eager step
+                host = np.asarray(masks.cpu() if torch.is_tensor(masks) else masks).astype(bool)
+                Hf, Wf = feature_size(host.shape[1], host.shape[2])
+                empty = [b for b in range(host.shape[0]) if downsample_mask_nearest(host[b:b + 1], Hf, Wf).all()]
+                if empty:
+                    raise ValueError(f"masks: image(s) {empty} have no valid (unpadded) position on the {Hf} x {Wf} feature map")
+                masks = torch.from_numpy(host.view(np.uint8))
+            if not (torch.is_tensor(masks) and masks.data_ptr() == st_mask.data_ptr()):
+                st_mask.copy_(torch.as_tensor(masks).to(torch.uint8), non_blocking=True)
         if not (torch.is_tensor(images) and images.data_ptr() == st_img.data_ptr()):
             st_img.copy_(torch.as_tensor(images), non_blocking=True)
         if not (torch.is_tensor(t_bbox) and t_bbox.data_ptr() == st_tb.data_ptr()):

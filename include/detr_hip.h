@@ -400,6 +400,26 @@ int64_t detr_hip_attention_dropmask_words(int32_t B, int32_t H, int32_t T, int32
 int detr_hip_attention_dropmask(const detr_attn_desc *d, void *stream);
 /* the same for n sites of one step in ONE launch (they must share B*H, dropout_p and dropout_step; a DETR step has 18 sites) */
 int detr_hip_attention_dropmask_many(const detr_attn_desc *descs, int32_t n, void *stream);
+/* Key padding mask (detr_tf/networks/transformer.py:322-337 -- the reference's commented-out key_padding_mask branch -- as if
+ * enabled, fed by source_key_padding_mask / memory_key_padding_mask, :43-50): the same attention with the scores of invalid keys
+ * set to -inf before the softmax.  key_valid: detr_hip_attention_keymask_words(B, S) uint32 words, word (b * ceil(S/32) + t) bit j
+ * = key 32 t + j of batch entry b is valid; bits past S must be 0.  Queries are never masked.  Only the exact-fp32 kernels
+ * (io_dtype = 0, compute = 0) and the all-bf16 kernels (io_dtype = 1) have a masked form; io_dtype = 0 with compute = 1 is
+ * rejected.  Every batch entry needs at least one valid key (otherwise its rows are NaN: see detr_hip_padding_mask_prepare's
+ * status).  Masked keys get exact zeros in dk / dv; dropout keep bits are those of the unmasked call. */
+int64_t detr_hip_attention_keymask_words(int32_t B, int32_t S);
+int detr_hip_attention_fwd_masked(const detr_attn_desc *d, const uint32_t *key_valid, void *stream);
+int detr_hip_attention_bwd_masked(const detr_attn_desc *d, const uint32_t *key_valid, void *stream);
+/* Padding mask -> transformer inputs (detr_tf/networks/detr.py:57-72 downsample_masks, position_embeddings.py:23-50 with
+ * normalize=True), one launch: mask [B, H, W] uint8 / bool (nonzero = padding) is brought to the Hf x Wf feature map by TF-legacy
+ * nearest neighbour (src = min(floor(dst * in / out), in - 1) per axis), and per image
+ *   key_valid [B][ceil(Hf*Wf/32)]  the words of detr_hip_attention_*_masked (bit = feature position is valid),
+ *   pos [B * Hf * Wf, 256]         [pos_y | pos_x] gathered from tab_y [Hf+1][Hf+1][128] / tab_x [Wf+1][Wf+1][128]: entry [n][c] is
+ *                                  the encoding of cumulative count c of an axis with n valid positions (c / (n + 1e-6) * 2 pi),
+ *   status [B]                     1 when the image has no valid feature position, else 0.
+ * Hf, Wf <= 128 and Hf * Wf <= 8192.  tab_y, tab_x and pos 16-byte aligned. */
+int detr_hip_padding_mask_prepare(const uint8_t *mask, int32_t B, int32_t H, int32_t W, int32_t Hf, int32_t Wf, const float *tab_y,
+                                  const float *tab_x, uint32_t *key_valid, float *pos, int32_t *status, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Hungarian set loss (detr_tf/loss/hungarian_matching.py:163-203, detr_tf/loss/loss.py:22-179,
@@ -460,6 +480,12 @@ typedef struct {
     int32_t interpolation;                           /* 0 nearest, 1 linear, 2 cubic (imgaug's Resize default) */
 } detr_input_desc;
 int detr_hip_input_stage(const detr_input_desc *d, void *stream);
+/* Padded mixed-size batch (the reference's (images, masks) input, detr_tf/networks/detr.py:65-72): image b, [hw[2b], hw[2b+1], 3]
+ * uint8 at src + offsets[b] (device arrays), is normalised through `lut` / `perm` (host array of 3) exactly as detr_hip_input_stage
+ * does and written to the top-left of the float32 canvas dst [B, H, W, 3]; the rest of the canvas is 0.0 and mask [B, H, W] (uint8)
+ * is 1 there (padding), 0 on valid pixels.  No resize.  Images larger than the canvas are cropped to it. */
+int detr_hip_input_stage_padded(const uint8_t *src, const int64_t *offsets, const int32_t *hw, int32_t B, int32_t H, int32_t W,
+                                const float *lut, const int32_t *perm, float *dst, uint8_t *mask, void *stream);
 int detr_hip_pad_labels(const float *boxes, const int64_t *classes, const int32_t *offsets, int32_t B, int32_t R,
                         float *t_bbox, int64_t *t_class, void *stream);
 
