@@ -41,6 +41,16 @@ Where the kernels round (attention_dma.hip), and what each rounding costs:
 NP = 8 is the largest number of runs per workgroup (the bounds hold for every DETR_HIP_ATTN_SPLIT).  Nothing here is fitted to a
 measurement: every constant is a count of roundings.
 
+Key padding mask (key_valid: bool [B, S], True = valid key; the MASK instantiations of the three kernels).  A masked key is exactly
+absent: its score is set to -inf before anything is formed from it, so P = 0 there and m, l and lse run over the valid keys only.
+The reference therefore zeroes the K and V rows of masked keys before it forms anything: every magnitude a bound is built from
+(R, sum_d |q_d k_d|, |V|, Hd = |dO| |V|^T) then runs over valid keys alone, garbage in a masked row cannot loosen a bound, and the
+bounds are bit-identical for any content of the masked rows.  The derivation is unchanged: a masked key adds no term to any sum
+above (its P, W and dS are exact zeros, and a tile without a valid key is skipped whole), so each rounding count is at most the
+unmasked one, and S, ntiles and NP stay valid upper bounds -- they are kept, not refitted.  The kernels store exact zeros in dK and
+dV at masked keys, so their bound there is 0: ratio() accepts only an exact 0.  Every image needs at least one valid key (the
+product rejects such masks; asserted here).
+
 simulate() is one admissible execution of the documented roundings (bf16 P before PV, l from the unrounded p, runs merged with their
 own maxima, bf16 dS / outputs, delta from the bf16 O) with optional injected faults; tests/test_attn_bounds_cpu.py uses it to show
 that the bounds accept a correct kernel and reject subtly wrong ones."""
@@ -95,8 +105,25 @@ def _dsc(p):
     return 1.0 / (1.0 - p) if p > 0.0 else 1.0
 
 
-def _problem_fwd(q, k, v, keep, dsc):
+def _valid(key_valid, B, S):
+    """bool [B, S] (every image with a valid key) or None."""
+    if key_valid is None:
+        return None
+    kv = torch.as_tensor(key_valid).bool()
+    assert tuple(kv.shape) == (B, S), f"key_valid must be [B, S] = [{B}, {S}], got {tuple(kv.shape)}"
+    assert bool(kv.any(dim=1).all()), "every image needs at least one valid key"
+    return kv
+
+
+def _absent(x, kv):
+    """x [B, S, D] with the rows of masked keys zeroed: nothing of their content reaches a value or a bound."""
+    return x if kv is None else x * kv.unsqueeze(2).to(x.dtype)
+
+
+def _problem_fwd(q, k, v, keep, dsc, valid=None):
     s = q @ k.T
+    if valid is not None:
+        s = s.masked_fill(~valid.unsqueeze(0), -math.inf)
     m = s.max(dim=1, keepdim=True).values
     e = torch.exp2(s - m)
     l = e.sum(dim=1, keepdim=True)
@@ -107,23 +134,26 @@ def _problem_fwd(q, k, v, keep, dsc):
 
 
 def _exp_err(q, k, s, lse):
-    R = s.abs().max(dim=1, keepdim=True).values + LOG2E * lse.abs().unsqueeze(1) + 2.0
+    """(k: masked rows already zero; s: -inf at masked keys, which are left out of R)"""
+    R = torch.where(torch.isfinite(s), s.abs(), torch.zeros_like(s)).max(dim=1, keepdim=True).values + LOG2E * lse.abs().unsqueeze(1) + 2.0
     Es = 34.0 * F * (q.abs() @ k.abs().T + R)
     return R, LN2 * Es + F
 
 
-def forward(qs, k, v, H, keep=None, p=0.0):
-    """Exact O [B, T, D], lse [B*H, T] and their bounds.  keep: bool [B*H, T, S] or None."""
+def forward(qs, k, v, H, keep=None, p=0.0, key_valid=None):
+    """Exact O [B, T, D], lse [B*H, T] and their bounds.  keep: bool [B*H, T, S] or None; key_valid: bool [B, S] or None."""
     B, T, _ = qs.shape
     S = k.shape[1]
     dsc = _dsc(p)
+    kv = _valid(key_valid, B, S)
+    k, v = _absent(k, kv), _absent(v, kv)
     ntiles = -(-S // 32)
     qh, kh, vh = heads(qs, H), heads(k, H), heads(v, H)
     O, BO, L, BL = (torch.empty(B * H, T, HD, dtype=torch.float64), torch.empty(B * H, T, HD, dtype=torch.float64),
                     torch.empty(B * H, T, dtype=torch.float64), torch.empty(B * H, T, dtype=torch.float64))
     for bh in range(B * H):
         kp = keep[bh].double() if keep is not None else None
-        s, P, W, lse = _problem_fwd(qh[bh], kh[bh], vh[bh], kp, dsc)
+        s, P, W, lse = _problem_fwd(qh[bh], kh[bh], vh[bh], kp, dsc, None if kv is None else kv[bh // H])
         R, e = _exp_err(qh[bh], kh[bh], s, lse)
         o = W @ vh[bh]
         Pv = W @ vh[bh].abs()
@@ -135,12 +165,14 @@ def forward(qs, k, v, H, keep=None, p=0.0):
     return dict(o=unheads(O, B, H), lse=L, bound_o=unheads(BO, B, H), bound_lse=BL)
 
 
-def backward(qs, k, v, do, o_kernel, H, keep=None, p=0.0, scale=HD ** -0.5):
+def backward(qs, k, v, do, o_kernel, H, keep=None, p=0.0, scale=HD ** -0.5, key_valid=None):
     """Exact dQ (w.r.t. the unscaled q = qs / (scale log2 e)) [B, T, D], dK, dV [B, S, D] and their bounds.  delta is formed from
-    o_kernel, the bf16 O the forward stored."""
+    o_kernel, the bf16 O the forward stored.  key_valid: bool [B, S] or None (masked keys: dK = dV = 0 with bound 0)."""
     B, T, _ = qs.shape
     S = k.shape[1]
     dsc = _dsc(p)
+    kv = _valid(key_valid, B, S)
+    k, v = _absent(k, kv), _absent(v, kv)
     ntiles = -(-S // 32)
     qh, kh, vh, dh, oh = heads(qs, H), heads(k, H), heads(v, H), heads(do, H), heads(o_kernel, H)
     z = lambda n: torch.empty(B * H, n, HD, dtype=torch.float64)
@@ -148,7 +180,7 @@ def backward(qs, k, v, do, o_kernel, H, keep=None, p=0.0, scale=HD ** -0.5):
     for bh in range(B * H):
         kp = keep[bh].double() if keep is not None else None
         q, kk, vv, dO = qh[bh], kh[bh], vh[bh], dh[bh]
-        s, P, W, lse = _problem_fwd(q, kk, vv, kp, dsc)
+        s, P, W, lse = _problem_fwd(q, kk, vv, kp, dsc, None if kv is None else kv[bh // H])
         R, e = _exp_err(q, kk, s, lse)
         den = (P * e).sum(dim=1, keepdim=True) + (5 + 2 * ntiles + 2 * NP) * F
         blse = (1 + 2 * U) * (den + F * (3 * R + lse.abs().unsqueeze(1)) + 8 * F)
@@ -174,30 +206,119 @@ def backward(qs, k, v, do, o_kernel, H, keep=None, p=0.0, scale=HD ** -0.5):
         BW = U * W + (1 + U) * eP * W
         dV[bh] = dv
         BdV[bh] = (1 + 2 * U) * (U * dv.abs() + BW.T @ dO.abs() + (T + NP) * F * (W.T @ dO.abs())) + TINY
+        if kv is not None:                   # masked keys: exact zeros (dS and W vanish there), nothing else is accepted
+            BdK[bh][~kv[bh // H]] = 0.0
+            BdV[bh][~kv[bh // H]] = 0.0
     return dict(dq=unheads(dQ, B, H), dk=unheads(dK, B, H), dv=unheads(dV, B, H),
                 bound_dq=unheads(BdQ, B, H), bound_dk=unheads(BdK, B, H), bound_dv=unheads(BdV, B, H))
 
 
 def ratio(got, ref, bound):
-    """max |got - ref| / bound (a NaN anywhere counts as infinitely wrong)."""
-    err = (got.detach().cpu().double() - ref).abs() / bound
-    if bool(torch.isnan(err).any()):
+    """max |got - ref| / bound (a NaN anywhere counts as infinitely wrong; where the bound is 0 -- dK / dV of a masked key -- only an
+    exact match passes: 0 / 0 counts as 0, anything else as infinitely wrong)."""
+    d = (got.detach().cpu().double() - ref).abs()
+    if bool(torch.isnan(d).any()):
         return math.inf
+    zero = bound == 0
+    if bool((d[zero] != 0).any()):
+        return math.inf
+    err = d / torch.where(zero, torch.ones_like(bound), bound)
     return float(err.max())
 
 
-def simulate(qs, k, v, do, H, keep=None, p=0.0, parts=4, scale=HD ** -0.5, fault=None):
+A2_SUM_LIMIT = 4096.0     # attention_dma.hip: a 16-key lane sum above this moves the forward's lazy reference
+M_EMPTY = -1.0e30         # attention_dma.hip A2_M_EMPTY: the reference a run without a valid key merges with
+
+
+def _lane_half(j):
+    """Lane half of the bf16 forward that holds key j of its tile: register r of half hi holds key 4 hi + (r & 3) + 8 (r >> 2)."""
+    return (j % 32 // 4) % 2
+
+
+def _faulty_valid(val, kind, fault, S):
+    """The validity a faulty masked kernel would apply in the forward and the dQ kernel (see simulate())."""
+    val = val.clone()
+    ntiles = -(-S // 32)
+    bits = torch.zeros(ntiles * 32, dtype=torch.bool)
+    bits[:S] = val
+    words = bits.view(ntiles, 32)
+    if kind == "leak_key":
+        j = fault[2]
+        assert not bool(val[j]) and bool(words[j // 32].any()), "leak_key: key j must be a masked key in a partial word"
+        val[j] = True
+    elif kind in ("mask_shift", "mask_half", "word_from"):
+        t = fault[2]
+        w = words[t].clone()
+        if kind == "mask_shift":                 # key i of the tile takes the bit of key i - 1 (key 0: key 31's)
+            nw = torch.roll(w, 1)
+        elif kind == "mask_half":                # the lane half 1 keys (4-7, 12-15, ...) take the bits of the keys 4 lower
+            i = torch.arange(32)
+            nw = torch.where(_lane_half(i) == 1, w[(i - 4) % 32], w)
+        else:
+            nw = words[fault[3]].clone()
+        assert not torch.equal(nw, w), f"{kind}: the fault leaves tile {t} unchanged"
+        words[t] = nw
+        val = words.reshape(-1)[:S].clone()
+    return val
+
+
+def _sim_fwd_masked(q, kk, vv, val, kdx, parts, T, S):
+    """The masked forward of one problem: fully masked tiles skipped, each run's reference the maximum of its first tile with a valid
+    key (moved up when a 32-key sum leaves the safe range, as the kernel does), runs without one merged as (M_EMPTY, 0, 0)."""
+    s = (q @ kk.T).float().double()
+    o = torch.zeros(T, HD, dtype=torch.float64)
+    l = torch.zeros(T, 1, dtype=torch.float64)
+    mn = torch.full((T, 1), -math.inf, dtype=torch.float64)
+    for r, (j0, j1) in enumerate(runs(S, parts)):
+        orun, lrun, m = torch.zeros(T, HD, dtype=torch.float64), torch.zeros(T, 1, dtype=torch.float64), None
+        for lo in range(j0, j1, 32):
+            hi_ = min(j1, lo + 32)
+            vt = val[lo:hi_]
+            if not bool(vt.any()):
+                continue                                                  # no valid key: skipped
+            st = s[:, lo:hi_].masked_fill(~vt.unsqueeze(0), -math.inf)
+            if m is None:
+                m = st.max(dim=1, keepdim=True).values                    # `fresh`: the first tile with a valid key
+            e = torch.exp2(st - m).float().double()
+            big = e.sum(dim=1, keepdim=True) > A2_SUM_LIMIT
+            if bool(big.any()):
+                d = torch.where(big, (st.max(dim=1, keepdim=True).values - m).clamp(min=0.0), torch.zeros_like(m))
+                c = torch.exp2(-d)
+                orun, lrun, m = orun * c, lrun * c, m + d
+                e = torch.exp2(st - m).float().double()
+            pb = bf16(e) * kdx[:, lo:hi_]
+            orun = orun + pb @ vv[lo:hi_]
+            lrun = lrun + e.sum(dim=1, keepdim=True)
+        if m is None:
+            m = torch.full((T, 1), M_EMPTY, dtype=torch.float64)
+        new = torch.maximum(mn, m)
+        ca, cb = torch.exp2(mn - new), torch.exp2(m - new)
+        o = o * ca + orun * cb
+        l = l * ca + lrun * cb
+        mn = new
+    return o, l, mn
+
+
+def simulate(qs, k, v, do, H, keep=None, p=0.0, parts=4, scale=HD ** -0.5, fault=None, key_valid=None):
     """One execution of the documented roundings (see the module docstring), optionally with a fault:
         ("drop_tile", bh, t)        key tile t of problem bh left out of the softmax
         ("pad_from_next", bh)       the padding keys of the ragged last tile of problem bh taken from the next batch element
         ("chain_scale", bh, x0)     the P of queries x0 .. x0 + 31 of problem bh scaled by 1 + 2^-6 before the PV product
         ("delta", bh)               delta of problem bh off by 1 %
         ("merge", bh, r, w)         run r of problem bh weighted by w in the merge
+    With key_valid (bool [B, S]) it follows the masked kernels instead (_sim_fwd_masked; the dQ kernel selects dS = 0 at masked keys,
+    the dK / dV kernel stores exact zeros there), and these faults apply to the validity the forward and the dQ kernel see:
+        ("leak_key", bh, j)         masked key j (in a partial word) treated as valid
+        ("mask_shift", bh, t)       tile t's word applied one key off (key i takes the bit of key i - 1)
+        ("mask_half", bh, t)        tile t's lane half 1 keys take the bits of lane half 0 (the `>> (4 * hi)` dropped)
+        ("word_from", bh, t, u)     tile t uses the validity word of tile u
+        ("masked_dkv", bh)          masked keys get the dK / dV a valid key would (no zeroing at the store)
     Returns o, lse (forward) and dq, dk, dv (backward, delta from the simulated bf16 O)."""
     B, T, _ = qs.shape
     S = k.shape[1]
     dsc = _dsc(p)
     kind = fault[0] if fault else None
+    kvm = _valid(key_valid, B, S)
     qh, kh, vh, dh = heads(qs, H), heads(k, H), heads(v, H), heads(do, H)
     O, L = torch.empty(B * H, T, HD, dtype=torch.float64), torch.empty(B * H, T, dtype=torch.float64)
     dQ, dK, dV = torch.empty(B * H, T, HD, dtype=torch.float64), torch.empty(B * H, S, HD, dtype=torch.float64), \
@@ -206,6 +327,23 @@ def simulate(qs, k, v, do, H, keep=None, p=0.0, parts=4, scale=HD ** -0.5, fault
         hit = fault is not None and fault[1] == bh
         q, kk, vv = qh[bh], kh[bh], vh[bh]
         kd = keep[bh].double() * dsc if keep is not None else torch.ones(T, S, dtype=torch.float64)
+        if kvm is not None:
+            val = kvm[bh // H]
+            vf = _faulty_valid(val, kind, fault, S) if hit else val
+            o, l, mn = _sim_fwd_masked(q, kk, vv, vf, kd, parts, T, S)
+            O[bh] = bf16(o / l)
+            L[bh] = (mn.squeeze(1) * LN2 + torch.log(l.squeeze(1))).float().double()
+            s = (q @ kk.T).float().double()
+            P = torch.exp2(s - LOG2E * L[bh].unsqueeze(1)).float().double()      # (the dK / dV kernel: every key)
+            delta = (dh[bh] * O[bh]).sum(dim=1, keepdim=True).float().double()
+            dS = bf16(P * (kd * (dh[bh] @ vv.T) - delta))
+            dQ[bh] = bf16(scale * (dS.masked_fill(~vf.unsqueeze(0), 0.0) @ kk))
+            dK[bh] = bf16(LN2 * (dS.T @ q))
+            dV[bh] = bf16(bf16(P * kd).T @ dh[bh])
+            if not (hit and kind == "masked_dkv"):
+                dK[bh][~val] = 0.0
+                dV[bh][~val] = 0.0
+            continue
         kx, vx, kdx = kk, vv, kd
         if hit and kind == "pad_from_next":
             npad = -S % 32

@@ -4,10 +4,15 @@ detr_tf/networks/transformer.py:285-356) through the C ABI, against an fp64 torc
 bit for bit.  Operands are rounded to bf16 on the host first, so the only differences left are the kernels' own roundings
 (P, dS, O, dQ, dK, dV in bf16; fp32 accumulation): tolerances are stated per check."""
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import attn_cases as AC          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -194,158 +199,11 @@ def test_attention_bf16_io_rejects_bad_descriptors(hip):
 # ------------------------------------------------------------------------------------------------
 # per-element bounds (oracle/attn_bounds.py) on scores built to drive the lazy reference, the recompute and the merge
 # ------------------------------------------------------------------------------------------------
-SITE, STEP = 77, 0xBEEF1234
 SPLITS = (0, 2, 5, 8)
-A2_SUM_LIMIT = 4096.0                    # attention_dma.hip: a lane's 16-key sum above this moves the reference
-
-
-def _keep(B, T, S, p):
-    from oracle import dropout_ref as DR
-    if p == 0.0:
-        return None
-    return torch.from_numpy(DR.keep_mask(DR.drop_key(SITE, STEP), DR.attn_index(B * H, T, S), p))
-
-
-def _lane_groups(S):
-    """key -> lane-pair half of the forward kernel: register r of lane half hi holds key 32 t + 4 hi + (r & 3) + 8 (r >> 2)."""
-    j = torch.arange(S)
-    return j // 32, (j % 32 // 4) % 2
-
-
-def _scores_case(case, B, T, S, p, parts, keep, g):
-    """Head-major operands [B*H, rows, 32] whose log2-unit scores s = q . k follow the case; q is the STORED query (scale * log2 e
-    already applied).  Every value is a bf16 of moderate size; every score is finite."""
-    from oracle import attn_bounds as AB
-    rn = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)
-    BH = B * H
-    q = 0.3 * rn(BH, T, HD)
-    k = rn(BH, S, HD)
-    v = rn(BH, S, HD)
-    tile = torch.arange(S, dtype=torch.float64) // 32
-    if case == "uniform":                          # O = mean of the kept V, lse = log S
-        q.zero_()
-    elif case == "ascending":                      # +13 log2 units per key tile: the reference moves (tile recomputed) on every tile
-        k[:, :, :8] = (tile / 4).view(1, S, 1)
-        q[:, :, :8] = 6.5
-        q[:, :, 8:] *= 1.0 / 6
-    elif case == "near_limit":                     # one key per 16-key lane group 11.5 above the first tile: lane sums near 4096
-        j = torch.arange(S)
-        high = ((j % 32 == 0) | (j % 32 == 4)) & (j >= 32)
-        k[:, :, 0] = 1.0
-        k[:, :, 1] = high.double().view(1, S)
-        q[:, :, 0] = 3.0 * torch.rand(BH, T, dtype=torch.float64, generator=g) - 1.5
-        q[:, :, 1] = 11.5
-        q[:, :, 2:] *= 1.0 / 30
-    elif case == "descending":                     # 60 .. -60 log2 units: early tiles dominate, late ones vanish
-        r = 1.0 - 2.0 * torch.arange(S, dtype=torch.float64) / max(S - 1, 1)
-        k[:, :, :8] = (4.0 * r).view(1, S, 1)
-        q[:, :, :8] = 60.0 / 32.0
-        q[:, :, 8:] *= 1.0 / 30
-    elif case == "distant_runs":                   # each row's maximum in its own run, the next run 20 lower, the rest 40 lower
-        rr = AB.runs(S, parts)
-        k[:, :, :8] = 0.0
-        for r, (j0, j1) in enumerate(rr):
-            k[:, j0:j1, r] = 1.0
-        n = len(rr)
-        i = torch.arange(T)
-        q[:, :, :8] = 0.0
-        q[:, i, i % n] = 40.0
-        if n > 1:
-            q[:, i, (i + 1) % n] = 20.0
-    elif case == "second_chain":                   # peaked rows only in the second 32 queries of each 64
-        q = rn(BH, T, HD)
-        q[:, torch.arange(T) % 64 < 32] = 0.0
-    elif case == "ragged_max":                     # every row's maximum is the last key (the ragged last tile), 20 above the rest
-        k[:, :, 0] = 0.0
-        k[:, S - 1, 0] = 1.0
-        q[:, :, 0] = 20.0
-    elif case == "dropped_dominant":               # the dominant key of a row (15 above the rest) is one the row drops
-        cand = torch.tensor([m * S // 16 for m in range(16)])
-        k[:, :, :16] = 0.0
-        k[:, cand, torch.arange(16)] = 1.0
-        q[:, :, :16] = 0.0
-        kc = keep[:, :, cand]                                                     # [BH, T, 16]
-        dropped = ~kc
-        m = torch.where(dropped.any(dim=2), dropped.double().argmax(dim=2), torch.zeros(BH, T, dtype=torch.long))
-        q.scatter_(2, m.unsqueeze(2), 15.0)
-        assert float(dropped.any(dim=2).double().mean()) > 0.5
-    else:
-        raise ValueError(case)
-    unh = lambda x: AB.bf16(AB.unheads(x, B, H))
-    return unh(q), unh(k), unh(v), AB.bf16(rn(B, T, D))
-
-
-def _assert_below_sum_limit(qs, k, B, T, S, p, parts):
-    """The near-limit inputs keep every lane's 16-key sum of exp2(score - reference) (reference = the run's first tile maximum,
-    shifted by log2 of the dropout scale as in the kernel) below A2_SUM_LIMIT in every tile, and some come within a factor 2 of it."""
-    from oracle import attn_bounds as AB
-    lg2scale = -np.log2(1.0 - p) if p > 0.0 else 0.0
-    tile, half = _lane_groups(S)
-    qh, kh = AB.heads(qs, H), AB.heads(k, H)
-    worst = 0.0
-    for bh in range(B * H):
-        s = qh[bh] @ kh[bh].T
-        for j0, j1 in AB.runs(S, parts):
-            m0 = s[:, j0:min(j1, j0 + 32)].max(dim=1, keepdim=True).values
-            e = torch.exp2(s[:, j0:j1] - m0 + lg2scale)
-            grp = (tile[j0:j1] - tile[j0]) * 2 + half[j0:j1]
-            sums = torch.zeros(T, int(grp.max()) + 1, dtype=torch.float64).index_add_(1, grp, e)
-            worst = max(worst, float(sums.max()))
-    assert worst < A2_SUM_LIMIT, f"near-limit inputs cross the sum limit ({worst:.1f})"
-    assert worst > A2_SUM_LIMIT / 2, f"near-limit inputs stay far from the sum limit ({worst:.1f})"
-    return worst
-
-
-def _device_operands(hip, qs, k, v, do, B, T, S, p, extra=0):
-    """bf16 device copies; outputs (and the lse / delta scratch) with `extra` trailing sentinel rows / entries."""
-    d = lambda t: t.to(torch.bfloat16).reshape(-1, D).to(DEV)
-    dev = dict(q=d(qs), k=d(k), v=d(v), do=d(do))
-    sent = lambda rows: torch.full((rows + extra, D), -1234.0, dtype=torch.bfloat16, device=DEV)
-    dev["o"], dev["dq"], dev["dk"], dev["dv"] = sent(B * T), sent(B * T), sent(B * S), sent(B * S)
-    dev["lse"] = torch.full((B * H * T + extra,), -4321.0, device=DEV)
-    dev["delta"] = torch.full((2 * B * H * T + extra,), -4321.0, device=DEV)
-    stepd = torch.tensor([STEP - (1 << 32)] + [0] * 7, dtype=torch.int32, device=DEV)
-    dev["kw"] = dict(scale=HD ** -0.5, dropout_p=p, dropout_site=SITE, dropout_step=stepd, dropmask=None)
-    if p > 0.0:
-        mask = torch.zeros(hip.attention_dropmask_words(B, H, T, S), dtype=torch.int32, device=DEV)
-        hip.attention_dropmask(mask, B, H, T, S, dropout_p=p, dropout_site=SITE, dropout_step=stepd)
-        dev["kw"]["dropmask"] = mask
-    return dev
-
-
-def _fwd(hip, dev, B, T, S, split, o=None, lse=None):
-    o = dev["o"] if o is None else o
-    lse = dev["lse"] if lse is None else lse
-    hip.set_tuning("DETR_HIP_ATTN_SPLIT", split if split else None)
-    try:
-        hip.attention(dev["q"], dev["k"], dev["v"], o[:B * T], lse, B, H, T, S, **dev["kw"])
-        torch.cuda.synchronize()
-    finally:
-        hip.set_tuning("DETR_HIP_ATTN_SPLIT", None)
-
-
-def _bwd(hip, dev, B, T, S, split, o, lse):
-    hip.set_tuning("DETR_HIP_ATTN_SPLIT", split if split else None)
-    try:
-        hip.attention(dev["q"], dev["k"], dev["v"], o[:B * T], lse, B, H, T, S, d_o=dev["do"], dq=dev["dq"][:B * T],
-                      dk=dev["dk"][:B * S], dv=dev["dv"][:B * S], delta=dev["delta"], **dev["kw"])
-        torch.cuda.synchronize()
-    finally:
-        hip.set_tuning("DETR_HIP_ATTN_SPLIT", None)
-
-
-def _check(what, got, ref, bound):
-    from oracle import attn_bounds as AB
-    r = AB.ratio(got, ref, bound)
-    assert r <= 1.0, f"{what}: max |err| / bound = {r:.3f} > 1"
-    return r
-
-
-CASES = ["uniform", "ascending", "near_limit", "descending", "distant_runs", "second_chain", "ragged_max", "dropped_dominant"]
 BOUND_SHAPES = [(2, 1050, 1050), (2, 100, 1050), (1, 300, 1344), (2, 70, 333)]
 
 
-BOUND_PARAMS = [(c, B, T, S, p) for c in CASES for B, T, S in BOUND_SHAPES for p in (0.0, 0.1)
+BOUND_PARAMS = [(c, B, T, S, p) for c in AC.CASES for B, T, S in BOUND_SHAPES for p in (0.0, 0.1)
                 if not (c == "dropped_dominant" and p == 0.0)]          # (the dominant key is a dropped one: needs dropout)
 
 
@@ -355,8 +213,8 @@ def test_attention_bf16_io_within_per_element_bounds(hip, case, B, T, S, p):
     DETR_HIP_ATTN_SPLIT = 2, 5, 8.  The backward of every split reads the same stored O (the heuristic forward's), which is the O the
     backward reference forms delta from; its lse is the split's own (the bound allows any lse within the forward's bound)."""
     from oracle import attn_bounds as AB
-    keep = _keep(B, T, S, p)
-    seed = 1000 * CASES.index(case) + T + S
+    keep = AC.keep_mask(B, T, S, p)
+    seed = 1000 * AC.CASES.index(case) + T + S
     ntk = -(-S // 32)
     dev = None
     fw = bw = None
@@ -365,45 +223,31 @@ def test_attention_bf16_io_within_per_element_bounds(hip, case, B, T, S, p):
         parts = AB.parts_for(ntk, split)
         if fw is None or case == "distant_runs":
             gg = torch.Generator().manual_seed(seed)
-            qs, k, v, do = _scores_case(case, B, T, S, p, parts, keep, gg)
+            qs, k, v, do = AC.scores_case(case, B, T, S, p, parts, keep, gg)
             if case == "near_limit":
-                print(f"near_limit B{B} T{T} S{S} p{p} parts{parts}: largest lane sum {_assert_below_sum_limit(qs, k, B, T, S, p, parts):.0f}")
-            dev = _device_operands(hip, qs, k, v, do, B, T, S, p, extra=64)
+                print(f"near_limit B{B} T{T} S{S} p{p} parts{parts}: largest lane sum {AC.assert_below_sum_limit(qs, k, B, T, S, p, parts):.0f}")
+            dev = AC.device_operands(hip, qs, k, v, do, B, T, S, p, extra=64)
             fw = AB.forward(qs, k, v, H, keep, p)
             if case == "uniform":                # closed form: lse = log S for every row, O = the kept mean of V
                 assert torch.allclose(fw["lse"], torch.full_like(fw["lse"], math.log(S)), rtol=0, atol=1e-9)
             o0 = torch.full_like(dev["o"], -1234.0)
-            _fwd(hip, dev, B, T, S, 0, o=o0)     # the stored O every backward below reads
+            AC.fwd(hip, dev, B, T, S, 0, o=o0)     # the stored O every backward below reads
             bw = AB.backward(qs, k, v, do, o0[:B * T].double().cpu().view(B, T, D), H, keep, p)
         o_s, lse_s = dev["o"], dev["lse"]
-        _fwd(hip, dev, B, T, S, split)
+        AC.fwd(hip, dev, B, T, S, split)
         tag = f"{case} B{B} T{T} S{S} p{p} split{split}"
-        r = dict(o=_check(f"O ({tag})", o_s[:B * T].float().view(B, T, D), fw["o"], fw["bound_o"]),
-                 lse=_check(f"lse ({tag})", lse_s[:B * H * T].view(B * H, T), fw["lse"], fw["bound_lse"]))
-        _bwd(hip, dev, B, T, S, split, o0, lse_s)
-        r["dq"] = _check(f"dQ ({tag})", dev["dq"][:B * T].float().view(B, T, D), bw["dq"], bw["bound_dq"])
-        r["dk"] = _check(f"dK ({tag})", dev["dk"][:B * S].float().view(B, S, D), bw["dk"], bw["bound_dk"])
-        r["dv"] = _check(f"dV ({tag})", dev["dv"][:B * S].float().view(B, S, D), bw["dv"], bw["bound_dv"])
+        r = dict(o=AC.check(f"O ({tag})", o_s[:B * T].float().view(B, T, D), fw["o"], fw["bound_o"]),
+                 lse=AC.check(f"lse ({tag})", lse_s[:B * H * T].view(B * H, T), fw["lse"], fw["bound_lse"]))
+        AC.bwd(hip, dev, B, T, S, split, o0, lse_s)
+        r["dq"] = AC.check(f"dQ ({tag})", dev["dq"][:B * T].float().view(B, T, D), bw["dq"], bw["bound_dq"])
+        r["dk"] = AC.check(f"dK ({tag})", dev["dk"][:B * S].float().view(B, S, D), bw["dk"], bw["bound_dk"])
+        r["dv"] = AC.check(f"dV ({tag})", dev["dv"][:B * S].float().view(B, S, D), bw["dv"], bw["bound_dv"])
         for n in worst:
             worst[n] = max(worst[n], r[n])
         for n in ("o", "dq", "dk", "dv"):
             assert bool((dev[n][dev[n].shape[0] - 64:] == -1234.0).all()), f"{n}: rows past the output written ({tag})"
         assert bool((dev["lse"][B * H * T:] == -4321.0).all()) and bool((dev["delta"][2 * B * H * T:] == -4321.0).all()), tag
     print(f"RATIO {case} B{B} T{T} S{S} p{p}: " + " ".join(f"{n} {x:.3g}" for n, x in worst.items()))
-
-
-def _all_outputs(hip, dev, B, T, S, split):
-    _fwd(hip, dev, B, T, S, split)
-    _bwd(hip, dev, B, T, S, split, dev["o"], dev["lse"])
-    return {n: dev[n].clone() for n in ("o", "lse", "dq", "dk", "dv", "delta")}
-
-
-def _sentinels_intact(dev, B, T, S, extra):
-    for n, rows in (("o", B * T), ("dq", B * T), ("dk", B * S), ("dv", B * S)):
-        assert bool((dev[n][rows:] == -1234.0).all()), f"{n}: sentinel rows overwritten"
-        assert bool(torch.isfinite(dev[n][:rows].float()).all()), f"{n}: not finite"
-    assert bool((dev["lse"][B * H * T:] == -4321.0).all()), "lse: sentinel entries overwritten"
-    assert bool((dev["delta"][2 * B * H * T:] == -4321.0).all()), "delta: sentinel entries overwritten"
 
 
 @pytest.mark.parametrize("split", [0, 8])
@@ -415,14 +259,14 @@ def test_attention_bf16_io_batch_elements_are_isolated(hip, split, p):
     g = torch.Generator().manual_seed(21)
     rn = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)
     qs, k, v, do = (rn(B, n, D) * c for n, c in ((T, 0.5), (S, 1.0), (S, 1.0), (T, 1.0)))
-    dev = _device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
-    a = _all_outputs(hip, dev, B, T, S, split)
-    _sentinels_intact(dev, B, T, S, X)
+    dev = AC.device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
+    a = AC.all_outputs(hip, dev, B, T, S, split)
+    AC.sentinels_intact(dev, B, T, S, X)
     for b in (0, 2):
         qs[b], k[b], v[b], do[b] = rn(T, D) * 3.0, rn(S, D) * 4.0, rn(S, D) * 50.0, rn(T, D) * 50.0
-    dev2 = _device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
-    c = _all_outputs(hip, dev2, B, T, S, split)
-    _sentinels_intact(dev2, B, T, S, X)
+    dev2 = AC.device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
+    c = AC.all_outputs(hip, dev2, B, T, S, split)
+    AC.sentinels_intact(dev2, B, T, S, X)
     for n, rows in (("o", slice(T, 2 * T)), ("dq", slice(T, 2 * T)), ("dk", slice(S, 2 * S)), ("dv", slice(S, 2 * S)),
                     ("lse", slice(H * T, 2 * H * T))):
         assert torch.equal(a[n][rows], c[n][rows]), f"{n} of batch element 1 depends on elements 0 / 2 (split {split}, p {p})"
@@ -437,15 +281,15 @@ def test_attention_bf16_io_heads_are_isolated(hip, split, p):
     g = torch.Generator().manual_seed(22)
     rn = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)
     qs, k, v, do = (rn(B, n, D) * c for n, c in ((T, 0.5), (S, 1.0), (S, 1.0), (T, 1.0)))
-    dev = _device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
-    a = _all_outputs(hip, dev, B, T, S, split)
+    dev = AC.device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
+    a = AC.all_outputs(hip, dev, B, T, S, split)
     for hh in (h - 1, h + 1):
         cols = slice(hh * HD, (hh + 1) * HD)
         qs[:, :, cols], k[:, :, cols] = rn(B, T, HD) * 3.0, rn(B, S, HD) * 4.0
         v[:, :, cols], do[:, :, cols] = rn(B, S, HD) * 50.0, rn(B, T, HD) * 50.0
-    dev2 = _device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
-    c = _all_outputs(hip, dev2, B, T, S, split)
-    _sentinels_intact(dev2, B, T, S, X)
+    dev2 = AC.device_operands(hip, qs, k, v, do, B, T, S, p, extra=X)
+    c = AC.all_outputs(hip, dev2, B, T, S, split)
+    AC.sentinels_intact(dev2, B, T, S, X)
     cols = slice(h * HD, (h + 1) * HD)
     for n in ("o", "dq", "dk", "dv"):
         assert torch.equal(a[n][:, cols], c[n][:, cols]), f"{n} of head {h} depends on its neighbours (split {split}, p {p})"

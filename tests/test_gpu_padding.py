@@ -226,7 +226,10 @@ def _prepare(hip, masks, Hf, Wf):
     return kv.cpu().numpy(), pos.cpu().numpy().reshape(B, Hf, Wf, 256), status.cpu().numpy(), ty.cpu().numpy(), tx.cpu().numpy()
 
 
-@pytest.mark.parametrize("H_,W_,Hf,Wf", [(800, 1333, 25, 42), (128, 160, 4, 5), (97, 131, 4, 5), (40, 40, 13, 7)])
+@pytest.mark.parametrize("H_,W_,Hf,Wf", [(800, 1333, 25, 42), (128, 160, 4, 5), (97, 131, 4, 5), (40, 40, 13, 7),
+                                         # the limits: 128 per side, 8192 positions (91 x 90 = 8190: a ragged last key word)
+                                         (1027, 515, 128, 64), (515, 1027, 64, 128), (9, 1031, 1, 128), (1031, 9, 128, 1),
+                                         (731, 725, 91, 90)])
 def test_padding_mask_prepare(hip, H_, W_, Hf, Wf):
     import padding_ref as PR
     from detr_tf import _hip
@@ -249,6 +252,24 @@ def test_padding_mask_prepare(hip, H_, W_, Hf, Wf):
     assert pos.tobytes() == host.astype(np.float32).tobytes(), "pos must be the host gather, bit for bit"
     ref = PR.position_embedding_sine_masked(torch.from_numpy(fm)).numpy()
     assert float(np.abs(pos - ref).max()) <= 1e-6
+
+
+@pytest.mark.parametrize("Hf,Wf", [(129, 8), (8, 129), (91, 91)])
+def test_padding_mask_prepare_rejects_maps_over_the_limits(hip, Hf, Wf):
+    """More than 128 per side or 8192 positions (91 x 91 = 8281) raises, and nothing is written to kv, pos or status."""
+    from detr_tf.engine import position_embedding_sine_table
+    B, L = 2, Hf * Wf
+    masks = np.zeros((B, 4 * Hf + 1, 4 * Wf + 3), bool)
+    masks[1, 2 * Hf:] = True
+    ty = torch.from_numpy(position_embedding_sine_table(Hf)).to(DEV)
+    tx = torch.from_numpy(position_embedding_sine_table(Wf)).to(DEV)
+    kv = torch.full((hip.attention_keymask_words(B, L),), -1, dtype=torch.int32, device=DEV)
+    pos = torch.full((B * L, 256), 9.0, device=DEV)
+    status = torch.full((B,), 7, dtype=torch.int32, device=DEV)
+    with pytest.raises((RuntimeError, ValueError), match="exceeds"):
+        hip.padding_mask_prepare(torch.from_numpy(masks).to(DEV), Hf, Wf, ty, tx, kv, pos, status)
+    torch.cuda.synchronize()
+    assert bool((kv == -1).all()) and bool((pos == 9.0).all()) and bool((status == 7).all()), "sentinels overwritten"
 
 
 def test_padding_mask_prepare_all_false_is_the_unmasked_constant(hip):
