@@ -1,5 +1,5 @@
-// attention_common.h -- definitions shared by the exact-fp32 (attention_f32.hip) and the bf16-MFMA
-// (attention_bf16.hip) fused attention kernels.
+// attention_common.h -- definitions shared by the exact-fp32 (attention_f32.hip) and the all-bf16
+// (attention_dma.hip) fused attention kernels.
 #pragma once
 #include "common.h"
 
@@ -175,8 +175,6 @@ static int attn_waves(int rows, int bh) {
     return ((long long)cdiv(rows, 128) * bh < 2048) ? 2 : 4;
 }
 
-int attn_fwd_bf16_launch(const AttnArgs &a, hipStream_t s);      // attention_bf16.hip
-int attn_bwd_bf16_launch(const AttnArgs &a, hipStream_t s);
 int attn2_fwd_from_desc(const detr_attn_desc *d, hipStream_t s, const uint32_t *key_valid = nullptr);    // attention_dma.hip (io_dtype = 1)
 int attn2_bwd_from_desc(const detr_attn_desc *d, hipStream_t s, const uint32_t *key_valid = nullptr);
 

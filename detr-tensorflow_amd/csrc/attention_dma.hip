@@ -2,15 +2,14 @@
 // operator's real bound at head_dim 32 (detr_tf/networks/transformer.py:308-345).
 //
 // What bounds it.  A 32 x 32 score tile is 4 MFMAs (2 for K Q^T, 2 for P V: 128 cycles of the matrix pipe) and one softmax
-// (16 scores per lane).  The kernels of attention_bf16.hip spent ~340 VALU issue slots on that tile -- 160 of them the dropout mask
+// (16 scores per lane).  The round-3 kernels (bf16 MFMAs on fp32 tensors, since removed) spent ~340 VALU issue slots on that tile -- 160 of them the dropout mask
 // (8 counter hashes per lane with two quarter-rate 32-bit multiplies each), re-evaluated by all three kernels --, staged fp32 K / V
 // through VGPRs with a bf16 packing pass in every workgroup that streamed them, and ran one workgroup barrier per 32 keys.  Here:
 //   * operands are bf16 in memory (the projection GEMMs store them; Q carries scale * log2(e)), outputs bf16: no conversion pass,
 //     half the bytes of every K / V re-stream;
 //   * the dropout keep flags are BITS, produced once per step by attn2_dropmask_kernel (one launch per attention site, off the
-//     critical path) in the two layouts the kernels want -- one word per (query, 32-key tile) with bit = key for the kernels whose
-//     lanes own queries, one word per (key, 32-query tile) with bit = query for the dK / dV kernel -- so that an element's flag is
-//     v_bfe_i32 + v_and_b32 on a word that arrived with the tile.  Same function as common.h::drop_keep, bit for bit;
+//     critical path) in ONE layout that all three kernels read -- one word per (query, 32-key tile), bit = key -- so that an
+//     element's flag is v_bfe_i32 + v_and_b32 on a word that arrived with the tile.  Same function as common.h::drop_keep, bit for bit;
 //   * a WAVE is the unit of work: 64 queries (two independent 32-query chains that share every K / V fragment) x a contiguous run
 //     of key tiles.  Its K / V / flag tiles arrive by LDS-DMA (buffer_load ... lds) in a wave-PRIVATE ring of three stages,
 //     published by the wave's own counted s_waitcnt vmcnt(N): no workgroup barrier in the key loop at all.  The workgroup exists
@@ -23,8 +22,7 @@
 //     comes out of the matrix pipe and an element costs exp2 + add-to-sum + 2 flag ops + half a cvt_pk;
 //   * the backward keeps its two deterministic kernels (dQ per query block, dK / dV per key block) in the same form; the dQ kernel
 //     leaves delta / scale and lse * log2(e) - log2(scale) in `stats` for the dK / dV kernel, which gets them by DMA with its tiles.
-// Fragment maps (K Q^T transposed so that a score row lives in one lane pair, P^T already in the B layout of the PV product) are
-// those of attention_bf16.hip.
+// Fragment maps: K Q^T is transposed so that a score row lives in one lane pair, and P^T is already in the B layout of the PV product.
 #include "attention_common.h"
 #include "gemm_ring.h"        // ring_dma_piece, ring_rsrc, ring_lds_addr, ring_wait_vmcnt
 #include <utility>
@@ -43,13 +41,7 @@ constexpr int A2_AUX = 256;              // one 64-lane x 4-byte piece (flag wor
 constexpr int A2_RING = 3;
 constexpr float A2_SUM_LIMIT = 4096.0f;
 constexpr float A2_M_EMPTY = -1.0e30f;   // masked forward: the reference of a run without a valid key (see attn2_fwd_kernel)  // a lane's 16-key sum of exp2(score - reference) above this moves the reference (forward kernel)
-// timing experiments only (scripts/experiments/attn2_ablate.sh; results are WRONG with any bit set): 1 = no DMA requests inside the key loop,
-// 2 = no fragment reads / MFMAs / softmax inside the key loop, 4 = no softmax arithmetic (the scores go straight into the PV product)
-#ifndef A2_ABLATE
-#define A2_ABLATE 0
-#endif
-// (bit 8: the exponentials of the forward kernel as one v_add each -- what the transcendental rate costs)
-__device__ __forceinline__ float a2_exp2(float x) { return (A2_ABLATE & 8) ? x + 1.0f : __builtin_amdgcn_exp2f(x); }
+__device__ __forceinline__ float a2_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 struct Attn2Args {
     const unsigned short *Q, *K, *V;
@@ -296,11 +288,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         constexpr int STG = decltype(stg_c)::value;
         unsigned kv = ~0u;
         if constexpr (MASK) kv = a2_kv_tile(kvl, kvw, i);
-        if constexpr ((A2_ABLATE & 1) == 0) {
-            issue((STG + 2) % A2_RING, t0 + i + 2);     // (the stage of tile i - 1: its reads were drained at the end of that tile)
-            ring_wait_vmcnt<2 * NP>();                  // tile i has landed
-        }
-        if constexpr ((A2_ABLATE & 2) != 0) return;
+        issue((STG + 2) % A2_RING, t0 + i + 2);         // (the stage of tile i - 1: its reads were drained at the end of that tile)
+        ring_wait_vmcnt<2 * NP>();                      // tile i has landed
         if constexpr (MASK) {
             if (kv == 0u) return;                       // no valid key: contributes nothing (no LDS read was issued)
         }
@@ -337,14 +326,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     A2_NO_IFCVT();
                     a2_mask_scores(s[c], kv, hi);
                 }
-            }
-            if constexpr ((A2_ABLATE & 4) != 0) {
-                float pa[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pa[r] = s[c][r];
-                o[c] = A2_MFMA(v0, a2_pack8(pa), o[c]);
-                o[c] = A2_MFMA(v1, a2_pack8(pa + 8), o[c]);
-                continue;
             }
             if (first) {
                 // a run's first tile sets the reference exactly to its maximum (o = l = 0 there)

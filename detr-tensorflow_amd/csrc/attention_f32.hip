@@ -394,14 +394,19 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dkv_kernel(AttnArgs a) {
 
 using namespace detr;
 
-/* one entry point per direction; detr_attn_desc.compute selects the exact-fp32 kernels above or the bf16-MFMA kernels of
- * attention_bf16.hip.  key_valid != null: the key-padding-masked instantiations (exact fp32 and all-bf16 operands only) */
+/* one entry point per direction; detr_attn_desc.io_dtype selects the all-bf16 kernels of attention_dma.hip (compute = 1) or the
+ * exact-fp32 kernels above (compute = 0, or 2: f32x3 mode runs them as well).  key_valid != null: the key-padding-masked instantiations */
+static int attn_f32_check(const detr_attn_desc *d) {
+    DETR_REQUIRE(d->io_dtype == 0, "attention: io_dtype must be 0 (fp32 tensors) or 1 (bf16 tensors)");
+    DETR_REQUIRE(d->compute != 1, "attention: no plain and no key-padding-masked form for io_dtype = 0, compute = 1 -- compute = 1 (bf16 MFMA) "
+                                  "needs bf16 operands (io_dtype = 1); fp32 tensors take compute = 0 or 2");
+    return 0;
+}
+
 static int attn_fwd_impl(const detr_attn_desc *d, const uint32_t *key_valid, hipStream_t s) {
     if (d->io_dtype == 1) return attn2_fwd_from_desc(d, s, key_valid);      // all-bf16 operands: attention_dma.hip
-    DETR_REQUIRE(d->io_dtype == 0, "attention: io_dtype must be 0 (fp32 tensors) or 1 (bf16 tensors)");
     AttnArgs a;
-    if (attn_from_desc(d, 0, a)) return -1;
-    if (d->compute == 1) return attn_fwd_bf16_launch(a, s);
+    if (attn_f32_check(d) || attn_from_desc(d, 0, a)) return -1;
     a.key_valid = key_valid;
     a.kv_words = cdiv(a.S, 32);
     const bool two = attn_waves(a.T, a.B * a.H) == 2;
@@ -417,10 +422,8 @@ static int attn_fwd_impl(const detr_attn_desc *d, const uint32_t *key_valid, hip
 
 static int attn_bwd_impl(const detr_attn_desc *d, const uint32_t *key_valid, hipStream_t s) {
     if (d->io_dtype == 1) return attn2_bwd_from_desc(d, s, key_valid);
-    DETR_REQUIRE(d->io_dtype == 0, "attention: io_dtype must be 0 (fp32 tensors) or 1 (bf16 tensors)");
     AttnArgs a;
-    if (attn_from_desc(d, 1, a)) return -1;
-    if (d->compute == 1) return attn_bwd_bf16_launch(a, s);
+    if (attn_f32_check(d) || attn_from_desc(d, 1, a)) return -1;
     a.key_valid = key_valid;
     a.kv_words = cdiv(a.S, 32);
     bool two = attn_waves(a.T, a.B * a.H) == 2;
@@ -462,11 +465,6 @@ extern "C" int64_t detr_hip_attention_keymask_words(int32_t B, int32_t S) {
 static int attn_masked_check(const detr_attn_desc *d, const uint32_t *key_valid) {
     DETR_REQUIRE(d, "attention masked: null descriptor");
     DETR_REQUIRE(key_valid, "attention masked: null key_valid words");
-    DETR_REQUIRE(d->io_dtype == 0 || d->io_dtype == 1, "attention masked: io_dtype must be 0 (fp32 tensors) or 1 (bf16 tensors)");
-    DETR_REQUIRE(!(d->io_dtype == 0 && d->compute == 1),
-                 "attention masked: no key-padding-masked form of the bf16-compute kernels on fp32 tensors (io_dtype = 0, compute = 1); "
-                 "use compute = 0 or bf16 operands (io_dtype = 1)");
-    DETR_REQUIRE(d->io_dtype == 0 || d->compute == 1, "attention masked: bf16 operands (io_dtype = 1) need compute = 1");
     DETR_REQUIRE(d->B > 0 && d->S > 0, "attention masked: bad shape B=%d S=%d", d->B, d->S);
     DETR_REQUIRE(((uintptr_t)key_valid & 3) == 0, "attention masked: key_valid must be 4-byte aligned");
     return 0;

@@ -29,16 +29,7 @@
 
 namespace detr {
 
-#ifndef DETR_BF_NS
-#define DETR_BF_NS 4
-#endif
-#ifndef DETR_BF_INTERLEAVE
-#define DETR_BF_INTERLEAVE 0   // 1: workgroup w takes strips w, w + nwg, w + 2 nwg, ... (one sweep over the tensors) instead of a contiguous range (A/B builds)
-#endif
-#ifndef DETR_BF_NT
-#define DETR_BF_NT 0           // 1: the strip requests carry the non-temporal hint (A/B builds)
-#endif
-constexpr int BF_D1 = 64, BF_D2 = 256, BF_SR = 32, BF_NS = DETR_BF_NS;
+constexpr int BF_D1 = 64, BF_D2 = 256, BF_SR = 32, BF_NS = 4;
 constexpr int BF_WAVES = 6, BF_THREADS = 64 * BF_WAVES;
 constexpr int BF_W_BYTES = BF_D1 * BF_D2 * 2;                    // 32 KB
 constexpr int BF_G_BYTES = BF_SR * BF_D2 * 2, BF_Y_BYTES = BF_SR * BF_D1 * 2, BF_STAGE = BF_G_BYTES + BF_Y_BYTES;      // 16 + 4 KB
@@ -64,11 +55,9 @@ __global__ __launch_bounds__(BF_THREADS, 1) void conv1x1_bwd_fused_bf16_kernel(B
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds0 = ring_lds_addr(bf_smem);
     const int wg = blockIdx.x;
-    // strips of this workgroup: v = 0 .. cnt - 1 -> strip sv(v)
-    const int s0 = DETR_BF_INTERLEAVE ? wg : (int)((long long)a.nstrips * wg / a.nwg);
-    const int cnt = DETR_BF_INTERLEAVE ? (a.nstrips - wg + a.nwg - 1) / a.nwg : (int)((long long)a.nstrips * (wg + 1) / a.nwg) - s0;
-    const int sstep = DETR_BF_INTERLEAVE ? a.nwg : 1;
-    auto sv = [&](const int v) { return s0 + v * sstep; };
+    // strips of this workgroup: v = 0 .. cnt - 1 -> strip s0 + v
+    const int s0 = (int)((long long)a.nstrips * wg / a.nwg);
+    const int cnt = (int)((long long)a.nstrips * (wg + 1) / a.nwg) - s0;
     const int l31 = lane & 31, hh = lane >> 5;
 
     if (wave < 4) {
@@ -88,7 +77,7 @@ __global__ __launch_bounds__(BF_THREADS, 1) void conv1x1_bwd_fused_bf16_kernel(B
             yvoff = (unsigned)r * (unsigned)a.ldy * 2u + 16u * (unsigned)(pos ^ (4 * ((r >> 1) & 1)));
         }
         auto issue_strip = [&](const int v, const int stage) {
-            const long long row0 = (long long)sv(v) * BF_SR;
+            const long long row0 = (long long)(s0 + v) * BF_SR;
             const long long left = (v < cnt && row0 < a.M) ? (long long)a.M - row0 : 0;            // rows of the strip onwards (0: nothing to fetch)
             const unsigned long long gb = left > 0 ? (unsigned long long)((left - 1) * a.ldg + BF_D2) * 2ull : 0ull;
             const unsigned long long yb = left > 0 ? (unsigned long long)((left - 1) * a.ldy + BF_D1) * 2ull : 0ull;
@@ -96,12 +85,8 @@ __global__ __launch_bounds__(BF_THREADS, 1) void conv1x1_bwd_fused_bf16_kernel(B
             const u32x4 ry = ring_rsrc(reinterpret_cast<const char *>(a.y) + row0 * a.ldy * 2, (unsigned)(yb > 0xFFFFFFFFull ? 0xFFFFFFFFull : yb));
             const unsigned base = lds0 + (unsigned)(BF_OFF_RING + stage * BF_STAGE);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if constexpr (DETR_BF_NT != 0) ring_dma_piece_nt(rg, base + (unsigned)((wave + 4 * i) * 1024), gvoff[i]);
-                else ring_dma_piece(rg, base + (unsigned)((wave + 4 * i) * 1024), gvoff[i]);
-            }
-            if constexpr (DETR_BF_NT != 0) ring_dma_piece_nt(ry, base + (unsigned)(BF_G_BYTES + wave * 1024), yvoff);
-            else ring_dma_piece(ry, base + (unsigned)(BF_G_BYTES + wave * 1024), yvoff);
+            for (int i = 0; i < 4; ++i) ring_dma_piece(rg, base + (unsigned)((wave + 4 * i) * 1024), gvoff[i]);
+            ring_dma_piece(ry, base + (unsigned)(BF_G_BYTES + wave * 1024), yvoff);
         };
         // W image: row n = 512 bytes, chunk c at position c ^ (n & 15); piece = 2 rows, lane: row 2 P + lane / 32, slot position lane & 31
         {
@@ -186,7 +171,7 @@ __global__ __launch_bounds__(BF_THREADS, 1) void conv1x1_bwd_fused_bf16_kernel(B
         unsigned short *dz = a.dz;
         int stage = 0;
         auto store_strip = [&](const int v) {        // rows 16 d .. 16 d + 15 of this workgroup's strip v out of staging buffer v & 1: two passes of 8 rows x 128 bytes
-            const int s = sv(v);
+            const int s = s0 + v;
             const char *sb = bf_smem + BF_OFF_ST + (v & 1) * (BF_SR * BF_ST_PITCH);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {

@@ -35,33 +35,10 @@ void launch_splitk_reduce(const float *ws, int splits, long long part_stride, in
                           float alpha, const float *scale, hipStream_t stream, const float *rs_ws = nullptr,
                           float *rs_out = nullptr, float rs_alpha = 1.0f, int ts_bm = 0, int ts_bn = 0, int ts_tiles_n = 0);
 
-// Minimum waves per SIMD requested for the 64x64-tile bf16 GEMM / conv kernels (second __launch_bounds__ argument):
-// tuning knob (make DEFS=-DDETR_GEMM64_MINW=6).  Measured: 6 (<= 64 VGPRs, 8 workgroups / CU instead of 5) buys the
-// HBM-bound short-K GEMMs 1-2 % and costs the long-K ones 10-25 % (tighter scheduling) -- left at 1.
-#ifndef DETR_GEMM64_MINW
-#define DETR_GEMM64_MINW 1
-#endif
-
-// Ablation builds for timing experiments only (scripts/experiments/ablate.sh; results are WRONG with any bit set): bit 0 = no
-// MFMA issue, bit 1 = no global operand requests inside the K loop, bit 2 = no LDS operand stores inside the K loop, bit 3 = no
-// workgroup barrier inside the K loop, bit 4 = no LDS fragment reads; gemm_stream.h: bit 5 = no residual / mask requests,
-// bit 6 = no output stores.  The product library is built with 0.
-#ifndef DETR_ABLATE
-#define DETR_ABLATE 0
-#endif
-// 1: the bf16 tile GEMM K loop in its explicitly pipelined form (gemm_bf16_core.h: KPipe); 0: compiler-scheduled (round 3) -- A/B builds
-#ifndef DETR_KLOOP_PIPE
-#define DETR_KLOOP_PIPE 1
-#endif
-
-#if defined(__HIPCC__)
-template <typename T>
-__device__ __forceinline__ void ablate_keep(const T &v) {      // keeps a loaded register alive without using it
-    const unsigned *p = reinterpret_cast<const unsigned *>(&v);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(T) / 4); ++i) asm volatile("" ::"v"(p[i]));
-}
-#endif
+// Minimum waves per SIMD requested for the 64x64-tile bf16 GEMM / conv kernels (second __launch_bounds__ argument).  Measured:
+// 6 (<= 64 VGPRs, 8 workgroups / CU instead of 5) buys the HBM-bound short-K GEMMs 1-2 % and costs the long-K ones 10-25 %
+// (tighter scheduling) -- left at 1.
+constexpr int MIN_WAVES_64X64 = 1;
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a workgroup-scope release / acquire of ALL address
 // spaces, and on gfx9 loads and stores share vmcnt -- it therefore drains every outstanding global load, which would
@@ -109,7 +86,6 @@ enum TuneKey {
     T_RING_WGS,          // workgroup target forced; 0 = cost model
     T_RING_ROWS,         // row pitch forced (sweeps)
     T_RING_WTILE,        // ring weight gradient on 128 x 256 (1) / 256 x 128 (2) tiles (experiments)
-    T_RING_ABLATE,       // timing experiments: RingArgs.ablate bits (results wrong when set)
     T_CONV_DMA,          // 2: the LDS-DMA form of the halo 3x3 kernel (conv_halo_dma.h, round 5) is off; 3: its requests in front of the fragment reads
     T_SPLIT3_T128,       // compute = 2 (f32x3): 128 x 128 tiles from this many of them on (0 = default rule)
     T_X3_DB,             // f32x3 GEMM (gemm_x3.h): 1 = double-buffered LDS form for every tile, 2 = single-buffered for every tile, 0 = rule

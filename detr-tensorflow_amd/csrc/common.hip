@@ -35,7 +35,6 @@ static const char *const g_tune_names[T_COUNT] = {
     "DETR_HIP_RING_WGS",
     "DETR_HIP_RING_ROWS",
     "DETR_HIP_RING_WTILE",
-    "DETR_HIP_RING_ABLATE",
     "DETR_HIP_CONV_DMA",
     "DETR_HIP_SPLIT3_T128",
     "DETR_HIP_X3_DB",

@@ -1,7 +1,7 @@
 // conv_halo.h -- stride-1 3x3 convolution forward / input gradient on bf16 tensors with the input HALO STAGED ONCE
 // (included by conv_f32.hip; reference: detr_tf/networks/resnet_backbone.py:98-137, the conv2 of every BottleNeck).
 //
-// Why (ablation builds, scripts/experiments/ablate.sh, profiles/r02_ablation_tile_kernels.txt): in the implicit-GEMM
+// Why (ablation builds, profiles/r02_ablation_tile_kernels.txt): in the implicit-GEMM
 // tile kernel the operand REQUESTS and their LDS stores cost 35-45 % of the kernel (C = 64: 108 us with them, 60 us
 // without) -- every one of the 9 taps re-fetches its [pixels][32 ch] operand through the vector memory path although
 // the taps of a tile read the same (tile + 1 pixel border) input patch, and a 64 / 128 pixel tile re-fetches the whole
@@ -257,23 +257,16 @@ __global__ __launch_bounds__(GEMM_THREADS, TH == 8 ? 2 : 3) void conv3x3_halo_bf
         for (int ks = 0; ks < BF_BK; ks += 16) {
             bf16x8 fa[T::TM], fb[T::TN];
 #pragma unroll
-            for (int mi = 0; mi < T::TM; ++mi) {
-                if constexpr ((DETR_ABLATE & 16) != 0) fa[mi] = __builtin_bit_cast(bf16x8, make_uint4(lane, mi, ks, 0x3f803f80u));
-                else fa[mi] = *reinterpret_cast<const bf16x8 *>(pa + mi * (CH_PW * BF_LD) + ks);
-            }
+            for (int mi = 0; mi < T::TM; ++mi) fa[mi] = *reinterpret_cast<const bf16x8 *>(pa + mi * (CH_PW * BF_LD) + ks);
 #pragma unroll
             for (int ni = 0; ni < T::TN; ++ni) {
-                if constexpr ((DETR_ABLATE & 16) != 0) fb[ni] = __builtin_bit_cast(bf16x8, make_uint4(lane, ni, ks, 0x3f803f80u));
-                else if (!DGRAD) fb[ni] = frag_tr<BN>(Bs, wn * T::WTN + ni * 32, ks, lane);
+                if (!DGRAD) fb[ni] = frag_tr<BN>(Bs, wn * T::WTN + ni * 32, ks, lane);
                 else fb[ni] = *reinterpret_cast<const bf16x8 *>(&Bs[0][0] + halo_bsw(wn * T::WTN + ni * 32 + l31, (ks + kh8) >> 3));
             }
 #pragma unroll
             for (int mi = 0; mi < T::TM; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < T::TN; ++ni) {
-                    if constexpr ((DETR_ABLATE & 1) != 0) { ablate_keep(fa[mi]); ablate_keep(fb[ni]); }
-                    else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
-                }
+                for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
         }
     };
 
@@ -300,23 +293,18 @@ __global__ __launch_bounds__(GEMM_THREADS, TH == 8 ? 2 : 3) void conv3x3_halo_bf
             const int cur = (PAR + tp) & 1;
             // kernel tile of the next step: register set `cur ^ PAR ...` -- step parity decides the set, statically
             if (((PAR + tp) & 1) == 0) {
-                if constexpr ((DETR_ABLATE & 4) == 0) { if constexpr (DGRAD) halo_store_b_swz<BN>(&sm.B[cur ^ 1][0][0], rb0, tid); else lb.store(sm.B[cur ^ 1], rb0); }
-                else for (int i = 0; i < NRB; ++i) ablate_keep(rb0[i]);
-                if constexpr ((DETR_ABLATE & 2) == 0) b_load(c + (tp + 3) / 9, (tp + 3) % 9, rb0);
+                if constexpr (DGRAD) halo_store_b_swz<BN>(&sm.B[cur ^ 1][0][0], rb0, tid);
+                else lb.store(sm.B[cur ^ 1], rb0);
+                b_load(c + (tp + 3) / 9, (tp + 3) % 9, rb0);
             } else {
-                if constexpr ((DETR_ABLATE & 4) == 0) { if constexpr (DGRAD) halo_store_b_swz<BN>(&sm.B[cur ^ 1][0][0], rb1, tid); else lb.store(sm.B[cur ^ 1], rb1); }
-                else for (int i = 0; i < NRB; ++i) ablate_keep(rb1[i]);
-                if constexpr ((DETR_ABLATE & 2) == 0) b_load(c + (tp + 3) / 9, (tp + 3) % 9, rb1);
+                if constexpr (DGRAD) halo_store_b_swz<BN>(&sm.B[cur ^ 1][0][0], rb1, tid);
+                else lb.store(sm.B[cur ^ 1], rb1);
+                b_load(c + (tp + 3) / 9, (tp + 3) % 9, rb1);
             }
-            if (tp == 2) {
-                if constexpr ((DETR_ABLATE & 4) == 0) patch_store((c + 1) & 1, rp);
-                else for (int i = 0; i < CH_NG; ++i) ablate_keep(rp[i]);
-            }
-            if (tp == 4) {
-                if constexpr ((DETR_ABLATE & 2) == 0) patch_load(c + 2, rp);
-            }
+            if (tp == 2) patch_store((c + 1) & 1, rp);
+            if (tp == 4) patch_load(c + 2, rp);
             mma_tap(c & 1, cur, tp);
-            if constexpr ((DETR_ABLATE & 8) == 0) lds_barrier();
+            lds_barrier();
         }
     };
     // S2C: four steps per chunk (step parity = tp & 1 in every chunk); the patch of chunk c + 1 -- requested one chunk ago -- is stored at

@@ -2,7 +2,7 @@
 // Same tile (4 x 32 output pixels x 128 channels), same 2 x 2 wave grid, same MFMA order per accumulator and the same epilogue as
 // conv3x3_halo_bf16_kernel<128, DGRAD, 4>: results are bit-identical.  What changes is who moves the operands:
 //
-// Ablation builds of the register-staged kernel (scripts/experiments/ablate.sh, profiles/r05_conv_ablation.txt), 50x84x256 forward:
+// Ablation builds of the register-staged kernel (profiles/r05_conv_ablation.txt), 50x84x256 forward:
 // 66.7 us complete | 42.5 without MFMAs | 43.2 without the operand requests and their LDS stores | 44.4 without fragment reads |
 // 37.5 with the MFMAs alone | 12.4 with an empty loop -- three phases of ~23 us each that do not overlap, three workgroups per CU or not:
 // a wave that waits for its 16-byte loads, writes them to LDS and waits at the barrier is not issuing MFMAs, and its neighbours are in the
@@ -24,8 +24,8 @@
 //
 // Measured (scripts/micro_conv.py, profiles/r05_micro_conv_dma.txt; us forward / input gradient, register-staged -> this kernel):
 // 100x167x128 53.2 / 54.0 -> 49.6 / 50.9, 50x84x256 54.7 / 55.3 -> 49.9 / 51.9, 25x42x512 66.0 / 68.9 -> 61.3 / 62.3: -5 ... -10 %, not
-// the -25 % the ablation promised.  A per-step timeline of the kernel (s_memtime stamps of one wave, -DDETR_ABLATE=64,
-// scripts/experiments/conv_trace.py, profiles/r05_conv_trace.txt) shows why: the counted wait and the barrier cost nothing beyond the
+// the -25 % the ablation promised.  A per-step timeline of the kernel (s_memtime stamps of one wave,
+// profiles/r05_conv_trace.txt) shows why: the counted wait and the barrier cost nothing beyond the
 // stamp itself (116-130 ticks each) -- the operands are always there -- and all of a step's 650-1500 ticks are its "work" section:
 // ~85 instructions of one wave around 8 MFMAs (256 cycles), three such waves per SIMD, 9.5 KB of DMA per 32 MFMAs of a workgroup
 // (437 MB per launch through L2 -> LDS, 8 TB/s).  Two variants that attack latency instead were built, measured and removed
@@ -50,19 +50,6 @@ constexpr int CHD_RING = CHD_OFF_DUMP + 1024;
 constexpr int CHD_EPI = StageCfg<CHD_BN, 2>::BYTES;
 constexpr int CHD_SMEM = CHD_RING > CHD_EPI ? CHD_RING : CHD_EPI;
 
-#if (DETR_ABLATE & 64) != 0
-// timeline experiment (scripts/experiments/conv_trace.py): wave 0 of three workgroups stamps the cycle counter in front of the counted wait,
-// in front of the barrier and behind it, every step; [workgroup][40 steps x 3 + kernel start, loop start, loop end, kernel end, and the
-// 100 MHz real-time counter at kernel start / end]
-constexpr int CHD_TR_STEPS = 40, CHD_TR_N = CHD_TR_STEPS * 3 + 6;
-__device__ long long chd_trace[3][CHD_TR_N];
-#define CHD_STAMP(idx) do { if (tr_w) { const long long t_ = __builtin_readcyclecounter(); if (lane == 0) trl[(idx)] = t_; } } while (0)
-#define CHD_STAMP_STEP(s, k) do { if ((s) < CHD_TR_STEPS) CHD_STAMP((s) * 3 + (k)); } while (0)
-#else
-#define CHD_STAMP(idx) do { } while (0)
-#define CHD_STAMP_STEP(s, k) do { } while (0)
-#endif
-
 template <bool DGRAD, bool LATE>
 __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -82,13 +69,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
     const int h0 = thi * TH, w0 = twi * CH_TW, n0 = tn * BN;
     const int nchunks = a.Cs / BF_BK;
     const unsigned lds0 = ring_lds_addr(chd_smem);
-#if (DETR_ABLATE & 64) != 0
-    long long *trl = reinterpret_cast<long long *>(chd_smem + CHD_SMEM);
-    const int tr_sel = blockIdx.x == 0 ? 0 : (blockIdx.x == gridDim.x / 2 ? 1 : (blockIdx.x == gridDim.x - 1 ? 2 : -1));
-    const bool tr_w = tr_sel >= 0 && wave == 0;
-    CHD_STAMP(CHD_TR_STEPS * 3 + 0);
-    if (tr_w && lane == 0) trl[CHD_TR_STEPS * 3 + 4] = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
 
     // ---- patch pieces of this wave: P = wave + 4 i (i < 4); lane -> patch pixel 16 P + lane / 4, slot position lane & 3
     const unsigned long long src_bytes = (unsigned long long)a.N * a.Hs * a.Ws * a.Cs * 2ull;
@@ -177,14 +157,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-            for (int mi = 0; mi < T::TM; ++mi) {
-                if constexpr ((DETR_ABLATE & 16) != 0) fa[kk][mi] = __builtin_bit_cast(bf16x8, make_uint4(lane, mi, kk, 0x3f803f80u));
-                else fa[kk][mi] = *reinterpret_cast<const bf16x8 *>(Pb + (pa[mi] ^ (32 * kk)));
-            }
+            for (int mi = 0; mi < T::TM; ++mi) fa[kk][mi] = *reinterpret_cast<const bf16x8 *>(Pb + (pa[mi] ^ (32 * kk)));
 #pragma unroll
             for (int ni = 0; ni < T::TN; ++ni) {
-                if constexpr ((DETR_ABLATE & 16) != 0) fb[kk][ni] = __builtin_bit_cast(bf16x8, make_uint4(lane, ni, kk, 0x3f803f80u));
-                else if constexpr (!DGRAD) fb[kk][ni] = ring_frag_tr<1>(Bs, btr[ni], kk);
+                if constexpr (!DGRAD) fb[kk][ni] = ring_frag_tr<1>(Bs, btr[ni], kk);
                 else fb[kk][ni] = *reinterpret_cast<const bf16x8 *>(Bs + (brow[ni] ^ (32 * kk)));
             }
         }
@@ -193,10 +169,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
 #pragma unroll
         for (int mi = 0; mi < T::TM; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < T::TN; ++ni) {
-                if constexpr ((DETR_ABLATE & 1) != 0) { ablate_keep(fa[kk][mi]); ablate_keep(fb[kk][ni]); }
-                else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk][mi], fb[kk][ni], acc[mi][ni], 0, 0, 0);
-            }
+            for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk][mi], fb[kk][ni], acc[mi][ni], 0, 0, 0);
     };
 
     // ---- pipeline.  Step s = 9 c + tp reads patch buffer c & 1 and kernel-tile slot tp % 3; during it the wave requests the tile of step
@@ -209,42 +182,32 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
     for (int i = 0; i < 4; ++i) patch_issue(i, 0);
     b_issue(0, 0, 0);
     b_issue(0, 1, 1);
-    CHD_STAMP(CHD_TR_STEPS * 3 + 1);
     for (int c = 0; c < nchunks; ++c) {
 #pragma unroll
         for (int tp = 0; tp < 9; ++tp) {
             constexpr int READS = 2 * T::TM + (DGRAD ? 2 : 4) * T::TN, MF = 2 * T::TM * T::TN;
-            CHD_STAMP_STEP(9 * c + tp, 0);
             if (tp >= 1 && tp <= 4) ring_wait_vmcnt<3>();
             else ring_wait_vmcnt<2>();
-            CHD_STAMP_STEP(9 * c + tp, 1);
-            if constexpr ((DETR_ABLATE & 8) == 0) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            CHD_STAMP_STEP(9 * c + tp, 2);
             auto issue = [&]() {
-                if constexpr ((DETR_ABLATE & 2) == 0) {
-                    int cc = c;
-                    asm volatile("" : "+s"(cc));         // opaque: the descriptors of the nine steps are computed where they are used, not kept in SGPRs
-                    if (tp < 4) patch_issue(tp, cc + 1);
-                    b_issue(cc + (tp + 2) / 9, (tp + 2) % 9, (tp + 2) % NB);
-                }
+                int cc = c;
+                asm volatile("" : "+s"(cc));             // opaque: the descriptors of the nine steps are computed where they are used, not kept in SGPRs
+                if (tp < 4) patch_issue(tp, cc + 1);
+                b_issue(cc + (tp + 2) / 9, (tp + 2) % 9, (tp + 2) % NB);
             };
             if constexpr (!LATE) {
                 issue();
                 read_tap(c & 1, tp % NB, tp);
                 mma_half(0);
                 mma_half(1);
-                if constexpr ((DETR_ABLATE & 17) == 0) {
-                    sgb_ds_read<READS>();
-                    sgb_mfma_block<MF, 0, 0, 0>();
-                }
+                sgb_ds_read<READS>();
+                sgb_mfma_block<MF, 0, 0, 0>();
             } else {
                 read_tap(c & 1, tp % NB, tp);
                 mma_half(0);
-                if constexpr ((DETR_ABLATE & 17) == 0) {
-                    sgb_ds_read<READS>();
-                    sgb_mfma_block<MF / 2, 0, 0, 0>();
-                }
+                sgb_ds_read<READS>();
+                sgb_mfma_block<MF / 2, 0, 0, 0>();
                 __builtin_amdgcn_sched_barrier(0);
                 issue();
                 __builtin_amdgcn_sched_barrier(0);
@@ -253,19 +216,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    CHD_STAMP(CHD_TR_STEPS * 3 + 2);
     ring_wait_vmcnt<0>();                                // the trailing empty requests still write (zeros) into the ring the epilogue reuses
     __syncthreads();
     halo_epilogue<BN, TH, false>(acc, reinterpret_cast<float *>(chd_smem), reinterpret_cast<unsigned short *>(a.dst), a, n, h0, w0, n0, wm, wn, lane, wave);
-#if (DETR_ABLATE & 64) != 0
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    CHD_STAMP(CHD_TR_STEPS * 3 + 3);
-    if (tr_w && lane == 0) trl[CHD_TR_STEPS * 3 + 5] = (long long)__builtin_amdgcn_s_memrealtime();
-    if (tr_w) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int i = lane; i < CHD_TR_N; i += 64) chd_trace[tr_sel][i] = trl[i];
-    }
-#endif
 #endif
 }
 
@@ -277,7 +230,7 @@ static int launch_conv_halo_dma(const ConvArgs &a0, bool dgrad, hipStream_t s) {
     a.tiles_m = a.N * a.Hp * a.Wp;
     a.tiles_n = cdiv(a.Cd, CHD_BN);
     const bool late = tune(T_CONV_DMA) != 3;
-    const int smem = CHD_SMEM + ((DETR_ABLATE & 64) != 0 ? 1024 : 0);
+    const int smem = CHD_SMEM;
     const int k = (dgrad ? 1 : 0) + (late ? 2 : 0);
     const void *fns[4] = {reinterpret_cast<const void *>(conv3x3_halo_dma_bf16_kernel<false, false>), reinterpret_cast<const void *>(conv3x3_halo_dma_bf16_kernel<true, false>),
                           reinterpret_cast<const void *>(conv3x3_halo_dma_bf16_kernel<false, true>), reinterpret_cast<const void *>(conv3x3_halo_dma_bf16_kernel<true, true>)};
@@ -298,9 +251,3 @@ static int launch_conv_halo_dma(const ConvArgs &a0, bool dgrad, hipStream_t s) {
 }
 
 }  // namespace detr
-
-#if (DETR_ABLATE & 64) != 0
-extern "C" int detr_hip_debug_conv_trace(long long *out) {       // experiment builds only: 3 x CHD_TR_N stamps of the last launch
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(detr::chd_trace), sizeof(detr::chd_trace)) == hipSuccess ? 0 : -1;
-}
-#endif

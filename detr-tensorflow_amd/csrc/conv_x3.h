@@ -143,7 +143,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 2 : (BM * BN
 #pragma unroll
             for (int mi = 0; mi < T::TM; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma<DETR_SPLIT3_TERMS>(fa[mi], fb[ni], acc[mi][ni]);
+                for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma(fa[mi], fb[ni], acc[mi][ni]);
         }
         lds_barrier();
     }
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 2 : 4) void 
 #pragma unroll
             for (int mi = 0; mi < T::TM; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma<DETR_SPLIT3_TERMS>(fa[mi], fb[ni], acc[mi][ni]);
+                for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma(fa[mi], fb[ni], acc[mi][ni]);
         }
         lds_barrier();
     }

@@ -313,7 +313,7 @@ __device__ __forceinline__ bf16x8 frag_tr(const unsigned short (*S)[LD], int row
     return __builtin_bit_cast(bf16x8, v);
 }
 
-// ---- explicitly pipelined K tile (round 4; DETR_KLOOP_PIPE) -----------------------------------------------------------------
+// ---- explicitly pipelined K tile (round 4) -----------------------------------------------------------------------------------
 // SQ counters of the split-K weight-gradient launches (one 4-wave workgroup per CU = ONE wave per SIMD, profiles/r03_rocprofv3_pmc_sq_bf16.txt):
 // a K tile costs a wave ~2500 cycles for 512 cycles of MFMA -- 37 % issuing, 33 % parked on s_waitcnt, 30 % issue stalls -- because
 // the compiler's order is [LDS stores of the next tile] -> [fragment reads] -> wait -> [MFMAs], i.e. every phase's latency is exposed
@@ -393,23 +393,18 @@ __device__ __forceinline__ void mma_ktile_bf16(const unsigned short (*As)[BK + 8
         bf16x8 a[T::TM], b[T::TN];
 #pragma unroll
         for (int mi = 0; mi < T::TM; ++mi) {
-            if constexpr ((DETR_ABLATE & 16) != 0) a[mi] = __builtin_bit_cast(bf16x8, make_uint4(lane, mi, ks, 0x3f803f80u));
-            else if (ATR) a[mi] = frag_tr<BM>(As, wm * T::WTM + mi * 32, ks, lane);
+            if (ATR) a[mi] = frag_tr<BM>(As, wm * T::WTM + mi * 32, ks, lane);
             else a[mi] = *reinterpret_cast<const bf16x8 *>(&As[wm * T::WTM + mi * 32 + l31][ks + kh]);
         }
 #pragma unroll
         for (int ni = 0; ni < T::TN; ++ni) {
-            if constexpr ((DETR_ABLATE & 16) != 0) b[ni] = __builtin_bit_cast(bf16x8, make_uint4(lane, ni, ks, 0x3f803f80u));
-            else if (BTR) b[ni] = frag_tr<BN>(Bs, wn * T::WTN + ni * 32, ks, lane);
+            if (BTR) b[ni] = frag_tr<BN>(Bs, wn * T::WTN + ni * 32, ks, lane);
             else b[ni] = *reinterpret_cast<const bf16x8 *>(&Bs[wn * T::WTN + ni * 32 + l31][ks + kh]);
         }
 #pragma unroll
         for (int mi = 0; mi < T::TM; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < T::TN; ++ni) {
-                if constexpr ((DETR_ABLATE & 1) != 0) { ablate_keep(a[mi]); ablate_keep(b[ni]); }
-                else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-            }
+            for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
     }
 }
 

@@ -44,7 +44,7 @@ struct EpiArgs {
     // (n, h2, w2) addresses pixel (n, 2*h2 + remap_ph, 2*w2 + remap_pw) of the [.., remap_H, remap_W, N] tensors
     // C / residual / mask.  remap_w2 == 0: identity.
     int remap_w2 = 0, remap_h2 = 0, remap_W = 0, remap_H = 0, remap_ph = 0, remap_pw = 0;
-    // bf16 STORAGE of the activation tensors (backbone, DETR_HIP_ACT16): C / residual / mask are bf16 in memory (uint16,
+    // bf16 STORAGE of the activation tensors (backbone, bf16 compute): C / residual / mask are bf16 in memory (uint16,
     // leading dimensions in elements); the arithmetic of the epilogue stays fp32, the result is rounded once (RNE)
     int c16 = 0, r16 = 0, m16 = 0;
     const uint32_t *drop_step = nullptr;
@@ -353,11 +353,7 @@ __device__ __forceinline__ f32x2_t bf16_pair_to_f32(unsigned p) {
 }
 // (x[0], x[1]) -> the three bf16 pairs h, m, l with x = h + m + l exactly; 9 VALU instructions per pair (3 conversions, 4 unpack
 // shifts / masks, 2 v_pk_add_f32)
-#ifndef DETR_X3_ABLATE
-#define DETR_X3_ABLATE 0         // timing experiments (results wrong): 1 = one MFMA term of six, 2 = no split arithmetic, 4 = no loop requests
-#endif
 __device__ __forceinline__ void split3_pair(f32x2_t x, unsigned &h, unsigned &m, unsigned &l) {
-    if constexpr ((DETR_X3_ABLATE & 2) != 0) { h = cvt_pk_bf16_asm(x); m = h; l = h; return; }
     h = cvt_pk_bf16_asm(x);
     f32x2_t r = x - bf16_pair_to_f32(h);
     m = cvt_pk_bf16_asm(r);
@@ -374,16 +370,8 @@ __device__ __forceinline__ Split3Frag split3_frag(const f32x2_t (&f)[4]) {
     r.l = __builtin_bit_cast(bf16x8_t, make_uint4(l[0], l[1], l[2], l[3]));
     return r;
 }
-// the product terms of one 32x32x16 block, smallest first
-template <int NT>
+// the six product terms of one 32x32x16 block, smallest first
 __device__ __forceinline__ f32x16 split3_mma(const Split3Frag &a, const Split3Frag &b, f32x16 c) {
-    static_assert(NT == 6 || NT == 9, "6 or 9 product terms");
-    if constexpr ((DETR_X3_ABLATE & 1) != 0) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, c, 0, 0, 0);
-    if constexpr (NT == 9) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.l, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.l, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.m, c, 0, 0, 0);
-    }
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, c, 0, 0, 0);
@@ -392,10 +380,7 @@ __device__ __forceinline__ f32x16 split3_mma(const Split3Frag &a, const Split3Fr
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, c, 0, 0, 0);
     return c;
 }
-#ifndef DETR_SPLIT3_TERMS
-#define DETR_SPLIT3_TERMS 6
-#endif
-template <int BM, int BN, int WGM, int WGN, int NT = DETR_SPLIT3_TERMS>
+template <int BM, int BN, int WGM, int WGN>
 __device__ __forceinline__ void mma_ktile_split3(const float (*As)[BM + GEMM_PAD], const float (*Bs)[BN + GEMM_PAD],
                                                  f32x16 (&acc)[TileCfg<BM, BN, WGM, WGN>::TM][TileCfg<BM, BN, WGM, WGN>::TN],
                                                  int wm, int wn, int lane) {
@@ -425,13 +410,13 @@ __device__ __forceinline__ void mma_ktile_split3(const float (*As)[BM + GEMM_PAD
 #pragma unroll
     for (int ni = 0; ni < T::TN; ++ni) {
         b[ni] = split3_frag(fb[ni]);
-        acc[0][ni] = split3_mma<NT>(a[0], b[ni], acc[0][ni]);
+        acc[0][ni] = split3_mma(a[0], b[ni], acc[0][ni]);
     }
 #pragma unroll
     for (int mi = 1; mi < T::TM; ++mi) {
         a[mi] = split3_frag(fa[mi]);
 #pragma unroll
-        for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma<NT>(a[mi], b[ni], acc[mi][ni]);
+        for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma(a[mi], b[ni], acc[mi][ni]);
     }
 }
 // K tile of the fp32-storage kernels: exact fp32 MFMA, or the 3-way bf16 split (SPLIT3)
@@ -481,20 +466,8 @@ __device__ __forceinline__ float epi_one(float v, float sc, float bi, const EpiA
 // (16-byte bf16 accesses, a wave instruction covers whole 128 / 256-byte row segments), the residual and mask rows of ALL passes
 // of a 32-row strip are requested before the accumulators are even staged, and the per-column scale / bias are loaded once.
 // The arithmetic per element is epi_one, unchanged: results are bit-identical to the 4-column form.
-// residual / mask operands of the wide epilogues: read once by the launch.  DETR_EPI_NT = 1 requests them non-temporal (A/B builds; the streaming
-// kernel gained 0.2 ms from the same hint, gemm_stream.h)
-#ifndef DETR_EPI_NT
-#define DETR_EPI_NT 0
-#endif
-__device__ __forceinline__ uint4 epi_ld16(const unsigned short *p) {
-#if DETR_EPI_NT
-    typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-    const u32x4v v = __builtin_nontemporal_load(reinterpret_cast<const u32x4v *>(p));
-    return make_uint4(v[0], v[1], v[2], v[3]);
-#else
-    return *reinterpret_cast<const uint4 *>(p);
-#endif
-}
+// residual / mask operands of the wide epilogues (read once by the launch)
+__device__ __forceinline__ uint4 epi_ld16(const unsigned short *p) { return *reinterpret_cast<const uint4 *>(p); }
 template <int BM, int BN, int WGM, int WGN>
 __device__ __forceinline__ void epilogue_wide16(const f32x16 (&acc)[TileCfg<BM, BN, WGM, WGN>::TM][TileCfg<BM, BN, WGM, WGN>::TN],
                                                 float *stage_base, float *C, long long ldc, int M, int N, int m0, int n0,

@@ -252,12 +252,11 @@ __device__ __forceinline__ void gemm_bf16c_body(const GemmArgs &g, const int id,
     LB lb;
     la.init(A, g.lda, m0, g.M, g.K, g.a_vec != 0, tid);
     lb.init(B, g.ldb, n0, g.N, g.K, g.b_vec != 0, tid);
-    if constexpr (DETR_KLOOP_PIPE != 0 && DETR_ABLATE == 0) {       // per-tile descriptors of the bf16-storage loaders
-        if constexpr (A16 && AK) la.init_tiles(A, g.lda, g.M, g.K);
-        if constexpr (A16 && !AK) la.init_tiles(A, g.lda, kend);
-        if constexpr (B16 && BKC) lb.init_tiles(B, g.ldb, g.N, g.K);
-        if constexpr (B16 && !BKC) lb.init_tiles(B, g.ldb, kend);
-    }
+    // per-tile descriptors of the bf16-storage loaders
+    if constexpr (A16 && AK) la.init_tiles(A, g.lda, g.M, g.K);
+    if constexpr (A16 && !AK) la.init_tiles(A, g.lda, kend);
+    if constexpr (B16 && BKC) lb.init_tiles(B, g.ldb, g.N, g.K);
+    if constexpr (B16 && !BKC) lb.init_tiles(B, g.ldb, kend);
     f32x16 acc[T::TM][T::TN];
 #pragma unroll
     for (int i = 0; i < T::TM; ++i)
@@ -312,7 +311,7 @@ __device__ __forceinline__ void gemm_bf16c_body(const GemmArgs &g, const int id,
         if (do_rs && kt + 1 < kt1) rs_add(rpa);
         // (128x128 tiles with an fp32-storage operand keep the compiler's order: their 168-register budget has no room for the
         //  second fragment set -- the pipelined form spilled up to 360 bytes there; no launch of the step uses them)
-        if constexpr (DETR_KLOOP_PIPE != 0 && DETR_ABLATE == 0 && ((A16 && B16) || BM * BN < 128 * 128)) {
+        if constexpr ((A16 && B16) || BM * BN < 128 * 128) {
             // explicitly pipelined iteration (gemm_bf16_core.h: KPipe): same stores, requests and MFMA order per accumulator
             using P = KPipe<BM, BN, WGM, WGN, !AK, !BKC, BK>;
             typename P::Frags f0, f1;
@@ -346,22 +345,12 @@ __device__ __forceinline__ void gemm_bf16c_body(const GemmArgs &g, const int id,
             lds_barrier();
             return;
         }
-        if constexpr ((DETR_ABLATE & 4) == 0) {
-            la.store(sm.A[cur ^ 1], rpa);          // (unconditional as well: after the last tile it writes a buffer nobody reads)
-            lb.store(sm.B[cur ^ 1], rpb);
-        } else {
-            for (int i = 0; i < NRA; ++i) ablate_keep(rpa[i]);
-            for (int i = 0; i < NRB; ++i) ablate_keep(rpb[i]);
-        }
-        if constexpr ((DETR_ABLATE & 2) == 0) {
-            la.load(kbeg + (kt + 1 + DEPTH) * BK, kend, rpa);
-            lb.load(kbeg + (kt + 1 + DEPTH) * BK, kend, rpb);
-        }
+        la.store(sm.A[cur ^ 1], rpa);              // (unconditional as well: after the last tile it writes a buffer nobody reads)
+        lb.store(sm.B[cur ^ 1], rpb);
+        la.load(kbeg + (kt + 1 + DEPTH) * BK, kend, rpa);
+        lb.load(kbeg + (kt + 1 + DEPTH) * BK, kend, rpb);
         mma_ktile_bf16<BM, BN, WGM, WGN, !AK, !BKC, BK>(sm.A[cur], sm.B[cur], acc, wm, wn, lane);
-#ifdef DETR_IGLP
-        __builtin_amdgcn_iglp_opt(DETR_IGLP);
-#endif
-        if constexpr ((DETR_ABLATE & 8) == 0) lds_barrier();
+        lds_barrier();
     };
     {   // whole pairs in the loop, an odd last tile after it: every path into the loop header carries the same
         // sequence of outstanding requests, so the compiler's vmcnt waits are exact (vmcnt(2) / vmcnt(3) before the stores)
@@ -390,7 +379,7 @@ __device__ __forceinline__ void gemm_bf16c_body(const GemmArgs &g, const int id,
 }
 
 template <int BM, int BN, int WGM, int WGN, bool AK, bool BKC, bool A16, bool B16>
-__global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : (BM * BN == 64 * 64 ? DETR_GEMM64_MINW : 1)) void gemm_bf16c_kernel(GemmArgs g) {
+__global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : (BM * BN == 64 * 64 ? MIN_WAVES_64X64 : 1)) void gemm_bf16c_kernel(GemmArgs g) {
     int tile, z;
     gemm_work_item(g, tile, z);
     gemm_bf16c_body<BM, BN, WGM, WGN, AK, BKC, A16, B16>(g, tile, z);
@@ -413,7 +402,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16c_ln_kernel(GemmArgs
 //  LDS, 2 workgroups per CU; bit-identical: M8400 N256 K2048 34.7 -> 40.2 us, M8400 N512 K2048 42.3 -> 50.3 us.  Not kept: these
 //  launches are bound by the bytes their tiles pull out of L2, not by the number of iterations -- NOTEBOOK 7c.)
 template <int BM, int BN, int WGM, int WGN, bool AK, bool BKC, bool A16, bool B16>
-__global__ __launch_bounds__(GEMM_THREADS, (BM * BN == 64 * 64) ? DETR_GEMM64_MINW : 1) void gemm_bf16c_group_kernel(GemmGroupArgs G) {
+__global__ __launch_bounds__(GEMM_THREADS, (BM * BN == 64 * 64) ? MIN_WAVES_64X64 : 1) void gemm_bf16c_group_kernel(GemmGroupArgs G) {
     int m, tile, z;
     if (!gemm_group_item(G, m, tile, z)) return;
     gemm_bf16c_body<BM, BN, WGM, WGN, AK, BKC, A16, B16>(G.g[m], tile, z);

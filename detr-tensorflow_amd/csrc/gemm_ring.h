@@ -44,9 +44,6 @@ struct RingArgs {
     int a_rows8;         // rows of the A stage image: tile_rows rounded up to a DMA piece (8 rows)
     int stage_bytes;     // a_rows8 * 128 + BN * 128
     int dump_off;        // byte offset of the 1 KB dump area behind the ring (pieces past the A image land there)
-    int trace_off;       // -DDETR_ABLATE=64 builds: byte offset of the 1 KB timeline area behind everything else (scripts/experiments/ring_trace.py)
-    int ablate;          // timing experiments only (DETR_HIP_RING_ABLATE; results are WRONG with any bit set): 1 no fragment reads / MFMAs,
-                         // 2 no A requests, 4 no B requests, 8 no epilogue, 16 no K loop at all
 };
 
 // host side (gemm_ring.hip)
@@ -63,18 +60,6 @@ int gemm_ring_launch(const GemmArgs &g, bool b_kcontig, const RingPlan &p, hipSt
 // fp32 form (exact-f32 parity mode): plan for MFMA-bound work (whole 32-row blocks, per-CU balance), launch
 bool gemm_ring_f32_plan(int M, int N, int K, RingPlan &p);
 int gemm_ring_f32_launch(const GemmArgs &g, bool b_kcontig, const RingPlan &p, hipStream_t s);
-
-#if (DETR_ABLATE & 64) != 0
-// timeline experiment: wave 0 of three workgroups stamps s_memtime in front of the counted wait of every K stage, in front of the barrier and
-// behind it; [workgroup][40 stages x 3 + kernel start, loop start, loop end, kernel end, 100 MHz counter at kernel start / end]
-constexpr int RING_TR_STEPS = 40, RING_TR_N = RING_TR_STEPS * 3 + 6;
-extern __device__ long long ring_trace[3][RING_TR_N];
-#define RING_STAMP(idx) do { if (tr_w) { const long long t_ = __builtin_readcyclecounter(); if (lane == 0) trl[(idx)] = t_; } } while (0)
-#define RING_STAMP_STEP(s, k) do { if ((s) < RING_TR_STEPS) RING_STAMP((s) * 3 + (k)); } while (0)
-#else
-#define RING_STAMP(idx) do { } while (0)
-#define RING_STAMP_STEP(s, k) do { } while (0)
-#endif
 
 template <int N>
 __device__ __forceinline__ void ring_wait_vmcnt() {
@@ -93,10 +78,6 @@ __device__ __forceinline__ void ring_wait_vmcnt() {
 __device__ __forceinline__ void ring_dma_piece(u32x4 rs, unsigned lds_addr, unsigned voff) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds_addr), "v"(voff), "s"(rs) : "memory", "m0");
 }
-// the same request with the non-temporal hint (a stream that is read once: experiment DETR_HIP_RING_NT)
-__device__ __forceinline__ void ring_dma_piece_nt(u32x4 rs, unsigned lds_addr, unsigned voff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen nt lds" ::"s"(lds_addr), "v"(voff), "s"(rs) : "memory", "m0");
-}
 __device__ __forceinline__ u32x4 ring_rsrc(const void *base, unsigned bytes) {
     const unsigned long long b = (unsigned long long)base;
     u32x4 r;
@@ -112,13 +93,7 @@ __device__ __forceinline__ unsigned ring_lds_addr(char *p) {      // LDS byte ad
 
 // K-contiguous operand [rows][k]: piece P = rows 8P .. 8P+7 of the stage image, lane (r = lane / 8, slot position lane % 8)
 // ES: bytes per element (2: bf16, 64-deep stages; 4: fp32, 32-deep stages -- a stage row is 128 bytes either way)
-#ifndef DETR_RING_ISSUE_STEPS
-#define DETR_RING_ISSUE_STEPS 4   // k-steps of a stage (of 4) that carry its DMA requests (A/B builds: 1, 2, 3)
-#endif
-#ifndef DETR_RING_NT
-#define DETR_RING_NT 0          // 1: the A requests of gemm_ring_kernel carry the non-temporal hint (A/B builds, scripts/experiments)
-#endif
-template <int NP, int ES = 2, bool NT = false>
+template <int NP, int ES = 2>
 struct RingDmaK {
     static constexpr int NPIECES = NP;
     const char *base;
@@ -152,8 +127,7 @@ struct RingDmaK {
     // which cut the stage into several basic blocks).
     __device__ __forceinline__ void issue_one(const int I, u32x4 rs, unsigned lds0, int img, int dump) const {
         const int off = dump + (in_img[I] & (img + lds_off[I] - dump));      // wave-uniform
-        if constexpr (NT) ring_dma_piece_nt(rs, lds0 + (unsigned)off, voff[I]);
-        else ring_dma_piece(rs, lds0 + (unsigned)off, voff[I]);
+        ring_dma_piece(rs, lds0 + (unsigned)off, voff[I]);
     }
     __device__ __forceinline__ void issue(int k0, int K, unsigned lds0, int img, int dump) const {
         const u32x4 rs = stage_rsrc(k0, K);
@@ -237,19 +211,18 @@ __device__ __forceinline__ bf16x8 ring_frag_tr(const char *img, int lane_off, in
 // part.  Now k-step kk carries the pieces [kk PW / 4, (kk + 1) PW / 4) in front of its MFMAs and the fragments of k-step kk + 1 are read
 // before the MFMAs of kk (sched_group_barrier pins reads against MFMAs).
 template <int IDX, int P0, int P1, int NPA_, class LA, class LB>
-__device__ __forceinline__ void ring_issue_range(const LA &la, const LB &lb, u32x4 rsa, u32x4 rsb, unsigned lds0, int ia, int ib, int dump, int abl) {
+__device__ __forceinline__ void ring_issue_range(const LA &la, const LB &lb, u32x4 rsa, u32x4 rsb, unsigned lds0, int ia, int ib, int dump) {
     if constexpr (IDX < P1) {
         if constexpr (IDX >= P0) {
-            if constexpr (IDX < NPA_) { if (!(abl & 2)) la.issue_one(IDX, rsa, lds0, ia, dump); }
-            else { if (!(abl & 4)) lb.issue_one(IDX - NPA_, rsb, lds0, ib, dump); }
+            if constexpr (IDX < NPA_) la.issue_one(IDX, rsa, lds0, ia, dump);
+            else lb.issue_one(IDX - NPA_, rsb, lds0, ib, dump);
         }
-        ring_issue_range<IDX + 1, P0, P1, NPA_>(la, lb, rsa, rsb, lds0, ia, ib, dump, abl);
+        ring_issue_range<IDX + 1, P0, P1, NPA_>(la, lb, rsa, rsb, lds0, ia, ib, dump);
     }
 }
-template <int NM, int TM, int TN, bool AKC, bool BKC, bool ABL, class LA, class LB>
+template <int NM, int TM, int TN, bool AKC, bool BKC, class LA, class LB>
 __device__ __forceinline__ void ring_stage(const char *As, const char *Bs, f32x16 (&acc)[TM][TN], int a_lane, const int (&atr)[TM], int b_lane, const int (&btr)[TN],
-                                           const int (&xo)[4], const LA &la, const LB &lb, int k_next, int K, unsigned lds0, int na, int nb, int dump,
-                                           int abl) {
+                                           const int (&xo)[4], const LA &la, const LB &lb, int k_next, int K, unsigned lds0, int na, int nb, int dump) {
     const u32x4 rsa = la.stage_rsrc(k_next, K), rsb = lb.stage_rsrc(k_next, K);
     constexpr int NPA = TM, NPB = 2 * TN, PW = NPA + NPB;
     constexpr int READS = NM * (AKC ? 1 : 2) + TN * (BKC ? 1 : 2), MF = NM * TN;
@@ -267,33 +240,19 @@ __device__ __forceinline__ void ring_stage(const char *As, const char *Bs, f32x1
         }
     };
     if constexpr (NM == 0) {             // a row wave without rows in this tile: it still issues its share of the requests
-        ring_issue_range<0, 0, PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, abl);
+        ring_issue_range<0, 0, PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
         return;
     } else {
-        if constexpr (ABL) {             // timing experiments (DETR_HIP_RING_ABLATE): requests up front, under their switches; plain k-steps
-            ring_issue_range<0, 0, PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, abl);
-            if (abl & 1) return;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                read(kk, 0);
-#pragma unroll
-                for (int mi = 0; mi < NM; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < TN; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][mi], b[0][ni], acc[mi][ni], 0, 0, 0);
-            }
-            return;
-        } else {
         read(0, 0);
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             if (kk + 1 < 4) read(kk + 1, (kk + 1) & 1);
-            // the stage's requests go out during its first RING_ISSUE_STEPS k-steps (a two-stage ring waits for ALL of them at the top of the
-            // next stage: what is requested in the last k-step has its whole latency exposed there -- profiles/r05_ring_trace.txt)
-            constexpr int IS = DETR_RING_ISSUE_STEPS;
-            if (kk == 0) ring_issue_range<0, (0 * PW) / IS, (1 * PW) / IS, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
-            if (kk == 1 && IS >= 2) ring_issue_range<0, (1 * PW) / IS, (IS >= 2 ? (2 * PW) / IS : PW), NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
-            if (kk == 2 && IS >= 3) ring_issue_range<0, (IS >= 3 ? (2 * PW) / IS : PW), (IS >= 3 ? (3 * PW) / IS : PW), NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
-            if (kk == 3 && IS >= 4) ring_issue_range<0, (IS >= 4 ? (3 * PW) / IS : PW), PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
+            // a quarter of the stage's requests per k-step (a two-stage ring waits for ALL of them at the top of the next stage: what is
+            // requested in the last k-step has its whole latency exposed there -- profiles/r05_ring_trace.txt)
+            if (kk == 0) ring_issue_range<0, 0, PW / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
+            if (kk == 1) ring_issue_range<0, PW / 4, (2 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
+            if (kk == 2) ring_issue_range<0, (2 * PW) / 4, (3 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
+            if (kk == 3) ring_issue_range<0, (3 * PW) / 4, PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
 #pragma unroll
             for (int mi = 0; mi < NM; ++mi)
 #pragma unroll
@@ -309,7 +268,6 @@ __device__ __forceinline__ void ring_stage(const char *As, const char *Bs, f32x1
         sgb_ds_read<READS>();
         sgb_mfma_block<MF, 0, 0, 0>();
         sgb_mfma_block<MF, 0, 0, 0>();
-        }
     }
 }
 template <int TM, int TN, bool BKC, int NS>
@@ -330,7 +288,7 @@ __device__ __forceinline__ void gemm_ring_body(const RingArgs &ra, const int id)
     const int nmi = my_rows <= 0 ? 0 : (my_rows >= T::WTM ? TM : (my_rows + 31) >> 5);
 
     constexpr int NPA = TM, NPB = 2 * TN, PW = NPA + NPB;            // DMA pieces per wave and stage
-    RingDmaK<NPA, 2, DETR_RING_NT != 0> la;
+    RingDmaK<NPA> la;
     la.init(g.A, g.lda, m0, row_end, g.M, g.K, ra.a_rows8, lane, wave);
     using LB = typename std::conditional<BKC, RingDmaK<NPB>, RingDmaMN<BN>>::type;
     LB lb;
@@ -364,70 +322,35 @@ __device__ __forceinline__ void gemm_ring_body(const RingArgs &ra, const int id)
     for (int ni = 0; ni < TN; ++ni) btr[ni] = ring_tr_lane_off<TN>(wn * T::WTN + ni * 32, lane);
 
     const int nkt = g.K / RING_BK;
-    const int abl = ra.ablate;                          // (kernel argument: uniform)
-#if (DETR_ABLATE & 64) != 0
-    long long *trl = reinterpret_cast<long long *>(ring_smem + ra.trace_off);
-    const int tr_sel = blockIdx.x == 0 ? 0 : (blockIdx.x == gridDim.x / 2 ? 1 : (blockIdx.x == gridDim.x - 1 ? 2 : -1));
-    const bool tr_w = tr_sel >= 0 && wave == 0;
-    RING_STAMP(RING_TR_STEPS * 3 + 0);
-    if (tr_w && lane == 0) trl[RING_TR_STEPS * 3 + 4] = (long long)__builtin_amdgcn_s_memrealtime();
-#endif
 #pragma unroll
     for (int t = 0; t < NS - 1; ++t) {
-        if (!(abl & 2)) la.issue(t * RING_BK, g.K, lds0, stage_a(t), dump);
-        if (!(abl & 4)) lb.issue(t * RING_BK, g.K, lds0, stage_b(t), dump);
+        la.issue(t * RING_BK, g.K, lds0, stage_a(t), dump);
+        lb.issue(t * RING_BK, g.K, lds0, stage_b(t), dump);
     }
     // The K loop exists once per block count NM a wave can have (chosen ONCE, outside the loop: a per-stage switch made the
     // compiler shuffle all accumulators between the branches' register assignments every iteration)
-    auto kloop_ab = [&](auto NMC, auto ABLC) {
+    auto kloop = [&](auto NMC) {
         constexpr int NM = decltype(NMC)::value;
-        constexpr bool ABL = decltype(ABLC)::value;
         int cur = 0, nxt = NS - 1;                      // ring slots of stage t and of stage t + NS - 1
-        for (int t = 0; t < ((abl & 16) ? 0 : nkt); ++t) {
-            RING_STAMP_STEP(t, 0);
+        for (int t = 0; t < nkt; ++t) {
             ring_wait_vmcnt<(NS - 2) * PW>();
-            RING_STAMP_STEP(t, 1);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            RING_STAMP_STEP(t, 2);
-            ring_stage<NM, TM, TN, true, BKC, ABL>(ring_smem + stage_a(cur), ring_smem + stage_b(cur), acc, a_lane, atr_unused, b_lane, btr, xo, la, lb,
-                                             (t + NS - 1) * RING_BK, g.K, lds0, stage_a(nxt), stage_b(nxt), dump, abl);
+            ring_stage<NM, TM, TN, true, BKC>(ring_smem + stage_a(cur), ring_smem + stage_b(cur), acc, a_lane, atr_unused, b_lane, btr, xo, la, lb,
+                                              (t + NS - 1) * RING_BK, g.K, lds0, stage_a(nxt), stage_b(nxt), dump);
             __builtin_amdgcn_sched_barrier(0);
             cur = (cur + 1 == NS) ? 0 : cur + 1;
             nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
         }
     };
-    // (the ablation form of the loop is a separate loop as well: a run-time switch inside the loop body costs the accumulator shuffle again)
-    auto kloop = [&](auto NMC) {
-        if (abl) kloop_ab(NMC, std::integral_constant<bool, true>{});
-        else kloop_ab(NMC, std::integral_constant<bool, false>{});
-    };
-    RING_STAMP(RING_TR_STEPS * 3 + 1);
     if (nmi == TM) kloop(std::integral_constant<int, TM>{});
     else if (TM >= 2 && nmi == TM - 1) kloop(std::integral_constant<int, (TM >= 2 ? TM - 1 : 0)>{});
     else if (TM >= 3 && nmi == TM - 2) kloop(std::integral_constant<int, (TM >= 3 ? TM - 2 : 0)>{});
     else if (TM >= 4 && nmi == TM - 3) kloop(std::integral_constant<int, (TM >= 4 ? TM - 3 : 0)>{});
     else kloop(std::integral_constant<int, 0>{});
-    RING_STAMP(RING_TR_STEPS * 3 + 2);
     ring_wait_vmcnt<0>();                               // the trailing empty requests still write (zeros) into the ring:
     __syncthreads();                                    // nobody reuses the array (epilogue staging) before they have landed
-    if (abl & 8) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) ablate_keep(acc[i][j]);
-        return;
-    }
     epilogue<BM, BN, WGM, WGN>(acc, reinterpret_cast<float *>(ring_smem), g.C, g.ldc, row_end, g.N, m0, n0, wm, wn, lane, wave, g.e);
-#if (DETR_ABLATE & 64) != 0
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    RING_STAMP(RING_TR_STEPS * 3 + 3);
-    if (tr_w && lane == 0) trl[RING_TR_STEPS * 3 + 5] = (long long)__builtin_amdgcn_s_memrealtime();
-    if (tr_w) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int i = lane; i < RING_TR_N; i += 64) ring_trace[tr_sel][i] = trl[i];
-    }
-#endif
 }
 
 template <int TM, int TN, bool BKC, int NS>
@@ -492,19 +415,15 @@ struct RingDmaMN32 {       // [k][mn] fp32: piece = 1 KB = 256 floats = 256 / BM
 };
 
 // one 32-deep fp32 stage: NM x TN accumulators x 16 MFMA steps; the requests of the stage NS - 1 ahead ride between the k groups
-template <int NM, int TM, int TN, bool AKC, bool BKC, int BM, int BN, bool ABL, class LA, class LB>
+template <int NM, int TM, int TN, bool AKC, bool BKC, int BM, int BN, class LA, class LB>
 __device__ __forceinline__ void ring_stage_f32(const char *As, const char *Bs, f32x16 (&acc)[TM][TN], int a_lane, int b_lane, const int (&xo8)[8],
-                                               int h, const LA &la, const LB &lb, int k_next, int K, unsigned lds0, int na, int nb, int dump, int abl) {
+                                               int h, const LA &la, const LB &lb, int k_next, int K, unsigned lds0, int na, int nb, int dump) {
     constexpr int NPA = LA::NPIECES, NPB = LB::NPIECES, PW = NPA + NPB;
     const u32x4 rsa = la.stage_rsrc(k_next, K), rsb = lb.stage_rsrc(k_next, K);
     if constexpr (NM == 0) {
-        ring_issue_range<0, 0, PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, ABL ? abl : 0);
+        ring_issue_range<0, 0, PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
         return;
     } else {
-        if constexpr (ABL) {             // timing experiments: requests up front under their switches; bit 0: no fragment reads / MFMAs
-            ring_issue_range<0, 0, PW, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, abl);
-            if (abl & 1) return;
-        }
 #pragma unroll
         for (int gq = 0; gq < 8; ++gq) {                 // k group of 4: two MFMA steps
             float av[2][NM], bv[2][TN];
@@ -530,12 +449,10 @@ __device__ __forceinline__ void ring_stage_f32(const char *As, const char *Bs, f
                     bv[1][ni] = *reinterpret_cast<const float *>(Bs + b_lane + ni * 128 + (4 * gq + 2) * (BN * 4));
                 }
             }
-            if constexpr (!ABL) {
-                if (gq == 1) ring_issue_range<0, (0 * PW) / 4, (1 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
-                if (gq == 3) ring_issue_range<0, (1 * PW) / 4, (2 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
-                if (gq == 5) ring_issue_range<0, (2 * PW) / 4, (3 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
-                if (gq == 7) ring_issue_range<0, (3 * PW) / 4, (4 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump, 0);
-            }
+            if (gq == 1) ring_issue_range<0, (0 * PW) / 4, (1 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
+            if (gq == 3) ring_issue_range<0, (1 * PW) / 4, (2 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
+            if (gq == 5) ring_issue_range<0, (2 * PW) / 4, (3 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
+            if (gq == 7) ring_issue_range<0, (3 * PW) / 4, (4 * PW) / 4, NPA>(la, lb, rsa, rsb, lds0, na, nb, dump);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -590,30 +507,24 @@ __device__ __forceinline__ void gemm_ring_f32_body(const RingArgs &ra, const int
     // [n][k]: row of the column block; [k][n]: dword (wn * WTN + l31) of image row h (the MFMA's k = 2 s + h)
     const int b_lane = BKC ? (wn * T::WTN + l31) * RING_STAGE_ROW : (wn * T::WTN + l31) * 4 + h * (BN * 4);
     const int nkt = g.K / BKF;
-    const int abl = ra.ablate;
 #pragma unroll
     for (int t = 0; t < NS - 1; ++t) {
-        if (!(abl & 2)) la.issue(t * BKF, g.K, lds0, stage_a(t), dump);
-        if (!(abl & 4)) lb.issue(t * BKF, g.K, lds0, stage_b(t), dump);
+        la.issue(t * BKF, g.K, lds0, stage_a(t), dump);
+        lb.issue(t * BKF, g.K, lds0, stage_b(t), dump);
     }
-    auto kloop_ab = [&](auto NMC, auto ABLC) {
+    auto kloop = [&](auto NMC) {
         constexpr int NM = decltype(NMC)::value;
-        constexpr bool ABL = decltype(ABLC)::value;
         int cur = 0, nxt = NS - 1;
-        for (int t = 0; t < ((abl & 16) ? 0 : nkt); ++t) {
+        for (int t = 0; t < nkt; ++t) {
             ring_wait_vmcnt<(NS - 2) * PW>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            ring_stage_f32<NM, TM, TN, true, BKC, BM, BN, ABL>(ring_smem + stage_a(cur), ring_smem + stage_b(cur), acc, a_lane, b_lane, xo8, h, la, lb,
-                                                               (t + NS - 1) * BKF, g.K, lds0, stage_a(nxt), stage_b(nxt), dump, abl);
+            ring_stage_f32<NM, TM, TN, true, BKC, BM, BN>(ring_smem + stage_a(cur), ring_smem + stage_b(cur), acc, a_lane, b_lane, xo8, h, la, lb,
+                                                          (t + NS - 1) * BKF, g.K, lds0, stage_a(nxt), stage_b(nxt), dump);
             __builtin_amdgcn_sched_barrier(0);
             cur = (cur + 1 == NS) ? 0 : cur + 1;
             nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
         }
-    };
-    auto kloop = [&](auto NMC) {
-        if (abl) kloop_ab(NMC, std::integral_constant<bool, true>{});
-        else kloop_ab(NMC, std::integral_constant<bool, false>{});
     };
     if (nmi == TM) kloop(std::integral_constant<int, TM>{});
     else if (TM >= 2 && nmi == TM - 1) kloop(std::integral_constant<int, (TM >= 2 ? TM - 1 : 0)>{});
@@ -622,13 +533,6 @@ __device__ __forceinline__ void gemm_ring_f32_body(const RingArgs &ra, const int
     else kloop(std::integral_constant<int, 0>{});
     ring_wait_vmcnt<0>();
     __syncthreads();
-    if (abl & 8) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) ablate_keep(acc[i][j]);
-        return;
-    }
     epilogue<BM, BN, WGM, WGN, false>(acc, reinterpret_cast<float *>(ring_smem), g.C, g.ldc, row_end, g.N, m0, n0, wm, wn, lane, wave, g.e);
 }
 
@@ -694,23 +598,17 @@ __device__ __forceinline__ void gemm_ring_wgrad_body(const RingArgs &ra) {
         la.issue(kbeg + t * RING_BK, kend, lds0, t * STAGE, 0);
         lb.issue(kbeg + t * RING_BK, kend, lds0, t * STAGE + A_BYTES, 0);
     }
-    const int abl = ra.ablate;
-    auto kloop = [&](auto ABLC) {
-        constexpr bool ABL = decltype(ABLC)::value;
-        int cur = 0, nxt = NS - 1;
-        for (int t = 0; t < nkt; ++t) {
-            ring_wait_vmcnt<(NS - 2) * PW>();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            ring_stage<TM, TM, TN, false, false, ABL>(ring_smem + cur * STAGE, ring_smem + cur * STAGE + A_BYTES, acc, 0, atr, 0, btr, xo, la, lb,
-                                                      kbeg + (t + NS - 1) * RING_BK, kend, lds0, nxt * STAGE, nxt * STAGE + A_BYTES, 0, abl);
-            __builtin_amdgcn_sched_barrier(0);
-            cur = (cur + 1 == NS) ? 0 : cur + 1;
-            nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
-        }
-    };
-    if (abl) kloop(std::integral_constant<bool, true>{});      // (DETR_HIP_RING_ABLATE timing experiments: bits 1, 2, 4 as in gemm_ring_body)
-    else kloop(std::integral_constant<bool, false>{});
+    int cur = 0, nxt = NS - 1;
+    for (int t = 0; t < nkt; ++t) {
+        ring_wait_vmcnt<(NS - 2) * PW>();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        ring_stage<TM, TM, TN, false, false>(ring_smem + cur * STAGE, ring_smem + cur * STAGE + A_BYTES, acc, 0, atr, 0, btr, xo, la, lb,
+                                             kbeg + (t + NS - 1) * RING_BK, kend, lds0, nxt * STAGE, nxt * STAGE + A_BYTES, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        cur = (cur + 1 == NS) ? 0 : cur + 1;
+        nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
+    }
     ring_wait_vmcnt<0>();
     // tile-ordered slab of this (split, tile), in the 2 x 2 grid's unit order
     float4 *slab = reinterpret_cast<float4 *>(g.C + (long long)split * g.part_stride + (long long)tile * (BM * BN));

@@ -48,30 +48,10 @@ struct StreamArgs {
 };
 
 // Cache policy of the epilogue streams.  The residual and the mask are read exactly once by this kernel and by nobody
-// after it, so they are requested non-temporal (bit 0): in the step that is -0.2 ms (20.07 -> 19.85 ms), e.g. M534400 N256
+// after it, so they are requested non-temporal: in the step that is -0.2 ms (20.07 -> 19.85 ms), e.g. M534400 N256
 // K64 +res+mask 166 -> 146 us, because they stop evicting the A rows the other slices of the workgroup are about to re-read.
 // The output stores stay temporal: the next kernel reads C, and non-temporal stores measured +-0 here and +0.02 ms on the consumers.
-#ifndef DETR_STREAM_NT
-#define DETR_STREAM_NT 1
-#endif
-__device__ __forceinline__ uint4 stream_ld_ep(const BufSrc &src, unsigned off) {
-#if DETR_STREAM_NT & 1
-    return src.ld16_nt(off);
-#else
-    return src.ld16(off);
-#endif
-}
-#ifndef DETR_STREAM_PIPE
-#define DETR_STREAM_PIPE 1                         // 0: the compiler's own order of fragment reads and MFMAs (A/B builds)
-#endif
-#ifndef DETR_STREAM_PROF
-#define DETR_STREAM_PROF 0                         // 1 (probe builds, scripts/experiments/stream_probe.py): s_memtime per strip section into maskbits_out
-#endif
-#if DETR_STREAM_PROF
-#define STREAM_TICK(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_readcyclecounter(); prof_acc[k] += t_ - prof_last; prof_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define STREAM_TICK(k) do { } while (0)
-#endif
+__device__ __forceinline__ uint4 stream_ld_ep(const BufSrc &src, unsigned off) { return src.ld16_nt(off); }
 constexpr int STREAM_LD = 68;                      // floats per staged row (64 + 4): conflict-free b128 writes and reads
 
 // SL = column slices (64 columns each) a workgroup owns: its 4 waves are SL slice owners x 4 / SL row walkers, and the SL
@@ -149,8 +129,7 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
 
     auto load_a = [&](int rt, int chunk, uint4 (&f)[KK]) {
         const int row = rt * 32 + l31;
-        const bool a_live = (DETR_ABLATE & 2) == 0 || rt < stride;      // ablation bit 1: only a wave's first strip is requested
-        const unsigned base = (a_live && rt < a.row_tiles && row < a.M) ? (unsigned)((long long)row * a.lda * 2) + a_lane + chunk * (KC * 2) : BUF_OOB;
+        const unsigned base = (rt < a.row_tiles && row < a.M) ? (unsigned)((long long)row * a.lda * 2) + a_lane + chunk * (KC * 2) : BUF_OOB;
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) f[kk] = srcA.ld16(base == BUF_OOB ? BUF_OOB : base + kk * 32);
     };
@@ -171,33 +150,23 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
         bf16x8 bq[2][NQ];
 #pragma unroll
         for (int nq = 0; nq < NQ; ++nq) bq[0][nq] = read_b(chunk, 0, nq);
-#if DETR_STREAM_PIPE
-        if constexpr ((DETR_ABLATE & 1) == 0) sgb_ds_read<RPF * NQ>();
-#endif
+        sgb_ds_read<RPF * NQ>();
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
             const bf16x8 af = __builtin_bit_cast(bf16x8, f[kk]);
 #pragma unroll
             for (int nq = 0; nq < NQ; ++nq) {
                 if (kk + 1 < KK) bq[(kk + 1) & 1][nq] = read_b(chunk, kk + 1, nq);
-                if constexpr ((DETR_ABLATE & 1) != 0) { ablate_keep(bq[kk & 1][nq]); ablate_keep(af); }
-                else acc[nq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[kk & 1][nq], af, acc[nq], 0, 0, 0);
+                acc[nq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[kk & 1][nq], af, acc[nq], 0, 0, 0);
             }
-#if DETR_STREAM_PIPE
-            if constexpr ((DETR_ABLATE & 1) == 0) {
 #pragma unroll
-                for (int nq = 0; nq < NQ; ++nq) {
-                    if (kk + 1 < KK) sgb_ds_read<RPF>();
-                    sgb_mfma();
-                }
+            for (int nq = 0; nq < NQ; ++nq) {
+                if (kk + 1 < KK) sgb_ds_read<RPF>();
+                sgb_mfma();
             }
-#endif
         }
     };
 
-#if DETR_STREAM_PROF
-    unsigned long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_last = 0;
-#endif
     // one strip: epilogue-operand requests, A prefetch, MFMAs, transposition, epilogue.  a_first holds chunk 0 of the
     // strip on entry.  NC == 1: the next strip's rows go to a_other and the two buffers swap roles from strip to strip
     // (the loop below is unrolled by two), so no register copy -- which would have to wait for the prefetch -- sits at
@@ -205,7 +174,6 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
     // a_first again.
     auto strip = [&](const int rt, uint4 (&a_first)[KK], uint4 (&a_other)[KK]) {
         const int r0 = rt * 32;
-        STREAM_TICK(7);                             // between strips (loop control)
         uint4 rres[NW][4], rmsk[NW][4];
 #pragma unroll
         for (int sw = 0; sw < NW; ++sw)
@@ -213,19 +181,17 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
         for (int it = 0; it < 4; ++it) {
             const int row = r0 + it * 8 + erow;
             const unsigned colb = (unsigned)((n0 + sw * 64 + ecg * 8) * 2);
-            const bool ep_live = (DETR_ABLATE & 32) == 0;               // ablation bit 5: no residual / mask requests
             // (byte offsets fit 32 bits: the host dispatch only sends tensors below 4 GB here)
-            if (RES) rres[sw][it] = stream_ld_ep(srcR, (ep_live && row < a.M) ? (unsigned)row * ldr2 + colb : BUF_OOB);
-            if (MASK == 1) rmsk[sw][it] = stream_ld_ep(srcM, (ep_live && row < a.M) ? (unsigned)row * ldm2 + colb : BUF_OOB);
+            if (RES) rres[sw][it] = stream_ld_ep(srcR, (row < a.M) ? (unsigned)row * ldr2 + colb : BUF_OOB);
+            if (MASK == 1) rmsk[sw][it] = stream_ld_ep(srcM, (row < a.M) ? (unsigned)row * ldm2 + colb : BUF_OOB);
             if (MASK == 2)      // one byte = the 8 columns of this lane; the 8 lanes of a row read 8 consecutive bytes
-                rmsk[sw][it].x = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(srcM.rsrc, (ep_live && row < a.M) ? (unsigned)row * ldm1 + (unsigned)(((n0 + sw * 64) >> 3) + ecg) : BUF_OOB, 0, 0);
+                rmsk[sw][it].x = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(srcM.rsrc, (row < a.M) ? (unsigned)row * ldm1 + (unsigned)(((n0 + sw * 64) >> 3) + ecg) : BUF_OOB, 0, 0);
         }
         f32x16 acc[2 * NW];
 #pragma unroll
         for (int nq = 0; nq < 2 * NW; ++nq)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nq][r] = 0.0f;
-        STREAM_TICK(0);                             // epilogue-operand requests issued
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const bool last = (c + 1 == NC);
@@ -236,7 +202,6 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
                 load_a(last ? rt + stride : rt, last ? 0 : c + 1, a_first);
                 mma(a_other, c, acc);
             }
-            STREAM_TICK(1 + (c & 1));               // chunk c: A requests + MFMAs issued (incl. the wait for its A rows)
         }
 #pragma unroll
         for (int sw = 0; sw < NW; ++sw) {
@@ -249,7 +214,6 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
                         make_float4(acc[2 * sw + nh][4 * g], acc[2 * sw + nh][4 * g + 1], acc[2 * sw + nh][4 * g + 2], acc[2 * sw + nh][4 * g + 3]);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            STREAM_TICK(3);                         // accumulators staged (the first one waits for the MFMAs to finish)
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int rl = it * 8 + erow;
@@ -302,16 +266,15 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
 #pragma unroll
                     for (int i = 0; i < 8; ++i) v[i] = ((mb >> i) & 1u) ? v[i] : 0.0f;
                 }
-                // branch-free: a row past M (or the ablation build's "no output stores") gets an out-of-range offset and stores nothing
-                const bool st_live = row < a.M && ((DETR_ABLATE & 64) == 0 || v[0] == 12345.678f);
+                // branch-free: a row past M gets an out-of-range offset and stores nothing
+                const bool st_live = row < a.M;
                 const u32x4 ov = {f32_to_bf16_pair(v[0], v[1]), f32_to_bf16_pair(v[2], v[3]), f32_to_bf16_pair(v[4], v[5]), f32_to_bf16_pair(v[6], v[7])};
                 dstC.st16(st_live ? (unsigned)row * ldc2 + (unsigned)((n0 + sw * 64 + ecg * 8) * 2) : BUF_OOB, ov);
-                if constexpr (MBO && !DETR_STREAM_PROF)
+                if constexpr (MBO)
                     dstB.st1(st_live ? (unsigned)row * ldb1 + (unsigned)(((n0 + sw * 64) >> 3) + ecg) : BUF_OOB, (unsigned char)bf16x8_gt0_bits(ov[0], ov[1], ov[2], ov[3]));
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            STREAM_TICK(4);                         // epilogue items: LDS reads, residual / mask waits, stores issued
         }
     };
 
@@ -340,10 +303,6 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
     }
     __syncthreads();
 
-#if DETR_STREAM_PROF
-    const unsigned long long prof_t0 = __builtin_readcyclecounter();
-    prof_last = prof_t0;
-#endif
     while (rt < a.row_tiles) {
         strip(rt, a0, a1);
         rt += stride;
@@ -353,14 +312,6 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
             rt += stride;
         }
     }
-#if DETR_STREAM_PROF
-    if (lane == 0 && a.mbits_out) {                // [workgroup][wave][8]: sections 0-4, 5 = prologue end, 6 = loop total, 7 = between strips
-        unsigned long long *o = reinterpret_cast<unsigned long long *>(a.mbits_out) + ((size_t)blockIdx.x * WAVES + wave) * 8;
-        prof_acc[6] = __builtin_readcyclecounter() - prof_t0;
-        prof_acc[5] = prof_t0;
-        for (int k = 0; k < 8; ++k) o[k] = prof_acc[k];
-    }
-#endif
 }
 
 // Host side: eligibility is decided by the caller (gemm_f32.hip); here the slice grouping and the grid.
@@ -400,8 +351,8 @@ static void launch_gemm_stream_sl(StreamArgs a, bool bkc, hipStream_t s, bool ma
 
 template <int K>
 static void launch_gemm_stream(StreamArgs a, bool bkc, hipStream_t s, bool mask_bits = false) {
-    // slices per workgroup, by measurement (scripts/experiments/ablate_stream.py with DETR_HIP_STREAM_SL = 1 / 2 / 4, the tuning
-    // hook below; SL 1 -> chosen): M534400 N256 K64 130 -> 123 us (+mask 180 -> 171), M133600 N512 K128 +res 95 -> 87 (SL 2),
+    // slices per workgroup, by measurement (DETR_HIP_STREAM_SL = 1 / 2 / 4, the tuning hook below;
+    // SL 1 -> chosen): M534400 N256 K64 130 -> 123 us (+mask 180 -> 171), M133600 N512 K128 +res 95 -> 87 (SL 2),
     // +res +mask 116 -> 95 (SL 4), M133600 N512 K256 144 -> 126 (SL 2); M33600 N1024 K256 stays at SL 1 (52 vs 57 us)
     // (in the step, HIP events: K = 256 without a residual / mask epilogue is SLOWER with 2 slices -- 102 KB of LDS, one workgroup per
     //  CU: M133600 N512 0.091 -> 0.120 ms -- so K = 256 groups only the epilogue-heavy form)

@@ -15,7 +15,7 @@
 //   * K tile 32.  ONE LDS buffer (3 x (BM + BN) x 80 B = 60 KB at 128 x 128: two workgroups per CU) and one register set:
 //     loop = [split + store tile t from registers] [request tile t+1] barrier [2 k-steps x 6 x TM x TN MFMAs] barrier --
 //     a workgroup's split phase (VALU, LDS writes) runs under the co-resident workgroup's MFMA phase.
-//   * (measured and NOT kept, scripts/experiments/gemm_x3pp.h: one 8-wave workgroup whose two 4-wave groups are held in anti-phase by the
+//   * (measured and NOT kept: one 8-wave workgroup whose two 4-wave groups are held in anti-phase by the
 //     workgroup barrier -- one splits while the other multiplies.  Bit-identical, 1.3-1.6x SLOWER (M33600 N256 K1024: 154 -> 246 us): two
 //     independent workgroups drift into whatever interleaving the SIMD arbitration finds; the barrier pins every half-iteration to the slower
 //     of the two phases.  profiles/r06_ab_results.txt #7)
@@ -253,10 +253,8 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs &g, const int id, co
             if constexpr (BKC) x3_store_k<BN>(sm.B[0], rb, tid);
             else x3_store_mn<BN>(sm.B[0], rb, tid);
             // the next tile's requests fly under this tile's MFMA phase (unconditional: past the range they resolve to the out-of-range offset)
-            if constexpr ((DETR_X3_ABLATE & 4) == 0) {
-                la.load((kt + 1) * X3_BK, kend, ra);
-                lb.load((kt + 1) * X3_BK, kend, rb);
-            }
+            la.load((kt + 1) * X3_BK, kend, ra);
+            lb.load((kt + 1) * X3_BK, kend, rb);
             lds_barrier();
 #pragma unroll
             for (int ks = 0; ks < X3_BK; ks += 16) {
@@ -268,7 +266,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs &g, const int id, co
 #pragma unroll
                 for (int mi = 0; mi < T::TM; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma<DETR_SPLIT3_TERMS>(a[mi], b[ni], acc[mi][ni]);
+                    for (int ni = 0; ni < T::TN; ++ni) acc[mi][ni] = split3_mma(a[mi], b[ni], acc[mi][ni]);
             }
             lds_barrier();
         }
@@ -308,7 +306,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs &g, const int id, co
                 for (int mi = 0; mi < T::TM; ++mi)
 #pragma unroll
                     for (int ni = 0; ni < T::TN; ++ni) {
-                        acc[mi][ni] = split3_mma<DETR_SPLIT3_TERMS>(a[mi], b[ni], acc[mi][ni]);
+                        acc[mi][ni] = split3_mma(a[mi], b[ni], acc[mi][ni]);
 #pragma unroll
                         for (int q = 0; q < UPG; ++q) {
                             const int u = grp * UPG + q;

@@ -152,7 +152,7 @@ __device__ __forceinline__ double wave_min_f64_dpp(double x) {
 //
 // Shape of the search (LAPJV's SCAN / TODO form of the Dijkstra, same labels as SciPy's loop): a wave-wide minimum is
 // only taken when the set of live columns whose label EQUALS the current minimum (`todo`) is empty.  Measured with
-// s_memtime (DETR_ASSIGN_PROF builds, scripts/experiments/assign_probe.py) on the 99-target problems of the bench step:
+// s_memtime counters (a probe build) on the 99-target problems of the bench step:
 // the loop is bound by the latency of ONE wave's dependent instructions, ~880 cycles per scanned row when every row scan
 // is followed by a minimum + owner selection (6 DPP stages of 64-bit moves and v_min_f64, then ballots, v_readlane and the
 // SALU <-> VALU round trips between them), of which the row scan itself is ~100.  About half of all scanned columns are
@@ -180,14 +180,6 @@ struct AssignPick {
     }
 };
 
-#ifndef DETR_ASSIGN_PROF
-#define DETR_ASSIGN_PROF 0       // 1: s_memtime segment counters of the step loop, written over pred_for_tgt[0..15] (probe builds only)
-#endif
-#if DETR_ASSIGN_PROF
-#define ASSIGN_TICK(k) do { const unsigned long long t_ = __builtin_readcyclecounter(); prof_acc[k] += t_ - prof_last; prof_last = t_; } while (0)
-#else
-#define ASSIGN_TICK(k) do { } while (0)
-#endif
 template <int MAXCPL, bool CD>
 __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ cost, int Q, int ldc,
                                                     const float *__restrict__ t_bbox, int B, int R,
@@ -289,14 +281,9 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
         }
     }
     __syncthreads();
-#if DETR_ASSIGN_PROF
-    unsigned long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_last = __builtin_readcyclecounter();
-    const unsigned long long prof_t0 = prof_last;
-#endif
     bool infeasible = false;
     for (int cur = 0; cur < n; ++cur) {
         if (col4row[cur] != -1) continue;                  // matched by the row-reduction start
-        ASSIGN_TICK(5);
         double minVal = 0.0;
         int i = cur;
         int sink = -1;
@@ -309,7 +296,6 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
             todo[s] = 0ull;
         }
         while (true) {
-            ASSIGN_TICK(0);
             // scan row i: both LDS reads (u[i] and one cost per slot) are issued together, the relaxations are selects;
             // a column whose new label equals minVal (reduced cost 0) joins `todo`
             const double ui = u[i * us];
@@ -328,7 +314,6 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
                 todo[s] |= __builtin_amdgcn_ballot_w64(r == minVal) & um;
                 any_todo |= todo[s];
             }
-            ASSIGN_TICK(1);
             if (any_todo == 0ull) {
                 // new level: exact minimum of the live labels, every live column that attains it goes to `todo`
                 double best = INFINITY;
@@ -344,7 +329,6 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
 #pragma unroll
                 for (int s = 0; s < MAXCPL; ++s) todo[s] = __builtin_amdgcn_ballot_w64(spc[s] == minVal) & live[s];
             }
-            ASSIGN_TICK(2);
             int jstar = 0, r4 = 0;
             bool isfree = false;
             AssignPick<0, MAXCPL>::run(todo, live, freecol, row4col, jstar, r4, isfree);
@@ -353,10 +337,8 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
                 break;
             }
             i = r4;
-            ASSIGN_TICK(3);
         }
         if (infeasible) break;
-        ASSIGN_TICK(4);
         // dual update (before the augmentation, with the old matching)
         if (lane == 0) u[cur * us] += minVal;
 #pragma unroll
@@ -401,13 +383,6 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
         pred_for_tgt[(long long)p * ldc + i] = q;
         if (q >= 0) tgt_for_pred[(long long)p * Q + q] = i;
     }
-#if DETR_ASSIGN_PROF
-    __syncthreads();
-    if (lane == 0) {
-        for (int k = 0; k < 6; ++k) pred_for_tgt[(long long)p * ldc + k] = (int)prof_acc[k];
-        pred_for_tgt[(long long)p * ldc + 6] = (int)(__builtin_readcyclecounter() - prof_t0);
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -812,11 +812,13 @@ def attention(q, k, v, o, lse, B, H, T, S, *, scale=1.0, dropout_p=0.0, dropout_
               d_o=None, dq=None, dk=None, dv=None, delta=None, dropmask=None, key_valid=None):
     """Fused attention core (include/detr_hip.h detr_attn_desc).  q / k / v / o (and the gradients) are 2-D views
     [rows, >= H*32] whose row stride is taken from the tensor, so they may be column blocks of a packed projection buffer.
-    Forward when d_o is None, otherwise the backward (dq / dk / dv / delta written).
-    All-bf16 operands (io_dtype = 1, csrc/attention_dma.hip): every tensor bf16, q pre-multiplied by scale * log2(e), delta with
-    2*B*H*T floats, and -- with dropout -- the keep bits of attention_dropmask() in `dropmask`.
+    Forward when d_o is None, otherwise the backward (dq / dk / dv / delta written).  The operand dtype picks the kernels:
+    fp32 tensors run the exact-fp32 kernels (compute = 0, csrc/attention_f32.hip); all-bf16 operands (io_dtype = 1,
+    compute = 1, csrc/attention_dma.hip) need every tensor bf16, q pre-multiplied by scale * log2(e), delta with 2*B*H*T
+    floats, and -- with dropout -- the keep bits of attention_dropmask() in `dropmask`.  compute: None takes it from the dtype;
+    fp32 tensors also accept 2 (the same exact kernels), and 1 on fp32 tensors is rejected by the library.
     key_valid: int32 / uint32 tensor of attention_keymask_words(B, S) key-validity words (the key padding mask, see
-    detr_hip_attention_fwd_masked); not with bf16 compute on fp32 tensors."""
+    detr_hip_attention_fwd_masked)."""
     if key_valid is not None:
         if not key_valid.is_cuda or key_valid.element_size() != 4 or key_valid.numel() < attention_keymask_words(B, S):
             raise ValueError("attention: key_valid must be a device tensor of attention_keymask_words(B, S) 32-bit words")
@@ -832,14 +834,12 @@ def attention(q, k, v, o, lse, B, H, T, S, *, scale=1.0, dropout_p=0.0, dropout_
         setattr(d, "ld" + name, t.stride(0))
     d.lse = lse.data_ptr()
     d.scale, d.dropout_p, d.dropout_site, d.dropout_step = scale, dropout_p, dropout_site & 0xFFFFFFFF, ptr(dropout_step)
-    d.compute = COMPUTE_BF16 if compute is None else int(compute)
     d.io_dtype = 1 if io16 else 0
-    if io16:
-        d.compute = 1
-        if dropout_p > 0.0:
-            if dropmask is None:
-                raise ValueError("attention: bf16 operands with dropout need the keep bits (attention_dropmask)")
-            d.dropmask = dropmask.data_ptr()
+    d.compute = 1 if io16 else (0 if compute is None else int(compute))
+    if io16 and dropout_p > 0.0:
+        if dropmask is None:
+            raise ValueError("attention: bf16 operands with dropout need the keep bits (attention_dropmask)")
+        d.dropmask = dropmask.data_ptr()
     ev0 = PROFILER.begin() if PROFILER is not None else None
     esz = 2.0 if io16 else 4.0
     prods = 2.0 * B * H * T * S * 32                   # FLOPs of one [T,S,32] product over all (batch, head) problems

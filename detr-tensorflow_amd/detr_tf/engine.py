@@ -31,24 +31,9 @@ FF = 2048
 BN_EPS = 1e-5
 KERAS_BN_EPS = 1.001e-5      # tf.keras.applications.resnet BatchNormalization(epsilon=1.001e-5) (tf_backbone=True)
 LN_EPS = 1e-5
-# bf16 STORAGE of the backbone activations and their gradients in precision="bf16" (default on; DETR_HIP_ACT16=0 keeps
-# fp32 storage with bf16 MFMA operands only)
-ACT16 = os.environ.get("DETR_HIP_ACT16", "1") != "0"
-# bf16 STORAGE of the FFN hidden activation in precision="bf16" (bit-identical: it only feeds GEMM operands; DETR_HIP_H16=0 = fp32)
-H16 = os.environ.get("DETR_HIP_H16", "1") != "0"
 DEFER_REDUCE = os.environ.get("DETR_HIP_DEFER_REDUCE", "1") != "0"     # queue the weight gradients' split-K reductions (A/B switch)
 WGRAD_STREAM = os.environ.get("DETR_HIP_WGRAD_STREAM", "1") != "0"      # backbone weight gradients on a second HIP stream (A/B switch)
-MASK_BITS = os.environ.get("DETR_HIP_MASK_BITS", "1") != "0"            # ReLU masks of the block outputs as bits (A/B switch, round 4)
 BWD_FUSED = os.environ.get("DETR_HIP_BWD_FUSED", "1") != "0"            # layer1: input + weight gradient of the 64 -> 256 1x1 convolutions in one pass over dY (round 5)
-# bf16 compute mode: the LayerNorm behind an attention out-projection (2, default) / also behind the FFN's second Linear (1) runs in
-# that GEMM's launch (detr_gemm_desc.ln_*, row-complete 32 x 256 tiles; same bits as the two launches); 0 = off.  Measured, same box:
-# 16.53 / 16.56 ms (2) vs 16.53 / 16.61 (0) vs 16.85 / 16.96 (1): the K = 256 launches absorb their LayerNorm at equal time (18 launches
-# fewer per step), the K = 2048 ones lose 0.35 ms -- a 32-row tile walks 64 K tiles behind one barrier each
-LN_FUSE = int(os.environ.get("DETR_HIP_LN_FUSE", "2"))
-# bf16 compute mode, round 6: the attention operands Q / K / V / O / dO / dQ / dK / dV are STORED in bf16 (the projection GEMMs write them, Q with
-# scale * log2(e) as its alpha) and the attention core is csrc/attention_dma.hip (LDS-DMA K / V rings per wave, dropout keep flags as bits
-# generated once per step).  DETR_HIP_ATTN16=0: the round-3 kernels on fp32 tensors (A/B switch)
-ATTN16 = os.environ.get("DETR_HIP_ATTN16", "1") != "0"
 # the NEXT step's keep bits generated during this step (eager launches): 2 (default) = next to the assignment kernel alone, behind the matcher's
 # cost kernel (pregen_dropmasks_at_matcher: -0.05 ms per step, profiles/r06_ab_results.txt #5); 1 = from the start of the decoder forward
 # (measured SLOWER, #3); 0 = at the head of their own step
@@ -343,8 +328,11 @@ class DetrEngine:
 
     def _ln_spec(self, rows, pfx, y, tag, add=None, y2=None, y16=None, ffn=False):
         """The same LayerNorm as an epilogue of the GEMM that produces its input (hip.linear_fwd(..., ln=spec)); None when this
-        pass runs them as two launches (fp32 compute mode, DETR_HIP_LN_FUSE)."""
-        if self.compute != 1 or LN_FUSE == 0 or (ffn and LN_FUSE == 2) or (ffn and not self.ffn16):
+        pass runs them as two launches.  Only bf16 compute mode fuses, and only behind the attention out-projections (row-complete
+        32 x 256 tiles, same bits as the two launches).  Measured, same box: 16.53 / 16.56 ms fused there vs 16.53 / 16.61 unfused
+        vs 16.85 / 16.96 also behind the FFN's second Linear -- the K = 256 launches absorb their LayerNorm at equal time (18
+        launches fewer per step), the K = 2048 ones lose 0.35 ms: a 32-row tile walks 64 K tiles behind one barrier each."""
+        if self.compute != 1 or ffn:
             return None
         return dict(gamma=self.P.views[f"{pfx}/gamma"], beta=self.P.views[f"{pfx}/beta"], y=y, mean=self.buf(f"{tag}:mean", (rows,)),
                     rstd=self.buf(f"{tag}:rstd", (rows,)), eps=LN_EPS, add=add, y2=y2, y16=y16)
@@ -420,9 +408,12 @@ class DetrEngine:
     # with N = 512 against rows 0..511 of in_proj_kernel.  The query scaling head_dim**-0.5 (:307) is folded into the
     # attention kernels (detr_attn_desc.scale).  In the backward the packed dQKV buffer turns the three data gradients
     # and the three residual-style adds into ONE GEMM with K = 768:  d_x = dQKV @ in_proj_kernel + d_residual.
+    # bf16 compute mode: the attention operands Q / K / V / O / dO / dQ / dK / dV are STORED in bf16 (the projection GEMMs write
+    # them, Q with scale * log2(e) as its alpha) and the attention core is csrc/attention_dma.hip (LDS-DMA K / V rings per wave,
+    # dropout keep flags as bits generated once per step).
     @property
     def attn16(self):
-        return self.compute == 1 and ATTN16
+        return self.compute == 1
 
     def _dropmask(self, site, B, T, S, which=None):
         """Keep bits of the attention-probability dropout of `site` (hip.attention_dropmask): one buffer per site and step parity,
@@ -455,9 +446,6 @@ class DetrEngine:
         dp, _ = self._drop
         if not (self.attn16 and dp > 0.0):
             return
-        if os.environ.get("DETR_HIP_DROPMASK_STALE") == "1" and getattr(self, "_mask_once", False):
-            return          # timing experiment only (profiles/r06_ab_results.txt): the keep bits of the first step are reused -- what their generation costs the step
-        self._mask_once = True
         self._mask_set = self._step_no & 1
         tags = self.__dict__.setdefault("_mask_tags", {})
         key = (self._step_seed, B, L, self.Q, dp)
@@ -469,9 +457,10 @@ class DetrEngine:
     def _pregen_dropmasks(self, B, L, now=False):
         """Called when the decoder forward begins (800-row kernels, then the matcher: most CUs idle for ~1.5 ms): the NEXT step's keep
         bits, from its seed in slot 1 of the device seed block, into the other buffer set.  Eager launches only (a recorded graph keeps
-        the generation at the head of its own step).  Off by default: measured +0.07 ms per step (DETR_HIP_DROPMASK_AHEAD=1 enables it; profiles/r06_ab_results.txt #3)."""
+        the generation at the head of its own step).  On by default at the matcher (DETR_HIP_DROPMASK_AHEAD=2, pregen_dropmasks_at_matcher); from the
+        start of the decoder forward (=1) it measured +0.07 ms per step (profiles/r06_ab_results.txt #3); 0 turns it off."""
         dp, _ = self._drop
-        if not (self.attn16 and dp > 0.0) or self._graph_replay or not DROPMASK_AHEAD or os.environ.get("DETR_HIP_DROPMASK_STALE") == "1":
+        if not (self.attn16 and dp > 0.0) or self._graph_replay or not DROPMASK_AHEAD:
             return
         if DROPMASK_AHEAD == 2 and not now:
             self._pregen_args = (B, L)          # launched by the set loss between its cost and assignment kernels
@@ -561,7 +550,7 @@ class DetrEngine:
     # [rows, 2048] tensors move half the bytes, and both weight gradients become one grouped launch of the all-bf16 variant.
     @property
     def ffn16(self):
-        return self.compute == 1 and H16
+        return self.compute == 1
 
     def _ffn_fwd(self, tag, pfx, x, out_pre_ln, seed=0, x16=None, ln=None):
         V = self.P.views
@@ -733,7 +722,7 @@ class DetrEngine:
         H1, W1 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
         M1 = B * H1 * W1
         ws = self._scaled_kernel(f"{self._stem['conv']}/kernel", self._stem["bn"])
-        adt = torch.bfloat16 if (self.compute == 1 and ACT16) else torch.float32      # storage type of backbone activations
+        adt = torch.bfloat16 if self.compute == 1 else torch.float32      # storage type of backbone activations (and their gradients)
         self._adt = adt
         stem = self.buf("stem:out", (B, H1, W1, 64), adt)
         # implicit GEMM: the 7x7x3 patches are gathered from the image by the A loader (stem_conv.hip), no im2col buffer
@@ -788,7 +777,7 @@ class DetrEngine:
                 nxt_d1 = 64 * 2 ** (li if b + 1 < nb else li + 1)        # d1 of the next block
                 last = (li + 1 == len(self.blocks)) and (b + 1 == nb)
                 obits = self.buf(f"{p}:out_bits", (M_out, d2 // 8), torch.uint8) \
-                    if (training and MASK_BITS and adt == torch.bfloat16 and not last and nxt_d1 <= 256) else None
+                    if (training and adt == torch.bfloat16 and not last and nxt_d1 <= 256) else None
                 self._conv1x1_fwd(y2, M_out, d1, d2, f"{n['conv3']}/kernel", n["bn3"], out, residual=idn, maskbits_out=obits)
                 self._block_meta.append(dict(p=p, n=n, x=x, xs=xs, x1=x1, y1=y1, y2=y2, out=out, h=h, w=w, ho=ho, wo=wo, h1=h1, w1=w1,
                                              M1=M1, s2=s2, cin=cin, d1=d1, d2=d2, stride=stride, first=(b == 0), out_bits=obits))

@@ -117,7 +117,7 @@ typedef struct {
      * engine keeps a per-step bf16 shadow of the weights so that the weight operand is read at half the bytes and
      * without conversion (K %% 8 == 0 for a k-contiguous B, N %% 4 == 0 otherwise). */
     int32_t b_dtype;
-    /* bf16 STORAGE of activation tensors (bf16 compute only; the engine's backbone tensors when DETR_HIP_ACT16=1): 1 = the
+    /* bf16 STORAGE of activation tensors (bf16 compute only; the engine's backbone tensors in bf16 mode): 1 = the
      * tensor is bf16 in memory (uint16, RNE; leading dimensions in elements), 0 = fp32.  The epilogue arithmetic stays
      * fp32 and the result is rounded once.  Not with split_k / batch (partial slabs and gradients of parameters stay fp32). */
     int32_t a_dtype, c_dtype, r_dtype, m_dtype;     /* A, C, residual, mask (m_dtype 2: bit-packed, see maskbits_out) */
@@ -378,8 +378,8 @@ typedef struct {
     /* attention-probability dropout (transformer.py:341): element index ((b*H + h)*T + t)*Sp + s, Sp = S rounded up to
      * even (one keyed counter hash per pair of adjacent keys, csrc/common.h); site / step as in detr_gemm_desc */
     float dropout_p; uint32_t dropout_site; const uint32_t *dropout_step;
-    /* 0 = exact fp32 MFMA; 1 = bf16 MFMA operands (Q, K, V, P, dO, dS rounded to bf16; accumulation, softmax
-     * statistics, LSE, delta and outputs fp32; csrc/attention_bf16.hip) */
+    /* 0 = exact fp32 MFMA on fp32 tensors (io_dtype = 0; 2 runs the same kernels); 1 = bf16 MFMA, valid only with
+     * bf16 tensors (io_dtype = 1, below) -- io_dtype = 0 with compute = 1 is rejected */
     int32_t compute;
     /* ABI 8.  io_dtype = 1 (compute = 1 only; csrc/attention_dma.hip): q, k, v, o, d_o, dq, dk, dv point to bf16 data (uint16, RNE;
      * row strides in elements, multiples of 8), `q` holds bf16(scale * log2(e) * q_unscaled) -- the projection GEMM's alpha -- and dq
@@ -403,9 +403,8 @@ int detr_hip_attention_dropmask_many(const detr_attn_desc *descs, int32_t n, voi
 /* Key padding mask (detr_tf/networks/transformer.py:322-337 -- the reference's commented-out key_padding_mask branch -- as if
  * enabled, fed by source_key_padding_mask / memory_key_padding_mask, :43-50): the same attention with the scores of invalid keys
  * set to -inf before the softmax.  key_valid: detr_hip_attention_keymask_words(B, S) uint32 words, word (b * ceil(S/32) + t) bit j
- * = key 32 t + j of batch entry b is valid; bits past S must be 0.  Queries are never masked.  Only the exact-fp32 kernels
- * (io_dtype = 0, compute = 0) and the all-bf16 kernels (io_dtype = 1) have a masked form; io_dtype = 0 with compute = 1 is
- * rejected.  Every batch entry needs at least one valid key (otherwise its rows are NaN: see detr_hip_padding_mask_prepare's
+ * = key 32 t + j of batch entry b is valid; bits past S must be 0.  Queries are never masked.  Both the exact-fp32 kernels
+ * (io_dtype = 0) and the all-bf16 kernels (io_dtype = 1) have a masked form.  Every batch entry needs at least one valid key (otherwise its rows are NaN: see detr_hip_padding_mask_prepare's
  * status).  Masked keys get exact zeros in dk / dv; dropout keep bits are those of the unmasked call. */
 int64_t detr_hip_attention_keymask_words(int32_t B, int32_t S);
 int detr_hip_attention_fwd_masked(const detr_attn_desc *d, const uint32_t *key_valid, void *stream);

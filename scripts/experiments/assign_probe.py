@@ -88,8 +88,8 @@ def main():
     t = np.zeros((1, 100, 4), np.float32)
     t[:, 0, 0] = 99
     cost = torch.from_numpy(d["cost3"][47:48]).to(dev)
-    us, pft, _ = time_assign(hip, cost, torch.from_numpy(t).to(dev), 1)
-    print(f"bench cost3[47] alone: {us:8.1f} us   (probe builds: s_memtime segments {pft[0, :7].tolist()})")
+    us, _, _ = time_assign(hip, cost, torch.from_numpy(t).to(dev), 1)
+    print(f"bench cost3[47] alone: {us:8.1f} us")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Micro-benchmark of the bf16 3x3 convolutions on the step's shapes (forward with bias + ReLU, input gradient with the ReLU
 mask, weight gradient): HIP events around `reps` back-to-back launches, or --cold: each launch alone after a 600 MB flush.
 usage: python scripts/micro_conv.py [--cold] [NAME=VAL[,NAME=VAL] ...]      (extra library tuning settings to time)
-DETR_HIP_LIB=<path> selects an experimental build of the library (e.g. one compiled with -DDETR_ABLATE=<bits>)."""
+DETR_HIP_LIB=<path> selects an experimental build of the library."""
 import os
 import sys
 

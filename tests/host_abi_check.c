@@ -90,6 +90,21 @@ int main(void) {
     memset(&a, 0, sizeof a);
     EXPECT(detr_hip_attention_fwd(&a, NULL) < 0);
     EXPECT(detr_hip_attention_bwd(&a, NULL) < 0);
+    {   /* compute = 1 (bf16 MFMA) needs bf16 operands: fp32 tensors with compute = 1 are rejected, masked or not (the operands
+         * are well-formed but never dereferenced) */
+        static float fake[64] __attribute__((aligned(16)));
+        static uint32_t kv[4];
+        a.B = 1; a.H = 8; a.T = a.S = 64;
+        a.q = a.k = a.v = a.d_o = fake; a.o = a.lse = a.dq = a.dk = a.dv = a.delta = fake;
+        a.ldq = a.ldk = a.ldv = a.ldo = a.ldd_o = a.lddq = a.lddk = a.lddv = 256;
+        a.scale = 1.0f;
+        a.compute = 1; a.io_dtype = 0;
+        EXPECT(detr_hip_attention_fwd(&a, NULL) < 0 && strstr(detr_hip_last_error(), "needs bf16 operands (io_dtype = 1)"));
+        EXPECT(detr_hip_attention_bwd(&a, NULL) < 0 && strstr(detr_hip_last_error(), "needs bf16 operands (io_dtype = 1)"));
+        EXPECT(detr_hip_attention_fwd_masked(&a, kv, NULL) < 0 && strstr(detr_hip_last_error(), "needs bf16 operands (io_dtype = 1)"));
+        EXPECT(detr_hip_attention_bwd_masked(&a, kv, NULL) < 0 && strstr(detr_hip_last_error(), "needs bf16 operands (io_dtype = 1)"));
+        memset(&a, 0, sizeof a);
+    }
     memset(&ln, 0, sizeof ln);
     EXPECT(detr_hip_layernorm_fwd(&ln, NULL) < 0);
     EXPECT(detr_hip_layernorm_bwd(&ln, NULL) < 0);

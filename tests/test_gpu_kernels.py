@@ -26,7 +26,7 @@ def _reset_library_tuning():
     yield
     from detr_tf import _hip
     leaked = [k for k in ("DETR_HIP_STEM_ROWS", "DETR_HIP_CONV_HALO", "DETR_HIP_DGRAD_S2_CLASSES", "DETR_HIP_GEMM_STREAM", "DETR_HIP_GEMM_TILE", "DETR_HIP_ATTN_SPLIT", "DETR_HIP_GEMM_K64", "DETR_HIP_EPI_WIDE",
-                          "DETR_HIP_GEMM_RING", "DETR_HIP_RING_NS", "DETR_HIP_RING_BN", "DETR_HIP_RING_WGS", "DETR_HIP_RING_ROWS", "DETR_HIP_RING_ABLATE", "DETR_HIP_CONV_DMA", "DETR_HIP_WGRAD_FUSED")
+                          "DETR_HIP_GEMM_RING", "DETR_HIP_RING_NS", "DETR_HIP_RING_BN", "DETR_HIP_RING_WGS", "DETR_HIP_RING_ROWS", "DETR_HIP_CONV_DMA", "DETR_HIP_WGRAD_FUSED")
               if k in os.environ]
     for k in leaked:
         _hip.set_tuning(k, None)
@@ -269,42 +269,6 @@ def test_fused_attention_fwd_bwd(hip, B, T, S):
     close(dq, q.grad, rtol=5e-5, what="attention dq")
     close(dk, k.grad, rtol=5e-5, what="attention dk")
     close(dv, v.grad, rtol=5e-5, what="attention dv")
-
-
-@pytest.mark.parametrize("B,T,S,p", [(2, 1050, 1050, 0.0), (2, 100, 1050, 0.1), (3, 100, 100, 0.0), (1, 37, 5, 0.0),
-                                     (1, 300, 1344, 0.0), (2, 70, 333, 0.1)])
-def test_fused_attention_bf16_mfma(hip, B, T, S, p):
-    """bf16-MFMA attention core (precision="bf16"): Q, K, V, P, dO, dS rounded to bf16, everything else fp32.  Checked
-    against the fp64 reference (with the hash dropout masks of the oracle when p > 0) at bf16-level tolerances; the
-    transposed-fragment paths (ds_read_b64_tr_b16) would be off by O(1) if a row / column mapping were wrong."""
-    from oracle import dropout_ref as DR
-    torch.manual_seed(B * 77 + T + S)
-    H, hd, seed = 8, 32, 991
-    D = H * hd
-    q = (torch.randn(B, T, D, dtype=torch.float64) * 0.6).requires_grad_(True)
-    k = torch.randn(B, S, D, dtype=torch.float64).requires_grad_(True)
-    v = torch.randn(B, S, D, dtype=torch.float64).requires_grad_(True)
-    qh, kh, vh = (t.view(B, -1, H, hd).transpose(1, 2) for t in (q, k, v))
-    sc = qh @ kh.transpose(-1, -2)
-    w = torch.softmax(sc, dim=-1)
-    if p > 0.0:
-        keep = torch.from_numpy(DR.keep_mask(DR.drop_key(seed, 0), DR.attn_index(B * H, T, S).reshape(B, H, T, S), p))
-        w = torch.where(keep, w / (1.0 - p), torch.zeros_like(w))
-    o = (w @ vh).transpose(1, 2).reshape(B, T, D)
-    do = torch.randn(B, T, D, dtype=torch.float64)
-    o.backward(do)
-    qd, kd, vd, dod = (t.view(-1, D) for t in (g(q.detach().float()), g(k.detach().float()), g(v.detach().float()), g(do.float())))
-    od, lse = torch.full((B * T, D), 7.0, device=DEV), torch.zeros(B * H, T, device=DEV)
-    hip.attention(qd, kd, vd, od, lse, B, H, T, S, compute=1, dropout_p=p, dropout_site=seed)
-    close(od.view(B, T, D), o, rtol=1.5e-2, what="bf16 attention fwd")
-    close(lse.view(B, H, T), torch.logsumexp(sc, dim=-1), rtol=3e-3, what="bf16 attention lse")
-    dq, dk, dv = (torch.zeros_like(t).view(B, -1, D) for t in (qd, kd, vd))
-    delta = torch.zeros(B * H, T, device=DEV)
-    hip.attention(qd, kd, vd, od, lse, B, H, T, S, compute=1, dropout_p=p, dropout_site=seed, d_o=dod, dq=dq.view(-1, D),
-                  dk=dk.view(-1, D), dv=dv.view(-1, D), delta=delta)
-    close(dq, q.grad, rtol=2.5e-2, what="bf16 attention dq")
-    close(dk, k.grad, rtol=2.5e-2, what="bf16 attention dk")
-    close(dv, v.grad, rtol=2.5e-2, what="bf16 attention dv")
 
 
 @pytest.mark.parametrize("N,H,W,compute", [(2, 37, 53, 0), (1, 128, 160, 0), (2, 37, 53, 1), (3, 64, 96, 1)])
@@ -846,7 +810,7 @@ def test_dropout_gemm_epilogue_and_elementwise(hip):
     close(out, torch.where(keep, gsrc.double() * scale, torch.zeros(M, N, dtype=torch.float64)), rtol=1e-6, what="dropout_f32")
 
 
-@pytest.mark.parametrize("B,T,S,compute", [(2, 100, 333, 0), (1, 70, 1050, 0), (2, 100, 333, 1)])
+@pytest.mark.parametrize("B,T,S,compute", [(2, 100, 333, 0), (1, 70, 1050, 0)])
 def test_fused_attention_dropout(hip, B, T, S, compute):
     """Dropout on the probabilities with the keyed counter-hash masks (site id as kernel argument, step seed in DEVICE
     memory), softmax scale folded into the kernel (transformer.py:307), and q / k / v / gradients addressed as column
@@ -1694,47 +1658,6 @@ def test_gemm_wide_bf16_epilogue_is_bit_identical(hip, tile, M, N, K, epi):
         assert float((narrow.double() - want).abs().max()) < 2.0 ** -7 * float(want.abs().max())
     assert float(narrow.abs().max()) > 0
     assert torch.equal(wide, narrow), float((wide - narrow).abs().max())
-
-
-@pytest.mark.parametrize("split", [1, 2, 4])
-@pytest.mark.parametrize("B,T,S,p", [(2, 200, 333, 0.1), (1, 70, 40, 0.0), (1, 129, 1050, 0.1)])
-def test_fused_attention_bf16_in_workgroup_split(hip, split, B, T, S, p):
-    """The bf16 attention kernels with the streamed dimension cut into 1 / 2 / 4 runs per workgroup (DETR_HIP_ATTN_SPLIT): forward merge of the partial softmaxes (incl. runs that own no keys:
-    S = 40 is two tiles for four runs), partial dQ / dK / dV sums, ragged last tiles -- all against the fp64 reference with the
-    oracle's dropout masks.  The split must not change what is computed."""
-    from oracle import dropout_ref as DR
-    torch.manual_seed(B * 13 + T + S)
-    H, hd, seed = 8, 32, 4242
-    D = H * hd
-    q = (torch.randn(B, T, D, dtype=torch.float64) * 0.6).requires_grad_(True)
-    k = torch.randn(B, S, D, dtype=torch.float64).requires_grad_(True)
-    v = torch.randn(B, S, D, dtype=torch.float64).requires_grad_(True)
-    qh, kh, vh = (t.view(B, -1, H, hd).transpose(1, 2) for t in (q, k, v))
-    sc = qh @ kh.transpose(-1, -2)
-    w = torch.softmax(sc, dim=-1)
-    if p > 0.0:
-        keep = torch.from_numpy(DR.keep_mask(DR.drop_key(seed, 0), DR.attn_index(B * H, T, S).reshape(B, H, T, S), p))
-        w = torch.where(keep, w / (1.0 - p), torch.zeros_like(w))
-    o = (w @ vh).transpose(1, 2).reshape(B, T, D)
-    do = torch.randn(B, T, D, dtype=torch.float64)
-    o.backward(do)
-    qd, kd, vd, dod = (t.view(-1, D) for t in (g(q.detach().float()), g(k.detach().float()), g(v.detach().float()), g(do.float())))
-    hip.set_tuning("DETR_HIP_ATTN_SPLIT", split)
-    try:
-        od, lse = torch.full((B * T, D), 7.0, device=DEV), torch.zeros(B * H, T, device=DEV)
-        hip.attention(qd, kd, vd, od, lse, B, H, T, S, compute=1, dropout_p=p, dropout_site=seed)
-        dq, dk, dv = (torch.full_like(t, 3.0).view(B, -1, D) for t in (qd, kd, vd))
-        delta = torch.zeros(B * H, T, device=DEV)
-        hip.attention(qd, kd, vd, od, lse, B, H, T, S, compute=1, dropout_p=p, dropout_site=seed, d_o=dod, dq=dq.view(-1, D),
-                      dk=dk.view(-1, D), dv=dv.view(-1, D), delta=delta)
-        torch.cuda.synchronize()
-    finally:
-        hip.set_tuning("DETR_HIP_ATTN_SPLIT", None)
-    close(od.view(B, T, D), o, rtol=1.5e-2, what=f"bf16 attention fwd (split {split})")
-    close(lse.view(B, H, T), torch.logsumexp(sc, dim=-1), rtol=3e-3, what=f"bf16 attention lse (split {split})")
-    close(dq, q.grad, rtol=2.5e-2, what=f"bf16 attention dq (split {split})")
-    close(dk, k.grad, rtol=2.5e-2, what=f"bf16 attention dk (split {split})")
-    close(dv, v.grad, rtol=2.5e-2, what=f"bf16 attention dv (split {split})")
 
 
 def _pack_bits(t):

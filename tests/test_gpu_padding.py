@@ -202,11 +202,30 @@ def test_all_valid_words_equal_the_unmasked_kernels(hip, bf16, p):
 
 
 def test_masked_entry_rejects_bf16_compute_on_fp32_tensors(hip):
+    """compute = 1 is valid only with bf16 operands (io_dtype = 1): fp32 tensors with compute = 1 are rejected by the masked and
+    the unmasked entry points of both directions, before anything is launched or written."""
+    from ctypes import byref
     B, T, S = 1, 64, 64
     q = torch.zeros(B * T, D, device=DEV)
+    o, lse, delta = torch.full_like(q, 7.0), torch.full((B * H, T), 7.0, device=DEV), torch.full((B * H, T), 7.0, device=DEV)
+    grads = [torch.full_like(q, 7.0) for _ in range(3)]
     kv = torch.from_numpy(hip.keymask_words_from_valid(np.ones((B, S), bool))).to(DEV)
     with pytest.raises(RuntimeError, match="no key-padding-masked form"):
         hip.attention(q, q, q, q.clone(), torch.zeros(B * H, T, device=DEV), B, H, T, S, compute=1, key_valid=kv)
+    d = hip.AttnDesc()
+    d.B, d.H, d.T, d.S, d.scale = B, H, T, S, 1.0
+    d.q = d.k = d.v = d.d_o = q.data_ptr()
+    d.o, d.lse, d.delta = o.data_ptr(), lse.data_ptr(), delta.data_ptr()
+    d.dq, d.dk, d.dv = (t.data_ptr() for t in grads)
+    d.ldq = d.ldk = d.ldv = d.ldo = d.ldd_o = d.lddq = d.lddk = d.lddv = D
+    d.compute, d.io_dtype = 1, 0
+    lib = hip.load()
+    for name, args in (("fwd", ()), ("bwd", ()), ("fwd_masked", (kv.data_ptr(),)), ("bwd_masked", (kv.data_ptr(),))):
+        fn = f"detr_hip_attention_{name}"
+        with pytest.raises(RuntimeError, match=r"compute = 1 \(bf16 MFMA\) needs bf16 operands \(io_dtype = 1\)"):
+            hip._check(getattr(lib, fn)(byref(d), *args, hip._stream()), fn)
+    torch.cuda.synchronize()
+    assert all(bool((t == 7.0).all()) for t in [o, lse, delta] + grads)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
