@@ -1,0 +1,242 @@
+// augment.hip -- training augmentation on the device: a ragged batch of uint8 images (each at its own size) -> the
+// augmented, resized and normalised float32 NHWC batch, one launch.  The reference runs this on the host per image with
+// imgaug (data/transformation.py:54-94,163-196: `detr_aug_seq`); here the host only draws one transform record per image
+// (detr_tf/data/transformation.py) and the kernel applies it, in the reference's order:
+//   F  horizontal flip (exact index mirror),
+//   B  none | resize to (Hd, Wd) with interpolation `ia` | crop to min(Hd, h0) x min(Wd, w0) at (y0, x0) |
+//      affine zoom about the centre (u = (x - cx) * (1/sx) + cx, cx = w0/2 - 0.5; bilinear, 0 outside the image),
+//      output rounded to uint8 as in imgaug,
+//   R  final resize of B's output to (Hd, Wd) with interpolation `if` (identity when the sizes agree),
+// then the normalisation table of detr_hip_input_stage.  Stage B is fused into R: every tap of the final resize recomputes
+// the stage-B pixel it reads (rounded to uint8 first), so the result is that of the two stages applied one after the other.
+//
+// Nearest / linear / cubic are input_stage_kernel's fp32 formulas in the same operation order (bit-identical results).
+// Area is OpenCV's INTER_AREA restated from its documentation: for r = src / dst >= 1 on both axes the fractional-overlap
+// box average of the source footprint divided by rx * ry, otherwise per axis the linear taps with OpenCV's area-mode
+// coefficient.  OpenCV's uint8 paths use fixed-point coefficients: parity with cv2 / imgaug is unpinned, as for cubic.
+//
+// Safety: every source index is clamped into its own image, and an image whose record does not fit in the `src_bytes`
+// bytes of `src` is read as a single pixel at offset 0, so no record can read outside src; writes depend on B, Hd, Wd only.
+#include "common.h"
+
+namespace detr {
+
+constexpr int AUG_THREADS = 256;
+constexpr int AUG_PIX = 4;               // output pixels per lane: 12 floats = three 16-byte stores
+
+struct AugArgs {
+    const unsigned char *src; long long src_bytes;
+    const int *irec;                     // [B][DETR_AUG_IREC]
+    const float *frec;                   // [B][DETR_AUG_FREC]
+    float *dst;                          // [B, Hd, Wd, 3]
+    const float *lut;                    // [3][256]
+    int B, Hd, Wd, perm0, perm1, perm2, vec;
+};
+
+struct AugImage {
+    const unsigned char *src; long long lo, hi;      // readable byte range of this image: [lo, hi]
+    int h0, w0, flip, cy0, cx0;
+    float isx, isy;
+};
+
+// pixel (y, x) of the flipped source image (stage F), clamped into the image
+__device__ __forceinline__ void fetch_f(const AugImage &m, int y, int x, float (&v)[3]) {
+    y = min(max(y, 0), m.h0 - 1);
+    x = min(max(x, 0), m.w0 - 1);
+    if (m.flip) x = m.w0 - 1 - x;
+    const long long o = min(max(m.lo + ((long long)y * m.w0 + x) * 3, m.lo), m.hi);
+    const unsigned char *p = m.src + o;
+    v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+}
+
+// stage B = none / crop: a shifted window of F
+struct FetchWindow {
+    const AugImage &m;
+    __device__ __forceinline__ void operator()(int y, int x, float (&v)[3]) const { fetch_f(m, y + m.cy0, x + m.cx0, v); }
+};
+
+// stage B = affine zoom about the image centre, bilinear, 0 outside the image, rounded to uint8
+struct FetchAffine {
+    const AugImage &m;
+    __device__ __forceinline__ void operator()(int y, int x, float (&v)[3]) const {
+        const float cx = (float)m.w0 * 0.5f - 0.5f, cy = (float)m.h0 * 0.5f - 0.5f;
+        // clamping keeps floorf finite and in int range; any u outside [-2, w0 + 1] has both taps outside the image anyway
+        const float u = fminf(fmaxf(((float)x - cx) * m.isx + cx, -2.0f), (float)m.w0 + 1.0f);
+        const float w = fminf(fmaxf(((float)y - cy) * m.isy + cy, -2.0f), (float)m.h0 + 1.0f);
+        const int x0 = (int)floorf(u), y0 = (int)floorf(w);
+        const float cxs[2] = {1.0f - (u - (float)x0), u - (float)x0};
+        const float cys[2] = {1.0f - (w - (float)y0), w - (float)y0};
+        float acc[3] = {0.f, 0.f, 0.f};
+        for (int j = 0; j < 2; ++j) {
+            const int yy = y0 + j;
+            float row[3] = {0.f, 0.f, 0.f};
+            for (int k = 0; k < 2; ++k) {
+                const int xx = x0 + k;
+                float p[3] = {0.f, 0.f, 0.f};
+                if (yy >= 0 && yy < m.h0 && xx >= 0 && xx < m.w0) fetch_f(m, yy, xx, p);
+                row[0] += cxs[k] * p[0]; row[1] += cxs[k] * p[1]; row[2] += cxs[k] * p[2];
+            }
+            acc[0] += cys[j] * row[0]; acc[1] += cys[j] * row[1]; acc[2] += cys[j] * row[2];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = fminf(fmaxf(rintf(acc[c]), 0.0f), 255.0f);
+    }
+};
+
+__device__ __forceinline__ void aug_cubic_coeffs(float f, float (&c)[4]) {     // = input_stage.hip: cubic_coeffs
+    const float A = -0.75f;
+    c[0] = ((A * (f + 1.0f) - 5.0f * A) * (f + 1.0f) + 8.0f * A) * (f + 1.0f) - 4.0f * A;
+    c[1] = ((A + 2.0f) * f - (A + 3.0f)) * f * f + 1.0f;
+    c[2] = ((A + 2.0f) * (1.0f - f) - (A + 3.0f)) * (1.0f - f) * (1.0f - f) + 1.0f;
+    c[3] = 1.0f - c[0] - c[1] - c[2];
+}
+
+// area mode, one axis, linear-tap form (some ratio < 1): s = floor(d * r), f = (d + 1) - (s + 1) / r, f <= 0 ? 0 : frac(f)
+__device__ __forceinline__ void area_linear_axis(int d, float r, int &s, float (&c)[4]) {
+    s = (int)floorf((float)d * r);
+    float f = ((float)d + 1.0f) - ((float)s + 1.0f) / r;
+    f = f <= 0.0f ? 0.0f : f - floorf(f);
+    c[0] = 1.0f - f; c[1] = f;
+}
+
+// resize of the Hs x Ws image `fetch` reads to Hd x Wd at output pixel (y, x); result rounded + saturated to uint8 values
+template <class Fetch>
+__device__ __forceinline__ void resample(const Fetch &fetch, int Hs, int Ws, int Hd, int Wd, int mode, int y, int x, float (&v)[3]) {
+    if (Hs == Hd && Ws == Wd) { fetch(y, x, v); return; }
+    const float sy = (float)Hs / (float)Hd, sx = (float)Ws / (float)Wd;
+    if (mode == 0) {
+        const int yy = min(max((int)floorf((float)y * sy), 0), Hs - 1), xx = min(max((int)floorf((float)x * sx), 0), Ws - 1);
+        fetch(yy, xx, v);
+        return;
+    }
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (mode == 3 && sy >= 1.0f && sx >= 1.0f) {
+        // box average: fractional overlap of [d * r, (d + 1) * r) with every source cell, / (rx * ry)
+        const float fy1 = (float)y * sy, fy2 = (float)(y + 1) * sy, fx1 = (float)x * sx, fx2 = (float)(x + 1) * sx;
+        const int ylo = min((int)floorf(fy1), Hs - 1), yhi = min((int)ceilf(fy2) - 1, Hs - 1);
+        const int xlo = min((int)floorf(fx1), Ws - 1), xhi = min((int)ceilf(fx2) - 1, Ws - 1);
+        for (int j = ylo; j <= yhi; ++j) {
+            const float oy = fminf(fy2, (float)(j + 1)) - fmaxf(fy1, (float)j);
+            float row[3] = {0.f, 0.f, 0.f};
+            for (int k = xlo; k <= xhi; ++k) {
+                const float ox = fminf(fx2, (float)(k + 1)) - fmaxf(fx1, (float)k);
+                float p[3];
+                fetch(j, k, p);
+                row[0] += ox * p[0]; row[1] += ox * p[1]; row[2] += ox * p[2];
+            }
+            acc[0] += oy * row[0]; acc[1] += oy * row[1]; acc[2] += oy * row[2];
+        }
+        const float inv = 1.0f / (sx * sy);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = acc[c] * inv;
+    } else {
+        int n, off, y0, x0;
+        float cy[4], cx[4];
+        if (mode == 3) {
+            area_linear_axis(y, sy, y0, cy);
+            area_linear_axis(x, sx, x0, cx);
+            n = 2; off = 0;
+        } else {
+            const float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
+            y0 = (int)floorf(fy); x0 = (int)floorf(fx);
+            if (mode == 1) {
+                cy[0] = 1.0f - (fy - (float)y0); cy[1] = fy - (float)y0;
+                cx[0] = 1.0f - (fx - (float)x0); cx[1] = fx - (float)x0;
+                n = 2; off = 0;
+            } else {
+                aug_cubic_coeffs(fy - (float)y0, cy);
+                aug_cubic_coeffs(fx - (float)x0, cx);
+                n = 4; off = -1;
+            }
+        }
+        for (int j = 0; j < n; ++j) {
+            const int yy = min(max(y0 + off + j, 0), Hs - 1);
+            float row[3] = {0.f, 0.f, 0.f};
+            for (int k = 0; k < n; ++k) {
+                const int xx = min(max(x0 + off + k, 0), Ws - 1);
+                float p[3];
+                fetch(yy, xx, p);
+                row[0] += cx[k] * p[0]; row[1] += cx[k] * p[1]; row[2] += cx[k] * p[2];
+            }
+            acc[0] += cy[j] * row[0]; acc[1] += cy[j] * row[1]; acc[2] += cy[j] * row[2];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = fminf(fmaxf(rintf(acc[c]), 0.0f), 255.0f);      // back to uint8 like cv2 (saturate_cast)
+}
+
+// grid = (ceil(Hd * Wd / (AUG_THREADS * AUG_PIX)), B): the image index is uniform per workgroup, so is its record
+__global__ __launch_bounds__(AUG_THREADS) void augment_kernel(AugArgs a) {
+    const int b = blockIdx.y;
+    const int *ir = a.irec + (long long)b * DETR_AUG_IREC;
+    const float *fr = a.frec + (long long)b * DETR_AUG_FREC;
+    AugImage m;
+    m.src = a.src;
+    long long off = (long long)(unsigned)ir[0] | ((long long)ir[1] << 32);
+    m.h0 = ir[2]; m.w0 = ir[3];
+    if (off < 0 || m.h0 < 1 || m.w0 < 1 || m.h0 > 65536 || m.w0 > 65536 || off + (long long)m.h0 * m.w0 * 3 > a.src_bytes) {
+        off = 0; m.h0 = 1; m.w0 = 1;                 // a record that does not fit: one pixel at offset 0
+    }
+    m.lo = off; m.hi = off + (long long)m.h0 * m.w0 * 3 - 3;
+    m.flip = ir[4] & 1;
+    const int kind = ir[5], ia = min(max(ir[6], 0), 3), ifin = min(max(ir[7], 0), 3);
+    m.cy0 = kind == 2 ? min(max(ir[8], 0), m.h0) : 0;   // crop offset (stage B = crop only)
+    m.cx0 = kind == 2 ? min(max(ir[9], 0), m.w0) : 0;
+    m.isx = fr[0]; m.isy = fr[1];
+    const int Hd = a.Hd, Wd = a.Wd;
+    const long long HW = (long long)Hd * Wd;
+    const long long p0 = ((long long)blockIdx.x * AUG_THREADS + threadIdx.x) * AUG_PIX;
+    if (p0 >= HW) return;
+    float out[AUG_PIX * 3];
+#pragma unroll
+    for (int q = 0; q < AUG_PIX; ++q) {
+        const long long p = min(p0 + q, HW - 1);
+        const int y = (int)(p / Wd), x = (int)(p % Wd);
+        float v[3];
+        if (kind == 1) {                             // resize to (Hd, Wd): the final resize is the identity
+            resample(FetchWindow{m}, m.h0, m.w0, Hd, Wd, ia, y, x, v);
+        } else if (kind == 3) {
+            resample(FetchAffine{m}, m.h0, m.w0, Hd, Wd, ifin, y, x, v);
+        } else if (kind == 2) {
+            resample(FetchWindow{m}, min(Hd, m.h0), min(Wd, m.w0), Hd, Wd, ifin, y, x, v);
+        } else {
+            resample(FetchWindow{m}, m.h0, m.w0, Hd, Wd, ifin, y, x, v);
+        }
+        out[3 * q + 0] = a.lut[(int)v[a.perm0]];
+        out[3 * q + 1] = a.lut[256 + (int)v[a.perm1]];
+        out[3 * q + 2] = a.lut[512 + (int)v[a.perm2]];
+    }
+    float *o = a.dst + ((long long)b * HW + p0) * 3;
+    if (a.vec && p0 + AUG_PIX <= HW) {
+        float4 *o4 = reinterpret_cast<float4 *>(o);
+        o4[0] = make_float4(out[0], out[1], out[2], out[3]);
+        o4[1] = make_float4(out[4], out[5], out[6], out[7]);
+        o4[2] = make_float4(out[8], out[9], out[10], out[11]);
+    } else {
+        for (int q = 0; q < AUG_PIX && p0 + q < HW; ++q) {
+            o[3 * q + 0] = out[3 * q + 0]; o[3 * q + 1] = out[3 * q + 1]; o[3 * q + 2] = out[3 * q + 2];
+        }
+    }
+}
+
+}  // namespace detr
+
+using namespace detr;
+
+extern "C" int detr_hip_augment(const uint8_t *src, int64_t src_bytes, const int32_t *irec, const float *frec, int32_t B, int32_t Hd,
+                                int32_t Wd, const float *lut, const int32_t *perm, float *dst, void *stream) {
+    DETR_REQUIRE(src && irec && frec && lut && perm && dst, "augment: null operand");
+    DETR_REQUIRE(B > 0 && B <= 65535 && Hd > 0 && Wd > 0 && (long long)Hd * Wd <= (1ll << 30),
+                 "augment: bad shape B=%d Hd=%d Wd=%d", B, Hd, Wd);
+    DETR_REQUIRE(src_bytes >= 3, "augment: src_bytes must cover at least one pixel");
+    for (int c = 0; c < 3; ++c) DETR_REQUIRE(perm[c] >= 0 && perm[c] < 3, "augment: channel permutation out of range");
+    AugArgs a;
+    a.src = src; a.src_bytes = src_bytes; a.irec = irec; a.frec = frec; a.dst = dst; a.lut = lut;
+    a.B = B; a.Hd = Hd; a.Wd = Wd; a.perm0 = perm[0]; a.perm1 = perm[1]; a.perm2 = perm[2];
+    const long long HW = (long long)Hd * Wd;
+    a.vec = aligned16(dst) && HW % AUG_PIX == 0;     // every lane's 12 floats start on a 16-byte boundary
+    const long long groups = (HW + (long long)AUG_THREADS * AUG_PIX - 1) / ((long long)AUG_THREADS * AUG_PIX);
+    hipLaunchKernelGGL(augment_kernel, dim3((unsigned)groups, (unsigned)B), dim3(AUG_THREADS), 0, (hipStream_t)stream, a);
+    DETR_LAUNCH_CHECK("augment");
+    return 0;
+}

@@ -1,0 +1,122 @@
+"""The batch pipeline shared by the COCO, VOC and CSV loaders (the reference's tf.data pipelines, data/coco.py:95-126,
+voc.py:79-127, tfcsv.py:51-77).
+
+The host decodes JPEG / PNG (PIL, a small thread pool with one batch of lookahead), draws the transform records and moves
+the boxes (transformation.py); the uint8 images go to the device, where csrc/augment.hip applies flip / stage B / final resize
+and the normalisation, and DeviceInputStage.targets builds the padded target layout.  Each iteration is a new shuffled epoch;
+`len()` is the number of whole batches (drop remainder).
+"""
+import os
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+from typing import NamedTuple
+
+import numpy as np
+
+from . import transformation as T
+
+
+class Sample(NamedTuple):
+    path: str
+    boxes: np.ndarray            # float32 [n, 4] normalised (cx, cy, w, h)
+    classes: np.ndarray          # int64 [n, 1]
+
+
+def resolve(data_dir, path):
+    """A dataset path as the reference joins it (config.data joins data_dir in already; an explicit argument is relative)."""
+    if path is None or data_dir is None or os.path.isabs(path) or os.path.exists(path):
+        return path
+    return os.path.join(data_dir, path)
+
+
+def decode_image(path):
+    """JPEG / PNG -> uint8 [h, w, 3] RGB (grey and RGBA converted)."""
+    try:
+        from PIL import Image
+    except ImportError as e:                     # pragma: no cover - PIL is a declared requirement of the loaders
+        raise ImportError("the dataset loaders decode images with Pillow (PIL): install it to use detr_tf.data") from e
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+class DetectionDataset:
+    """Re-iterable dataset of (images, t_bbox, t_class) batches on the device, in the layout fit / eval take.
+
+    augmentation: True = the reference's training augmentation, False = resize to config.image_size (cubic), None = no
+    transform at all: batch size 1 gives the image at its native size, a larger batch a padded (images, masks) pair.
+    An image that loses all its boxes to augmentation is skipped (the next one takes its place), so an epoch can yield fewer
+    than len() batches."""
+
+    def __init__(self, samples, config, batch_size, augmentation=False, seed=None, num_workers=4, device=None):
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.samples = list(samples)
+        self.config = config
+        self.batch_size = int(batch_size)
+        self.augmentation = augmentation
+        self.image_size = tuple(int(v) for v in config.image_size)
+        self.num_workers = max(1, int(num_workers))
+        self.device = device
+        self.rng = np.random.default_rng(seed)
+        self._stage = None
+
+    def __len__(self):
+        return len(self.samples) // self.batch_size
+
+    def stage(self):
+        if self._stage is None:
+            from .processing import DeviceInputStage
+            self._stage = DeviceInputStage(self.config, device=self.device)
+        return self._stage
+
+    def host_batches(self):
+        """One epoch on the host: lists of (image uint8 [h, w, 3], record or None, boxes, classes), batch_size each."""
+        order = self.rng.permutation(len(self.samples))
+        lookahead = 2 * self.batch_size                       # the batch being assembled + one batch ahead
+        with ThreadPoolExecutor(max_workers=self.num_workers) as pool:
+            pending = deque()
+            nxt = 0
+
+            def fill():
+                nonlocal nxt
+                while len(pending) < lookahead and nxt < len(order):
+                    s = self.samples[int(order[nxt])]
+                    pending.append((s, pool.submit(decode_image, s.path)))
+                    nxt += 1
+
+            batch = []
+            fill()
+            while pending:
+                s, fut = pending.popleft()
+                fill()
+                image = fut.result()
+                h0, w0 = image.shape[:2]
+                if self.augmentation is None:
+                    batch.append((image, None, s.boxes, s.classes))
+                else:
+                    rec = T.draw_transform(self.rng, h0, w0, self.image_size, self.augmentation)
+                    boxes, classes = T.transform_boxes(s.boxes, s.classes, h0, w0, rec, self.image_size)
+                    if len(boxes) == 0:
+                        continue
+                    batch.append((image, rec, boxes, classes))
+                if len(batch) == self.batch_size:
+                    yield batch
+                    batch = []
+
+    def __iter__(self):
+        st = self.stage()
+        for batch in self.host_batches():
+            images = [b[0] for b in batch]
+            if self.augmentation is None:
+                if len(images) == 1:                     # the native size: images() copies without resizing
+                    st.image_size = images[0].shape[:2]
+                    try:
+                        dev = st.images(images[0][None])
+                    finally:
+                        st.image_size = self.image_size
+                else:
+                    dev = st.images_padded(images)
+            else:
+                dev = st.augmented(images, [b[1] for b in batch])
+            t_bbox, t_class = st.targets([b[2] for b in batch], [b[3] for b in batch])
+            yield dev, t_bbox, t_class

@@ -73,6 +73,7 @@ class DeviceInputStage:
         lut, self.perm = normalization_table(config.normalized_method)
         self.lut = torch.from_numpy(lut).to(self.device)
         self.interpolation = INTERPOLATIONS[interpolation]
+        self._aug_img = self._aug_rec = self._aug_event = None         # augmented(): pinned staging buffers, last copy's event
         hip.load()
 
     def images(self, batch_uint8, out=None):
@@ -118,6 +119,49 @@ class DeviceInputStage:
                                                           ctypes.cast(perm, ctypes.c_void_p), dst.data_ptr(), mask.data_ptr(), hip._stream()),
                    "detr_hip_input_stage_padded")
         return dst, mask.view(torch.bool)
+
+    def augmented(self, images_uint8, records):
+        """Training batch with augmentation: a list of uint8 images [h_i, w_i, 3] (host, each at its own size) and one
+        transformation.Transform record per image -> float32 [B, image_size[0], image_size[1], 3] on the device: flip,
+        stage B, final resize and normalisation in one launch of csrc/augment.hip.  Images and records cross PCIe through
+        pinned staging buffers, one copy each; the buffers are reused across batches once their last copy has finished."""
+        from . import transformation as T
+        srcs = [np.asarray(im) for im in images_uint8]
+        if not srcs or len(srcs) != len(records) or any(s.dtype != np.uint8 or s.ndim != 3 or s.shape[-1] != 3 for s in srcs):
+            raise TypeError("DeviceInputStage.augmented expects a non-empty list of uint8 images [h, w, 3] and one record per image")
+        for s, t in zip(srcs, records):
+            if (t.h0, t.w0) != s.shape[:2]:
+                raise ValueError(f"transform record for a {t.h0} x {t.w0} image given a {s.shape[0]} x {s.shape[1]} image")
+            T.check_record(t, self.image_size)
+        sizes = np.array([s.size for s in srcs], np.int64)
+        offsets = np.zeros(len(srcs), np.int64)
+        offsets[1:] = np.cumsum(sizes)[:-1]
+        total = int(sizes.sum())
+        irec, frec = T.pack_records(records, offsets)
+        rec_bytes = irec.nbytes + frec.nbytes
+        if self._aug_event is not None:
+            self._aug_event.synchronize()           # the previous batch's copies out of the staging buffers have finished
+        if self._aug_img is None or self._aug_img.numel() < total:
+            self._aug_img = torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        if self._aug_rec is None or self._aug_rec.numel() < rec_bytes:
+            self._aug_rec = torch.empty(max(rec_bytes, 4096), dtype=torch.uint8, pin_memory=True)
+        img_h, rec_h = self._aug_img.numpy(), self._aug_rec.numpy()
+        for s, o in zip(srcs, offsets):
+            img_h[o:o + s.size] = s.reshape(-1)
+        rec_h[:irec.nbytes] = irec.view(np.uint8).reshape(-1)
+        rec_h[irec.nbytes:rec_bytes] = frec.view(np.uint8).reshape(-1)
+        src = self._aug_img[:total].to(self.device, non_blocking=True)
+        rec = self._aug_rec[:rec_bytes].to(self.device, non_blocking=True)
+        self._aug_event = torch.cuda.Event()
+        self._aug_event.record()
+        B = len(srcs)
+        Hd, Wd = self.image_size
+        dst = torch.empty(B, Hd, Wd, 3, dtype=torch.float32, device=self.device)
+        perm = (ctypes.c_int32 * 3)(*self.perm)
+        hip._check(hip.load().detr_hip_augment(src.data_ptr(), total, rec.data_ptr(), rec.data_ptr() + irec.nbytes, B, Hd, Wd,
+                                               self.lut.data_ptr(), ctypes.cast(perm, ctypes.c_void_p), dst.data_ptr(), hip._stream()),
+                   "detr_hip_augment")
+        return dst
 
     def targets(self, boxes_per_image, classes_per_image):
         """lists (one entry per image) of [n_i, 4] cx,cy,w,h boxes and [n_i] class ids -> (t_bbox [B,100,4] float32,

@@ -487,6 +487,21 @@ int detr_hip_input_stage_padded(const uint8_t *src, const int64_t *offsets, cons
                                 const float *lut, const int32_t *perm, float *dst, uint8_t *mask, void *stream);
 int detr_hip_pad_labels(const float *boxes, const int64_t *classes, const int32_t *offsets, int32_t B, int32_t R,
                         float *t_bbox, int64_t *t_class, void *stream);
+/* Training augmentation (the reference's imgaug `detr_aug_seq`, data/transformation.py:54-94; csrc/augment.hip): image b of a
+ * ragged uint8 batch, packed back to back in src (src_bytes bytes, device), goes through flip -> stage B -> final resize to
+ * (Hd, Wd) and the normalisation of detr_hip_input_stage (lut / perm as there, perm a host array of 3) into dst [B, Hd, Wd, 3]
+ * float32.  One launch.  Per-image records (device arrays):
+ *   irec[b][DETR_AUG_IREC] int32: 0,1 byte offset of image b in src (low, high 32 bits); 2 h0; 3 w0; 4 flip (0/1);
+ *     5 stage B: 0 none, 1 resize to (Hd, Wd), 2 crop to min(Hd, h0) x min(Wd, w0) at (8, 9), 3 affine zoom about the centre;
+ *     6 stage-B resize interpolation; 7 final interpolation (0 nearest, 1 linear, 2 cubic, 3 area); 8 crop y0; 9 crop x0
+ *   frec[b][DETR_AUG_FREC] float32: 0 1/sx, 1 1/sy (affine: source x = (x - cx) * (1/sx) + cx, cx = w0/2 - 0.5, bilinear,
+ *     0 outside the image)
+ * Stage B's output is rounded to uint8 before the final resize, as in imgaug.  Source reads are clamped into each image and
+ * into src_bytes, so a wrong record cannot read outside src. */
+#define DETR_AUG_IREC 10
+#define DETR_AUG_FREC 2
+int detr_hip_augment(const uint8_t *src, int64_t src_bytes, const int32_t *irec, const float *frec, int32_t B, int32_t Hd, int32_t Wd,
+                     const float *lut, const int32_t *perm, float *dst, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched post-processing (detr_tf/inference.py:68-95, which handles batch element 0 only; the validation loops call it
