@@ -141,6 +141,7 @@ _SIGNATURES = {
     "detr_hip_attention_dropmask_many": [POINTER(AttnDesc), c_int32, c_void_p],
     "detr_hip_attention_fwd_masked": [POINTER(AttnDesc), c_void_p, c_void_p],
     "detr_hip_attention_bwd_masked": [POINTER(AttnDesc), c_void_p, c_void_p],
+    "detr_hip_attention_weights": [POINTER(AttnDesc), c_void_p, c_void_p, c_int64, c_void_p],
     "detr_hip_padding_mask_prepare": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, f32p, f32p, c_void_p, f32p, c_void_p, c_void_p],
     "detr_hip_input_stage_padded": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, f32p, c_void_p, f32p, c_void_p, c_void_p],
     "detr_hip_dropout_f32": [f32p, f32p, c_int64, c_float, ctypes.c_uint32, c_void_p, c_void_p],
@@ -868,6 +869,42 @@ def attention(q, k, v, o, lse, B, H, T, S, *, scale=1.0, dropout_p=0.0, dropout_
         _check(load().detr_hip_attention_bwd(byref(d), _stream()), "detr_hip_attention_bwd")
     if ev0 is not None:      # dQ kernel: S, dP, dQ; dK/dV kernel: S, dP, dV, dK (the probabilities are recomputed twice)
         PROFILER.end("attention_bwd", 7 * prods, ev0, f"B{B} H{H} T{T} S{S}", 2.5 * io + 2 * bits)
+
+
+def attention_weights(q, k, lse, w, B, H, T, S, *, scale, compute=None, key_valid=None):
+    """Head-averaged attention map (detr_hip_attention_weights; transformer.py:349-354): w [B, T, >= S] fp32 (row stride taken from
+    the tensor) = (1/H) sum_h softmax_s(scale q.k), from the q / k the forward attention() call read and the lse it wrote.  Same
+    dtype / stride rules as attention(): fp32 tensors (compute None / 0 / 2) or bf16 tensors with q pre-multiplied by
+    scale * log2(e); key_valid as there (a masked key gets an exact 0)."""
+    kv = None
+    if key_valid is not None:
+        if not key_valid.is_cuda or key_valid.element_size() != 4 or key_valid.numel() < attention_keymask_words(B, S):
+            raise ValueError("attention_weights: key_valid must be a device tensor of attention_keymask_words(B, S) 32-bit words")
+        kv = key_valid.data_ptr()
+    d = AttnDesc()
+    d.B, d.H, d.T, d.S = B, H, T, S
+    io16 = q.dtype == torch.bfloat16
+    want = torch.bfloat16 if io16 else torch.float32
+    for name, t in (("q", q), ("k", k)):
+        if t.stride(1) != 1 or t.dtype != want:
+            raise TypeError(f"attention_weights: {name} must be {want} with a unit column stride")
+        setattr(d, name, t.data_ptr())
+        setattr(d, "ld" + name, t.stride(0))
+    if lse.dtype != torch.float32 or lse.numel() < B * H * T or not lse.is_contiguous():
+        raise TypeError("attention_weights: lse must be a contiguous fp32 tensor [B*H, T]")
+    if w.dtype != torch.float32 or w.dim() != 3 or w.shape[0] != B or w.shape[1] != T or w.shape[2] < S or w.stride(2) != 1 \
+            or w.stride(0) != T * w.stride(1):
+        raise TypeError("attention_weights: w must be fp32 [B, T, >= S] with a unit column stride and batch stride T * row stride")
+    d.lse = lse.data_ptr()
+    d.scale = scale
+    d.io_dtype = 1 if io16 else 0
+    d.compute = 1 if io16 else (0 if compute is None else int(compute))
+    ev0 = PROFILER.begin() if PROFILER is not None else None
+    _check(load().detr_hip_attention_weights(byref(d), kv, w.data_ptr(), w.stride(1), _stream()), "detr_hip_attention_weights")
+    if ev0 is not None:
+        esz = 2.0 if io16 else 4.0
+        PROFILER.end("attention_weights", 2.0 * B * H * T * S * 32, ev0, f"B{B} H{H} T{T} S{S}",
+                     esz * 256 * (B * T + B * S) + 4.0 * B * H * T + 4.0 * B * T * S)
 
 
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps, *, add=None, y2=None, y16=None):

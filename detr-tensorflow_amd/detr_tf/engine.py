@@ -132,6 +132,8 @@ class DetrEngine:
         self._pos_cache = {}
         self._pos_tables = {}
         self.key_valid = None        # key-validity words of the current masked pass (None: unmasked)
+        self._attn_sites = ()        # attention sites whose head-averaged map this pass writes (forward(attn_sites=...))
+        self.attn_maps = {}          # site name -> engine buffer [B, T, S] fp32 of the last pass that requested it
         self._shape = None
         self.bn_scale, self.bn_shift = {}, {}
         self._weights_version, self._built = 0, {}
@@ -503,8 +505,38 @@ class DetrEngine:
             O = self.buf(f"{tag}:O", (B * T, D))
             hip.attention(QKV[:, 0:D], QKV[:, D:2 * D], QKV[:, 2 * D:], O, lse, B, HEADS, T, T, scale=float(HD) ** -0.5,
                           dropout_p=dp, dropout_site=site, dropout_step=self._seed_dev, key_valid=key_valid)     # :307-345
+        if pfx in self._attn_sites:
+            self._attn_map(pfx, QKV[:, 0:D], QKV[:, D:2 * D], lse, B, T, T, key_valid)
         hip.linear_fwd(O, self._w(f"{pfx}/out_proj_kernel"), self.P.views[f"{pfx}/out_proj_bias"], out, residual=v_in,
                        dropout_p=dp, dropout_seed=site + 1, dropout_step=self._seed_dev, ln=ln)        # :346-347 + :169 (+ the LayerNorm behind it)
+
+    def attn_site_names(self):
+        """The attention sites of this model, by the parameter paths of the weight files, in launch order."""
+        names = [f"transformer/encoder/layer_{i}/self_attn" for i in range(self.num_enc)]
+        for i in range(self.num_dec):
+            names += [f"transformer/decoder/layer_{i}/self_attn", f"transformer/decoder/layer_{i}/multihead_attn"]
+        return names
+
+    def _check_attn_sites(self, attn_sites, training):
+        if not attn_sites:
+            return ()
+        if isinstance(attn_sites, str):
+            attn_sites = (attn_sites,)
+        sites, valid = tuple(dict.fromkeys(attn_sites)), self.attn_site_names()
+        unknown = [s for s in sites if s not in valid]
+        if unknown:
+            raise ValueError(f"attn_sites: unknown attention site(s) {unknown}; valid names: {valid}")
+        if training:
+            # the reference averages the weights AFTER the attention dropout there (transformer.py:341, 349-354)
+            raise NotImplementedError("attention maps (attn_sites / need_weights) are returned in evaluation mode only: with training=True "
+                                      "the reference averages the weights after their dropout, which the maps kernel does not apply")
+        return sites
+
+    def _attn_map(self, site, q, k, lse, B, T, S, key_valid):
+        """The head-averaged map of `site` right behind its attention launch (same stream, same q / k / lse / key_valid), :349-354."""
+        w = self.buf(f"attnw:{site}", (B, T, S))
+        hip.attention_weights(q, k, lse, w, B, HEADS, T, S, scale=float(HD) ** -0.5, key_valid=key_valid)
+        self.attn_maps[site] = w
 
     def _self_attn_bwd(self, tag, pfx, d_out, d_res, qk_in, v_in, B, T, d_x, site, acc_qk=None, key_valid=None):
         """d_out: gradient of the out-projection output (dropout backward already applied), d_res: gradient of the
@@ -607,11 +639,17 @@ class DetrEngine:
         return self._cross[key]
 
     # ---- forward ----------------------------------------------------------------------------------
-    def forward(self, images, training=False, masks=None):
+    def forward(self, images, training=False, masks=None, attn_sites=None):
         """See _forward_impl.  GEMM / conv compute mode: self.compute (0 = exact fp32, 1 = bf16 MFMA).
+        attn_sites: iterable of attention site names (attn_site_names(): the parameter paths `transformer/encoder/layer_{i}/self_attn`,
+        `transformer/decoder/layer_{i}/self_attn`, `transformer/decoder/layer_{i}/multihead_attn`).  For each, one extra launch
+        behind that site's attention launch writes the head-averaged attention map [B, T, S] (fp32, transformer.py:349-354) into
+        self.attn_maps[name]; evaluation mode only.  None / empty: the launch sequence is unchanged.
         masks: optional padding mask [B, H, W] (True = padding, detr.py:65-72) as a device uint8 / bool tensor or a host array
         (validated on the host: an image without a valid feature position raises ValueError).  A device mask is validated on
         the device: check_mask_status() reads the result where the caller synchronises anyway."""
+        self._attn_sites = self._check_attn_sites(attn_sites, training)
+        self.attn_maps = {}
         hip.COMPUTE_BF16 = self.gemm_mode
         if self.compute == 1 and (self._stale("shadow16") or self.P.views16 is None):
             self._refresh_shadow()
@@ -869,6 +907,8 @@ class DetrEngine:
             hip.attention(Qc, KV[:, i * D:(i + 1) * D], KV[:, (nd + i) * D:(nd + i + 1) * D], Oc, lse, B, HEADS, Q, L,
                           scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=ds + 2, dropout_step=self._seed_dev,
                           dropmask=self._dropmask(ds + 2, B, Q, L) if (a16 and dp > 0.0) else None, key_valid=self.key_valid)
+            if cp in self._attn_sites:
+                self._attn_map(cp, Qc, KV[:, i * D:(i + 1) * D], lse, B, Q, L, self.key_valid)
             a2 = self.buf(f"{tag}:a2", (B * Q, D))
             t2 = self.buf(f"{tag}:t2", (B * Q, D))
             t2h = self.buf(f"{tag}:t2h", (B * Q, D), torch.bfloat16) if self.ffn16 else None

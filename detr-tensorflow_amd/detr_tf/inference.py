@@ -54,3 +54,20 @@ def get_model_inference(m_outputs: dict, background_class, bbox_format="xy_cente
     out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"][0:1], m_outputs["pred_boxes"][0:1], background_class, bbox_format)
     k = int(counts[0])
     return out_b[0, :k], out_l[0, :k], out_s[0, :k]
+
+
+def get_attention_maps(model, images, need_weights=True):
+    """(m_outputs, maps): one evaluation forward with `need_weights` (DetrModel.__call__: True = last encoder self-attention and last
+    decoder cross-attention, or an iterable of site names), every map [B, T, S] reshaped to [B, T, Hf, Wf] over the Hf x Wf feature map
+    (engine.feature_size of the input) -- the shape a user overlays on the image.  Encoder maps and decoder cross-attention maps have
+    S = Hf * Wf keys; a decoder self-attention map (keys = object queries) is returned as [B, Q, Q].  `images` may be the
+    (images, masks) pair of a padded batch: the map is then zero on the padded feature positions."""
+    from .engine import feature_size
+    m_outputs = model(images, training=False, need_weights=need_weights)
+    imgs = images[0] if isinstance(images, (tuple, list)) else images
+    Hf, Wf = feature_size(int(imgs.shape[1]), int(imgs.shape[2]))
+    maps = {}
+    for name, w in m_outputs["attn"].items():
+        B, T, S = w.shape
+        maps[name] = w if "/decoder/" in name and name.endswith("/self_attn") else w.reshape(B, T, Hf, Wf)
+    return m_outputs, maps

@@ -123,17 +123,18 @@ class DetrModel:
         self.engine.P.save(self._npz(path))
 
     # ---- forward ----------------------------------------------------------------------------
-    def _eval_forward(self, images, masks=None):
+    def _eval_forward(self, images, masks=None, attn_sites=()):
         """Eval-mode forward.  The launch sequence of a fixed input shape is static, so the second call with the same shape
         (and the same weights version) records it as a hipGraph and later calls replay it: a single 480x640 image is ~300
         launches whose host cost (ctypes, ~10 us each) exceeds their GPU time.  DETR_HIP_GRAPH=0 / model.eval_graph = False:
-        always eager.  Outputs are views of the engine's buffers either way (the caller clones)."""
+        always eager.  Outputs are views of the engine's buffers either way (the caller clones).  attn_sites: the attention maps this
+        call also writes (engine.attn_maps); they are part of the graph key, and a replay refills the same buffers."""
         eng = self.engine
         if masks is not None and not (torch.is_tensor(masks) and masks.is_cuda):
             masks = eng._host_masks(masks, tuple(images.shape[:3]))      # validated on the host, then a device input like any other
         if not (self.eval_graph and os.environ.get("DETR_HIP_GRAPH", "1") != "0" and images.is_cuda):
-            return eng.forward(images, training=False, masks=masks)
-        key = (tuple(images.shape), eng._weights_version, eng.compute, masks is not None)
+            return eng.forward(images, training=False, masks=masks, attn_sites=attn_sites)
+        key = (tuple(images.shape), eng._weights_version, eng.compute, tuple(attn_sites), masks is not None)
         g = self._eval_graph
         # a graph addresses the engine's buffers as they were at capture: any later re-allocation (a forward of another
         # shape in between) makes it unusable -- engine.buf_generation tells
@@ -142,12 +143,13 @@ class DetrModel:
             if masks is not None:
                 g["static_mask"].copy_(masks)
             g["graph"].replay()
+            eng.attn_maps = dict(g["maps"])
             return g["out"]
         if g is not None and g["gen"] != eng.buf_generation:
             self._eval_graph = g = None
         if self._eval_seen != (key, eng.buf_generation):
             # first sighting of this shape with these buffers: eager (allocates the buffers, refreshes derived weight copies)
-            out = eng.forward(images, training=False, masks=masks)
+            out = eng.forward(images, training=False, masks=masks, attn_sites=attn_sites)
             self._eval_seen = (key, eng.buf_generation)
             return out
         static = g["static"] if g is not None and g["static"].shape == images.shape else torch.empty_like(images)
@@ -158,15 +160,21 @@ class DetrModel:
             static_mask.copy_(masks)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):       # (see training._Segments.begin)
-            out = eng.forward(static, training=False, masks=static_mask)
-        self._eval_graph = dict(key=key, static=static, static_mask=static_mask, graph=graph, out=out, gen=eng.buf_generation)
+            out = eng.forward(static, training=False, masks=static_mask, attn_sites=attn_sites)
+        self._eval_graph = dict(key=key, static=static, static_mask=static_mask, graph=graph, out=out, gen=eng.buf_generation,
+                                maps=dict(eng.attn_maps))
         graph.replay()
         return out
 
-    def __call__(self, images, training=False, masks=None):
+    def __call__(self, images, training=False, masks=None, need_weights=None):
         """images: [B, H, W, 3] float32, or the reference's `(images, masks)` pair (detr.py:65-72); masks: [B, H, W] bool, True =
         padding (a padded mixed-size batch).  Host masks are validated here (ValueError for an image without a
-        valid feature position); device masks on the device (engine.check_mask_status)."""
+        valid feature position); device masks on the device (engine.check_mask_status).
+        need_weights (the reference's MultiHeadAttention need_weights, transformer.py:285-286, 349-354; evaluation mode only): True
+        = the head-averaged maps of the last encoder layer's self-attention [B, L, L] and of the last decoder layer's
+        cross-attention [B, Q, L] (L = Hf * Wf); an iterable of site names (engine.attn_site_names()) = those.  The result gains
+        out["attn"] = {site name: fp32 tensor [B, T, S]}."""
+        sites = self._need_weights_sites(need_weights, training)
         if isinstance(images, (tuple, list)):
             if masks is not None or len(images) != 2:
                 raise TypeError("model((images, masks)): pass the mask once, either in the tuple or as masks=")
@@ -178,7 +186,7 @@ class DetrModel:
             if masks.dtype not in (torch.bool, torch.uint8):
                 masks = masks != 0
             masks = masks.contiguous()
-        logits, boxes = self.engine.forward(images, training=True, masks=masks) if training else self._eval_forward(images, masks)
+        logits, boxes = self.engine.forward(images, training=True, masks=masks) if training else self._eval_forward(images, masks, sites)
         if self.headless:
             hs = self.engine._bufs["dec:hs"].view(self.engine.num_dec, images.shape[0], self.engine.Q, 256)
             return hs if training else hs.clone()
@@ -191,9 +199,29 @@ class DetrModel:
         out["pred_logits"], out["pred_boxes"] = logits[-1], boxes[-1]
         out["aux"] = [{"pred_logits": logits[i], "pred_boxes": boxes[i]} for i in range(logits.shape[0] - 1)]
         out.levels_logits, out.levels_boxes, out.model = logits, boxes, self
+        if sites:
+            out["attn"] = {name: self.engine.attn_maps[name].clone() for name in sites}
         if self.dp is not None:
             out.reduce_sums = self.dp.reduce_sums
         return out
+
+    def default_attn_sites(self):
+        """The two maps of need_weights=True: last encoder self-attention, last decoder cross-attention."""
+        eng = self.engine
+        sites = [f"transformer/encoder/layer_{eng.num_enc - 1}/self_attn"] if eng.num_enc > 0 else []
+        if eng.num_dec > 0:
+            sites.append(f"transformer/decoder/layer_{eng.num_dec - 1}/multihead_attn")
+        return tuple(sites)
+
+    def _need_weights_sites(self, need_weights, training):
+        if need_weights is None or need_weights is False:
+            return ()
+        sites = self.default_attn_sites() if need_weights is True else need_weights
+        sites = self.engine._check_attn_sites(sites, training)          # unknown names, training=True: rejected here
+        if sites and self.headless:
+            raise NotImplementedError("need_weights: the headless mode (include_top=False, nb_class=None) returns a bare tensor and "
+                                      "cannot carry attention maps; build the model with a head")
+        return sites
 
 
 def get_detr_model(config, include_top=False, nb_class=None, weights=None, tf_backbone=False, num_decoder_layers=6,

@@ -409,6 +409,13 @@ int detr_hip_attention_dropmask_many(const detr_attn_desc *descs, int32_t n, voi
 int64_t detr_hip_attention_keymask_words(int32_t B, int32_t S);
 int detr_hip_attention_fwd_masked(const detr_attn_desc *d, const uint32_t *key_valid, void *stream);
 int detr_hip_attention_bwd_masked(const detr_attn_desc *d, const uint32_t *key_valid, void *stream);
+/* transformer.py:349-354 (need_weights): w[b, t, s] = (1/H) sum_h softmax_s(scale q.k)[b,h,t,s], written as fp32 rows of
+ * stride ldw (floats, >= S); uses B, H, T, S, q/ldq, k/ldk, lse, scale, compute, io_dtype of the descriptor (v, o and the
+ * gradient fields are ignored); lse is the one the forward wrote for the same q, k (and the same key_valid).
+ * key_valid: NULL or the words of detr_hip_attention_fwd_masked; a masked key gets an exact 0.
+ * dropout_p must be 0 (rejected otherwise).  H <= 8, S <= 8192.  One pass that never forms the per-head [B*H, T, S] tensor: the H
+ * score tiles of a 32 x 32 block are accumulated in registers (csrc/attention_weights.hip); bound by the B*T*S*4 bytes it writes. */
+int detr_hip_attention_weights(const detr_attn_desc *d, const uint32_t *key_valid, float *w, int64_t ldw, void *stream);
 /* Padding mask -> transformer inputs (detr_tf/networks/detr.py:57-72 downsample_masks, position_embeddings.py:23-50 with
  * normalize=True), one launch: mask [B, H, W] uint8 / bool (nonzero = padding) is brought to the Hf x Wf feature map by TF-legacy
  * nearest neighbour (src = min(floor(dst * in / out), in - 1) per axis), and per image
