@@ -206,6 +206,16 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_postprocess_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_postprocess_desc, out_labels));
         DETR_PUT(DETR_OFF(detr_postprocess_desc, out_scores)); DETR_PUT(DETR_OFF(detr_postprocess_desc, counts));
         break;
+    case 9:   // detr_map_match_desc
+        DETR_PUT((int32_t)sizeof(detr_map_match_desc));
+        DETR_PUT(DETR_OFF(detr_map_match_desc, B)); DETR_PUT(DETR_OFF(detr_map_match_desc, Q)); DETR_PUT(DETR_OFF(detr_map_match_desc, R));
+        DETR_PUT(DETR_OFF(detr_map_match_desc, nb_class)); DETR_PUT(DETR_OFF(detr_map_match_desc, n_thr)); DETR_PUT(DETR_OFF(detr_map_match_desc, boxes));
+        DETR_PUT(DETR_OFF(detr_map_match_desc, labels)); DETR_PUT(DETR_OFF(detr_map_match_desc, scores)); DETR_PUT(DETR_OFF(detr_map_match_desc, counts));
+        DETR_PUT(DETR_OFF(detr_map_match_desc, sD_b)); DETR_PUT(DETR_OFF(detr_map_match_desc, t_bbox)); DETR_PUT(DETR_OFF(detr_map_match_desc, sT_b));
+        DETR_PUT(DETR_OFF(detr_map_match_desc, t_class)); DETR_PUT(DETR_OFF(detr_map_match_desc, sC_b)); DETR_PUT(DETR_OFF(detr_map_match_desc, thresholds));
+        DETR_PUT(DETR_OFF(detr_map_match_desc, rec_score)); DETR_PUT(DETR_OFF(detr_map_match_desc, rec_class)); DETR_PUT(DETR_OFF(detr_map_match_desc, rec_flags));
+        DETR_PUT(DETR_OFF(detr_map_match_desc, num_gt)); DETR_PUT(DETR_OFF(detr_map_match_desc, status));
+        break;
     default:
         detr::set_error("struct_layout: unknown struct %d", which);
         return -1;

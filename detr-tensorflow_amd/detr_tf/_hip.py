@@ -102,6 +102,19 @@ class PostprocessDesc(Structure):
                 ("out_boxes", c_void_p), ("out_labels", c_void_p), ("out_scores", c_void_p), ("counts", c_void_p)]
 
 
+MAP_MAX_THR = 16                                                               # DETR_MAP_MAX_THR
+MAP_BAD = {1: "a predicted label outside [0, nb_class)", 2: "a target class outside [0, nb_class)",
+           4: "a target header count outside [0, R-1]", 8: "a detection count outside [0, Q]"}      # DETR_MAP_BAD_*
+
+
+class MapMatchDesc(Structure):
+    _fields_ = [("B", c_int32), ("Q", c_int32), ("R", c_int32), ("nb_class", c_int32), ("n_thr", c_int32),
+                ("boxes", c_void_p), ("labels", c_void_p), ("scores", c_void_p), ("counts", c_void_p), ("sD_b", c_int64),
+                ("t_bbox", c_void_p), ("sT_b", c_int64), ("t_class", c_void_p), ("sC_b", c_int64),
+                ("thresholds", ctypes.c_double * MAP_MAX_THR),
+                ("rec_score", c_void_p), ("rec_class", c_void_p), ("rec_flags", c_void_p), ("num_gt", c_void_p), ("status", c_void_p)]
+
+
 class SetLossDesc(Structure):
     _fields_ = [("levels", c_int32), ("B", c_int32), ("Q", c_int32), ("C", c_int32), ("R", c_int32),
                 ("logits", c_void_p), ("sL_l", c_int64), ("sL_b", c_int64), ("sL_q", c_int64),
@@ -161,6 +174,7 @@ _SIGNATURES = {
     "detr_hip_scale_cols_t_f32": [f32p, f32p, f32p, c_int32, c_int32, c_void_p],
     "detr_hip_bn_fold_f32": [f32p, f32p, f32p, f32p, f32p, f32p, c_int32, c_float, c_void_p],
     "detr_hip_postprocess": [POINTER(PostprocessDesc), c_void_p],
+    "detr_hip_map_match": [POINTER(MapMatchDesc), c_void_p],
     "detr_hip_input_stage": [POINTER(InputDesc), c_void_p],
     "detr_hip_pad_labels": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     "detr_hip_augment": [c_void_p, c_int64, c_void_p, f32p, c_int32, c_int32, c_int32, f32p, c_void_p, f32p, c_void_p],
@@ -188,7 +202,8 @@ _SIGNATURES_I64 = {
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
 # order of detr_hip_struct_layout's `which`
-LAYOUT_STRUCTS = (ReduceDesc, GemmDesc, Conv3x3Desc, StemDesc, LayerNormDesc, AttnDesc, SetLossDesc, InputDesc, PostprocessDesc)
+LAYOUT_STRUCTS = (ReduceDesc, GemmDesc, Conv3x3Desc, StemDesc, LayerNormDesc, AttnDesc, SetLossDesc, InputDesc, PostprocessDesc,
+                  MapMatchDesc)
 
 _lib = None
 

@@ -1,28 +1,45 @@
 """mAP evaluation loop -- what the reference's eval.py:30-61 `eval_model` does, for any batch size: forward (eval mode),
 batched device post-processing (one launch per batch instead of one get_model_inference per image), header-stripped
-targets converted to [y1, x1, y2, x2] (bbox.py:186-196), the vectorised COCO-style accumulator, the reference's table."""
+targets converted to [y1, x1, y2, x2] (bbox.py:186-196), the vectorised COCO-style accumulator, the reference's table.
+
+accumulate="device" keeps the per-image matching on the device as well (loss/compute_map.py: DeviceAPAccumulator, one more
+launch per batch): nothing is read back per batch, so the loop enqueues batch i+1 while batch i still runs; the result is the
+same to the last bit."""
 import numpy as np
 import torch
 
 from . import bbox
 from .inference import get_model_inference_batched
-from .loss.compute_map import APAccumulator
+from .loss.compute_map import APAccumulator, DeviceAPAccumulator
 
 
-def eval_model(model, config, class_names, valid_dt, max_batches=None, print_result=True):
+def _add_batch_host(acc, model, m_outputs, target_bbox, target_class, background_class):
+    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx")
+    if getattr(model, "engine", None) is not None:
+        model.engine.check_mask_status()      # (padded batches with a device mask; the detections are read on the host anyway)
+    tb = torch.as_tensor(np.asarray(target_bbox) if not torch.is_tensor(target_bbox) else target_bbox).float().cpu()
+    tc = torch.as_tensor(np.asarray(target_class) if not torch.is_tensor(target_class) else target_class).cpu()
+    for b, (p_bbox, p_labels, p_scores) in enumerate(dets):
+        n = int(tb[b, 0, 0])                                          # header row (data/processing.py:35-55)
+        t_bbox = bbox.xcycwh_to_yx_min_yx_max(tb[b, 1:1 + n])
+        t_class = tc[b, 1:1 + n].reshape(-1)
+        acc.add_image(p_bbox.cpu().numpy(), p_labels.cpu().numpy(), p_scores.cpu().numpy(), t_bbox.numpy(), t_class.numpy())
+
+
+def eval_model(model, config, class_names, valid_dt, max_batches=None, print_result=True, accumulate="host"):
+    if accumulate not in ("host", "device"):
+        raise ValueError(f"eval_model: accumulate must be 'host' or 'device', got {accumulate!r}")
     acc = APAccumulator(len(class_names))
     for it, (images, target_bbox, target_class) in enumerate(valid_dt):
         m_outputs = model(images, training=False)
-        dets = get_model_inference_batched(m_outputs, config.background_class, bbox_format="yxyx")
-        if getattr(model, "engine", None) is not None:
-            model.engine.check_mask_status()      # (padded batches with a device mask; the detections are read on the host anyway)
-        tb = torch.as_tensor(np.asarray(target_bbox) if not torch.is_tensor(target_bbox) else target_bbox).float().cpu()
-        tc = torch.as_tensor(np.asarray(target_class) if not torch.is_tensor(target_class) else target_class).cpu()
-        for b, (p_bbox, p_labels, p_scores) in enumerate(dets):
-            n = int(tb[b, 0, 0])                                          # header row (data/processing.py:35-55)
-            t_bbox = bbox.xcycwh_to_yx_min_yx_max(tb[b, 1:1 + n])
-            t_class = tc[b, 1:1 + n].reshape(-1)
-            acc.add_image(p_bbox.cpu().numpy(), p_labels.cpu().numpy(), p_scores.cpu().numpy(), t_bbox.numpy(), t_class.numpy())
+        if accumulate == "device":
+            if it == 0:
+                acc = DeviceAPAccumulator(len(class_names), device=m_outputs["pred_logits"].device)
+            acc.add_batch(m_outputs, target_bbox, target_class, config.background_class)
+            if getattr(model, "engine", None) is not None:
+                model.engine.check_mask_status()  # (reads the mask status words of a padded batch; a no-op for an unpadded one)
+        else:
+            _add_batch_host(acc, model, m_outputs, target_bbox, target_class, config.background_class)
         if max_batches is not None and it + 1 >= max_batches:
             break
     return acc.result(class_names, print_result=print_result)

@@ -15,8 +15,12 @@ that claims it), and the AP integration is cummax + searchsorted.  Semantics kep
     positive there, so every non-empty class has mask AP 0; `result()` reports exactly that.
 """
 from collections import OrderedDict
+from ctypes import byref
 
 import numpy as np
+import torch
+
+from .. import _hip as hip
 
 IOU_THRESHOLDS = [x / 100.0 for x in range(50, 100, 5)]          # eval.py:33
 
@@ -116,6 +120,113 @@ class APAccumulator:
         if print_result:
             print_maps(all_maps)
         return {k: {j: round(u, 2) for j, u in v.items()} for k, v in all_maps.items()}
+
+
+def group_records(rec_score, rec_class, rec_flags, nb_class, n_thr):
+    """Records of detr_hip_map_match -> (scores, flags) as APAccumulator holds them.  The records are flat arrays in push order
+    (image after image, inside an image by descending score): rec_score fp32, rec_class int32 (-1 = empty slot or skipped
+    detection), rec_flags uint32 with bit t = true positive at threshold t.  scores[c] is the list of class c's scores in that
+    order; flags[c] is [] or one [n_det, n_thr] bool array (APAccumulator keeps one array per image; only their concatenation
+    is ever read)."""
+    score = np.ascontiguousarray(rec_score, np.float32).reshape(-1)
+    cls = np.ascontiguousarray(rec_class, np.int32).reshape(-1)
+    word = np.ascontiguousarray(rec_flags, np.uint32).reshape(-1)
+    if cls.size and int(cls.max()) >= nb_class:
+        raise ValueError(f"group_records: class {int(cls.max())} in the records, nb_class is {nb_class}")
+    keep = cls >= 0
+    score, cls, word = score[keep].astype(np.float64), cls[keep], word[keep]
+    bits = ((word[:, None] >> np.arange(n_thr, dtype=np.uint32)[None, :]) & np.uint32(1)).astype(bool)
+    order = np.argsort(cls, kind="stable")
+    bounds = np.searchsorted(cls[order], np.arange(nb_class + 1))
+    scores, flags = [], []
+    for c in range(nb_class):
+        idx = order[bounds[c]:bounds[c + 1]]
+        scores.append(score[idx].tolist())
+        flags.append([bits[idx]] if len(idx) else [])
+    return scores, flags
+
+
+class DeviceAPAccumulator:
+    """APAccumulator whose per-image work runs on the device: one detr_hip_map_match launch per batch (after the one of
+    detr_hip_postprocess), no host synchronisation until `to_host()`.  The flags, scores and ground-truth counts are the host
+    path's exactly (same fp64 IoU arithmetic, same visiting order, same tie rules)."""
+
+    def __init__(self, nb_class, iou_thresholds=None, device=None):
+        self.thresholds = list(IOU_THRESHOLDS if iou_thresholds is None else iou_thresholds)
+        self.nb_class = int(nb_class)
+        if not 1 <= len(self.thresholds) <= hip.MAP_MAX_THR:
+            raise ValueError(f"DeviceAPAccumulator: {len(self.thresholds)} thresholds, 1..{hip.MAP_MAX_THR} are supported")
+        if self.nb_class <= 0:
+            raise ValueError("DeviceAPAccumulator: nb_class must be positive")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceAPAccumulator: the matching is a HIP kernel; there is no CPU fallback (use APAccumulator)")
+        self._num_gt = torch.zeros(self.nb_class, dtype=torch.int64, device=self.device)
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._records = []                        # per batch: int32 [3, B, Q] = score bits, class, flag word
+
+    def _device(self, x, dtype):
+        if torch.is_tensor(x) and x.is_cuda:
+            return x.to(device=self.device, dtype=dtype)
+        t = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(dtype)
+        return t.pin_memory().to(self.device, non_blocking=True)      # pinned + asynchronous: the upload does not block the host
+
+    def add_detections(self, boxes, labels, scores, counts, t_bbox, t_class):
+        """Device tensors: what detr_hip_postprocess wrote in "yxyx" format (boxes [B, Q, 4] fp32, labels [B, Q] int64, scores
+        [B, Q] fp32, counts [B] int32) and the padded targets t_bbox [B, R, 4] fp32 (header row 0), t_class [B, R, 1] int64."""
+        want = (("boxes", boxes, torch.float32, 3), ("labels", labels, torch.int64, 2), ("scores", scores, torch.float32, 2),
+                ("counts", counts, torch.int32, 1), ("t_bbox", t_bbox, torch.float32, 3), ("t_class", t_class, torch.int64, None))
+        for name, t, dt, nd in want:
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dt and (nd is None or t.dim() == nd)):
+                raise TypeError(f"add_detections: {name} must be a {dt} tensor on {self.device}" + (f" with {nd} dimensions" if nd else ""))
+        B, Q = labels.shape
+        R = t_bbox.shape[1]
+        if tuple(boxes.shape) != (B, Q, 4) or tuple(scores.shape) != (B, Q) or tuple(counts.shape) != (B,) or \
+                tuple(t_bbox.shape) != (B, R, 4) or tuple(t_class.shape) not in ((B, R, 1), (B, R)):
+            raise ValueError("add_detections: shapes must be boxes [B, Q, 4], labels / scores [B, Q], counts [B], t_bbox [B, R, 4], "
+                             "t_class [B, R, 1]")
+        boxes, labels, scores, counts = boxes.contiguous(), labels.contiguous(), scores.contiguous(), counts.contiguous()
+        t_bbox, t_class = t_bbox.contiguous(), t_class.contiguous()
+        rec = torch.empty(3, B, Q, dtype=torch.int32, device=self.device)
+        d = hip.MapMatchDesc()
+        d.B, d.Q, d.R, d.nb_class, d.n_thr = B, Q, R, self.nb_class, len(self.thresholds)
+        d.boxes, d.labels, d.scores, d.counts, d.sD_b = boxes.data_ptr(), labels.data_ptr(), scores.data_ptr(), counts.data_ptr(), Q
+        d.t_bbox, d.sT_b, d.t_class, d.sC_b = t_bbox.data_ptr(), R * 4, t_class.data_ptr(), R
+        for t, th in enumerate(self.thresholds):
+            d.thresholds[t] = float(th)
+        d.rec_score, d.rec_class, d.rec_flags = rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr()
+        d.num_gt, d.status = self._num_gt.data_ptr(), self._status.data_ptr()
+        hip._check(hip.load().detr_hip_map_match(byref(d), hip._stream()), "detr_hip_map_match")
+        self._records.append(rec)
+
+    def add_batch(self, m_outputs, t_bbox, t_class, background_class):
+        """The post-processing launch plus the match launch for one batch of model outputs; host / NumPy targets are uploaded
+        asynchronously.  No host synchronisation."""
+        from ..inference import _post
+        out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"], m_outputs["pred_boxes"], background_class, "yxyx")
+        self.add_detections(out_b, out_l, out_s, counts, self._device(t_bbox, torch.float32), self._device(t_class, torch.int64))
+
+    def to_host(self):
+        """One synchronisation, one device-to-host copy (status word, ground-truth counts and every batch's records in one
+        buffer) -> the APAccumulator the host path would hold.  ValueError when the kernel flagged an input."""
+        shapes = [tuple(r.shape[1:]) for r in self._records]
+        buf = torch.cat([self._status, self._num_gt.view(torch.int32)] + [r.reshape(-1) for r in self._records]).cpu().numpy()
+        status, num_gt = int(buf[0]), buf[1:1 + 2 * self.nb_class].copy().view(np.int64)
+        if status:
+            raise ValueError("DeviceAPAccumulator: " + "; ".join(text for bit, text in hip.MAP_BAD.items() if status & bit))
+        off, parts = 1 + 2 * self.nb_class, []
+        for B, Q in shapes:
+            parts.append(buf[off:off + 3 * B * Q].reshape(3, B * Q))
+            off += 3 * B * Q
+        rec = np.concatenate(parts, 1) if parts else np.zeros((3, 0), np.int32)
+        acc = APAccumulator(self.nb_class, self.thresholds)
+        acc.scores, acc.flags = group_records(np.ascontiguousarray(rec[0]).view(np.float32), rec[1], np.ascontiguousarray(rec[2]).view(np.uint32),
+                                              self.nb_class, len(self.thresholds))
+        acc.num_gt = num_gt.astype(np.int64)
+        return acc
+
+    def result(self, class_names=None, print_result=False):
+        return self.to_host().result(class_names, print_result=print_result)
 
 
 def print_maps(all_maps):

@@ -38,7 +38,7 @@ int detr_hip_abi_version(void);
 int detr_hip_reload_tuning(void);
 /* ABI self-check for hand-written mirrors of the descriptor structs below (ctypes / cgo / JNI): for struct `which`
  * (0 detr_reduce_desc, 1 detr_gemm_desc, 2 detr_conv3x3_desc, 3 detr_stem_desc, 4 detr_layernorm_desc, 5 detr_attn_desc,
- * 6 detr_setloss_desc, 7 detr_input_desc, 8 detr_postprocess_desc) writes out[0] = sizeof, out[1..] = offsetof of every field in
+ * 6 detr_setloss_desc, 7 detr_input_desc, 8 detr_postprocess_desc, 9 detr_map_match_desc) writes out[0] = sizeof, out[1..] = offsetof of every field in
  * declaration order, and returns the number of values (negative: unknown struct). */
 int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap);
 /* zero fill of accumulators (an ordinary kernel: a captured hipMemsetAsync node did not replay reliably) */
@@ -529,6 +529,46 @@ typedef struct {
     int32_t *counts;                             /* [B] */
 } detr_postprocess_desc;
 int detr_hip_postprocess(const detr_postprocess_desc *d, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * mAP accumulation, per-image half (compute_map.py:183-272 cal_map, which eval.py:41-55 calls once per image on the host;
+ * semantics pinned by detr_tf/loss/compute_map.py: APAccumulator.add_image).  One launch per batch, one workgroup per image
+ * (csrc/map_match.hip).  Inputs: what detr_hip_postprocess wrote with bbox_format 2 ("yxyx") -- boxes / labels / scores, image b
+ * at row b * sD_b, counts[b] of them -- and the padded targets as the loaders ship them: t_bbox [B, R, 4] cx, cy, w, h with the
+ * header row 0 (t_bbox[b][0][0] = number of targets, data/processing.py:35-55), t_class [B, R, 1].
+ * Outputs, for image b, in DESCENDING-SCORE order (stable: ties by position, i.e. np.argsort(-scores, kind="stable")):
+ *   rec_score[b][r], rec_class[b][r], rec_flags[b][r] with bit t set = true positive at thresholds[t]: the detection took the
+ *   unused same-class ground truth of largest IoU strictly above thresholds[t] (lowest index on ties; a ground truth is consumed
+ *   per threshold; IoU in fp64 exactly as compute_overlaps, targets converted in fp32 with the clip to [0, 1]).  All Q slots are
+ *   written: r >= counts[b] and skipped detections get rec_class -1, score 0, flags 0.
+ *   num_gt[c] += ground truths of class c (integer atomics; the caller zeroes it once per evaluation).
+ *   status |= DETR_MAP_BAD_*: a label or target class outside [0, nb_class) (that detection / ground truth is skipped), a header
+ *   count outside [0, R-1] (the image is treated as having no targets), counts[b] outside [0, Q] (clamped).  Nothing is accessed
+ *   out of bounds; the caller zeroes the word once and reads it with the records.
+ * Limits: Q <= 1024, R <= 256, 1..DETR_MAP_MAX_THR finite thresholds; boxes 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_MAP_MAX_THR 16
+#define DETR_MAP_BAD_LABEL 1
+#define DETR_MAP_BAD_TARGET_CLASS 2
+#define DETR_MAP_BAD_HEADER 4
+#define DETR_MAP_BAD_COUNT 8
+typedef struct {
+    int32_t B, Q, R, nb_class, n_thr;
+    const float *boxes;                          /* [B, Q, 4] y1, x1, y2, x2 */
+    const int64_t *labels;                       /* [B, Q] */
+    const float *scores;                         /* [B, Q] */
+    const int32_t *counts;                       /* [B] */
+    int64_t sD_b;                                /* rows between two images of boxes / labels / scores (>= Q) */
+    const float *t_bbox;  int64_t sT_b;          /* [B, R, 4]; floats between two images (>= 4 R) */
+    const int64_t *t_class; int64_t sC_b;        /* [B, R, 1]; elements between two images (>= R) */
+    double thresholds[DETR_MAP_MAX_THR];
+    float *rec_score;                            /* [B, Q] */
+    int32_t *rec_class;                          /* [B, Q] */
+    uint32_t *rec_flags;                         /* [B, Q] */
+    int64_t *num_gt;                             /* [nb_class] */
+    int32_t *status;                             /* [1] */
+} detr_map_match_desc;
+int detr_hip_map_match(const detr_map_match_desc *d, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimiser (detr_tf/optimizers.py:86-88,137-163): per-tensor clip-by-norm then Keras Adam on
