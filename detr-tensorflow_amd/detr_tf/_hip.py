@@ -178,6 +178,7 @@ _SIGNATURES = {
     "detr_hip_input_stage": [POINTER(InputDesc), c_void_p],
     "detr_hip_pad_labels": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     "detr_hip_augment": [c_void_p, c_int64, c_void_p, f32p, c_int32, c_int32, c_int32, f32p, c_void_p, f32p, c_void_p],
+    "detr_hip_augment_padded": [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, f32p, c_void_p, f32p, c_void_p, c_void_p],
     "detr_hip_match_cost_f32": [POINTER(SetLossDesc), f32p, c_void_p],
     "detr_hip_assign_f32": [f32p, c_int32, c_int32, c_int32, f32p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
     "detr_hip_set_loss_sums_f32": [POINTER(SetLossDesc), c_void_p, f32p, c_void_p],

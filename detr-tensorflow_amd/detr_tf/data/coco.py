@@ -52,7 +52,7 @@ def coco_samples(ann_file, img_dir):
 
 
 def load_coco_dataset(config, batch_size, augmentation=False, ann_dir=None, ann_file=None, img_dir=None, ann_fil=None, seed=None,
-                      num_workers=4, device=None):
+                      num_workers=4, device=None, scales=None, max_size=None, canvas=None):
     """coco.py:95-126.  Returns (dataset, class_names) and sets config.background_class = max category id + 1.
     `ann_fil` is accepted as an alias of `ann_file` (train_coco.py:51 passes that spelling); `seed` makes the order, the
     augmentation records and therefore the batches reproducible."""
@@ -61,4 +61,5 @@ def load_coco_dataset(config, batch_size, augmentation=False, ann_dir=None, ann_
     img_dir = config.data.img_dir if img_dir is None else resolve(config.data.data_dir, img_dir)
     samples, class_names, background = coco_samples(ann_file, img_dir)
     config.background_class = background
-    return DetectionDataset(samples, config, batch_size, augmentation, seed=seed, num_workers=num_workers, device=device), class_names
+    return DetectionDataset(samples, config, batch_size, augmentation, seed=seed, num_workers=num_workers, device=device, scales=scales,
+                            max_size=max_size, canvas=canvas), class_names

@@ -3,7 +3,8 @@ voc.py:79-127, tfcsv.py:51-77).
 
 The host decodes JPEG / PNG (PIL, a small thread pool with one batch of lookahead), draws the transform records and moves
 the boxes (transformation.py); the uint8 images go to the device, where csrc/augment.hip applies flip / stage B / final resize
-and the normalisation, and DeviceInputStage.targets builds the padded target layout.  Each iteration is a new shuffled epoch;
+and the normalisation (csrc/augment_padded.hip for the aspect-preserving modes, which yield a padded (images, masks) pair),
+and DeviceInputStage.targets builds the padded target layout.  Each iteration is a new shuffled epoch;
 `len()` is the number of whole batches (drop remainder).
 """
 import os
@@ -44,12 +45,26 @@ class DetectionDataset:
 
     augmentation: True = the reference's training augmentation, False = resize to config.image_size (cubic), None = no
     transform at all: batch size 1 gives the image at its native size, a larger batch a padded (images, masks) pair.
+    "multiscale" (training) and "shortest_side" (evaluation) keep the aspect ratio (transformation.draw_multiscale /
+    eval_record: shortest side from `scales` -- "shortest_side" takes the largest --, longest side <= max_size) and yield
+    ((images, masks), t_bbox, t_class) with the boxes normalised per image; `canvas` = (H, W) fixes the padded shape, so that a
+    captured training or evaluation graph keeps replaying (and every rank of a data-parallel run sees one shape); None sizes
+    each batch's canvas to its largest image, rounded up to 32.
     An image that loses all its boxes to augmentation is skipped (the next one takes its place), so an epoch can yield fewer
     than len() batches."""
 
-    def __init__(self, samples, config, batch_size, augmentation=False, seed=None, num_workers=4, device=None):
+    PADDED_MODES = ("multiscale", "shortest_side")
+
+    def __init__(self, samples, config, batch_size, augmentation=False, seed=None, num_workers=4, device=None, scales=None,
+                 max_size=None, canvas=None):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
+        if isinstance(augmentation, str) and augmentation not in self.PADDED_MODES:
+            raise ValueError(f"augmentation must be True, False, None or one of {self.PADDED_MODES}, got {augmentation!r}")
+        self.padded = isinstance(augmentation, str)
+        self.scales = T.MULTISCALE_SCALES if scales is None else tuple(int(v) for v in scales)
+        self.max_size = T.MULTISCALE_MAX_SIZE if max_size is None else int(max_size)
+        self.canvas = None if canvas is None else (int(canvas[0]), int(canvas[1]))
         self.samples = list(samples)
         self.config = config
         self.batch_size = int(batch_size)
@@ -93,6 +108,15 @@ class DetectionDataset:
                 h0, w0 = image.shape[:2]
                 if self.augmentation is None:
                     batch.append((image, None, s.boxes, s.classes))
+                elif self.padded:
+                    if self.augmentation == "multiscale":
+                        rec = T.draw_multiscale(self.rng, h0, w0, self.scales, self.max_size)
+                    else:
+                        rec = T.eval_record(h0, w0, max(self.scales), self.max_size)
+                    boxes, classes = T.transform_boxes_padded(s.boxes, s.classes, h0, w0, rec)
+                    if len(boxes) == 0:
+                        continue
+                    batch.append((image, rec, boxes, classes))
                 else:
                     rec = T.draw_transform(self.rng, h0, w0, self.image_size, self.augmentation)
                     boxes, classes = T.transform_boxes(s.boxes, s.classes, h0, w0, rec, self.image_size)
@@ -116,6 +140,8 @@ class DetectionDataset:
                         st.image_size = self.image_size
                 else:
                     dev = st.images_padded(images)
+            elif self.padded:
+                dev = st.augmented_padded(images, [b[1] for b in batch], canvas=self.canvas)
             else:
                 dev = st.augmented(images, [b[1] for b in batch])
             t_bbox, t_class = st.targets([b[2] for b in batch], [b[3] for b in batch])

@@ -120,6 +120,36 @@ class DeviceInputStage:
                    "detr_hip_input_stage_padded")
         return dst, mask.view(torch.bool)
 
+    def _upload_ragged(self, srcs, rec_arrays):
+        """Staging shared by augmented() and augmented_padded(): the uint8 images are packed back to back, `rec_arrays(offsets)`
+        builds the record arrays (NumPy) from the images' byte offsets, and both cross PCIe through the pinned staging buffers,
+        one copy each; the buffers are reused across batches once their last copy has finished.  Returns (src on the device,
+        its size in bytes, the record bytes on the device laid out back to back, the record arrays on the host)."""
+        sizes = np.array([s.size for s in srcs], np.int64)
+        offsets = np.zeros(len(srcs), np.int64)
+        offsets[1:] = np.cumsum(sizes)[:-1]
+        total = int(sizes.sum())
+        recs = rec_arrays(offsets)
+        rec_bytes = sum(r.nbytes for r in recs)
+        if self._aug_event is not None:
+            self._aug_event.synchronize()           # the previous batch's copies out of the staging buffers have finished
+        if self._aug_img is None or self._aug_img.numel() < total:
+            self._aug_img = torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        if self._aug_rec is None or self._aug_rec.numel() < rec_bytes:
+            self._aug_rec = torch.empty(max(rec_bytes, 4096), dtype=torch.uint8, pin_memory=True)
+        img_h, rec_h = self._aug_img.numpy(), self._aug_rec.numpy()
+        for s, o in zip(srcs, offsets):
+            img_h[o:o + s.size] = s.reshape(-1)
+        at = 0
+        for r in recs:
+            rec_h[at:at + r.nbytes] = r.view(np.uint8).reshape(-1)
+            at += r.nbytes
+        src = self._aug_img[:total].to(self.device, non_blocking=True)
+        rec = self._aug_rec[:rec_bytes].to(self.device, non_blocking=True)
+        self._aug_event = torch.cuda.Event()
+        self._aug_event.record()
+        return src, total, rec, recs
+
     def augmented(self, images_uint8, records):
         """Training batch with augmentation: a list of uint8 images [h_i, w_i, 3] (host, each at its own size) and one
         transformation.Transform record per image -> float32 [B, image_size[0], image_size[1], 3] on the device: flip,
@@ -133,27 +163,7 @@ class DeviceInputStage:
             if (t.h0, t.w0) != s.shape[:2]:
                 raise ValueError(f"transform record for a {t.h0} x {t.w0} image given a {s.shape[0]} x {s.shape[1]} image")
             T.check_record(t, self.image_size)
-        sizes = np.array([s.size for s in srcs], np.int64)
-        offsets = np.zeros(len(srcs), np.int64)
-        offsets[1:] = np.cumsum(sizes)[:-1]
-        total = int(sizes.sum())
-        irec, frec = T.pack_records(records, offsets)
-        rec_bytes = irec.nbytes + frec.nbytes
-        if self._aug_event is not None:
-            self._aug_event.synchronize()           # the previous batch's copies out of the staging buffers have finished
-        if self._aug_img is None or self._aug_img.numel() < total:
-            self._aug_img = torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        if self._aug_rec is None or self._aug_rec.numel() < rec_bytes:
-            self._aug_rec = torch.empty(max(rec_bytes, 4096), dtype=torch.uint8, pin_memory=True)
-        img_h, rec_h = self._aug_img.numpy(), self._aug_rec.numpy()
-        for s, o in zip(srcs, offsets):
-            img_h[o:o + s.size] = s.reshape(-1)
-        rec_h[:irec.nbytes] = irec.view(np.uint8).reshape(-1)
-        rec_h[irec.nbytes:rec_bytes] = frec.view(np.uint8).reshape(-1)
-        src = self._aug_img[:total].to(self.device, non_blocking=True)
-        rec = self._aug_rec[:rec_bytes].to(self.device, non_blocking=True)
-        self._aug_event = torch.cuda.Event()
-        self._aug_event.record()
+        src, total, rec, (irec, _) = self._upload_ragged(srcs, lambda offsets: T.pack_records(records, offsets))
         B = len(srcs)
         Hd, Wd = self.image_size
         dst = torch.empty(B, Hd, Wd, 3, dtype=torch.float32, device=self.device)
@@ -162,6 +172,36 @@ class DeviceInputStage:
                                                self.lut.data_ptr(), ctypes.cast(perm, ctypes.c_void_p), dst.data_ptr(), hip._stream()),
                    "detr_hip_augment")
         return dst
+
+    def augmented_padded(self, images_uint8, records, canvas=None, multiple=32):
+        """Aspect-preserving multi-scale batch: a list of uint8 images [h_i, w_i, 3] (host, each at its own size) and one
+        transformation.PaddedRecord per image -> (images float32 [B, H, W, 3], masks bool [B, H, W]) on the device.  Image i is
+        flipped, windowed, resized to its own (hd_i, wd_i) and normalised at the top-left of the canvas; the padding is 0.0 and
+        masks is True there.  One launch of csrc/augment_padded.hip; staging as in augmented().  canvas=None: the batch's
+        largest hd / wd, each rounded up to `multiple`; canvas=(H, W): fixed (what a captured graph needs), ValueError if an
+        image does not fit."""
+        from . import transformation as T
+        srcs = [np.asarray(im) for im in images_uint8]
+        if not srcs or len(srcs) != len(records) or any(s.dtype != np.uint8 or s.ndim != 3 or s.shape[-1] != 3 for s in srcs):
+            raise TypeError("DeviceInputStage.augmented_padded expects a non-empty list of uint8 images [h, w, 3] and one record per image")
+        if canvas is None:
+            m = max(1, int(multiple))
+            H, W = (-(-max(int(t.hd) for t in records) // m) * m, -(-max(int(t.wd) for t in records) // m) * m)
+        else:
+            H, W = int(canvas[0]), int(canvas[1])
+        for s, t in zip(srcs, records):
+            if (t.h0, t.w0) != s.shape[:2]:
+                raise ValueError(f"padded record for a {t.h0} x {t.w0} image given a {s.shape[0]} x {s.shape[1]} image")
+            T.check_padded_record(t, (H, W))
+        src, total, rec, _ = self._upload_ragged(srcs, lambda offsets: (T.pack_padded_records(records, offsets),))
+        B = len(srcs)
+        dst = torch.empty(B, H, W, 3, dtype=torch.float32, device=self.device)
+        mask = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        perm = (ctypes.c_int32 * 3)(*self.perm)
+        hip._check(hip.load().detr_hip_augment_padded(src.data_ptr(), total, rec.data_ptr(), B, H, W, self.lut.data_ptr(),
+                                                      ctypes.cast(perm, ctypes.c_void_p), dst.data_ptr(), mask.data_ptr(), hip._stream()),
+                   "detr_hip_augment_padded")
+        return dst, mask.view(torch.bool)
 
     def targets(self, boxes_per_image, classes_per_image):
         """lists (one entry per image) of [n_i, 4] cx,cy,w,h boxes and [n_i] class ids -> (t_bbox [B,100,4] float32,

@@ -28,10 +28,11 @@ def tfcsv_samples(csv_path, img_dir, exclude=()):
 
 
 def load_tfcsv_dataset(config, batch_size, augmentation=False, exclude=[], ann_dir=None, ann_file=None, img_dir=None, seed=None,
-                       num_workers=4, device=None):
+                       num_workers=4, device=None, scales=None, max_size=None, canvas=None):
     """tfcsv.py:51-77.  Returns (dataset, class_names) and sets config.background_class = 0."""
     config.background_class = 0
     csv_path = config.data.ann_file if ann_file is None else resolve(config.data.data_dir, ann_file)
     img_dir = config.data.img_dir if img_dir is None else resolve(config.data.data_dir, img_dir)
     samples, class_names = tfcsv_samples(csv_path, img_dir, exclude)
-    return DetectionDataset(samples, config, batch_size, augmentation, seed=seed, num_workers=num_workers, device=device), class_names
+    return DetectionDataset(samples, config, batch_size, augmentation, seed=seed, num_workers=num_workers, device=device, scales=scales,
+                            max_size=max_size, canvas=canvas), class_names

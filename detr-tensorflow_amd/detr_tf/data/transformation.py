@@ -13,6 +13,16 @@ Record semantics (one per image, applied in this order):
   iff     interpolation of the final resize to (Hd, Wd) (identity when the sizes already agree)
 Interpolations are imgaug's `ia.ALL`: nearest, linear, area, cubic.  imgaug's random stream and OpenCV's fixed-point
 rounding cannot be reproduced: the distributions are the reference's, the individual draws are not.
+
+Aspect-preserving multi-scale input (padded batches).  The reference names the constants of the recipe DETR is trained with
+(transformation.py:59-64) and keeps the evaluation rule as commented-out code (:96-112) but resizes every image to one fixed
+size.  `draw_multiscale` / `eval_record` draw a `PaddedRecord` per image: flip, a source window, and the image's own
+destination size from `target_size` (shortest side S, longest side <= max_size, aspect ratio kept); csrc/augment_padded.hip
+(`DeviceInputStage.augmented_padded`) writes every image at the top-left of a zero-padded canvas with its padding mask, and
+`transform_boxes_padded` moves the boxes, normalised to the image's own (wd, hd), not to the canvas.
+One deviation from resize -> crop -> resize: the intermediate resize of the crop branch is not materialised.  The crop window
+drawn in the intermediate image is mapped back to the source and its edges are rounded to WHOLE source pixels (at least one
+pixel, inside the image); the destination size is `target_size` of that window.
 """
 from typing import NamedTuple
 
@@ -133,6 +143,124 @@ def transform_boxes(bbox_xcycwh, t_class, h0, w0, record, image_size):
     x1, x2 = np.clip(x1[keep], 0, Wd), np.clip(x2[keep], 0, Wd)
     y1, y2 = np.clip(y1[keep], 0, Hd), np.clip(y2[keep], 0, Hd)
     out = np.stack([(x1 + x2) / 2 / Wd, (y1 + y2) / 2 / Hd, (x2 - x1) / Wd, (y2 - y1) / Hd], 1).astype(np.float32)
+    return out.reshape(-1, 4), cls[keep]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# aspect-preserving multi-scale records (padded batches, csrc/augment_padded.hip)
+# ------------------------------------------------------------------------------------------------------------------------------
+LINEAR = 1
+PADDED_IREC = 12                                             # include/detr_hip.h: DETR_AUGP_IREC
+MULTISCALE_SCALES = tuple(range(480, 801, 32))
+MULTISCALE_MAX_SIZE = 1333
+CROP_SCALES = (400, 500, 600)                                # the crop branch: intermediate shortest side, no maximum
+CROP_MIN, CROP_MAX = 384, 600                                # side range of the window drawn in the intermediate image
+
+
+class PaddedRecord(NamedTuple):
+    """One image's record of the padded path: the window (y0, x0, hc, wc) of the flipped h0 x w0 source, in whole source
+    pixels, is resized to hd x wd with interpolation `interp`."""
+    h0: int
+    w0: int
+    flip: bool
+    y0: int
+    x0: int
+    hc: int
+    wc: int
+    hd: int
+    wd: int
+    interp: int = LINEAR
+
+
+def target_size(h, w, short, max_size=None):
+    """(height, width) of an h x w image resized so that its shortest side is `short` unless its longest side would then
+    exceed `max_size` (None: no limit), which then binds instead.  Integer arithmetic only: the reference's commented rule
+    takes int() of a float scale, which can land one pixel off."""
+    h, w, short = int(h), int(w), int(short)
+    mn, mx = min(h, w), max(h, w)
+    if max_size is not None and short * mx > int(max_size) * mn:
+        lng = int(max_size)
+        sht = max(1, lng * mn // mx)
+    else:
+        sht = short
+        lng = short * mx // mn
+    return (sht, lng) if h <= w else (lng, sht)
+
+
+def _to_source(v, n0, n1):
+    """Coordinate v of the n1-pixel intermediate axis on the n0-pixel source axis, rounded half up to a whole pixel."""
+    return (2 * v * n0 + n1) // (2 * n1)
+
+
+def draw_multiscale(rng, h0, w0, scales=MULTISCALE_SCALES, max_size=MULTISCALE_MAX_SIZE, interp=LINEAR):
+    """One training record for an h0 x w0 image, drawn with the numpy Generator `rng`: flip (p = 0.5), then with p = 0.5 the
+    full image at a random shortest side S of `scales`, otherwise a random crop (resize to 400 / 500 / 600, window sides uniform
+    in [384, min(side, 600)] at a uniform origin) resized to a random S; longest side <= max_size both times."""
+    h0, w0 = int(h0), int(w0)
+    scales = tuple(int(v) for v in scales)
+    flip = bool(rng.random() < 0.5)
+    if rng.random() < 0.5:
+        y0, x0, hc, wc = 0, 0, h0, w0
+    else:
+        h1, w1 = target_size(h0, w0, CROP_SCALES[int(rng.integers(0, len(CROP_SCALES)))])
+        wn = int(rng.integers(min(CROP_MIN, w1), min(w1, CROP_MAX) + 1))
+        hn = int(rng.integers(min(CROP_MIN, h1), min(h1, CROP_MAX) + 1))
+        yn, xn = int(rng.integers(0, h1 - hn + 1)), int(rng.integers(0, w1 - wn + 1))
+        y0, x0 = min(_to_source(yn, h0, h1), h0 - 1), min(_to_source(xn, w0, w1), w0 - 1)
+        hc = min(max(_to_source(yn + hn, h0, h1) - y0, 1), h0 - y0)
+        wc = min(max(_to_source(xn + wn, w0, w1) - x0, 1), w0 - x0)
+    hd, wd = target_size(hc, wc, scales[int(rng.integers(0, len(scales)))], max_size)
+    return PaddedRecord(h0, w0, flip, y0, x0, hc, wc, hd, wd, int(interp))
+
+
+def eval_record(h0, w0, short=800, max_size=MULTISCALE_MAX_SIZE, interp=LINEAR):
+    """The evaluation record: no flip, the full image, shortest side `short`, longest side <= max_size."""
+    h0, w0 = int(h0), int(w0)
+    hd, wd = target_size(h0, w0, short, max_size)
+    return PaddedRecord(h0, w0, False, 0, 0, h0, w0, hd, wd, int(interp))
+
+
+def check_padded_record(t, canvas=None):
+    """Host validation of one padded record (the kernel also clamps, but a wrong record is a caller's bug)."""
+    if t.h0 < 1 or t.w0 < 1:
+        raise ValueError(f"padded record: bad source size {t.h0} x {t.w0}")
+    if t.interp not in range(4):
+        raise ValueError(f"padded record: bad interpolation {t}")
+    if t.hc < 1 or t.wc < 1 or not (0 <= t.y0 <= t.h0 - t.hc and 0 <= t.x0 <= t.w0 - t.wc):
+        raise ValueError(f"padded record: window {t.hc} x {t.wc} at ({t.y0}, {t.x0}) leaves the {t.h0} x {t.w0} image")
+    if t.hd < 1 or t.wd < 1:
+        raise ValueError(f"padded record: bad destination size {t.hd} x {t.wd}")
+    if canvas is not None and (t.hd > int(canvas[0]) or t.wd > int(canvas[1])):
+        raise ValueError(f"padded record: destination {t.hd} x {t.wd} does not fit the {int(canvas[0])} x {int(canvas[1])} canvas")
+
+
+def pack_padded_records(records, offsets):
+    """records + byte offsets of the images in the packed source -> irec int32 [B, PADDED_IREC] in the layout of
+    detr_hip_augment_padded."""
+    irec = np.zeros((len(records), PADDED_IREC), np.int32)
+    for b, (t, off) in enumerate(zip(records, offsets)):
+        irec[b, 0:2] = np.array([int(off)], "<i8").view("<i4")
+        irec[b, 2:] = [t.h0, t.w0, int(bool(t.flip)), t.y0, t.x0, t.hc, t.wc, t.hd, t.wd, t.interp]
+    return irec
+
+
+def transform_boxes_padded(bbox_xcycwh, t_class, h0, w0, record):
+    """Move normalised (cx, cy, w, h) boxes with the image (NumPy, float64): flip, shift by the window and clip to it, drop
+    the boxes whose clipped width or height is not positive.  Returns (boxes float32 [n, 4] normalised to the image's own
+    (wd, hd) -- what the per-image sine encoding and the set loss assume, not the canvas -- and the classes of the kept boxes)."""
+    t = record
+    b = np.asarray(bbox_xcycwh, np.float64).reshape(-1, 4)
+    cls = np.asarray(t_class)
+    x1, x2 = (b[:, 0] - b[:, 2] / 2) * w0, (b[:, 0] + b[:, 2] / 2) * w0
+    y1, y2 = (b[:, 1] - b[:, 3] / 2) * h0, (b[:, 1] + b[:, 3] / 2) * h0
+    if t.flip:
+        x1, x2 = w0 - x2, w0 - x1
+    x1, x2 = np.clip(x1 - t.x0, 0, t.wc), np.clip(x2 - t.x0, 0, t.wc)
+    y1, y2 = np.clip(y1 - t.y0, 0, t.hc), np.clip(y2 - t.y0, 0, t.hc)
+    keep = (x2 - x1 > 0) & (y2 - y1 > 0)
+    # window pixels -> destination pixels -> normalised by the destination size: the two factors of wd (hd) cancel
+    x1, x2, y1, y2 = x1[keep] / t.wc, x2[keep] / t.wc, y1[keep] / t.hc, y2[keep] / t.hc
+    out = np.stack([(x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1], 1).astype(np.float32)
     return out.reshape(-1, 4), cls[keep]
 
 

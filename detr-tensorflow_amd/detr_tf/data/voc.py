@@ -52,10 +52,11 @@ def voc_samples(image_dir, anno_dir):
 
 
 def load_voc_dataset(config, batch_size, augmentation=False, ann_dir=None, ann_file=None, img_dir=None, seed=None, num_workers=4,
-                     device=None):
+                     device=None, scales=None, max_size=None, canvas=None):
     """voc.py:79-127.  Returns (dataset, class_names) and sets config.background_class = 0."""
     config.background_class = 0
     image_dir = config.data.img_dir if img_dir is None else resolve(config.data.data_dir, img_dir)
     anno_dir = config.data.ann_dir if ann_dir is None else resolve(config.data.data_dir, ann_dir)
     samples, class_names = voc_samples(image_dir, anno_dir)
-    return DetectionDataset(samples, config, batch_size, augmentation, seed=seed, num_workers=num_workers, device=device), class_names
+    return DetectionDataset(samples, config, batch_size, augmentation, seed=seed, num_workers=num_workers, device=device, scales=scales,
+                            max_size=max_size, canvas=canvas), class_names

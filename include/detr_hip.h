@@ -509,6 +509,19 @@ int detr_hip_pad_labels(const float *boxes, const int64_t *classes, const int32_
 #define DETR_AUG_FREC 2
 int detr_hip_augment(const uint8_t *src, int64_t src_bytes, const int32_t *irec, const float *frec, int32_t B, int32_t Hd, int32_t Wd,
                      const float *lut, const int32_t *perm, float *dst, void *stream);
+/* Aspect-preserving multi-scale input (csrc/augment_padded.hip): image b of a ragged uint8 batch, packed back to back in src
+ * (src_bytes bytes, device), is flipped, windowed, resized to its own (hd, wd) with detr_hip_augment's resize formulas, normalised
+ * through lut / perm (as detr_hip_input_stage; perm a host array of 3) and written at the top-left of the float32 canvas
+ * dst [B, H, W, 3]; the rest of the canvas is 0.0 and mask [B, H, W] (uint8) is 1 there (padding), 0 on valid pixels.  One launch
+ * for pixels and mask.  Per-image records (device array):
+ *   irec[b][DETR_AUGP_IREC] int32: 0,1 byte offset of image b in src (low, high 32 bits); 2 h0; 3 w0; 4 flip (0/1);
+ *     5 y0, 6 x0, 7 hc, 8 wc: the source window, in whole pixels of the flipped image; 9 hd, 10 wd: destination size;
+ *     11 interpolation (0 nearest, 1 linear, 2 cubic, 3 area)
+ * The window is clamped into the image, (hd, wd) to the canvas, and source reads into src_bytes, so a wrong record cannot read
+ * outside src; writes depend on B, H, W only. */
+#define DETR_AUGP_IREC 12
+int detr_hip_augment_padded(const uint8_t *src, int64_t src_bytes, const int32_t *irec, int32_t B, int32_t H, int32_t W,
+                            const float *lut, const int32_t *perm, float *dst, uint8_t *mask, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched post-processing (detr_tf/inference.py:68-95, which handles batch element 0 only; the validation loops call it
