@@ -188,6 +188,9 @@ _SIGNATURES = {
     "detr_hip_clip_adam_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, c_int32, c_int32, c_void_p],
     "detr_hip_axpy_f32": [f32p, f32p, c_float, c_int64, c_void_p],
     "detr_hip_set_floats8_f32": [f32p] + [c_float] * 8 + [c_void_p],
+    "detr_hip_set_floats16_f32": [f32p, POINTER(c_float * 16), c_void_p],
+    "detr_hip_global_clip_scale_f32": [f32p, c_void_p, c_void_p, f32p, c_int32, f32p, c_void_p],
+    "detr_hip_adamw_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, f32p, c_int32, c_int32, c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {

@@ -6,6 +6,7 @@ synchronisation and no allocation, so `fit` can record it ONCE as a hipGraph (`G
 every further batch of the same shape: whatever changes between steps -- the batch, the dropout step seed, the Adam step
 sizes -- lives in device memory that is refreshed before each replay.
 """
+import gc
 import os
 import time
 
@@ -16,7 +17,7 @@ from . import _hip as hip
 from .engine import downsample_mask_nearest, feature_size
 from .loss import hungarian_matching as _matching
 from .loss.loss import get_losses, log_from_losses
-from .optimizers import GROUPS, aggregate_grad_and_apply, gather_gradient
+from .optimizers import GROUPS, aggregate_grad_and_apply, clip_mode, decay_active, gather_gradient, joint_optimizer
 
 PRINT_EVERY_TRAIN = 100         # training.py:57
 PRINT_EVERY_VAL = 10            # training.py:80
@@ -123,7 +124,8 @@ class GraphedTrainStep:
 
     The first `eager_steps` calls run eagerly (they also allocate every buffer of the static memory plan); the next call
     records the launch sequence -- forward, set loss, backward into one graph (cut at the data-parallel exchange points
-    when training on several GPUs), clip + Adam of the three groups into another -- and from then on a replayed step is:
+    when training on several GPUs), clip + Adam of the three groups (or the joint AdamW sequence of config.global_clipnorm) into
+    another -- and from then on a replayed step is:
     copy the batch into the static input buffers, write the new dropout seed / Adam step sizes to device memory, replay.
     A new batch shape (or set of trained groups), and any re-allocation of an engine buffer since the recording (a forward
     of another shape in between: engine.buf_generation), drop the recording: one eager step, then a new one.  Gradient
@@ -155,7 +157,7 @@ class GraphedTrainStep:
         images, masks = split_images(images)
         return (tuple(images.shape), masks is not None, tuple(t_bbox.shape), bool(c.train_backbone), bool(c.train_transformers),
                 bool(c.train_nlayers), int(c.background_class), self.model.engine.compute, float(self.model.engine.dropout_p),
-                bool(getattr(c, "check_matching", False)))
+                bool(getattr(c, "check_matching", False)), clip_mode(c), decay_active(c))      # (other optimiser launches: re-record)
 
     def _capture(self, images, t_bbox, t_class):
         model, opts, cfg = self.model, self.optimizers, self.config
@@ -169,12 +171,20 @@ class GraphedTrainStep:
         self.static = (st_img, st_tb, st_tc, st_mask)
         self._load_inputs(images, t_bbox, t_class)
         dp = model.dp
+        if clip_mode(cfg) == "joint":           # its tables are device tensors: built before the recording, not inside it
+            joint_optimizer(opts, cfg).prepare()
         seg = _Segments()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         eng._graph_replay = True
         eng.bump_weights_version()          # the derived weight copies are rebuilt inside the recorded step, as in every eager step
         prev_hooks = None
+        # No cyclic garbage collection inside the recording: an engine and its parameter store reference each other, so a dropped
+        # model (its buffers, recorded graphs, events) is only released by the collector -- and when that ran in the middle of a
+        # stream capture, destroying those device objects aborted the process.  Collect now, keep the collector off until the end.
+        gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
         try:
             with torch.cuda.stream(side):
                 if dp is not None and dp.active:      # collectives run eagerly between graph segments
@@ -193,15 +203,21 @@ class GraphedTrainStep:
                 app.pool = seg.pool
                 app.begin()
                 store = opts["_store"]
+                joint = clip_mode(cfg) == "joint"
                 for name in GROUPS:
                     if getattr(cfg, f"train_{name}"):
                         opts[f"{name}_gradients"] = store.grad
-                        opts[f"{name}_optimizer"].apply_gradients(store.grad, hyper_ready=True)
+                        if not joint:
+                            opts[f"{name}_optimizer"].apply_gradients(store.grad, hyper_ready=True)
+                if joint:                   # config.global_clipnorm: all trained groups in one sequence (optimizers.JointAdam)
+                    joint_optimizer(opts, cfg).apply(store.grad, hyper_ready=True)
                 app.end()
         finally:
             if prev_hooks is not None:
                 dp.on_bucket, dp.reduce_sums, dp.finish = prev_hooks
             eng._graph_replay = False
+            if gc_was_on:
+                gc.enable()
         torch.cuda.current_stream().wait_stream(side)
         self.step_graph, self.apply_graph = seg, app
         self.result = (m_outputs, m_outputs.set_loss)
@@ -240,9 +256,12 @@ class GraphedTrainStep:
         try:
             if eng.dropout_p > 0.0:
                 eng.advance_dropout_step()                         # new masks: the kernels read the seed from device memory
-            for name in GROUPS:
-                if getattr(cfg, f"train_{name}"):
-                    self.optimizers[f"{name}_optimizer"].set_step_hyper()
+            if clip_mode(cfg) == "joint":
+                joint_optimizer(self.optimizers, cfg).set_step_hyper()
+            else:
+                for name in GROUPS:
+                    if getattr(cfg, f"train_{name}"):
+                        self.optimizers[f"{name}_optimizer"].set_step_hyper()
             self.step_graph.replay()
             if model.dp is not None:
                 model.dp.finish()

@@ -40,6 +40,8 @@ _FLAGS = (
     ("target_batch", int, None, False),
     ("backbone_lr", float, 1e-5, False), ("transformers_lr", float, 1e-4, False), ("nlayers_lr", float, 1e-4, False),
     ("log", None, False, True),
+    # not in the reference: AdamW decay, one model-wide gradient norm, Adam's epsilon (optimizers.py)
+    ("weight_decay", float, 0.0, False), ("global_clipnorm", float, None, False), ("adam_epsilon", float, 1e-7, False),
 )
 
 
@@ -59,6 +61,10 @@ _DEFAULTS = dict(
     train_backbone=False, train_transformers=False, train_nlayers=False,
     finetuning=False, batch_size=1, gradient_norm_clipping=0.1, target_batch=1,
     global_step=0, log=False, normalized_method="torch_resnet",
+    # Optimiser extensions, all read at EVERY step.  weight_decay: decoupled (AdamW) decay of every trained tensor.
+    # global_clipnorm: clip by ONE L2 norm over all tensors of the trained groups; when it is not None it REPLACES the
+    # per-tensor gradient_norm_clipping ("global wins": Keras refuses both, but gradient_norm_clipping defaults to 0.1 here).
+    weight_decay=0.0, global_clipnorm=None, adam_epsilon=1e-7,
 )
 
 

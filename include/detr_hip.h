@@ -607,6 +607,26 @@ int detr_hip_set_floats8_f32(float *dst, float v0, float v1, float v2, float v3,
 int detr_hip_axpy_f32(float *acc, const float *g, float a, int64_t n, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * AdamW (opt-in): decoupled weight decay, and the clip either per tensor (as above) or over ONE norm of every trained
+ * tensor (tf.clip_by_global_norm).  Same chunk tables as above; one table may span all groups.
+ *   hyper (device, float[16]) = {lr_t group0..2, clip, beta1, beta2, eps, weight_decay, lr group0..2,
+ *                                trained group0..2 (1 or 0), -, -}
+ *   per element:  g *= s;  m, v as Adam;  p -= lr*weight_decay*p;  p -= lr_t * m / (sqrt(v) + eps)
+ * Joint sequence: detr_hip_sumsq_segments_f32 over the table, detr_hip_global_clip_scale_f32 (one workgroup sums the
+ * partials of the trained groups in a fixed order: scale[0] = clip / max(G, clip), exactly 1 when G <= clip or clip <= 0;
+ * scale[1] = G), detr_hip_adamw_f32 with that `scale`.  With scale == NULL detr_hip_adamw_f32 clips per tensor, like
+ * detr_hip_clip_adam_f32.  Tensors of a group with trained == 0 (or tensor_group < 0) are neither counted nor touched.
+ * ------------------------------------------------------------------------------------------- */
+/* dst[0..15] = values[0..15] (values: HOST memory, read before the call returns; they travel as kernel arguments) */
+int detr_hip_set_floats16_f32(float *dst, const float *values, void *stream);
+int detr_hip_global_clip_scale_f32(const float *sumsq, const int32_t *chunk_tensor, const int32_t *tensor_group,
+                                   const float *hyper, int32_t n_chunks, float *scale, void *stream);
+int detr_hip_adamw_f32(float *param, const float *g, float *m, float *v, const int32_t *chunk_tensor,
+                       const int64_t *chunk_start, const int64_t *seg_end, const int32_t *tensor_group,
+                       const float *sumsq, const float *hyper, const float *scale, int32_t n_chunks, int32_t chunk,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scratch sizing: the number of bytes `workspace` must hold for the call described by the descriptor to take its
  * DETERMINISTIC split-reduction path (0 = the call needs no scratch; negative = malformed descriptor).  Pointers inside the
  * descriptor are not dereferenced; only shapes, split counts, dtypes and (gemm) whether rowsum_a is set are read.  The same
