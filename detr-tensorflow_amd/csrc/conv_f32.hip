@@ -6,36 +6,7 @@
 // Reference: detr_tf/networks/resnet_backbone.py:11-32,98-137 (see include/detr_hip.h).
 #include "gemm_core.h"
 #include "gemm_bf16_core.h"
-
-namespace detr {
-
-// ------------------------------------------------------------------------------------------------
-// forward / dgrad : rows = destination pixels, K = 9 taps x source channels
-// ------------------------------------------------------------------------------------------------
-struct ConvArgs {
-    int N, Hs, Ws, Cs;  // source tensor (A operand): fwd x[N,Hi,Wi,Ci]; dgrad dy[N,Ho,Wo,Co]
-    int Hd, Wd, Cd;     // destination tensor: fwd y[N,Ho,Wo,Co]; dgrad dx[N,Hi,Wi,Ci]
-    int stride, pad;
-    int Ci, Co;
-    int M;
-    const float *src;
-    const float *w;
-    float *dst;
-    int tiles_m, tiles_n;
-    EpiArgs e;
-    // stride-2 dgrad, one launch per destination-pixel parity class (ph, pw): rows = (n, h2, w2) with h = 2*h2 + ph,
-    // w = 2*w2 + pw; only the taps with kh = kh0 (+2), kw = kw0 (+2) contribute (1, 2, 2 or 4 of the 9), so the classes
-    // together do 9/4 tap-GEMMs per pixel instead of 9 with 3/4 of the rows masked.
-    int par_on, Hp, Wp, ph, pw, kh0, kw0, nth, ntw;
-    int w16;                     // the kernel tensor is bf16 in memory (bf16 compute only)
-    int x16;                     // the source tensor (x for fwd, dy for dgrad) is bf16 in memory
-    // all four parity classes in ONE launch of the halo kernel's class form (conv_halo.h): class k = 0..3 is (ph, pw) =
-    // (1,1), (0,1), (1,0), (0,0) -- heaviest first --, owns workgroups [cls_off[k], cls_off[k + 1]) and cls_hp / cls_wp tiles along H / W
-    int cls_off[5], cls_hp[4], cls_wp[4];
-    int cls_mix;                 // 1: the classes' workgroups round-robin in the grid instead of one class after the other (conv_halo.h)
-};
-
-}  // namespace detr
+#include "conv_args.h"
 #include "conv_halo.h"
 #include "conv_halo_dma.h"
 namespace detr {
@@ -51,7 +22,8 @@ __device__ __forceinline__ void conv_tap(const ConvArgs &a, int t, int &kh, int 
     }
 }
 
-template <int BM, bool DGRAD>
+// DIL: pixel step of the taps (2: the dilated entry point, conv_dilated.hip)
+template <int BM, bool DGRAD, int DIL = 1>
 struct LoaderConvA {
     static constexpr int NV = BM / 64;
     BufSrc src;
@@ -99,7 +71,7 @@ struct LoaderConvA {
             int hs, ws;
             bool v = ok[i];
             if (DGRAD) {
-                const int th = h_[i] - kh, tw = w_[i] - kw;
+                const int th = h_[i] - kh * DIL, tw = w_[i] - kw * DIL;
                 v = v && th >= 0 && tw >= 0;
                 if (a.stride == 2) {
                     v = v && ((th & 1) == 0) && ((tw & 1) == 0);
@@ -111,8 +83,8 @@ struct LoaderConvA {
                 }
                 v = v && hs < a.Hs && ws < a.Ws;
             } else {
-                hs = h_[i] + kh;
-                ws = w_[i] + kw;
+                hs = h_[i] + kh * DIL;
+                ws = w_[i] + kw * DIL;
                 v = v && hs >= 0 && ws >= 0 && hs < a.Hs && ws < a.Ws;
             }
             const unsigned off = ((unsigned)((n_[i] * a.Hs + hs) * a.Ws + ws) * (unsigned)a.Cs + (unsigned)c0) * 4u;
@@ -133,7 +105,7 @@ struct LoaderConvA {
 };
 
 // SPLIT3: the K tiles run on the bf16 matrix pipe at fp32 accuracy (gemm_core.h: mma_ktile_split3; detr_conv3x3_desc.compute = 2)
-template <int BM, int BN, int WGM, int WGN, bool DGRAD, bool SPLIT3 = false>
+template <int BM, int BN, int WGM, int WGN, bool DGRAD, bool SPLIT3 = false, int DIL = 1>
 __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_kernel(ConvArgs a) {
     using T = TileCfg<BM, BN, WGM, WGN>;
     __shared__ __attribute__((aligned(16))) char smem_raw[SmemBytes<BM, BN, WGN>::VALUE];
@@ -148,7 +120,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_kernel(ConvArgs a) {
     const int nkt = (a.par_on ? a.nth * a.ntw : 9) * cpt;
     const long long tapstride = (long long)a.Ci * a.Co;
 
-    LoaderConvA<BM, DGRAD> la;
+    LoaderConvA<BM, DGRAD, DIL> la;
     la.init(a, m0, tid);
     // B operand per tap: fwd  B[k=ci][n=co] = w[tap][ci][co]  (n contiguous, ld = Co, K = Ci)
     //                    dgrad B[k=co][n=ci] = w[tap][ci][co]  (k contiguous, ld = Co, K = Co)
@@ -164,7 +136,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    float4 ra[LoaderConvA<BM, DGRAD>::NV], rb[LB::NV];
+    float4 ra[LoaderConvA<BM, DGRAD, DIL>::NV], rb[LB::NV];
     // K tiles are requested strictly in order: tap and channel tile are running counters (the kt / cpt and conv_tap()
     // divisions cost ~40 scalar instructions per 16-deep K tile)
     const int tap_cols = a.par_on ? a.ntw : 3;
@@ -205,24 +177,12 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_kernel(ConvArgs a) {
 // wgrad : per tap, dw[tap][ci][co] += scale[co] * sum_m x[pix(m,tap)][ci] * dy[m][co]
 // grid = (ci tiles * co tiles, 9 taps, row splits); reduction rows are the output pixels.
 // ------------------------------------------------------------------------------------------------
-struct ConvWgradArgs {
-    int N, Hi, Wi, Ci, Ho, Wo, Co, stride, pad;
-    const float *x;
-    const float *dy;
-    float *dw;
-    int M, rows_per_split;
-    long long part_stride;   // 9*Ci*Co when the splits write partial slabs, 0 for the atomic fallback
-    int tiles_m, tiles_n;
-    EpiArgs e;
-    int s16;                 // x and dy are bf16 in memory (bf16 activation storage; bf16 compute only)
-    int slab_ts;             // partial slabs in tile order (gemm_core.h: store_slab_ts; tile = (tap * tiles_m + tm) * tiles_n + tn)
-};
 
 }  // namespace detr
 #include "conv_x3.h"
 namespace detr {
 
-template <int BM>
+template <int BM, int DIL = 1>
 struct LoaderWgradA {
     static constexpr int VPR = BM / 4;
     static constexpr int TOTAL = GEMM_BK * VPR;
@@ -256,8 +216,8 @@ struct LoaderWgradA {
         for (int i = 0; i < NV; ++i) {
             const int idx = tid + GEMM_THREADS * i;
             const int c4 = (idx % VPR) * 4;
-            const int hs = h_[i] * a.stride - a.pad + kh;
-            const int ws = w_[i] * a.stride - a.pad + kw;
+            const int hs = h_[i] * a.stride - a.pad + kh * DIL;
+            const int ws = w_[i] * a.stride - a.pad + kw * DIL;
             const bool v = (idx < TOTAL) && (m_[i] < m_end) && hs >= 0 && ws >= 0 && hs < a.Hi && ws < a.Wi &&
                            (ci0 + c4 < a.Ci);
             const unsigned off = ((unsigned)((n_[i] * a.Hi + hs) * a.Wi + ws) * (unsigned)a.Ci + (unsigned)(ci0 + c4)) * 4u;
@@ -293,7 +253,7 @@ struct LoaderWgradA {
     }
 };
 
-template <int BM, int BN, int WGM, int WGN, bool SPLIT3 = false>
+template <int BM, int BN, int WGM, int WGN, bool SPLIT3 = false, int DIL = 1>
 __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_wgrad_kernel(ConvWgradArgs a) {
     using T = TileCfg<BM, BN, WGM, WGN>;
     __shared__ __attribute__((aligned(16))) char smem_raw[SmemBytes<BM, BN, WGN>::VALUE];
@@ -308,7 +268,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_wgrad_kernel(ConvWgradAr
     if (m_begin >= m_end) return;
     const int nkt = (m_end - m_begin + GEMM_BK - 1) / GEMM_BK;
 
-    LoaderWgradA<BM> la;
+    LoaderWgradA<BM, DIL> la;
     la.init(a, ci0, tap, m_begin, tid);
     LoaderMN<BN> lb;
     lb.init(a.dy, a.Co, co0, a.Co, a.M, true, tid);
@@ -321,7 +281,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_wgrad_kernel(ConvWgradAr
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    float4 ra[LoaderWgradA<BM>::NV], rb[LoaderMN<BN>::NV];
+    float4 ra[LoaderWgradA<BM, DIL>::NV], rb[LoaderMN<BN>::NV];
     la.load(a, m_end, ra);
     lb.load(m_begin, m_end, rb);
     la.store(sm.A[0], ra);
@@ -358,7 +318,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_wgrad_kernel(ConvWgradAr
 // bf16-compute variants (fp32 storage, bf16 MFMA; see gemm_bf16_core.h).  Channel counts must be % 32.
 // ------------------------------------------------------------------------------------------------
 // X16: the source tensor is bf16 in memory (bf16 activation storage): 16-byte chunks of 8 channels, no conversion
-template <int BM, bool DGRAD, bool X16>
+template <int BM, bool DGRAD, bool X16, int DIL = 1>
 struct LoaderConvAb {
     static constexpr int NV = X16 ? BM / 64 : BM / 32;
     typedef typename std::conditional<X16, uint4, float4>::type Reg;
@@ -409,7 +369,7 @@ struct LoaderConvAb {
             int hs, ws;
             bool v = ok[i] && live;
             if (DGRAD) {
-                const int th = h_[i] - kh, tw = w_[i] - kw;
+                const int th = h_[i] - kh * DIL, tw = w_[i] - kw * DIL;
                 v = v && th >= 0 && tw >= 0;
                 if (a.stride == 2) {
                     v = v && ((th & 1) == 0) && ((tw & 1) == 0);
@@ -421,8 +381,8 @@ struct LoaderConvAb {
                 }
                 v = v && hs < a.Hs && ws < a.Ws;
             } else {
-                hs = h_[i] + kh;
-                ws = w_[i] + kw;
+                hs = h_[i] + kh * DIL;
+                ws = w_[i] + kw * DIL;
                 v = v && hs >= 0 && ws >= 0 && hs < a.Hs && ws < a.Ws;
             }
             const unsigned off = ((unsigned)((n_[i] * a.Hs + hs) * a.Ws + ws) * (unsigned)a.Cs + (unsigned)c0) * (X16 ? 2u : 4u);
@@ -443,7 +403,7 @@ struct LoaderConvAb {
     }
 };
 
-template <int BM, int BN, int WGM, int WGN, bool DGRAD, bool W16, bool X16>
+template <int BM, int BN, int WGM, int WGN, bool DGRAD, bool W16, bool X16, int DIL = 1>
 __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : (BM * BN == 64 * 64 ? MIN_WAVES_64X64 : 1)) void conv3x3_bf16c_kernel(ConvArgs a) {
     using T = TileCfg<BM, BN, WGM, WGN>;
     __shared__ __attribute__((aligned(16))) char smem_raw[BfSmemBytes<BM, BN, WGN>::VALUE];
@@ -456,7 +416,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : (BM * BN
     const int cpt = a.Cs / BF_BK;
     const int nkt = (a.par_on ? a.nth * a.ntw : 9) * cpt;
     const long long tapstride = (long long)a.Ci * a.Co;
-    LoaderConvAb<BM, DGRAD, X16> la;
+    LoaderConvAb<BM, DGRAD, X16, DIL> la;
     la.init(a, m0, tid);
     // fwd weights: transpose-read image; W16: the kernel is already bf16 in memory (per-step weight shadow)
     using LB = typename std::conditional<W16, typename std::conditional<DGRAD, LoaderKh<BN>, LoaderMNth<BN, true>>::type,
@@ -474,7 +434,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : (BM * BN
     // Operand pipeline two K tiles deep with LDS-only barriers -- see gemm_bf16c_body (gemm_f32.hip): requests and LDS
     // stores are unconditional (past the last tile they resolve to the out-of-range offset / write a buffer nobody reads)
     // so that the compiler's vmcnt waits stay exact.
-    using LAc = LoaderConvAb<BM, DGRAD, X16>;
+    using LAc = LoaderConvAb<BM, DGRAD, X16, DIL>;
     typename LAc::Reg ra0[LAc::NV], ra1[LAc::NV];
     typename LB::Reg rb0[NRB], rb1[NRB];
     // K tiles are requested strictly in order (0, 1, 2, then kt + 3 per iteration): the tap and the channel tile inside it
@@ -522,7 +482,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : (BM * BN
 
 // wgrad: A'[i = ci][k = m] gathered into a transpose-read image (gemm_bf16_core.h LoaderMNt): unit u = t + 256*i holds
 // the float4 of channels ci0 + 16*ib + 4*c of reduction row (output pixel) k = 4*kb + kr of the tile.
-template <int BM, bool S16>
+template <int BM, bool S16, int DIL = 1>
 struct LoaderWgradAt {
     static constexpr int NB = BM / 16;
     static constexpr int NU = BM / 32;
@@ -551,7 +511,7 @@ struct LoaderWgradAt {
         for (int i = 0; i < NU; ++i) {
             const int u = tid + 256 * i;
             const int c = ci0 + 16 * ((u >> 4) & (NB - 1)) + 4 * (u & 3);
-            const int hs = h_[i] * a.stride - a.pad + kh, ws = w_[i] * a.stride - a.pad + kw;
+            const int hs = h_[i] * a.stride - a.pad + kh * DIL, ws = w_[i] * a.stride - a.pad + kw * DIL;
             const bool v = m_[i] < m_end && hs >= 0 && ws >= 0 && hs < a.Hi && ws < a.Wi && c < a.Ci;
             const unsigned off = ((unsigned)((n_[i] * a.Hi + hs) * a.Wi + ws) * (unsigned)a.Ci + (unsigned)c) * (S16 ? 2u : 4u);
             if constexpr (S16) r[i] = src.ld8(v ? off : BUF_OOB);
@@ -577,7 +537,7 @@ struct LoaderWgradAt {
     }
 };
 
-template <int BM, int BN, int WGM, int WGN, bool S16>
+template <int BM, int BN, int WGM, int WGN, bool S16, int DIL = 1>
 __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : 1) void conv3x3_wgrad_bf16c_kernel(ConvWgradArgs a) {
     using T = TileCfg<BM, BN, WGM, WGN>;
     __shared__ __attribute__((aligned(16))) char smem_raw[BfSmemBytes<BM, BN, WGN>::VALUE];
@@ -591,7 +551,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : 1) void 
     const int m_end = min(a.M, m_begin + a.rows_per_split);
     if (m_begin >= m_end) return;
     const int nkt = (m_end - m_begin + BF_BK - 1) / BF_BK;
-    LoaderWgradAt<BM, S16> la;
+    LoaderWgradAt<BM, S16, DIL> la;
     la.init(a, ci0, tap, m_begin, tid);
     typename std::conditional<S16, LoaderMNth<BN>, LoaderMNt<BN>>::type lb;      // dy: same storage type as x
     lb.init(a.dy, a.Co, co0, a.Co, a.M, true, tid);
@@ -602,7 +562,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : 1) void 
         for (int j = 0; j < T::TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    typename LoaderWgradAt<BM, S16>::Reg ra[LoaderWgradAt<BM, S16>::NU];
+    typename LoaderWgradAt<BM, S16, DIL>::Reg ra[LoaderWgradAt<BM, S16, DIL>::NU];
     typename std::conditional<S16, uint2, float4>::type rb[LoaderMNt<BN>::NU];
     la.load(a, m_end, ra);
     lb.load(m_begin, m_end, rb);
@@ -1249,6 +1209,12 @@ static void launch_wgrad(const ConvWgradArgs &a0, int split, float *ws, long lon
         a.e.atomic = 1;   // accumulate onto dw
     }
     dim3 grid((unsigned)tiles, 9, (unsigned)split), block(GEMM_THREADS);
+    if (a.dil == 2) {                  // taps two pixels apart (conv_dilated.hip): the per-tap bodies, same split plan and reduction
+        if (bf16c && a.s16) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, true, 2>), grid, block, 0, s, a);
+        else if (bf16c) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, false, 2>), grid, block, 0, s, a);
+        else if (split3) hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN, WGM, WGN, true, 2>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN, WGM, WGN, false, 2>), grid, block, 0, s, a);
+    } else
     if (bf16c && a.s16) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, true>), grid, block, 0, s, a);
     else if (bf16c) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, false>), grid, block, 0, s, a);
     else if (split3 && BM == BN && WGM == 2 && WGN == 2 && tune(T_X3_CONV) != 2) {
@@ -1293,6 +1259,51 @@ static void launch_wgrad_fused(const ConvWgradArgs &a0, int split, float *ws, lo
     else hipLaunchKernelGGL(conv3x3_wgrad_fused_bf16_kernel<false>, grid, block, 0, s, a, ups, chunks);
     if (partial) launch_splitk_reduce(ws, split, part, 9 * a.Ci, a.Co, dw_final, a.Co, final_e.alpha, final_e.scale, s, nullptr, nullptr, 1.0f,
                                       ts ? 64 : 0, ts ? 64 : 0, a.tiles_n);
+}
+
+// ------------------------------------------------------------------------------------------------
+// dilation 2 (conv_dilated.hip; conv_args.h declares these): the implicit-GEMM tile bodies above with their taps two pixels
+// apart -- forward / input gradient on 64 x 64 tiles, weight gradient per tap on the dense rule's tiles
+// ------------------------------------------------------------------------------------------------
+void conv_dilated_tiles(const ConvArgs &a0, bool dgrad, int compute, hipStream_t s) {
+    ConvArgs a = a0;
+    a.tiles_m = cdiv(a.M, 64);
+    a.tiles_n = cdiv(a.Cd, 64);
+    dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(GEMM_THREADS);
+#define DETR_CONVD_LAUNCH(W16_, X16_)                                                                                       \
+    do {                                                                                                                        \
+        if (dgrad) hipLaunchKernelGGL((conv3x3_bf16c_kernel<64, 64, 2, 2, true, W16_, X16_, 2>), grid, block, 0, s, a);           \
+        else hipLaunchKernelGGL((conv3x3_bf16c_kernel<64, 64, 2, 2, false, W16_, X16_, 2>), grid, block, 0, s, a);                 \
+    } while (0)
+    if (compute == 1) {
+        if (a.w16 && a.x16) DETR_CONVD_LAUNCH(true, true);
+        else if (a.w16) DETR_CONVD_LAUNCH(true, false);
+        else if (a.x16) DETR_CONVD_LAUNCH(false, true);
+        else DETR_CONVD_LAUNCH(false, false);
+    } else if (compute == 2) {
+        if (dgrad) hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, true, true, 2>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, false, true, 2>), grid, block, 0, s, a);
+    } else {
+        if (dgrad) hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, true, false, 2>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, false, false, 2>), grid, block, 0, s, a);
+    }
+#undef DETR_CONVD_LAUNCH
+}
+
+static int conv_dilated_wgrad_tile(int Ci, int Co) { return (Ci >= 128 && Co >= 128) ? 128 : 64; }
+
+void conv_dilated_wgrad_tiles(const ConvWgradArgs &a, int compute, int split, float *ws, long long ws_bytes, hipStream_t s) {
+    const bool bf = compute == 1, s3 = compute == 2;
+    if (conv_dilated_wgrad_tile(a.Ci, a.Co) == 128) launch_wgrad<128, 128, 2, 2>(a, split, ws, ws_bytes, s, bf, s3);
+    else launch_wgrad<64, 64, 2, 2>(a, split, ws, ws_bytes, s, bf, s3);
+}
+
+// row splits launch_wgrad will use for that call (the scratch-size query)
+int conv_dilated_wgrad_splits(int M, int Ci, int Co, int compute, int split) {
+    const int t = conv_dilated_wgrad_tile(Ci, Co), tiles = cdiv(Ci, t) * cdiv(Co, t);
+    if (compute == 2 && split <= 0 && tune(T_X3_CONV) != 2) split = wgrad_x3_split(M, tiles, t);
+    int rps;
+    return wgrad_split_plan(M, tiles, split, rps);
 }
 
 }  // namespace detr

@@ -14,6 +14,7 @@
 // The dgrad form reads dy through the same patch with the taps flipped and the kernel transposed (K = Co).
 #pragma once
 #include "gemm_bf16_core.h"
+#include "conv_args.h"
 
 namespace detr {
 
@@ -136,15 +137,52 @@ __device__ __forceinline__ void halo_store_b_swz(unsigned short *flat, const uin
     for (int i = 0; i < BN / 64; ++i) *reinterpret_cast<uint4 *>(flat + halo_bsw((tid >> 2) + 64 * i, tid & 3)) = r[i];
 }
 
+// Workgroup id -> pixel-parity class k = 0..3 = (ph, pw) (1,1), (0,1), (1,0), (0,0), its tile counts and the id inside the class (ConvArgs.cls_*).
+// Shared by the class form of the stride-2 input gradient (S2C) and the PLANE form of the dilation-2 convolution (DIL, conv_dilated.hip).
+__device__ __forceinline__ void halo_class_decode(const ConvArgs &a, int &id, int &ph, int &pw, int &Hp, int &Wp) {
+    int k;
+    if (a.cls_mix) {
+        // Grid order: the four classes ROUND-ROBIN (workgroup id -> class id & 3), the classes' surplus tiles behind them.  A class writes (and reads the mask
+        // of) the pixels of ONE column parity only -- at 128 channels that is address bit 8, every other 256-byte block of the tensor, for the whole lifetime
+        // of its workgroups -- so with one class after the other (round 3's "heaviest first") the launch used half of the memory channels at a time:
+        // 120.2 / 94.1 / 113.9 us at 128 / 256 / 512 channels against 115.5 / 81.7 / 99.6 round-robin (profiles/r05_ab_results.txt #9).
+        const int nk[4] = {a.cls_off[1], a.cls_off[2] - a.cls_off[1], a.cls_off[3] - a.cls_off[2], a.cls_off[4] - a.cls_off[3]};
+        int m = nk[0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) m = nk[q] < m ? nk[q] : m;
+        if (id < 4 * m) { k = id & 3; id >>= 2; }
+        else {
+            int j = id - 4 * m;
+            k = 0;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (k == q && j >= nk[q] - m) { j -= nk[q] - m; k = q + 1; }
+            id = m + j;
+        }
+    } else {
+        k = (id >= a.cls_off[1]) + (id >= a.cls_off[2]) + (id >= a.cls_off[3]);
+        id -= a.cls_off[k];
+    }
+    ph = (k == 0 || k == 2) ? 1 : 0;
+    pw = (k == 0 || k == 1) ? 1 : 0;
+    Hp = a.cls_hp[k];
+    Wp = a.cls_wp[k];
+}
+
 // ConvArgs as for conv3x3_bf16c_kernel (stride 1, pad 1, bf16 src / w / dst); Hp / Wp carry the tile counts along H / W.
 // S2C: the four pixel-parity classes (ph, pw) of the STRIDE-2 input gradient in one launch (ConvArgs.cls_*).  dx[2 h2 + ph, 2 w2 + pw] only receives the taps kh = ph + 1
 // (mod 2), kw = pw + 1 (mod 2), reading dy[h2 + dh, w2 + dw] with dh, dw in {0, 1}: a stride-1 "2 x 2" convolution over dy in class
 // coordinates.  The kernel walks FOUR taps per chunk (patch offsets (1..2, 1..2) of the same haloed dy patch) for every class; the taps
 // a class does not have request no kernel tile (out-of-range offsets) and skip their MFMAs -- wave-uniform, the pipeline keeps its
 // static shape.  (The tile kernel ran the four class launches of a conv at 220-330 TFLOP/s: gathered operands, 1-4 short tap-GEMMs.)
-template <int BN, bool DGRAD, int TH = 8, bool S2C = false>
+// DIL (conv_dilated.hip; resnet_backbone.py:74-85,98,104-105): the dilation-2, pad-2 convolution as four dense pad-1 convolutions, one per
+// pixel-parity PLANE in_p(i, j) = in(2 i + ph, 2 j + pw) of source and destination, in one launch: tile coordinates are plane coordinates, the
+// patch loader reads plane pixels (row pitch 2 W C, pixel pitch 2 C, base (ph W + pw) C -- out-of-range plane pixels are zero on both sides of
+// the identity), the epilogue writes them (the S2C pixel map).  The LDS images, the nine taps and the MFMA order are the dense kernel's.
+template <int BN, bool DGRAD, int TH = 8, bool S2C = false, bool DIL = false>
 __global__ __launch_bounds__(GEMM_THREADS, TH == 8 ? 2 : 3) void conv3x3_halo_bf16_kernel(ConvArgs a) {
     static_assert(!S2C || DGRAD, "the class form exists for the input gradient only");
+    static_assert(!(S2C && DIL), "the class form and the plane form exclude each other");
     using T = TileCfg<TH * CH_TW, BN, 2, 2>;             // wave tile: TH / 2 pixel rows x BN / 2 channels
     using G = HaloGeom<TH>;
     constexpr int CH_PIX = G::PIX, CH_GRAN = G::GRAN, CH_NG = G::NG;
@@ -154,35 +192,7 @@ __global__ __launch_bounds__(GEMM_THREADS, TH == 8 ? 2 : 3) void conv3x3_halo_bf
     const int wm = wave >> 1, wn = wave & 1;
     int id = xcd_remap(blockIdx.x, gridDim.x);
     int ph = 0, pw = 0, Hp = a.Hp, Wp = a.Wp;
-    if constexpr (S2C) {                                 // the four classes share the launch: [cls_off[k], cls_off[k + 1])
-        int k;
-        if (a.cls_mix) {
-            // Grid order: the four classes ROUND-ROBIN (workgroup id -> class id & 3), the classes' surplus tiles behind them.  A class writes (and reads the mask
-            // of) the pixels of ONE column parity only -- at 128 channels that is address bit 8, every other 256-byte block of the tensor, for the whole lifetime
-            // of its workgroups -- so with one class after the other (round 3's "heaviest first") the launch used half of the memory channels at a time:
-            // 120.2 / 94.1 / 113.9 us at 128 / 256 / 512 channels against 115.5 / 81.7 / 99.6 round-robin (profiles/r05_ab_results.txt #9).
-            const int nk[4] = {a.cls_off[1], a.cls_off[2] - a.cls_off[1], a.cls_off[3] - a.cls_off[2], a.cls_off[4] - a.cls_off[3]};
-            int m = nk[0];
-#pragma unroll
-            for (int q = 1; q < 4; ++q) m = nk[q] < m ? nk[q] : m;
-            if (id < 4 * m) { k = id & 3; id >>= 2; }
-            else {
-                int j = id - 4 * m;
-                k = 0;
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    if (k == q && j >= nk[q] - m) { j -= nk[q] - m; k = q + 1; }
-                id = m + j;
-            }
-        } else {
-            k = (id >= a.cls_off[1]) + (id >= a.cls_off[2]) + (id >= a.cls_off[3]);
-            id -= a.cls_off[k];
-        }
-        ph = (k == 0 || k == 2) ? 1 : 0;
-        pw = (k == 0 || k == 1) ? 1 : 0;
-        Hp = a.cls_hp[k];
-        Wp = a.cls_wp[k];
-    }
+    if constexpr (S2C || DIL) halo_class_decode(a, id, ph, pw, Hp, Wp);      // the four classes / planes share the launch
     const int tn = id % a.tiles_n;
     int t = id / a.tiles_n;
     const int twi = t % Wp;
@@ -202,8 +212,9 @@ __global__ __launch_bounds__(GEMM_THREADS, TH == 8 ? 2 : 3) void conv3x3_halo_bf
         const int g = tid + 256 * i;
         const int px = g >> 2;
         const int pr = px / CH_PW, pc = px - pr * CH_PW;
-        const int h = h0 - 1 + pr, w = w0 - 1 + pc;
-        const bool ok = g < CH_GRAN && h >= 0 && h < a.Hs && w >= 0 && w < a.Ws;
+        const int hq = h0 - 1 + pr, wq = w0 - 1 + pc;                 // tile-space (DIL: plane) coordinates of the patch pixel
+        const int h = DIL ? 2 * hq + ph : hq, w = DIL ? 2 * wq + pw : wq;
+        const bool ok = g < CH_GRAN && hq >= 0 && h < a.Hs && wq >= 0 && w < a.Ws;
         goff[i] = ok ? ((unsigned)((n * a.Hs + h) * a.Ws + w) * (unsigned)a.Cs + (unsigned)(g & 3) * 8u) * 2u : BUF_OOB;
     }
     auto patch_load = [&](int c, uint4 (&r)[CH_NG]) {      // chunk c >= nchunks: every lane out of range, no traffic
@@ -341,7 +352,7 @@ __global__ __launch_bounds__(GEMM_THREADS, TH == 8 ? 2 : 3) void conv3x3_halo_bf
         if (c < nchunks) chunk(c, std::integral_constant<int, 0>{});
     }
     __syncthreads();
-    halo_epilogue<BN, TH, S2C>(acc, reinterpret_cast<float *>(halo_smem), reinterpret_cast<unsigned short *>(a.dst), a, n, h0, w0, n0, wm, wn, lane, wave, ph, pw);
+    halo_epilogue<BN, TH, S2C || DIL>(acc, reinterpret_cast<float *>(halo_smem), reinterpret_cast<unsigned short *>(a.dst), a, n, h0, w0, n0, wm, wn, lane, wave, ph, pw);
 }
 
 template <int BN, int TH>
@@ -366,12 +377,8 @@ static int launch_conv_halo_t(const ConvArgs &a0, bool dgrad, hipStream_t s) {
     return 0;
 }
 
-// the four pixel-parity classes of a stride-2 input gradient in one launch (4-row tiles; heaviest class first)
-template <int BN>
-static int launch_conv_halo_s2classes(const ConvArgs &a0, hipStream_t s) {
-    constexpr int TH = 4;
-    ConvArgs a = a0;
-    a.tiles_n = cdiv(a.Cd, BN);
+// tile table of the four pixel-parity classes of the destination (a.tiles_n set): cls_hp / cls_wp / cls_off
+static void halo_class_plan(ConvArgs &a, int TH) {
     a.cls_off[0] = 0;
     for (int k = 0; k < 4; ++k) {
         const int ph = (k == 0 || k == 2) ? 1 : 0, pw = (k == 0 || k == 1) ? 1 : 0;
@@ -380,6 +387,15 @@ static int launch_conv_halo_s2classes(const ConvArgs &a0, hipStream_t s) {
         a.cls_wp[k] = cdiv(Wc, CH_TW);
         a.cls_off[k + 1] = a.cls_off[k] + a.N * a.cls_hp[k] * a.cls_wp[k] * a.tiles_n;
     }
+}
+
+// the four pixel-parity classes of a stride-2 input gradient in one launch (4-row tiles; heaviest class first)
+template <int BN>
+static int launch_conv_halo_s2classes(const ConvArgs &a0, hipStream_t s) {
+    constexpr int TH = 4;
+    ConvArgs a = a0;
+    a.tiles_n = cdiv(a.Cd, BN);
+    halo_class_plan(a, TH);
     if (a.cls_off[4] <= 0) return 0;
     a.cls_mix = tune(T_DGRAD_S2_CLASSES) == 4 ? 0 : 1;       // DETR_HIP_DGRAD_S2_CLASSES = 4: one class after the other (A/B of the grid order)
     constexpr int smem = ConvHaloSmemBytes<BN, TH>::VALUE;
@@ -391,6 +407,30 @@ static int launch_conv_halo_s2classes(const ConvArgs &a0, hipStream_t s) {
         reserved = true;
     }
     hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<BN, true, TH, true>), dim3((unsigned)a.cls_off[4]), dim3(GEMM_THREADS), smem, s, a);
+    return 0;
+}
+
+// the four parity planes of a dilation-2 convolution in one launch (forward / input gradient); the planes' workgroups round-robin in the
+// grid for the reason given at cls_mix: a plane touches the pixels of one column parity only
+template <int BN, int TH>
+static int launch_conv_halo_planes(const ConvArgs &a0, bool dgrad, hipStream_t s) {
+    ConvArgs a = a0;
+    a.tiles_n = cdiv(a.Cd, BN);
+    halo_class_plan(a, TH);
+    if (a.cls_off[4] <= 0) return 0;
+    a.cls_mix = 1;
+    constexpr int smem = ConvHaloSmemBytes<BN, TH>::VALUE;
+    static bool reserved[2] = {false, false};
+    const void *fn = dgrad ? reinterpret_cast<const void *>(conv3x3_halo_bf16_kernel<BN, true, TH, false, true>)
+                           : reinterpret_cast<const void *>(conv3x3_halo_bf16_kernel<BN, false, TH, false, true>);
+    if (!reserved[dgrad ? 1 : 0]) {
+        hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        DETR_REQUIRE(err == hipSuccess, "conv3x3 dilated (halo planes): cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(err));
+        reserved[dgrad ? 1 : 0] = true;
+    }
+    const dim3 grid((unsigned)a.cls_off[4]), block(GEMM_THREADS);
+    if (dgrad) hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<BN, true, TH, false, true>), grid, block, smem, s, a);
+    else hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<BN, false, TH, false, true>), grid, block, smem, s, a);
     return 0;
 }
 

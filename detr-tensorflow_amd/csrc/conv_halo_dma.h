@@ -50,7 +50,8 @@ constexpr int CHD_RING = CHD_OFF_DUMP + 1024;
 constexpr int CHD_EPI = StageCfg<CHD_BN, 2>::BYTES;
 constexpr int CHD_SMEM = CHD_RING > CHD_EPI ? CHD_RING : CHD_EPI;
 
-template <bool DGRAD, bool LATE>
+// DIL: the parity-plane form of conv3x3_halo_bf16_kernel<.., DIL> -- only the global side of the patch pieces and the epilogue's pixel map change
+template <bool DGRAD, bool LATE, bool DIL = false>
 __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BN = CHD_BN, TH = CHD_TH, NB = CHD_NB;
@@ -59,13 +60,15 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int id = xcd_remap(blockIdx.x, gridDim.x);
+    int id = xcd_remap(blockIdx.x, gridDim.x);
+    int ph = 0, pw = 0, Hp = a.Hp, Wp = a.Wp;
+    if constexpr (DIL) halo_class_decode(a, id, ph, pw, Hp, Wp);
     const int tn = id % a.tiles_n;
     int t = id / a.tiles_n;
-    const int twi = t % a.Wp;
-    t /= a.Wp;
-    const int thi = t % a.Hp;
-    const int n = t / a.Hp;
+    const int twi = t % Wp;
+    t /= Wp;
+    const int thi = t % Hp;
+    const int n = t / Hp;
     const int h0 = thi * TH, w0 = twi * CH_TW, n0 = tn * BN;
     const int nchunks = a.Cs / BF_BK;
     const unsigned lds0 = ring_lds_addr(chd_smem);
@@ -79,9 +82,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
         const int P = wave + 4 * i;
         const int px = 16 * P + (lane >> 2);
         const int pr = px / CH_PW, pc = px - pr * CH_PW;
-        const int h = h0 - 1 + pr, w = w0 - 1 + pc;
+        const int hq = h0 - 1 + pr, wq = w0 - 1 + pc;                 // tile-space (DIL: plane) coordinates of the patch pixel
+        const int h = DIL ? 2 * hq + ph : hq, w = DIL ? 2 * wq + pw : wq;
         const int c = (lane & 3) ^ ((px >> 2) & 3);                  // source chunk that belongs at this lane's slot
-        const bool ok = px < CHD_PIX && h >= 0 && h < a.Hs && w >= 0 && w < a.Ws;
+        const bool ok = px < CHD_PIX && hq >= 0 && h < a.Hs && wq >= 0 && w < a.Ws;
         pvoff[i] = ok ? ((unsigned)((n * a.Hs + h) * a.Ws + w) * (unsigned)a.Cs) * 2u + 16u * (unsigned)c : BUF_OOB;
         plds[i] = P < CHD_PP ? P * 1024 : -1;                        // (wave-uniform) spare slots: dump area
     }
@@ -218,7 +222,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void conv3x3_halo_dma_bf16_kernel(
     }
     ring_wait_vmcnt<0>();                                // the trailing empty requests still write (zeros) into the ring the epilogue reuses
     __syncthreads();
-    halo_epilogue<BN, TH, false>(acc, reinterpret_cast<float *>(chd_smem), reinterpret_cast<unsigned short *>(a.dst), a, n, h0, w0, n0, wm, wn, lane, wave);
+    halo_epilogue<BN, TH, DIL>(acc, reinterpret_cast<float *>(chd_smem), reinterpret_cast<unsigned short *>(a.dst), a, n, h0, w0, n0, wm, wn, lane, wave, ph, pw);
 #endif
 }
 
@@ -247,6 +251,28 @@ static int launch_conv_halo_dma(const ConvArgs &a0, bool dgrad, hipStream_t s) {
         case 2: hipLaunchKernelGGL((conv3x3_halo_dma_bf16_kernel<false, true>), grid, block, smem, s, a); break;
         default: hipLaunchKernelGGL((conv3x3_halo_dma_bf16_kernel<true, true>), grid, block, smem, s, a); break;
     }
+    return 0;
+}
+
+// the four parity planes of a dilation-2 convolution in one launch (see launch_conv_halo_planes)
+static int launch_conv_halo_dma_planes(const ConvArgs &a0, bool dgrad, hipStream_t s) {
+    ConvArgs a = a0;
+    a.tiles_n = cdiv(a.Cd, CHD_BN);
+    halo_class_plan(a, CHD_TH);
+    if (a.cls_off[4] <= 0) return 0;
+    a.cls_mix = 1;
+    const int smem = CHD_SMEM;
+    const void *fns[2] = {reinterpret_cast<const void *>(conv3x3_halo_dma_bf16_kernel<false, true, true>), reinterpret_cast<const void *>(conv3x3_halo_dma_bf16_kernel<true, true, true>)};
+    static bool reserved[2] = {false, false};
+    const int k = dgrad ? 1 : 0;
+    if (!reserved[k]) {
+        hipError_t err = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        DETR_REQUIRE(err == hipSuccess, "conv3x3 dilated (halo planes, DMA): cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(err));
+        reserved[k] = true;
+    }
+    const dim3 grid((unsigned)a.cls_off[4]), block(GEMM_THREADS);
+    if (dgrad) hipLaunchKernelGGL((conv3x3_halo_dma_bf16_kernel<true, true, true>), grid, block, smem, s, a);
+    else hipLaunchKernelGGL((conv3x3_halo_dma_bf16_kernel<false, true, true>), grid, block, smem, s, a);
     return 0;
 }
 

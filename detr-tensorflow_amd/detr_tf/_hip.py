@@ -88,6 +88,11 @@ class Conv3x3Desc(Structure):
                 ("maskbits_out", c_void_p)]                                   # ABI 5: bit-packed ReLU masks
 
 
+class Conv3x3DDesc(Structure):
+    """detr_conv3x3d_desc: the fields of detr_conv3x3_desc plus `dilation` (appended entry point, ABI version unchanged)."""
+    _fields_ = list(Conv3x3Desc._fields_) + [("dilation", c_int32)]
+
+
 class InputDesc(Structure):
     _fields_ = [("B", c_int32), ("Hs", c_int32), ("Ws", c_int32), ("Hd", c_int32), ("Wd", c_int32),
                 ("src", c_void_p), ("src_batch_stride", c_int64), ("dst", c_void_p), ("lut", c_void_p),
@@ -191,6 +196,7 @@ _SIGNATURES = {
     "detr_hip_set_floats16_f32": [f32p, POINTER(c_float * 16), c_void_p],
     "detr_hip_global_clip_scale_f32": [f32p, c_void_p, c_void_p, f32p, c_int32, f32p, c_void_p],
     "detr_hip_adamw_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, f32p, c_int32, c_int32, c_void_p],
+    "detr_hip_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32, c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
@@ -202,6 +208,7 @@ _SIGNATURES_I64 = {
     "detr_hip_workspace_bytes_conv3x3": [POINTER(Conv3x3Desc), c_int32],
     "detr_hip_workspace_bytes_stem": [POINTER(StemDesc), c_int32],
     "detr_hip_workspace_bytes_layernorm": [POINTER(LayerNormDesc)],
+    "detr_hip_workspace_bytes_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
@@ -698,8 +705,16 @@ def conv1x1_bwd_fused(dy, a, w, da, dw, scratch, *, scale=None, use_mask=True, a
 
 
 def conv3x3(mode, x, w, y, N, Hi, Wi, Ci, Ho, Wo, Co, stride, *, pad=1, alpha=1.0, scale=None, bias=None,
-            residual=None, mask=None, act=0, split=0, compute=None, maskbits_out=None):
-    d = Conv3x3Desc()
+            residual=None, mask=None, act=0, split=0, compute=None, maskbits_out=None, dilation=1):
+    """dilation=2 (pad 2, stride 1, Ho x Wo = Hi x Wi): the appended entry point detr_hip_conv3x3_dilated (csrc/conv_dilated.hip)."""
+    if dilation not in (1, 2):
+        raise ValueError(f"conv3x3: dilation {dilation} unsupported (1 or 2)")
+    dil = dilation == 2
+    d = Conv3x3DDesc() if dil else Conv3x3Desc()
+    if dil:
+        d.dilation = 2
+    fn, ws_fn = ("detr_hip_conv3x3_dilated", "detr_hip_workspace_bytes_conv3x3_dilated") if dil else \
+        ("detr_hip_conv3x3_f32", "detr_hip_workspace_bytes_conv3x3")
     d.N, d.Hi, d.Wi, d.Ci, d.Ho, d.Wo, d.Co, d.stride, d.pad = N, Hi, Wi, Ci, Ho, Wo, Co, stride, pad
     d.x, d.w, d.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
     is16 = lambda t: 1 if (t is not None and t.dtype == torch.bfloat16) else 0      # bf16 weight shadow / activation storage
@@ -712,17 +727,17 @@ def conv3x3(mode, x, w, y, N, Hi, Wi, Ci, Ho, Wo, Co, stride, *, pad=1, alpha=1.
     d.act, d.split = act, split
     d.compute = COMPUTE_BF16 if compute is None else int(compute)
     if mode == 2 and WORKSPACE is not None:      # weight gradient: per-split partial kernels, sized by the library
-        need_workspace(_ws_query("detr_hip_workspace_bytes_conv3x3", ("conv", N, Hi, Wi, Ci, Ho, Wo, Co, stride, pad, split, d.compute, d.x_dtype),
+        need_workspace(_ws_query(ws_fn, ("convd" if dil else "conv", N, Hi, Wi, Ci, Ho, Wo, Co, stride, pad, split, d.compute, d.x_dtype),
                                  byref(d), mode))
     d.workspace, d.workspace_bytes = (WORKSPACE.data_ptr(), WORKSPACE.numel() * 4) if WORKSPACE is not None else (None, 0)
     ev0 = PROFILER.begin() if PROFILER is not None else None
-    _check(load().detr_hip_conv3x3_f32(byref(d), mode, _stream()), "detr_hip_conv3x3_f32")
+    _check(getattr(load(), fn)(byref(d), mode, _stream()), fn)
     if ev0 is not None:
         rows = N * (Hi * Wi if mode == 1 else Ho * Wo)
         # FLOPs: every mode performs the forward convolution's multiply-adds, N Ho Wo 9 Ci Co (until round 5 the input gradient was counted over its
         # OUTPUT rows N Hi Wi: four times too many for the three stride-2 convolutions, which inflated conv3x3_dgrad's rate by 1.56x)
         PROFILER.end(("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad")[mode], 2.0 * (N * Ho * Wo) * 9 * Ci * Co, ev0,
-                     f"N{N} {Hi}x{Wi}x{Ci}->{Ho}x{Wo}x{Co} s{stride}",
+                     f"N{N} {Hi}x{Wi}x{Ci}->{Ho}x{Wo}x{Co} s{stride}" + (" d2" if dil else ""),
                      float(x.element_size() * (N * Hi * Wi * Ci if mode != 1 else N * Ho * Wo * Co)
                            + (w.element_size() * 9 * Ci * Co if mode != 2 else w.element_size() * N * Ho * Wo * Co)
                            + y.element_size() * (N * Ho * Wo * Co if mode == 0 else (N * Hi * Wi * Ci if mode == 1 else 9 * Ci * Co))

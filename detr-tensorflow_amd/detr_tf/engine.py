@@ -101,16 +101,34 @@ def downsample_mask_nearest(mask, Hf, Wf):
     return mask[:, sy][:, :, sx]
 
 
-def feature_size(H, W):
-    """Feature-map size of an H x W input: stem conv, max-pool, layer2..4 each take ceil(n / 2)."""
-    for _ in range(5):
-        H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+def dilation_flags(replace_stride_with_dilation):
+    """replace_stride_with_dilation (None or one flag each for layer2, layer3, layer4; resnet_backbone.py:36-49) as a tuple of 3 bools."""
+    if replace_stride_with_dilation is None:
+        return (False, False, False)
+    flags = tuple(bool(f) for f in replace_stride_with_dilation)
+    if len(flags) != 3:
+        raise ValueError(f"replace_stride_with_dilation: expected 3 flags (layer2, layer3, layer4), got {len(flags)}")
+    return flags
+
+
+def feature_size(H, W, replace_stride_with_dilation=None):
+    """Feature-map size of an H x W input: stem conv, max-pool, layer2..4 each take ceil(n / 2) -- except the stages whose
+    stride is replaced by dilation (resnet_backbone.py:74-76), which keep their input size."""
+    for halves in (True, True) + tuple(not f for f in dilation_flags(replace_stride_with_dilation)):
+        if halves:
+            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     return H, W
 
 
 class DetrEngine:
     def __init__(self, device="cuda:0", blocks=RESNET50_BLOCKS, num_enc=6, num_dec=6, num_queries=100,
-                 num_classes=92, nb_class=None, seed=0, tf_backbone=False):
+                 num_classes=92, nb_class=None, seed=0, tf_backbone=False, replace_stride_with_dilation=(False, False, False)):
+        # replace_stride_with_dilation (resnet_backbone.py:36-49,74-85): one flag each for layer2..4.  A flagged stage keeps its input
+        # size (stride 1) and the 3x3 convs of its blocks >= 1 run at dilation 2 (DETR-DC5: layer4 flagged, feature stride 16)
+        self.dilate = dilation_flags(replace_stride_with_dilation)
+        if tf_backbone and any(self.dilate):
+            raise ValueError("replace_stride_with_dilation needs the reference backbone: tf.keras.applications.ResNet50 "
+                             "(tf_backbone=True) has no such option")
         hip.load()
         self.device = torch.device(device)
         hip.ensure_workspace(self.device)
@@ -718,7 +736,7 @@ class DetrEngine:
         host = np.asarray(masks.cpu() if torch.is_tensor(masks) else masks).astype(bool)
         if host.shape != shape:
             raise ValueError(f"masks: expected shape {shape}, got {host.shape}")
-        Hf, Wf = feature_size(shape[1], shape[2])
+        Hf, Wf = feature_size(shape[1], shape[2], self.dilate)
         empty = [b for b in range(shape[0]) if downsample_mask_nearest(host[b:b + 1], Hf, Wf).all()]
         if empty:
             raise ValueError(f"masks: image(s) {empty} have no valid (unpadded) position on the {Hf} x {Wf} feature map")
@@ -749,9 +767,7 @@ class DetrEngine:
         B, H, W, _ = images.shape
         self._shape = (B, H, W)
         if dp > 0.0:
-            hf, wf = H, W
-            for _ in range(5):                                   # stem conv, max-pool, layer2..4: each ceil(n / 2)
-                hf, wf = (hf - 1) // 2 + 1, (wf - 1) // 2 + 1
+            hf, wf = feature_size(H, W, self.dilate)        # stem conv, max-pool, layer2..4: each ceil(n / 2) unless dilated
             self._gen_dropmasks(B, hf * wf)
         self.images = images
         V = self.P.views
@@ -778,7 +794,9 @@ class DetrEngine:
             for b in range(nb):
                 n = block_names(li, b, self.tf_backbone)
                 p = n["tag"]
-                stride = 2 if (b == 0 and li > 0) else 1
+                dilated = li > 0 and self.dilate[li - 1]         # the stage trades its stride for dilation (resnet_backbone.py:74-85)
+                stride = 2 if (b == 0 and li > 0 and not dilated) else 1
+                dil = 2 if (dilated and b > 0) else 1            # the stage's first block keeps dilation 1
                 ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
                 M_in, M_out = B * h * w, B * ho * wo
                 xs = x
@@ -803,7 +821,7 @@ class DetrEngine:
                 self._conv1x1_fwd(x1, M1, cin, d1, f"{n['conv1']}/kernel", n["bn1"], y1)
                 y2 = self.buf(f"{p}:y2", (B, ho, wo, d1), adt)
                 hip.conv3x3(0, y1, self._scaled_kernel(f"{n['conv2']}/kernel", n["bn2"]), y2, B, h1, w1, d1, ho, wo, d1,
-                            s2, bias=self.bn_shift[n["bn2"]], act=1)
+                            s2, bias=self.bn_shift[n["bn2"]], act=1, pad=dil, dilation=dil)
                 if b == 0:
                     self._side_join()
                 out = self.buf(f"{p}:out", (B, ho, wo, d2), adt)
@@ -818,7 +836,7 @@ class DetrEngine:
                     if (training and adt == torch.bfloat16 and not last and nxt_d1 <= 256) else None
                 self._conv1x1_fwd(y2, M_out, d1, d2, f"{n['conv3']}/kernel", n["bn3"], out, residual=idn, maskbits_out=obits)
                 self._block_meta.append(dict(p=p, n=n, x=x, xs=xs, x1=x1, y1=y1, y2=y2, out=out, h=h, w=w, ho=ho, wo=wo, h1=h1, w1=w1,
-                                             M1=M1, s2=s2, cin=cin, d1=d1, d2=d2, stride=stride, first=(b == 0), out_bits=obits))
+                                             M1=M1, s2=s2, cin=cin, d1=d1, d2=d2, stride=stride, first=(b == 0), out_bits=obits, dil=dil))
                 x, h, w, cin = out, ho, wo, d2
         feat, Hf, Wf = x, h, w
         L = Hf * Wf
@@ -1195,11 +1213,12 @@ class DetrEngine:
             # conv2 (3x3)
 
             def wg2():
-                hip.conv3x3(2, y1, dz2, G[f"{n['conv2']}/kernel"], B, h1, w1, d1, ho, wo, d1, s2, scale=self.bn_scale[n["bn2"]])
+                hip.conv3x3(2, y1, dz2, G[f"{n['conv2']}/kernel"], B, h1, w1, d1, ho, wo, d1, s2, scale=self.bn_scale[n["bn2"]],
+                            pad=m["dil"], dilation=m["dil"])
                 bias_grad(n["conv2"], n["bn2"], dz2, M_out, d1)
             on_side(wg2)
             dz1 = self.buf(f"scratch:dz1:{d1}:{h1}{par}", (B, h1, w1, d1), adt)
-            hip.conv3x3(1, dz2, ws2, dz1, B, h1, w1, d1, ho, wo, d1, s2, mask=y1)
+            hip.conv3x3(1, dz2, ws2, dz1, B, h1, w1, d1, ho, wo, d1, s2, mask=y1, pad=m["dil"], dilation=m["dil"])
             # conv1
 
             def wg1():

@@ -65,7 +65,7 @@ def get_attention_maps(model, images, need_weights=True):
     from .engine import feature_size
     m_outputs = model(images, training=False, need_weights=need_weights)
     imgs = images[0] if isinstance(images, (tuple, list)) else images
-    Hf, Wf = feature_size(int(imgs.shape[1]), int(imgs.shape[2]))
+    Hf, Wf = feature_size(int(imgs.shape[1]), int(imgs.shape[2]), model.engine.dilate)
     maps = {}
     for name, w in m_outputs["attn"].items():
         B, T, S = w.shape

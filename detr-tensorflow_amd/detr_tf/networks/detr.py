@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from ..engine import DetrEngine
+from ..engine import DetrEngine, dilation_flags
 from ..params import RESNET50_BLOCKS, RESNET101_BLOCKS
 
 
@@ -29,20 +29,44 @@ class _Layer:
         self.trainable_variables = variables
 
 
+BACKBONES = {"resnet50": RESNET50_BLOCKS, "resnet101": RESNET101_BLOCKS}
+
+
+def resolve_backbone(backbone, replace_stride_with_dilation=None, tf_backbone=False):
+    """(blocks, dilation flags) of a backbone name.  "resnet50-dc5" / "resnet101-dc5" name replace_stride_with_dilation =
+    [False, False, True] (DETR-DC5: layer4 at stride 1, dilation 2 -- feature stride 16; resnet_backbone.py:36-85).  Pure host
+    code: raises ValueError for an unknown name, contradicting arguments, or flags together with tf_backbone=True."""
+    base, dc5 = (backbone[:-4], True) if isinstance(backbone, str) and backbone.endswith("-dc5") else (backbone, False)
+    if base not in BACKBONES:
+        raise ValueError(f"backbone must be one of {sorted(BACKBONES)} or their '-dc5' variants, got {backbone!r}")
+    flags = dilation_flags(replace_stride_with_dilation)
+    if dc5:
+        if replace_stride_with_dilation is not None and flags != (False, False, True):
+            raise ValueError(f"backbone={backbone!r} means replace_stride_with_dilation=[False, False, True], got {list(flags)}")
+        flags = (False, False, True)
+    if tf_backbone and any(flags):
+        raise ValueError("replace_stride_with_dilation needs the reference backbone: tf.keras.applications.ResNet50 "
+                         "(tf_backbone=True) has no such option")
+    return BACKBONES[base], flags
+
+
 class DetrModel:
     def __init__(self, include_top=True, nb_class=None, num_decoder_layers=6, num_encoder_layers=6, num_queries=100,
-                 backbone="resnet50", device=None, seed=0, dropout=0.1, precision="fp32", tf_backbone=False):
+                 backbone="resnet50", device=None, seed=0, dropout=0.1, precision="fp32", tf_backbone=False,
+                 replace_stride_with_dilation=None):
+        blocks, dilate = resolve_backbone(backbone, replace_stride_with_dilation, tf_backbone)      # argument errors before any device is needed
         device = device or (f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else None)
         if device is None:
             raise RuntimeError("DETR HIP model needs a GPU: the hot path has no CPU fallback")
-        blocks = {"resnet50": RESNET50_BLOCKS, "resnet101": RESNET101_BLOCKS}[backbone]
         self.include_top = include_top
         self.headless = (not include_top) and nb_class is None
         self.name = "detr" if self.headless else "detr_finetuning"
         self.tf_backbone = bool(tf_backbone)
         self.eval_graph, self._eval_graph, self._eval_seen = True, None, None     # hipGraph replay of the eval forward (_eval_forward)
         self.engine = DetrEngine(device, blocks, num_encoder_layers, num_decoder_layers, num_queries, 92, nb_class, seed,
-                                 tf_backbone=tf_backbone)
+                                 tf_backbone=tf_backbone, replace_stride_with_dilation=dilate)
+        self.backbone = backbone
+        self.replace_stride_with_dilation = dilate
         if precision not in ("fp32", "bf16", "fp32x3"):
             raise ValueError("precision must be 'fp32' (exact fp32 MFMA, parity mode), 'fp32x3' (fp32 storage and accuracy on the bf16 matrix "
                              "pipe: 3-way operand split, detr_gemm_desc.compute = 2) or 'bf16' (bf16 MFMA, fp32 accumulate)")
@@ -78,6 +102,11 @@ class DetrModel:
         n_train = sum(n for _, n in P.offsets.values())
         n_frozen = sum(4 * c for c in P.bn.values())
         print(f'Model: "{self.name}"  trainable params: {n_train:,}  non-trainable (frozen BN): {n_frozen:,}')
+        dilate = self.replace_stride_with_dilation
+        variant = "plain (feature stride 32)" if not any(dilate) else \
+            ("DC5 (layer4 dilated, feature stride 16)" if dilate == (False, False, True) else
+             "dilated " + "+".join(f"layer{i + 2}" for i, f in enumerate(dilate) if f) + f" (feature stride {32 >> sum(dilate)})")
+        print(f"  backbone: {self.backbone}, {variant}, replace_stride_with_dilation={list(dilate)}")
         for l in self.layers:
             print(f"  {l.name:28s} {sum(v.numel() for v in l.trainable_variables):>12,}")
 
@@ -134,7 +163,7 @@ class DetrModel:
             masks = eng._host_masks(masks, tuple(images.shape[:3]))      # validated on the host, then a device input like any other
         if not (self.eval_graph and os.environ.get("DETR_HIP_GRAPH", "1") != "0" and images.is_cuda):
             return eng.forward(images, training=False, masks=masks, attn_sites=attn_sites)
-        key = (tuple(images.shape), eng._weights_version, eng.compute, tuple(attn_sites), masks is not None)
+        key = (tuple(images.shape), eng._weights_version, eng.compute, tuple(eng.dilate), tuple(attn_sites), masks is not None)
         g = self._eval_graph
         # a graph addresses the engine's buffers as they were at capture: any later re-allocation (a forward of another
         # shape in between) makes it unusable -- engine.buf_generation tells
@@ -226,11 +255,15 @@ class DetrModel:
 
 def get_detr_model(config, include_top=False, nb_class=None, weights=None, tf_backbone=False, num_decoder_layers=6,
                    num_encoder_layers=6, num_queries=100, backbone="resnet50", device=None, seed=0, dropout=0.1,
-                   precision="fp32"):
+                   precision="fp32", replace_stride_with_dilation=None):
     """Same arguments and three output modes as the reference (detr.py:116-204); `num_queries`,
     `backbone` ("resnet50" | "resnet101", resnet_backbone.py:35-66), `device` and `seed` are
     extensions (the reference never exposes num_queries / ResNet101); `dropout` is the
-    transformer dropout rate of training mode (the reference hard-codes 0.1, transformer.py:9)."""
+    transformer dropout rate of training mode (the reference hard-codes 0.1, transformer.py:9).
+    `replace_stride_with_dilation` (one flag each for layer2..4, resnet_backbone.py:36-85) or the backbone names
+    "resnet50-dc5" / "resnet101-dc5" (= [False, False, True]) build the dilated variants.  A DC5 checkpoint has the same
+    variable names and shapes as a plain one: it loads into either model, so the flag must be given with it."""
+    resolve_backbone(backbone, replace_stride_with_dilation, tf_backbone)      # argument errors first: before the config is touched
     if tf_backbone:
         # detr.py:146-148: the backbone becomes tf.keras.applications.ResNet50 (ResNet v1, conv biases, BatchNormalization in
         # inference mode) and the data pipeline switches to the caffe-style BGR mean subtraction.  (The reference also
@@ -240,7 +273,8 @@ def get_detr_model(config, include_top=False, nb_class=None, weights=None, tf_ba
         config.normalized_method = "tf_resnet"
     model = DetrModel(include_top=include_top, nb_class=nb_class, num_decoder_layers=num_decoder_layers,
                       num_encoder_layers=num_encoder_layers, num_queries=num_queries, backbone=backbone, device=device,
-                      seed=seed, dropout=dropout, precision=precision, tf_backbone=tf_backbone)
+                      seed=seed, dropout=dropout, precision=precision, tf_backbone=tf_backbone,
+                      replace_stride_with_dilation=replace_stride_with_dilation)
     if weights is not None:
         if isinstance(weights, str) and weights == "detr":
             # the reference downloads three files from GCS into weights/detr/ (weights.py:5-11,24-32) and loads

@@ -157,7 +157,7 @@ class GraphedTrainStep:
         images, masks = split_images(images)
         return (tuple(images.shape), masks is not None, tuple(t_bbox.shape), bool(c.train_backbone), bool(c.train_transformers),
                 bool(c.train_nlayers), int(c.background_class), self.model.engine.compute, float(self.model.engine.dropout_p),
-                bool(getattr(c, "check_matching", False)), clip_mode(c), decay_active(c))      # (other optimiser launches: re-record)
+                bool(getattr(c, "check_matching", False)), clip_mode(c), decay_active(c), tuple(self.model.engine.dilate))      # (other optimiser launches: re-record)
 
     def _capture(self, images, t_bbox, t_class):
         model, opts, cfg = self.model, self.optimizers, self.config
@@ -230,7 +230,7 @@ class GraphedTrainStep:
             if not (torch.is_tensor(masks) and masks.is_cuda):
                 # host masks are validated on the host, as in an eager step
                 host = np.asarray(masks.cpu() if torch.is_tensor(masks) else masks).astype(bool)
-                Hf, Wf = feature_size(host.shape[1], host.shape[2])
+                Hf, Wf = feature_size(host.shape[1], host.shape[2], self.model.engine.dilate)
                 empty = [b for b in range(host.shape[0]) if downsample_mask_nearest(host[b:b + 1], Hf, Wf).all()]
                 if empty:
                     raise ValueError(f"masks: image(s) {empty} have no valid (unpadded) position on the {Hf} x {Wf} feature map")

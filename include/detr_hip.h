@@ -154,7 +154,8 @@ int detr_hip_splitk_reduce_many(const detr_reduce_desc *descs, int32_t n, void *
 int detr_hip_gemm_group_f32(const detr_gemm_desc *descs, int32_t n, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
- * 3x3 convolution (explicit zero pad `pad`, then VALID, stride 1|2, dilation 1), NHWC / HWIO,
+ * 3x3 convolution (explicit zero pad `pad`, then VALID, stride 1|2; dilation 1 -- dilation 2 is detr_hip_conv3x3_dilated at the
+ * end of this header), NHWC / HWIO,
  * as an implicit GEMM (no im2col buffer):
  *   replaces: ZeroPadding2D + Conv2D(3x3) + FrozenBatchNorm2D + ReLU
  *             detr_tf/networks/resnet_backbone.py:98,104-105,123-126 and its gradients.
@@ -643,6 +644,38 @@ int64_t detr_hip_workspace_bytes_layernorm(const detr_layernorm_desc *d);
  * grid, tiles along M, tiles along N, workgroups, LDS bytes}.  Returns 1 when the shape has a plan, 0 when it has none.  Pure
  * host arithmetic (tests, tuning scripts); `out` may be null. */
 int detr_hip_gemm_ring_plan(int32_t M, int32_t N, int32_t K, int32_t *out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Dilation-2 3x3 convolution, appended (the ABI version and detr_conv3x3_desc are unchanged):
+ *   replaces: ZeroPadding2D(2) + Conv2D(3x3, dilation_rate=2) + FrozenBatchNorm2D + ReLU of the blocks >= 1 of a stage built with
+ *             replace_stride_with_dilation (DETR-DC5), detr_tf/networks/resnet_backbone.py:74-85,98,104-105, and its gradients.
+ * The fields of detr_conv3x3_desc with the same meaning -- modes 0 / 1 / 2, epilogue (alpha, scale, bias, residual, mask, act),
+ * compute 0 / 1 / 2, bf16 storage flags, maskbits_out, split / workspace -- plus `dilation`.  Accepted: dilation == 2, stride == 1,
+ * pad == 2, Ho == Hi, Wo == Wi; anything else is rejected with a message (detr_hip_last_error).  Tap (kh, kw) of output pixel (h, w)
+ * reads input pixel (h - 2 + 2 kh, w - 2 + 2 kw).  bf16 tensors: modes 0 / 1 are one launch that walks the four pixel-parity planes
+ * as dense convolutions (csrc/conv_dilated.hip); mode 2 reduces its row splits through `workspace` in a fixed order.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t N, Hi, Wi, Ci, Ho, Wo, Co, stride, pad;
+    const float *x;
+    const float *w;
+    float *y;
+    float alpha;
+    const float *scale;
+    const float *bias;
+    const float *residual;
+    const float *mask;
+    int32_t act;
+    int32_t split;
+    float *workspace; int64_t workspace_bytes;
+    int32_t compute;
+    int32_t w_dtype;
+    int32_t x_dtype, y_dtype, r_dtype, m_dtype;
+    uint8_t *maskbits_out;
+    int32_t dilation;    /* 2 */
+} detr_conv3x3d_desc;
+int detr_hip_conv3x3_dilated(const detr_conv3x3d_desc *d, int32_t mode, void *stream);
+int64_t detr_hip_workspace_bytes_conv3x3_dilated(const detr_conv3x3d_desc *d, int32_t mode);
 
 #ifdef __cplusplus
 }
