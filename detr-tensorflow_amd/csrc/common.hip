@@ -216,6 +216,17 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_map_match_desc, rec_score)); DETR_PUT(DETR_OFF(detr_map_match_desc, rec_class)); DETR_PUT(DETR_OFF(detr_map_match_desc, rec_flags));
         DETR_PUT(DETR_OFF(detr_map_match_desc, num_gt)); DETR_PUT(DETR_OFF(detr_map_match_desc, status));
         break;
+    case 100:   // detr_detect_desc (appended descriptors count from 100, include/detr_hip.h)
+        DETR_PUT((int32_t)sizeof(detr_detect_desc));
+        DETR_PUT(DETR_OFF(detr_detect_desc, B)); DETR_PUT(DETR_OFF(detr_detect_desc, Q)); DETR_PUT(DETR_OFF(detr_detect_desc, C));
+        DETR_PUT(DETR_OFF(detr_detect_desc, logits)); DETR_PUT(DETR_OFF(detr_detect_desc, sL_b)); DETR_PUT(DETR_OFF(detr_detect_desc, sL_q));
+        DETR_PUT(DETR_OFF(detr_detect_desc, boxes)); DETR_PUT(DETR_OFF(detr_detect_desc, sB_b)); DETR_PUT(DETR_OFF(detr_detect_desc, sB_q));
+        DETR_PUT(DETR_OFF(detr_detect_desc, sizes)); DETR_PUT(DETR_OFF(detr_detect_desc, background_class));
+        DETR_PUT(DETR_OFF(detr_detect_desc, score_threshold)); DETR_PUT(DETR_OFF(detr_detect_desc, max_detections));
+        DETR_PUT(DETR_OFF(detr_detect_desc, bbox_format)); DETR_PUT(DETR_OFF(detr_detect_desc, clip));
+        DETR_PUT(DETR_OFF(detr_detect_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_detect_desc, out_labels));
+        DETR_PUT(DETR_OFF(detr_detect_desc, out_scores)); DETR_PUT(DETR_OFF(detr_detect_desc, out_query)); DETR_PUT(DETR_OFF(detr_detect_desc, counts));
+        break;
     default:
         detr::set_error("struct_layout: unknown struct %d", which);
         return -1;

@@ -6,11 +6,9 @@
 // statistics (score = max probability, label = first arg-max, inference.py:73-75), drops the background queries
 // (:78-83, order preserved like tf.where) by an in-workgroup prefix count, converts the boxes (:86-93, bbox.py:171-196
 // incl. the clip to [0, 1]) and writes the kept detections compacted per image.
-#include "common.h"
+#include "postprocess_score.h"
 
 namespace detr {
-
-constexpr int PP_MAXQ = 1024;
 
 struct PostArgs {
     const float *logits; long long sl_b, sl_q;      // [B, Q, C]
@@ -28,30 +26,7 @@ __global__ __launch_bounds__(256) void postprocess_kernel(PostArgs a) {
     __shared__ int s_wave_cnt[4];
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float *lg = a.logits + b * a.sl_b;
-    for (int q = wave; q < a.Q; q += 4) {
-        const float *row = lg + q * a.sl_q;
-        float mx = -INFINITY;
-        for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, row[c]);
-        mx = wave_max(mx);
-        float s = 0.f;
-        for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
-        s = wave_sum(s);
-        // arg-max of the PROBABILITIES (inference.py:75 takes argmax(softmax)), first occurrence on ties
-        float best = -1.f;
-        int arg = INT_MAX;
-        for (int c = lane; c < a.C; c += 64) {
-            const float p = expf(row[c] - mx) / s;
-            if (p > best) { best = p; arg = c; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64);
-            const int oa = __shfl_xor(arg, o, 64);
-            if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-        }
-        if (lane == 0) { s_score[q] = best; s_label[q] = arg; }
-    }
+    query_scores_labels(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label);      // postprocess_score.h, shared with detect.hip
     __syncthreads();
     // order-preserving compaction: 256 queries per pass
     int base = 0;

@@ -107,6 +107,15 @@ class PostprocessDesc(Structure):
                 ("out_boxes", c_void_p), ("out_labels", c_void_p), ("out_scores", c_void_p), ("counts", c_void_p)]
 
 
+class DetectDesc(Structure):
+    _fields_ = [("B", c_int32), ("Q", c_int32), ("C", c_int32),
+                ("logits", c_void_p), ("sL_b", c_int64), ("sL_q", c_int64),
+                ("boxes", c_void_p), ("sB_b", c_int64), ("sB_q", c_int64),
+                ("sizes", c_void_p), ("background_class", c_int32), ("score_threshold", c_float), ("max_detections", c_int32),
+                ("bbox_format", c_int32), ("clip", c_int32),
+                ("out_boxes", c_void_p), ("out_labels", c_void_p), ("out_scores", c_void_p), ("out_query", c_void_p), ("counts", c_void_p)]
+
+
 MAP_MAX_THR = 16                                                               # DETR_MAP_MAX_THR
 MAP_BAD = {1: "a predicted label outside [0, nb_class)", 2: "a target class outside [0, nb_class)",
            4: "a target header count outside [0, R-1]", 8: "a detection count outside [0, Q]"}      # DETR_MAP_BAD_*
@@ -197,6 +206,7 @@ _SIGNATURES = {
     "detr_hip_global_clip_scale_f32": [f32p, c_void_p, c_void_p, f32p, c_int32, f32p, c_void_p],
     "detr_hip_adamw_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, f32p, c_int32, c_int32, c_void_p],
     "detr_hip_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32, c_void_p],
+    "detr_hip_detect": [POINTER(DetectDesc), c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
@@ -215,6 +225,8 @@ ABI_VERSION = 9
 # order of detr_hip_struct_layout's `which`
 LAYOUT_STRUCTS = (ReduceDesc, GemmDesc, Conv3x3Desc, StemDesc, LayerNormDesc, AttnDesc, SetLossDesc, InputDesc, PostprocessDesc,
                   MapMatchDesc)
+# descriptors appended after ABI 9: `which` -> mirror (numbered from 100, include/detr_hip.h)
+APPENDED_LAYOUT_STRUCTS = {100: DetectDesc}
 
 _lib = None
 
@@ -449,7 +461,7 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in enumerate(LAYOUT_STRUCTS):
+    for which, S in list(enumerate(LAYOUT_STRUCTS)) + sorted(APPENDED_LAYOUT_STRUCTS.items()):
         want = struct_layout_mirror(S)
         buf = (c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)

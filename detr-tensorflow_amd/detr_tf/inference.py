@@ -5,14 +5,22 @@ element 0 only).  `get_model_inference_batched` is the same for EVERY image of t
 `detr_hip_postprocess` (csrc/postprocess.hip): softmax score / arg-max label per query, background queries dropped with the
 order preserved, boxes converted (xyxy / yxyx clipped to [0, 1] like bbox.py:171-183).  CUDA inputs only -- there is no
 eager fallback; tensors on the CPU are moved to the model's device first by the caller.
-"""
-from ctypes import byref
 
+`detect_batched` goes the rest of the way to what a user draws (webcam_inference.py:26-34, eval.py:41-55), in one launch of
+`detr_hip_detect` (csrc/detect.hip): score threshold, detections sorted by score with a top-k cap, boxes in PIXELS of each image's
+own original size.  `Detector` wraps the whole chain: raw uint8 images -> input stage -> model -> `detect_batched`.
+"""
+import math
+from ctypes import byref
+from typing import NamedTuple
+
+import numpy as np
 import torch
 
 from . import _hip as hip
 
 BBOX_FORMATS = {"xy_center": 0, "xyxy": 1, "yxyx": 2}
+DETECT_FORMATS = {"xy_center": 0, "xyxy": 1, "yxyx": 2, "xywh": 3}       # xywh: top-left + width / height, the COCO results form
 
 
 def _post(logits, boxes, background_class, bbox_format):
@@ -56,18 +64,188 @@ def get_model_inference(m_outputs: dict, background_class, bbox_format="xy_cente
     return out_b[0, :k], out_l[0, :k], out_s[0, :k]
 
 
+def _feature_maps(model, image_shape, attn):
+    """Attention maps [B, T, S] -> [B, T, Hf, Wf] over the feature map of a [B, H, W, 3] input (a decoder self-attention map, whose
+    keys are the object queries, stays [B, Q, Q])."""
+    from .engine import feature_size
+    Hf, Wf = feature_size(int(image_shape[1]), int(image_shape[2]), model.engine.dilate)
+    maps = {}
+    for name, w in attn.items():
+        B, T, S = w.shape
+        maps[name] = w if "/decoder/" in name and name.endswith("/self_attn") else w.reshape(B, T, Hf, Wf)
+    return maps
+
+
 def get_attention_maps(model, images, need_weights=True):
     """(m_outputs, maps): one evaluation forward with `need_weights` (DetrModel.__call__: True = last encoder self-attention and last
     decoder cross-attention, or an iterable of site names), every map [B, T, S] reshaped to [B, T, Hf, Wf] over the Hf x Wf feature map
     (engine.feature_size of the input) -- the shape a user overlays on the image.  Encoder maps and decoder cross-attention maps have
     S = Hf * Wf keys; a decoder self-attention map (keys = object queries) is returned as [B, Q, Q].  `images` may be the
     (images, masks) pair of a padded batch: the map is then zero on the padded feature positions."""
-    from .engine import feature_size
     m_outputs = model(images, training=False, need_weights=need_weights)
     imgs = images[0] if isinstance(images, (tuple, list)) else images
-    Hf, Wf = feature_size(int(imgs.shape[1]), int(imgs.shape[2]), model.engine.dilate)
-    maps = {}
-    for name, w in m_outputs["attn"].items():
-        B, T, S = w.shape
-        maps[name] = w if "/decoder/" in name and name.endswith("/self_attn") else w.reshape(B, T, Hf, Wf)
-    return m_outputs, maps
+    return m_outputs, _feature_maps(model, imgs.shape, m_outputs["attn"])
+
+
+class Detections(NamedTuple):
+    """The detections of ONE image, best first: boxes [k, 4] float32 in pixels, labels [k] int64, scores [k] float32 and
+    query [k] int32, the object query each came from (the row of a decoder attention map)."""
+    boxes: torch.Tensor
+    labels: torch.Tensor
+    scores: torch.Tensor
+    query: torch.Tensor
+
+
+def _check_detect_args(bbox_format, score_threshold, max_detections, Q=None):
+    if bbox_format not in DETECT_FORMATS:
+        raise RuntimeError(f"detect: unknown bbox_format {bbox_format!r}, expected one of {tuple(DETECT_FORMATS)}")
+    if not math.isfinite(float(score_threshold)):
+        raise RuntimeError(f"detect: score_threshold={score_threshold} is not finite")
+    if max_detections is not None and (int(max_detections) < 1 or (Q is not None and int(max_detections) > Q)):
+        raise RuntimeError(f"detect: max_detections={max_detections} must be in 1..Q" + ("" if Q is None else f"={Q} (the number of queries)"))
+
+
+def _detect(logits, boxes, sizes, background_class, score_threshold, max_detections, bbox_format, clip):
+    if logits.dim() != 3 or boxes.dim() != 3 or boxes.shape[-1] != 4 or tuple(boxes.shape[:2]) != tuple(logits.shape[:2]):
+        raise RuntimeError(f"detect: expected pred_logits [B, Q, C] and pred_boxes [B, Q, 4], got {tuple(logits.shape)} and {tuple(boxes.shape)}")
+    B, Q, C = logits.shape
+    _check_detect_args(bbox_format, score_threshold, max_detections, Q)
+    K = Q if max_detections is None else int(max_detections)
+    if not (logits.is_cuda and boxes.is_cuda):
+        raise RuntimeError("detect_batched: the outputs must live on the GPU (the post-processing is a HIP kernel; no CPU fallback)")
+    logits, boxes = logits.float(), boxes.float()
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    if boxes.stride(-1) != 1:
+        boxes = boxes.contiguous()
+    dev = logits.device
+    sizes = torch.as_tensor(sizes).to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(sizes.shape) != (B, 2):
+        raise RuntimeError(f"detect: sizes must be [B, 2] = (height, width) of every image, got {tuple(sizes.shape)} for B={B}")
+    out_b = torch.empty(B, K, 4, dtype=torch.float32, device=dev)         # the kernel writes every row: detections, then zeros
+    out_l = torch.empty(B, K, dtype=torch.int64, device=dev)
+    out_s = torch.empty(B, K, dtype=torch.float32, device=dev)
+    out_q = torch.empty(B, K, dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    d = hip.DetectDesc()
+    d.B, d.Q, d.C = B, Q, C
+    d.logits, d.sL_b, d.sL_q = logits.data_ptr(), logits.stride(0), logits.stride(1)
+    d.boxes, d.sB_b, d.sB_q = boxes.data_ptr(), boxes.stride(0), boxes.stride(1)
+    d.sizes, d.background_class, d.score_threshold = sizes.data_ptr(), int(background_class), float(score_threshold)
+    d.max_detections, d.bbox_format, d.clip = K, DETECT_FORMATS[bbox_format], int(bool(clip))
+    d.out_boxes, d.out_labels, d.out_scores, d.out_query, d.counts = (out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), out_q.data_ptr(),
+                                                                      counts.data_ptr())
+    hip._check(hip.load().detr_hip_detect(byref(d), hip._stream()), "detr_hip_detect")
+    return out_b, out_l, out_s, out_q, counts
+
+
+def detect_batched(m_outputs: dict, sizes, background_class, *, score_threshold=0.0, max_detections=None, bbox_format="xyxy", clip=True):
+    """[Detections] for every image of the batch, in pixels.  `sizes` [B, 2] = (height, width) of every ORIGINAL image (host
+    array or device tensor): the model's boxes are normalised to the image's own extent -- in a padded batch too, where the canvas
+    is larger --, so that is what they are scaled by.  A query is kept when its label is not `background_class` and its score
+    (max softmax probability, exactly get_model_inference's) is >= score_threshold; the kept ones are sorted by descending score
+    (ties: lower query index first) and cut to max_detections (None: all Q).  bbox_format: "xy_center" (cx, cy, w, h), "xyxy",
+    "yxyx" or "xywh" (top-left + width / height); clip clamps the corners of the last three to the image.  One launch of
+    detr_hip_detect and ONE host synchronisation (the per-image counts).  CUDA inputs only."""
+    out_b, out_l, out_s, out_q, counts = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, background_class,
+                                                 score_threshold, max_detections, bbox_format, clip)
+    return [Detections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k]) for b, k in enumerate(counts.tolist())]
+
+
+class Detector:
+    """Raw images in, pixel-space detections out (what the reference's webcam_inference.py:26-34 and eval.py:41-55 assemble by hand).
+
+        detector = Detector(model, config, score_threshold=0.7)
+        detections = detector([image_a, image_b])            # uint8 [h, w, 3] arrays of any, mixed sizes
+        for box, label, score in zip(detections[0].boxes.tolist(), detections[0].labels.tolist(), detections[0].scores.tolist()): ...
+
+    resize="shortest_side" (the DETR evaluation rule): every image keeps its aspect ratio -- transformation.eval_record, the record
+    the loaders' "shortest_side" mode draws: shortest side `shortest_side`, longest side <= max_size --, the batch is padded
+    (DeviceInputStage.augmented_padded) and the model runs on the (images, masks) pair.  `canvas` = (H, W) fixes the padded shape,
+    so that the model's captured evaluation graph keeps replaying from call to call; None sizes it per call.
+    resize="fixed" (the reference's path): every image is resized to config.image_size (DeviceInputStage.images); the images of one
+    call must then have one size.
+    The boxes come back in pixels of each ORIGINAL image whichever way it was resized.  The remaining arguments are
+    detect_batched's; background_class defaults to config.background_class."""
+
+    RESIZE_MODES = ("shortest_side", "fixed")
+
+    def __init__(self, model, config, *, background_class=None, score_threshold=0.7, max_detections=100, bbox_format="xyxy",
+                 resize="shortest_side", shortest_side=800, max_size=1333, canvas=None, interpolation="cubic"):
+        from .data import processing, transformation
+        if resize not in self.RESIZE_MODES:
+            raise ValueError(f"Detector: resize must be one of {self.RESIZE_MODES}, got {resize!r}")
+        names = transformation.INTERP_NAMES if resize == "shortest_side" else tuple(processing.INTERPOLATIONS)
+        if interpolation not in names:
+            raise ValueError(f"Detector: interpolation must be one of {names} with resize={resize!r}, got {interpolation!r}")
+        _check_detect_args(bbox_format, score_threshold, max_detections)
+        if background_class is None:
+            background_class = getattr(config, "background_class", None)
+        if background_class is None:
+            raise ValueError("Detector: background_class is not given and config.background_class is not set")
+        if int(shortest_side) < 1 or (max_size is not None and int(max_size) < 1):
+            raise ValueError(f"Detector: bad shortest_side={shortest_side} / max_size={max_size}")
+        self.model, self.config = model, config
+        self.background_class, self.score_threshold, self.max_detections = int(background_class), float(score_threshold), int(max_detections)
+        self.bbox_format, self.resize, self.interpolation = bbox_format, resize, interpolation
+        self.shortest_side, self.max_size = int(shortest_side), None if max_size is None else int(max_size)
+        self.canvas = None if canvas is None else (int(canvas[0]), int(canvas[1]))
+        self._stage = None
+
+    def stage(self):
+        if self._stage is None:
+            from .data.processing import DeviceInputStage
+            self._stage = DeviceInputStage(self.config, device=self.model.device,
+                                           interpolation=self.interpolation if self.resize == "fixed" else "cubic")
+        return self._stage
+
+    def records(self, images):
+        """The evaluation PaddedRecord of every image (resize="shortest_side")."""
+        from .data import transformation as T
+        interp = T.INTERP_NAMES.index(self.interpolation)
+        return [T.eval_record(im.shape[0], im.shape[1], self.shortest_side, self.max_size, interp) for im in images]
+
+    def __call__(self, images, need_weights=None):
+        """images: one uint8 [h, w, 3] array -> Detections, or a list of them -> [Detections].  With need_weights (DetrModel.__call__)
+        the result is (detections, maps), maps as get_attention_maps returns them."""
+        single = not isinstance(images, (list, tuple))
+        srcs = [np.asarray(im) for im in ([images] if single else images)]
+        if not srcs or any(s.dtype != np.uint8 or s.ndim != 3 or s.shape[-1] != 3 for s in srcs):
+            raise TypeError("Detector expects a uint8 image [h, w, 3] or a non-empty list of them")
+        sizes = np.array([s.shape[:2] for s in srcs], np.int32)
+        if self.resize == "fixed":
+            if (sizes != sizes[0]).any():
+                raise ValueError(f"Detector: resize='fixed' takes images of ONE size per call, got {sorted(set(map(tuple, sizes.tolist())))}; "
+                                 "resize='shortest_side' batches mixed sizes")
+            inputs = self.stage().images(np.stack(srcs))
+            shape = inputs.shape
+        else:
+            inputs = self.stage().augmented_padded(srcs, self.records(srcs), canvas=self.canvas)
+            shape = inputs[0].shape
+        m_outputs = self.model(inputs, training=False, need_weights=need_weights)
+        detections = detect_batched(m_outputs, sizes, self.background_class, score_threshold=self.score_threshold,
+                                    max_detections=self.max_detections, bbox_format=self.bbox_format)
+        detections = detections[0] if single else detections
+        if "attn" in m_outputs:
+            return detections, _feature_maps(self.model, shape, m_outputs["attn"])
+        return detections
+
+    def to_coco_results(self, detections, image_ids, category_ids=None):
+        """COCO results records [{"image_id", "category_id", "bbox": [x, y, w, h], "score"}] (Python numbers) of the detections
+        of the images `image_ids`; needs bbox_format="xywh".  category_ids maps a label to its COCO category id (a dict or a
+        sequence indexed by label; None: the label itself).  One copy to the host for the whole list."""
+        if self.bbox_format != "xywh":
+            raise ValueError(f"to_coco_results: COCO boxes are [x, y, w, h]: build the Detector with bbox_format='xywh', not {self.bbox_format!r}")
+        if isinstance(detections, Detections):
+            detections, image_ids = [detections], [image_ids]
+        if len(detections) != len(image_ids):
+            raise ValueError(f"to_coco_results: {len(detections)} images of detections, {len(image_ids)} image ids")
+        if not detections:
+            return []
+        boxes = torch.cat([d.boxes.reshape(-1, 4) for d in detections]).cpu().tolist()
+        labels = torch.cat([d.labels for d in detections]).cpu().tolist()
+        scores = torch.cat([d.scores for d in detections]).cpu().tolist()
+        owner = [image_id for image_id, d in zip(image_ids, detections) for _ in range(int(d.scores.shape[0]))]
+        return [{"image_id": image_id, "category_id": label if category_ids is None else category_ids[label],
+                 "bbox": [float(v) for v in box], "score": float(score)}
+                for image_id, box, label, score in zip(owner, boxes, labels, scores)]

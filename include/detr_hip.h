@@ -39,7 +39,8 @@ int detr_hip_reload_tuning(void);
 /* ABI self-check for hand-written mirrors of the descriptor structs below (ctypes / cgo / JNI): for struct `which`
  * (0 detr_reduce_desc, 1 detr_gemm_desc, 2 detr_conv3x3_desc, 3 detr_stem_desc, 4 detr_layernorm_desc, 5 detr_attn_desc,
  * 6 detr_setloss_desc, 7 detr_input_desc, 8 detr_postprocess_desc, 9 detr_map_match_desc) writes out[0] = sizeof, out[1..] = offsetof of every field in
- * declaration order, and returns the number of values (negative: unknown struct). */
+ * declaration order, and returns the number of values (negative: unknown struct).  Descriptors appended after ABI 9 are numbered
+ * from 100 (100 detr_detect_desc): binders probe the id behind the last one they know to find the end of the first list. */
 int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap);
 /* zero fill of accumulators (an ordinary kernel: a captured hipMemsetAsync node did not replay reliably) */
 int detr_hip_memset_zero(void *ptr, size_t bytes, void *stream);
@@ -676,6 +677,41 @@ typedef struct {
 } detr_conv3x3d_desc;
 int detr_hip_conv3x3_dilated(const detr_conv3x3d_desc *d, int32_t mode, void *stream);
 int64_t detr_hip_workspace_bytes_conv3x3_dilated(const detr_conv3x3d_desc *d, int32_t mode);
+
+/* ---------------------------------------------------------------------------------------------
+ * Detections in pixel space, appended (the ABI version is unchanged):
+ *   replaces: get_model_inference (detr_tf/inference.py:68-95) + the host-side numpy rescale of bbox.py:230-294 + the score
+ *             threshold / ordering every caller adds (webcam_inference.py:26-34, eval.py:41-55).
+ * One launch per batch, one workgroup per image (csrc/detect.hip), Q <= 1024.  Per query score = max softmax probability and
+ * label = first arg-max, the very code of detr_hip_postprocess (bit-identical).  A query is kept when
+ * label != background_class and score >= score_threshold; the kept queries are ordered by descending score, ties by ascending
+ * query index (np.argsort(-score, kind="stable")), and cut to max_detections.  Boxes: (cx, cy, w, h) * (W_b, H_b, W_b, H_b) with
+ * sizes[b] = (H_b, W_b) the ORIGINAL size of image b (the boxes of a padded batch are normalised per image, not per canvas), then
+ *   bbox_format 0 "xy_center": cx, cy, w, h        (never clipped)
+ *               1 "xyxy":      x0, y0, x1, y1      corners cx -+ w / 2, cy -+ h / 2
+ *               2 "yxyx":      y0, x0, y1, x1
+ *               3 "xywh":      x0, y0, x1 - x0, y1 - y0   (top-left + extent: the COCO results form)
+ * clip = 1 clamps the corners of formats 1..3 to [0, W_b] x [0, H_b] (format 3 takes its extent from the clamped corners).
+ * Outputs for image b at rows [b * max_detections, (b + 1) * max_detections): counts[b] detections, then zeros.  out_query is the
+ * source query index (the row of an attention map).  No atomics: a rerun is bit-identical.  out_boxes 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t B, Q, C;
+    const float *logits; int64_t sL_b, sL_q;     /* [B, Q, C], unit class stride */
+    const float *boxes;  int64_t sB_b, sB_q;     /* [B, Q, 4] cx, cy, w, h in [0, 1] */
+    const int32_t *sizes;                        /* [B, 2] (height, width), DEVICE memory */
+    int32_t background_class;
+    float score_threshold;                       /* finite */
+    int32_t max_detections;                      /* 1..Q */
+    int32_t bbox_format;                         /* 0..3, above */
+    int32_t clip;                                /* 0 | 1 */
+    float *out_boxes;                            /* [B, max_detections, 4] */
+    int64_t *out_labels;                         /* [B, max_detections] */
+    float *out_scores;                           /* [B, max_detections] */
+    int32_t *out_query;                          /* [B, max_detections] */
+    int32_t *counts;                             /* [B] */
+} detr_detect_desc;
+int detr_hip_detect(const detr_detect_desc *d, void *stream);
 
 #ifdef __cplusplus
 }
