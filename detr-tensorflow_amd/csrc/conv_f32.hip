@@ -1436,7 +1436,8 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
         a.Cd <= 512 && (!d->mask || e.m16) && !d->residual && !d->scale && d->alpha == 1.0f && (d->act == 0 || d->act == 1) &&
         tune(T_CONV_HALO) != 2) {
         if (a.Cd >= 128 && a.Cd % 128 == 0 && tune(T_CONV_DMA) != 2 && tune(T_CONV_HALO) != 4) { if (launch_conv_halo_dma(a, dgrad, s)) return -1; }
-        else if (a.Cd >= 128) { if (launch_conv_halo<128>(a, dgrad, s)) return -1; }
+        // (the halo epilogue has no column guard: a 128-channel tile needs Cd % 128 == 0; 192 / 320 / 448 channels take 64-channel tiles)
+        else if (a.Cd % 128 == 0) { if (launch_conv_halo<128>(a, dgrad, s)) return -1; }
         else if (launch_conv_halo<64>(a, dgrad, s)) return -1;
         DETR_LAUNCH_CHECK("conv3x3 (halo)");
         return 0;
@@ -1475,7 +1476,7 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
                               a.Cd <= 512 && (!d->mask || e.m16) && !d->residual && !d->scale && !d->bias && d->alpha == 1.0f &&
                               d->act == 0 && tune(T_DGRAD_S2_CLASSES) != 3 && tune(T_CONV_HALO) != 2;
         if (halo_cls) {
-            if (a.Cd >= 128) { if (launch_conv_halo_s2classes<128>(a, s)) return -1; }
+            if (a.Cd % 128 == 0) { if (launch_conv_halo_s2classes<128>(a, s)) return -1; }
             else if (launch_conv_halo_s2classes<64>(a, s)) return -1;
             DETR_LAUNCH_CHECK("conv3x3 (halo, stride-2 classes)");
             return 0;

@@ -358,6 +358,7 @@ __global__ __launch_bounds__(GEMM_THREADS, TH == 8 ? 2 : 3) void conv3x3_halo_bf
 template <int BN, int TH>
 static int launch_conv_halo_t(const ConvArgs &a0, bool dgrad, hipStream_t s) {
     ConvArgs a = a0;
+    DETR_REQUIRE(a.Cd % BN == 0, "conv3x3 (halo): %d output channels are not whole %d-channel tiles (the epilogue has no column guard)", a.Cd, BN);
     a.Hp = cdiv(a.Hd, TH);
     a.Wp = cdiv(a.Wd, CH_TW);
     a.tiles_m = a.N * a.Hp * a.Wp;
@@ -394,6 +395,7 @@ template <int BN>
 static int launch_conv_halo_s2classes(const ConvArgs &a0, hipStream_t s) {
     constexpr int TH = 4;
     ConvArgs a = a0;
+    DETR_REQUIRE(a.Cd % BN == 0, "conv3x3 (halo, stride-2 classes): %d output channels are not whole %d-channel tiles", a.Cd, BN);
     a.tiles_n = cdiv(a.Cd, BN);
     halo_class_plan(a, TH);
     if (a.cls_off[4] <= 0) return 0;
