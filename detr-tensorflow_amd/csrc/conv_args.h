@@ -1,4 +1,5 @@
-// conv_args.h -- argument structs of the 3x3 convolution kernels (conv_f32.hip, conv_halo.h, conv_halo_dma.h, conv_dilated.hip)
+// conv_args.h -- argument structs of the 3x3 convolution kernels (conv_f32.hip, conv_x3.h, conv_halo.h, conv_halo_dma.h) and the
+// dilation-2 launches conv_dilated.hip makes through conv_f32.hip
 #pragma once
 #include "gemm_core.h"
 
@@ -53,6 +54,7 @@ struct ConvWgradArgs {
 // dilation-2 launches of the tile bodies (defined in conv_f32.hip next to the kernels, called by conv_dilated.hip)
 void conv_dilated_tiles(const ConvArgs &a, bool dgrad, int compute, hipStream_t s);
 void conv_dilated_wgrad_tiles(const ConvWgradArgs &a, int compute, int split, float *ws, long long ws_bytes, hipStream_t s);
-int conv_dilated_wgrad_splits(int M, int Ci, int Co, int compute, int split);
+// row splits of that launch for an N x H x W map, from the same plan (the scratch-size query)
+int conv_dilated_wgrad_splits(int N, int H, int W, int Ci, int Co, int compute, int split);
 
 }  // namespace detr

@@ -23,7 +23,7 @@ using namespace detr;
 extern "C" int64_t detr_hip_workspace_bytes_conv3x3_dilated(const detr_conv3x3d_desc *d, int32_t mode) {
     if (!d || d->N <= 0 || d->Ci <= 0 || d->Co <= 0 || d->dilation != 2 || d->stride != 1 || d->pad != 2 || d->Ho != d->Hi || d->Wo != d->Wi) return -1;
     if (mode != 2) return 0;                       // forward / input gradient: no scratch
-    const int split = conv_dilated_wgrad_splits(d->N * d->Ho * d->Wo, d->Ci, d->Co, d->compute, d->split);
+    const int split = conv_dilated_wgrad_splits(d->N, d->Ho, d->Wo, d->Ci, d->Co, d->compute, d->split);
     return split > 1 ? (int64_t)split * 9LL * d->Ci * d->Co * 4 : 0;
 }
 

@@ -1,8 +1,8 @@
 // conv_f32.hip -- ResNet backbone convolution kernels (NHWC / HWIO, fp32) for gfx950:
-//   * 3x3 implicit-GEMM convolution forward / dgrad / wgrad on the MFMA tile engine
-//     (no im2col buffer: the A-operand loader gathers input pixels, zero-filling the halo);
-//   * stem helpers: 3x3/s2 max pool over the zero-padded map + its backward, stride-2 subsample gather/scatter
-//     (the 7x7 stem convolution itself is stem_conv.hip).
+//   3x3 implicit-GEMM convolution forward / dgrad / wgrad on the MFMA tile engine (no im2col buffer: the A-operand loader
+//   gathers input pixels, zero-filling the halo; the f32x3 forms are conv_x3.h), the fused nine-tap bf16
+//   weight gradient, and the dispatch of detr_hip_conv3x3_f32 (halo-staged kernels: conv_halo.h, conv_halo_dma.h).
+//   The 7x7 stem convolution is stem_conv.hip, max pooling and the stride-2 subsample are pool.hip.
 // Reference: detr_tf/networks/resnet_backbone.py:11-32,98-137 (see include/detr_hip.h).
 #include "gemm_core.h"
 #include "gemm_bf16_core.h"
@@ -10,17 +10,6 @@
 #include "conv_halo.h"
 #include "conv_halo_dma.h"
 namespace detr {
-
-// tap (kh, kw) of K-tile group t (t-th tap of the launch)
-__device__ __forceinline__ void conv_tap(const ConvArgs &a, int t, int &kh, int &kw) {
-    if (a.par_on) {
-        kh = a.kh0 + 2 * (t / a.ntw);
-        kw = a.kw0 + 2 * (t - (t / a.ntw) * a.ntw);
-    } else {
-        kh = t / 3;
-        kw = t - kh * 3;
-    }
-}
 
 // DIL: pixel step of the taps (2: the dilated entry point, conv_dilated.hip)
 template <int BM, bool DGRAD, int DIL = 1>
@@ -57,12 +46,6 @@ struct LoaderConvA {
         }
     }
     // halo / stride-parity / tile-edge lanes take the out-of-range offset: the descriptor returns zeros, no branch
-    __device__ __forceinline__ void load(const ConvArgs &a, int kt, int cpt, float4 (&r)[NV]) const {
-        const int tap = kt / cpt;
-        int kh, kw;
-        conv_tap(a, tap, kh, kw);
-        load_tap(a, kh, kw, kt - tap * cpt, r);
-    }
     // tap (kh, kw) and channel tile kc given by the caller (running counters in the main loop instead of divisions)
     __device__ __forceinline__ void load_tap(const ConvArgs &a, int kh, int kw, int kc, float4 (&r)[NV]) const {
         const int c0 = kc * GEMM_BK + kq;
@@ -137,8 +120,8 @@ __global__ __launch_bounds__(GEMM_THREADS) void conv3x3_kernel(ConvArgs a) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
     float4 ra[LoaderConvA<BM, DGRAD, DIL>::NV], rb[LB::NV];
-    // K tiles are requested strictly in order: tap and channel tile are running counters (the kt / cpt and conv_tap()
-    // divisions cost ~40 scalar instructions per 16-deep K tile)
+    // K tiles are requested strictly in order: tap and channel tile are running counters (a kt / cpt division and a tap
+    // decode cost ~40 scalar instructions per 16-deep K tile)
     const int tap_cols = a.par_on ? a.ntw : 3;
     int it_kc = 0, it_ti = 0, it_tj = 0;
     auto load_ab = [&]() {
@@ -354,14 +337,8 @@ struct LoaderConvAb {
     }
     // halo / stride-parity / tile-edge lanes take the out-of-range offset: the descriptor returns zeros, no branch
     // live = false: a request past the last K tile (operand pipeline tail) -- every lane takes the out-of-range offset
-    __device__ __forceinline__ void load(const ConvArgs &a, int kt, int cpt, Reg (&r)[NV], bool live = true) const {
-        const int tap = kt / cpt;
-        int kh, kw;
-        conv_tap(a, tap, kh, kw);
-        load_tap(a, kh, kw, kt - tap * cpt, r, live);
-    }
-    // the same with the tap (kh, kw) and the channel tile kc inside the tap given by the caller (the main loop keeps them
-    // as running counters: the divisions of load() are ~40 scalar instructions per K tile, more than the tile's MFMAs)
+    // the tap (kh, kw) and the channel tile kc inside the tap are given by the caller (the main loop keeps them as running
+    // counters: dividing kt by the tiles per tap is ~40 scalar instructions per K tile, more than the tile's MFMAs)
     __device__ __forceinline__ void load_tap(const ConvArgs &a, int kh, int kw, int kc, Reg (&r)[NV], bool live = true) const {
         const int c0 = kc * BF_BK + kq;
 #pragma unroll
@@ -438,7 +415,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (BM * BN >= 128 * 128) ? 3 : (BM * BN
     typename LAc::Reg ra0[LAc::NV], ra1[LAc::NV];
     typename LB::Reg rb0[NRB], rb1[NRB];
     // K tiles are requested strictly in order (0, 1, 2, then kt + 3 per iteration): the tap and the channel tile inside it
-    // are running counters instead of kt / cpt and conv_tap()'s divisions
+    // are running counters instead of divisions of kt
     const int tap_cols = a.par_on ? a.ntw : 3;
     int it_kc = 0, it_ti = 0, it_tj = 0;
     auto load_ab = [&](int kt, typename LAc::Reg (&ra)[LAc::NV], typename LB::Reg (&rb)[NRB]) {
@@ -794,333 +771,53 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv3x3_wgrad_fused_bf16_kern
 }
 
 // ------------------------------------------------------------------------------------------------
-// stem / pooling / subsample elementwise kernels
+// launchers
 // ------------------------------------------------------------------------------------------------
-__global__ void maxpool_fwd_kernel(const float *__restrict__ x, float *__restrict__ y, uint8_t *__restrict__ amax,
-                                   int N, int H, int W, int C, int Ho, int Wo, long long total) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C);
-        long long t = idx / C;
-        const int wo = (int)(t % Wo);
-        t /= Wo;
-        const int ho = (int)(t % Ho);
-        const int n = (int)(t / Ho);
-        float best = -INFINITY;
-        int bi = 0;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int hi = 2 * ho - 1 + kh, wi = 2 * wo - 1 + kw;
-                float v = 0.0f;  // the explicit ZeroPadding2D(1) takes part in the max
-                if (hi >= 0 && wi >= 0 && hi < H && wi < W) v = x[(((long long)n * H + hi) * W + wi) * C + c];
-                if (v > best) {
-                    best = v;
-                    bi = kh * 3 + kw;
-                }
-            }
-        y[idx] = best;
-        amax[idx] = (uint8_t)bi;
-    }
-}
+typedef void (*ConvKernel)(ConvArgs);
+typedef void (*WgradKernel)(ConvWgradArgs);
 
-// dx[n,h,w,c] = (x > 0) * sum over the (<= 4) pooling windows that contain (h,w) and selected it.
-// Four channels per thread: float4 x / dy / dx accesses, one 32-bit load of the four argmax bytes.
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float *__restrict__ dy, const uint8_t *__restrict__ amax,
-                                                          const float *__restrict__ x, float *__restrict__ dx, int N, int H,
-                                                          int W, int C, int Ho, int Wo, long long total4) {
-    const int C4 = C >> 2;
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total4;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % C4);
-        const unsigned pix = (unsigned)(idx / C4);
-        const int w = (int)(pix % (unsigned)W);
-        const unsigned t = pix / (unsigned)W;
-        const int h = (int)(t % (unsigned)H);
-        const int n = (int)(t / (unsigned)H);
-        const float4 xv = reinterpret_cast<const float4 *>(x)[idx];
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int th = h + 1 - kh;
-            if (th < 0 || (th & 1)) continue;
-            const int ho = th >> 1;
-            if (ho >= Ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int tw = w + 1 - kw;
-                if (tw < 0 || (tw & 1)) continue;
-                const int wo = tw >> 1;
-                if (wo >= Wo) continue;
-                const long long o4 = ((long long)(n * Ho + ho) * Wo + wo) * C4 + c4;
-                const uint32_t am = reinterpret_cast<const uint32_t *>(amax)[o4];
-                const float4 d = reinterpret_cast<const float4 *>(dy)[o4];
-                const uint32_t tap = (uint32_t)(kh * 3 + kw);
-                if ((am & 0xFFu) == tap) g.x += d.x;
-                if (((am >> 8) & 0xFFu) == tap) g.y += d.y;
-                if (((am >> 16) & 0xFFu) == tap) g.z += d.z;
-                if ((am >> 24) == tap) g.w += d.w;
-            }
-        }
-        g.x = xv.x > 0.0f ? g.x : 0.0f;
-        g.y = xv.y > 0.0f ? g.y : 0.0f;
-        g.z = xv.z > 0.0f ? g.z : 0.0f;
-        g.w = xv.w > 0.0f ? g.w : 0.0f;
-        reinterpret_cast<float4 *>(dx)[idx] = g;
-    }
-}
-
-// bf16-storage twins of the two pooling kernels (4 channels = 8 bytes per thread)
-__device__ __forceinline__ float4 bf4_to_f4(uint2 v) {
-    return make_float4(bf16_bits_to_f32(v.x & 0xFFFFu), bf16_bits_to_f32(v.x >> 16), bf16_bits_to_f32(v.y & 0xFFFFu), bf16_bits_to_f32(v.y >> 16));
-}
-__global__ __launch_bounds__(256) void maxpool_fwd_bf16_kernel(const uint2 *__restrict__ x, uint2 *__restrict__ y,
-                                                               uint32_t *__restrict__ amax, int N, int H, int W, int C4,
-                                                               int Ho, int Wo, long long total4) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total4;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % C4);
-        const unsigned pix = (unsigned)(idx / C4);
-        const int wo = (int)(pix % (unsigned)Wo);
-        const unsigned t = pix / (unsigned)Wo;
-        const int ho = (int)(t % (unsigned)Ho);
-        const int n = (int)(t / (unsigned)Ho);
-        float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        uint32_t bi[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int hi = 2 * ho - 1 + kh, wi = 2 * wo - 1 + kw;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);   // the explicit ZeroPadding2D(1) takes part in the max
-                if (hi >= 0 && wi >= 0 && hi < H && wi < W) v = bf4_to_f4(x[((long long)(n * H + hi) * W + wi) * C4 + c4]);
-                const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (vv[e] > best[e]) { best[e] = vv[e]; bi[e] = (uint32_t)(kh * 3 + kw); }
-            }
-        y[idx] = make_uint2(f32_to_bf16_pair(best[0], best[1]), f32_to_bf16_pair(best[2], best[3]));   // exact: inputs are bf16
-        amax[idx] = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
-    }
-}
-
-__global__ __launch_bounds__(256) void maxpool_bwd_bf16_kernel(const uint2 *__restrict__ dy, const uint32_t *__restrict__ amax,
-                                                               const uint2 *__restrict__ x, uint2 *__restrict__ dx, int N, int H,
-                                                               int W, int C4, int Ho, int Wo, long long total4) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total4;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % C4);
-        const unsigned pix = (unsigned)(idx / C4);
-        const int w = (int)(pix % (unsigned)W);
-        const unsigned t = pix / (unsigned)W;
-        const int h = (int)(t % (unsigned)H);
-        const int n = (int)(t / (unsigned)H);
-        const float4 xv = bf4_to_f4(x[idx]);
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int th = h + 1 - kh;
-            if (th < 0 || (th & 1)) continue;
-            const int ho = th >> 1;
-            if (ho >= Ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int tw = w + 1 - kw;
-                if (tw < 0 || (tw & 1)) continue;
-                const int wo = tw >> 1;
-                if (wo >= Wo) continue;
-                const long long o4 = ((long long)(n * Ho + ho) * Wo + wo) * C4 + c4;
-                const uint32_t am = amax[o4];
-                const float4 d = bf4_to_f4(dy[o4]);
-                const uint32_t tap = (uint32_t)(kh * 3 + kw);
-                if ((am & 0xFFu) == tap) g.x += d.x;
-                if (((am >> 8) & 0xFFu) == tap) g.y += d.y;
-                if (((am >> 16) & 0xFFu) == tap) g.z += d.z;
-                if ((am >> 24) == tap) g.w += d.w;
-            }
-        }
-        g.x = xv.x > 0.0f ? g.x : 0.0f;
-        g.y = xv.y > 0.0f ? g.y : 0.0f;
-        g.z = xv.z > 0.0f ? g.z : 0.0f;
-        g.w = xv.w > 0.0f ? g.w : 0.0f;
-        dx[idx] = make_uint2(f32_to_bf16_pair(g.x, g.y), f32_to_bf16_pair(g.z, g.w));
-    }
-}
-// 8-channel (16-byte) forms of the two bf16 pooling kernels: half the memory instructions and half the index arithmetic per
-// byte of the 4-channel forms above (which stay for C % 8 != 0).  rocprofv3, stem map 8 x 400 x 667 x 64: backward 266 us
-// at 2.3 TB/s with 8-byte accesses.
-__device__ __forceinline__ void bf8_to_f8(uint4 v, float (&o)[8]) {
-    o[0] = __builtin_bit_cast(float, v.x << 16); o[1] = __builtin_bit_cast(float, v.x & 0xFFFF0000u);
-    o[2] = __builtin_bit_cast(float, v.y << 16); o[3] = __builtin_bit_cast(float, v.y & 0xFFFF0000u);
-    o[4] = __builtin_bit_cast(float, v.z << 16); o[5] = __builtin_bit_cast(float, v.z & 0xFFFF0000u);
-    o[6] = __builtin_bit_cast(float, v.w << 16); o[7] = __builtin_bit_cast(float, v.w & 0xFFFF0000u);
-}
-
-__global__ __launch_bounds__(256) void maxpool_fwd_bf16x8_kernel(const uint4 *__restrict__ x, uint4 *__restrict__ y,
-                                                                 uint2 *__restrict__ amax, int N, int H, int W, int C8,
-                                                                 int Ho, int Wo, long long total8) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total8;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c8 = (int)(idx % C8);
-        const unsigned pix = (unsigned)(idx / C8);
-        const int wo = (int)(pix % (unsigned)Wo);
-        const unsigned t = pix / (unsigned)Wo;
-        const int ho = (int)(t % (unsigned)Ho);
-        const int n = (int)(t / (unsigned)Ho);
-        // bf16 values compare like their bit patterns moved to the high half of a float: keep the raw winners, no re-rounding
-        float best[8];
-        uint32_t bi[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int hi = 2 * ho - 1 + kh, wi = 2 * wo - 1 + kw;
-                uint4 raw = make_uint4(0u, 0u, 0u, 0u);       // the explicit ZeroPadding2D(1) takes part in the max
-                if (hi >= 0 && wi >= 0 && hi < H && wi < W) raw = x[((long long)(n * H + hi) * W + wi) * C8 + c8];
-                float vv[8];
-                bf8_to_f8(raw, vv);
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (vv[e] > best[e]) { best[e] = vv[e]; bi[e] = (uint32_t)(kh * 3 + kw); }
-            }
-        y[idx] = make_uint4(f32_to_bf16_pair(best[0], best[1]), f32_to_bf16_pair(best[2], best[3]),
-                            f32_to_bf16_pair(best[4], best[5]), f32_to_bf16_pair(best[6], best[7]));      // exact: inputs are bf16
-        amax[idx] = make_uint2(bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24), bi[4] | (bi[5] << 8) | (bi[6] << 16) | (bi[7] << 24));
-    }
-}
-
-__global__ __launch_bounds__(256) void maxpool_bwd_bf16x8_kernel(const uint4 *__restrict__ dy, const uint2 *__restrict__ amax,
-                                                                 const uint4 *__restrict__ x, uint4 *__restrict__ dx, int N, int H,
-                                                                 int W, int C8, int Ho, int Wo, long long total8) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total8;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c8 = (int)(idx % C8);
-        const unsigned pix = (unsigned)(idx / C8);
-        const int w = (int)(pix % (unsigned)W);
-        const unsigned t = pix / (unsigned)W;
-        const int h = (int)(t % (unsigned)H);
-        const int n = (int)(t / (unsigned)H);
-        const uint4 xraw = x[idx];
-        float g[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = 0.0f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int th = h + 1 - kh;
-            if (th < 0 || (th & 1)) continue;
-            const int ho = th >> 1;
-            if (ho >= Ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int tw = w + 1 - kw;
-                if (tw < 0 || (tw & 1)) continue;
-                const int wo = tw >> 1;
-                if (wo >= Wo) continue;
-                const long long o8 = ((long long)(n * Ho + ho) * Wo + wo) * C8 + c8;
-                const uint2 am = amax[o8];
-                float d[8];
-                bf8_to_f8(dy[o8], d);
-                const uint32_t tap = (uint32_t)(kh * 3 + kw);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (((am.x >> (8 * e)) & 0xFFu) == tap) g[e] += d[e];
-                    if (((am.y >> (8 * e)) & 0xFFu) == tap) g[4 + e] += d[4 + e];
-                }
-            }
-        }
-        float xv[8];
-        bf8_to_f8(xraw, xv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = xv[e] > 0.0f ? g[e] : 0.0f;
-        dx[idx] = make_uint4(f32_to_bf16_pair(g[0], g[1]), f32_to_bf16_pair(g[2], g[3]), f32_to_bf16_pair(g[4], g[5]), f32_to_bf16_pair(g[6], g[7]));
-    }
-}
-
-
-
-__global__ void subsample2_fwd_kernel(const float4 *__restrict__ x, float4 *__restrict__ y, int H, int W, int C4,
-                                      int Ho, int Wo, long long total) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C4);
-        long long t = idx / C4;
-        const int wo = (int)(t % Wo);
-        t /= Wo;
-        const int ho = (int)(t % Ho);
-        const long long n = t / Ho;
-        y[idx] = x[((n * H + 2 * ho) * W + 2 * wo) * C4 + c];
-    }
-}
-
-__global__ void subsample2_bwd_kernel(const float4 *__restrict__ dy, float4 *__restrict__ dx, int H, int W, int C4,
-                                      int Ho, int Wo, long long total) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C4);
-        long long t = idx / C4;
-        const int w = (int)(t % W);
-        t /= W;
-        const int h = (int)(t % H);
-        const long long n = t / H;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (!(h & 1) && !(w & 1) && (h >> 1) < Ho && (w >> 1) < Wo)
-            v = dy[((n * Ho + (h >> 1)) * Wo + (w >> 1)) * C4 + c];
-        dx[idx] = v;
-    }
-}
-
-static inline int ew_grid(long long total, int block) {
-    long long g = (total + block - 1) / block;
-    return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
-template <int BM, int BN, int WGM, int WGN>
-static void launch_conv_bf16(const ConvArgs &a0, bool dgrad, hipStream_t s) {
+// forward / input gradient: one workgroup per bm x bn tile of [destination pixels][destination channels]
+static void launch_conv_tiles(ConvKernel kernel, int bm, int bn, const ConvArgs &a0, hipStream_t s) {
     ConvArgs a = a0;
-    a.tiles_m = cdiv(a.M, BM);
-    a.tiles_n = cdiv(a.Cd, BN);
+    a.tiles_m = cdiv(a.M, bm);
+    a.tiles_n = cdiv(a.Cd, bn);
     dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(GEMM_THREADS);
-#define DETR_CONV_LAUNCH(W16_, X16_)                                                                                        \
-    do {                                                                                                                        \
-        if (dgrad) hipLaunchKernelGGL((conv3x3_bf16c_kernel<BM, BN, WGM, WGN, true, W16_, X16_>), grid, block, 0, s, a);          \
-        else hipLaunchKernelGGL((conv3x3_bf16c_kernel<BM, BN, WGM, WGN, false, W16_, X16_>), grid, block, 0, s, a);                \
-    } while (0)
-    if (a.w16 && a.x16) DETR_CONV_LAUNCH(true, true);
-    else if (a.w16) DETR_CONV_LAUNCH(true, false);
-    else if (a.x16) DETR_CONV_LAUNCH(false, true);
-    else DETR_CONV_LAUNCH(false, false);
-#undef DETR_CONV_LAUNCH
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, a);
 }
 
-template <int BM, int BN, int WGM, int WGN>
-static void launch_conv(const ConvArgs &a0, bool dgrad, hipStream_t s, bool split3 = false) {
-    ConvArgs a = a0;
-    a.tiles_m = cdiv(a.M, BM);
-    a.tiles_n = cdiv(a.Cd, BN);
-    dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(GEMM_THREADS);
+// bf16-compute kernel for the storage types of the kernel tensor (W16) and the source tensor (X16)
+template <int BM, int BN, int DIL, bool W16, bool X16>
+static ConvKernel conv_bf16c_dir(bool dgrad) {
+    return dgrad ? conv3x3_bf16c_kernel<BM, BN, 2, 2, true, W16, X16, DIL> : conv3x3_bf16c_kernel<BM, BN, 2, 2, false, W16, X16, DIL>;
+}
+template <int BM, int BN, int DIL>
+static ConvKernel conv_bf16c_for(const ConvArgs &a, bool dgrad) {
+    if (a.w16 && a.x16) return conv_bf16c_dir<BM, BN, DIL, true, true>(dgrad);
+    if (a.w16) return conv_bf16c_dir<BM, BN, DIL, true, false>(dgrad);
+    if (a.x16) return conv_bf16c_dir<BM, BN, DIL, false, true>(dgrad);
+    return conv_bf16c_dir<BM, BN, DIL, false, false>(dgrad);
+}
+
+// f32x3 split once into LDS (conv_x3.h): 1.0-1.25x the per-wave split (conv3x3_kernel<.., SPLIT3>) on the stride-1 / forward shapes, 0.92x on the
+// parity classes of the stride-2 input gradient (1-4 taps: short K loops), which keep the first form (profiles/r06_micro_split3.txt).
+// DETR_HIP_X3_CONV=2: first form everywhere, =1: second form everywhere
+static bool x3_form(const ConvArgs &a) { return a.Cs % 32 == 0 && tune(T_X3_CONV) != 2 && (!a.par_on || tune(T_X3_CONV) == 1); }
+
+template <int BM, int BN>
+static void launch_conv(const ConvArgs &a, bool dgrad, hipStream_t s, bool split3 = false) {
+    ConvKernel k = dgrad ? conv3x3_kernel<BM, BN, 2, 2, true> : conv3x3_kernel<BM, BN, 2, 2, false>;
     if constexpr (BM == BN) {
-        // split once into LDS (conv_x3.h): 1.0-1.25x the per-wave split below on the stride-1 / forward shapes, 0.92x on the parity classes of the
-        // stride-2 input gradient (1-4 taps: short K loops), which keep the first form (profiles/r06_micro_split3.txt).  DETR_HIP_X3_CONV=2: first
-        // form everywhere, =1: second form everywhere
-        if (split3 && a.Cs % 32 == 0 && tune(T_X3_CONV) != 2 && (!a.par_on || tune(T_X3_CONV) == 1)) {
-            if (dgrad) hipLaunchKernelGGL((conv3x3_x3_kernel<BM, BN, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_x3_kernel<BM, BN, false>), grid, block, 0, s, a);
-            return;
-        }
-        if (split3) {
-            if (dgrad) hipLaunchKernelGGL((conv3x3_kernel<BM, BN, WGM, WGN, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_kernel<BM, BN, WGM, WGN, false, true>), grid, block, 0, s, a);
-            return;
-        }
+        if (split3 && x3_form(a)) k = dgrad ? conv3x3_x3_kernel<BM, BN, true> : conv3x3_x3_kernel<BM, BN, false>;
+        else if (split3) k = dgrad ? conv3x3_kernel<BM, BN, 2, 2, true, true> : conv3x3_kernel<BM, BN, 2, 2, false, true>;
     }
-    if (dgrad) hipLaunchKernelGGL((conv3x3_kernel<BM, BN, WGM, WGN, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_kernel<BM, BN, WGM, WGN, false>), grid, block, 0, s, a);
+    launch_conv_tiles(k, BM, BN, a, s);
 }
 
-// row splits of the per-tap weight gradient (tiles = (Ci / BM) * (Co / BN) output tiles per tap) and of the fused nine-tap one
+// ------------------------------------------------------------------------------------------------
+// weight-gradient plan: which kernel, which tile, how many splits of the reduction and how much scratch.  The scratch-size
+// queries and the launches all read this one plan, so the caller's workspace is the size the launch expects.
+// ------------------------------------------------------------------------------------------------
+// row splits of the per-tap weight gradient (tiles = (Ci / tile) * (Co / tile) output tiles per tap)
 static int wgrad_split_plan(int M, int tiles, int split, int &rps) {
     if (split <= 0) {
         split = cdiv(1536, tiles * 9);
@@ -1143,7 +840,7 @@ static int wgrad_x3_split(int M, int tiles, int bm) {
     if (split > max_split) split = max_split;
     return split < 1 ? 1 : split;
 }
-
+// unit splits of the fused nine-tap weight gradient (units of 32 output pixels of one output row)
 static int wgrad_fused_split_plan(int units, int tiles, int split, int &ups) {
     if (split <= 0) {
         int wgs = tune(T_WGRAD_FUSED_WGS);      // tuning hook: target workgroup count (512 measured best: 2 per CU)
@@ -1156,187 +853,151 @@ static int wgrad_fused_split_plan(int units, int tiles, int split, int &ups) {
     return cdiv(units, ups);
 }
 
-// f32x3 forward / input gradient on 192 x 128 tiles (conv_x3.h; the rule is in detr_hip_conv3x3_f32)
-static void launch_conv_x3_192(const ConvArgs &a0, bool dgrad, hipStream_t s) {
-    ConvArgs a = a0;
-    a.tiles_m = cdiv(a.M, 192);
-    a.tiles_n = cdiv(a.Cd, 128);
-    dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(GEMM_THREADS);
-    if (dgrad) hipLaunchKernelGGL((conv3x3_x3_kernel<192, 128, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_x3_kernel<192, 128, false>), grid, block, 0, s, a);
+struct WgradPlan {
+    bool fused;         // the nine-tap bf16 kernel (reduction in units of 32 output pixels) | a per-tap kernel (reduction rows)
+    int tile;           // 64 | 128: (ci, co) tile of a workgroup
+    int split;          // grid.z: splits of the reduction
+    int per_split;      // units (fused) or rows per split
+    long long bytes;    // scratch for the splits' partial slabs (0: a single split accumulates onto dw)
+};
+
+// s16: x and dy are bf16 in memory; compute: detr_conv3x3_desc.compute; split: the descriptor's request (<= 0: ours)
+static WgradPlan wgrad_plan(int N, int Ho, int Wo, int Ci, int Co, int stride, int pad, bool s16, int compute, int dil, int split) {
+    WgradPlan p;
+    const bool bf = compute == 1 && Ci % 32 == 0 && Co % 32 == 0;
+    // nine taps per launch at stride 2 (round 5): bf16-stored tensors only, and only up to 128 channels -- measured (scripts/micro_conv.py,
+    // profiles/r05_micro_conv_dma.txt; nine-tap | per-tap, us): 200x334x128 -> 100x167 100.1 | 115.9, 100x167x256 -> 50x84 96.7 | 90.5, 50x84x512 ->
+    // 25x42 116.0 | 105.0: the stride-2 patch is twice the bytes per MFMA of the stride-1 one and every (ci, co) tile re-fetches it.
+    // DETR_HIP_WGRAD_FUSED = 2: never, 3: per-tap kernel for all stride-2 convolutions, 4: nine-tap kernel for all (A/B).
+    const int fmode = tune(T_WGRAD_FUSED);
+    const bool s_ok = stride == 1 || (stride == 2 && s16 && fmode != 3 && (fmode == 4 || (Ci <= 128 && Co <= 128)));
+    p.fused = dil == 1 && bf && s_ok && pad == 1 && Ci % 64 == 0 && Co % 64 == 0 && fmode != 2;
+    if (p.fused) {
+        p.tile = 64;
+        p.split = wgrad_fused_split_plan(N * Ho * cdiv(Wo, 32), (Ci / 64) * (Co / 64), split, p.per_split);
+    } else {
+        const int wforce = (bf || dil != 1) ? 0 : tune(T_WGRAD_TILE);
+        p.tile = (wforce == 3) ? 64 : ((wforce == 1 || (Ci >= 128 && Co >= 128)) ? 128 : 64);
+        const int M = N * Ho * Wo, tiles = cdiv(Ci, p.tile) * cdiv(Co, p.tile);
+        if (compute == 2 && split <= 0 && tune(T_X3_CONV) != 2) split = wgrad_x3_split(M, tiles, p.tile);
+        p.split = wgrad_split_plan(M, tiles, split, p.per_split);
+    }
+    p.bytes = p.split > 1 ? (long long)p.split * 9LL * Ci * Co * 4 : 0;
+    return p;
 }
 
-// f32x3 forward / input gradient on 128 x 64 tiles, three workgroups per CU
-static void launch_conv_x3_128x64(const ConvArgs &a0, bool dgrad, hipStream_t s) {
-    ConvArgs a = a0;
-    a.tiles_m = cdiv(a.M, 128);
-    a.tiles_n = cdiv(a.Cd, 64);
-    dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(GEMM_THREADS);
-    if (dgrad) hipLaunchKernelGGL((conv3x3_x3_kernel<128, 64, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_x3_kernel<128, 64, false>), grid, block, 0, s, a);
-}
-
-template <int BM, int BN, int WGM, int WGN>
-static void launch_wgrad(const ConvWgradArgs &a0, int split, float *ws, long long ws_bytes, hipStream_t s, bool bf16c = false, bool split3 = false) {
+// Runs `launch(a, grid)` for the plan's (tiles, taps, splits) grid.  With a workspace the splits write partial slabs (tile-ordered where the
+// tiles are whole and the final tensors 16-byte aligned -- the rule of gemm_slab_ts) and a fixed-order reduction applies alpha / scale onto dw;
+// without one they accumulate onto dw (float atomics when split > 1).
+template <class Launch>
+static void wgrad_run(const ConvWgradArgs &a0, const WgradPlan &p, int taps_y, float *ws, long long ws_bytes, hipStream_t s, Launch launch) {
     ConvWgradArgs a = a0;
-    a.tiles_m = cdiv(a.Ci, BM);
-    a.tiles_n = cdiv(a.Co, BN);
-    const int tiles = a.tiles_m * a.tiles_n;
-    int rps;
-    if (split3 && split <= 0 && BM == BN && tune(T_X3_CONV) != 2) split = wgrad_x3_split(a.M, tiles, BM);
-    split = wgrad_split_plan(a.M, tiles, split, rps);
-    a.rows_per_split = rps;
+    a.tiles_m = cdiv(a.Ci, p.tile);
+    a.tiles_n = cdiv(a.Co, p.tile);
+    a.rows_per_split = p.per_split;
     const long long part = 9LL * a.Ci * a.Co;
-    const bool partial = split > 1 && ws && aligned16(ws) && ws_bytes >= (long long)split * part * 4;
+    const bool partial = p.split > 1 && ws && aligned16(ws) && ws_bytes >= p.bytes;
     float *dw_final = a.dw;
     const EpiArgs final_e = a.e;
     a.part_stride = 0;
     a.slab_ts = 0;
-    // whole tiles (channel counts are multiples of the tile): the tile-ordered slab has exactly the row-major slab's size
     // (the tile-ordered reduce does 16-byte read-modify-writes of dw and 16-byte slab loads: `partial` already holds aligned16(ws);
-    //  a gradient buffer that is only 4-byte aligned keeps the row-major slabs and the scalar reduce -- the rule of gemm_slab_ts)
-    const bool ts = partial && WGM == 2 && WGN == 2 && a.Ci % BM == 0 && a.Co % BN == 0 && (!final_e.scale || aligned16(final_e.scale)) &&
+    //  a gradient buffer that is only 4-byte aligned keeps the row-major slabs and the scalar reduce)
+    const bool ts = partial && a.Ci % p.tile == 0 && a.Co % p.tile == 0 && (!final_e.scale || aligned16(final_e.scale)) &&
                     aligned16(dw_final) && tune(T_SLAB_TS) != 2;
     if (partial) {
-        a.dw = ws;
-        a.part_stride = part;
-        a.e.alpha = 1.0f;
-        a.e.scale = nullptr;
-        a.e.atomic = 0;
-        a.e.vec = 1;
-        a.slab_ts = ts ? 1 : 0;
-    } else if (split == 1) {
-        a.e.atomic = 1;   // accumulate onto dw
-    }
-    dim3 grid((unsigned)tiles, 9, (unsigned)split), block(GEMM_THREADS);
-    if (a.dil == 2) {                  // taps two pixels apart (conv_dilated.hip): the per-tap bodies, same split plan and reduction
-        if (bf16c && a.s16) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, true, 2>), grid, block, 0, s, a);
-        else if (bf16c) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, false, 2>), grid, block, 0, s, a);
-        else if (split3) hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN, WGM, WGN, true, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN, WGM, WGN, false, 2>), grid, block, 0, s, a);
-    } else
-    if (bf16c && a.s16) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, true>), grid, block, 0, s, a);
-    else if (bf16c) hipLaunchKernelGGL((conv3x3_wgrad_bf16c_kernel<BM, BN, WGM, WGN, false>), grid, block, 0, s, a);
-    else if (split3 && BM == BN && WGM == 2 && WGN == 2 && tune(T_X3_CONV) != 2) {
-        if constexpr (BM == BN && WGM == 2 && WGN == 2) hipLaunchKernelGGL((conv3x3_wgrad_x3_kernel<BM, BN>), grid, block, 0, s, a);
-    } else if (split3) hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN, WGM, WGN, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN, WGM, WGN>), grid, block, 0, s, a);
-    if (partial) launch_splitk_reduce(ws, split, part, 9 * a.Ci, a.Co, dw_final, a.Co, final_e.alpha, final_e.scale, s, nullptr, nullptr, 1.0f,
-                                      ts ? BM : 0, ts ? BN : 0, a.tiles_n);
-}
-
-// fused-tap bf16 weight gradient (stride 1, pad 1, channel counts % 64 == 0)
-static void launch_wgrad_fused(const ConvWgradArgs &a0, int split, float *ws, long long ws_bytes, hipStream_t s) {
-    ConvWgradArgs a = a0;
-    a.tiles_m = a.Ci / 64;
-    a.tiles_n = a.Co / 64;
-    const int tiles = a.tiles_m * a.tiles_n;
-    const int chunks = cdiv(a.Wo, 32);
-    const int units = a.N * a.Ho * chunks;
-    int ups;
-    split = wgrad_fused_split_plan(units, tiles, split, ups);
-    const long long part = 9LL * a.Ci * a.Co;
-    const bool partial = split > 1 && ws && aligned16(ws) && ws_bytes >= (long long)split * part * 4;
-    float *dw_final = a.dw;
-    const EpiArgs final_e = a.e;
-    a.part_stride = 0;
-    a.slab_ts = 0;
-    const bool ts = partial && (!final_e.scale || aligned16(final_e.scale)) && aligned16(dw_final) && tune(T_SLAB_TS) != 2;
-    if (partial) {
-        a.dw = ws;
-        a.part_stride = part;
+        a.dw = ws; a.part_stride = part;
         a.e.alpha = 1.0f;
         a.e.scale = nullptr;
         a.e.atomic = 0;
         a.e.vec = 1;
         a.slab_ts = ts ? 1 : 0;
     } else {
-        a.e.atomic = 1;   // accumulate onto dw (split == 1, or the atomic fallback without a workspace)
+        a.e.atomic = 1;   // accumulate onto dw
     }
-    dim3 grid((unsigned)tiles, 1, (unsigned)split), block(GEMM_THREADS);
-    if (a.stride == 2) hipLaunchKernelGGL((conv3x3_wgrad_fused_bf16_kernel<true, 2>), grid, block, 0, s, a, ups, chunks);
-    else if (a.s16) hipLaunchKernelGGL(conv3x3_wgrad_fused_bf16_kernel<true>, grid, block, 0, s, a, ups, chunks);
-    else hipLaunchKernelGGL(conv3x3_wgrad_fused_bf16_kernel<false>, grid, block, 0, s, a, ups, chunks);
-    if (partial) launch_splitk_reduce(ws, split, part, 9 * a.Ci, a.Co, dw_final, a.Co, final_e.alpha, final_e.scale, s, nullptr, nullptr, 1.0f,
-                                      ts ? 64 : 0, ts ? 64 : 0, a.tiles_n);
+    launch(a, dim3((unsigned)(a.tiles_m * a.tiles_n), (unsigned)taps_y, (unsigned)p.split));
+    if (partial) launch_splitk_reduce(ws, p.split, part, 9 * a.Ci, a.Co, dw_final, a.Co, final_e.alpha, final_e.scale, s, nullptr, nullptr, 1.0f,
+                                      ts ? p.tile : 0, ts ? p.tile : 0, a.tiles_n);
+}
+
+// per-tap weight gradient on BT x BT tiles (BT = plan.tile)
+template <int BT>
+static void launch_wgrad(const ConvWgradArgs &a0, const WgradPlan &p, float *ws, long long ws_bytes, hipStream_t s, bool bf16c, bool split3) {
+    WgradKernel k;
+    if (a0.dil == 2) {                 // taps two pixels apart (conv_dilated.hip): the per-tap bodies, same plan and reduction
+        if (bf16c) k = a0.s16 ? conv3x3_wgrad_bf16c_kernel<BT, BT, 2, 2, true, 2> : conv3x3_wgrad_bf16c_kernel<BT, BT, 2, 2, false, 2>;
+        else k = split3 ? conv3x3_wgrad_kernel<BT, BT, 2, 2, true, 2> : conv3x3_wgrad_kernel<BT, BT, 2, 2, false, 2>;
+    } else if (bf16c) k = a0.s16 ? conv3x3_wgrad_bf16c_kernel<BT, BT, 2, 2, true> : conv3x3_wgrad_bf16c_kernel<BT, BT, 2, 2, false>;
+    else if (split3) k = tune(T_X3_CONV) != 2 ? conv3x3_wgrad_x3_kernel<BT, BT> : conv3x3_wgrad_kernel<BT, BT, 2, 2, true>;
+    else k = conv3x3_wgrad_kernel<BT, BT, 2, 2>;
+    wgrad_run(a0, p, 9, ws, ws_bytes, s, [&](const ConvWgradArgs &a, dim3 grid) { hipLaunchKernelGGL(k, grid, dim3(GEMM_THREADS), 0, s, a); });
+}
+
+// fused-tap bf16 weight gradient (pad 1, channel counts % 64 == 0)
+static void launch_wgrad_fused(const ConvWgradArgs &a0, const WgradPlan &p, float *ws, long long ws_bytes, hipStream_t s) {
+    const int chunks = cdiv(a0.Wo, 32);
+    wgrad_run(a0, p, 1, ws, ws_bytes, s, [&](const ConvWgradArgs &a, dim3 grid) {
+        const dim3 block(GEMM_THREADS);
+        if (a.stride == 2) hipLaunchKernelGGL((conv3x3_wgrad_fused_bf16_kernel<true, 2>), grid, block, 0, s, a, p.per_split, chunks);
+        else if (a.s16) hipLaunchKernelGGL(conv3x3_wgrad_fused_bf16_kernel<true>, grid, block, 0, s, a, p.per_split, chunks);
+        else hipLaunchKernelGGL(conv3x3_wgrad_fused_bf16_kernel<false>, grid, block, 0, s, a, p.per_split, chunks);
+    });
+}
+
+static void launch_wgrad_plan(const ConvWgradArgs &a, const WgradPlan &p, float *ws, long long ws_bytes, hipStream_t s, bool bf16c, bool split3) {
+    if (p.fused) launch_wgrad_fused(a, p, ws, ws_bytes, s);
+    else if (p.tile == 128) launch_wgrad<128>(a, p, ws, ws_bytes, s, bf16c, split3);
+    else launch_wgrad<64>(a, p, ws, ws_bytes, s, bf16c, split3);
 }
 
 // ------------------------------------------------------------------------------------------------
 // dilation 2 (conv_dilated.hip; conv_args.h declares these): the implicit-GEMM tile bodies above with their taps two pixels
 // apart -- forward / input gradient on 64 x 64 tiles, weight gradient per tap on the dense rule's tiles
 // ------------------------------------------------------------------------------------------------
-void conv_dilated_tiles(const ConvArgs &a0, bool dgrad, int compute, hipStream_t s) {
-    ConvArgs a = a0;
-    a.tiles_m = cdiv(a.M, 64);
-    a.tiles_n = cdiv(a.Cd, 64);
-    dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(GEMM_THREADS);
-#define DETR_CONVD_LAUNCH(W16_, X16_)                                                                                       \
-    do {                                                                                                                        \
-        if (dgrad) hipLaunchKernelGGL((conv3x3_bf16c_kernel<64, 64, 2, 2, true, W16_, X16_, 2>), grid, block, 0, s, a);           \
-        else hipLaunchKernelGGL((conv3x3_bf16c_kernel<64, 64, 2, 2, false, W16_, X16_, 2>), grid, block, 0, s, a);                 \
-    } while (0)
-    if (compute == 1) {
-        if (a.w16 && a.x16) DETR_CONVD_LAUNCH(true, true);
-        else if (a.w16) DETR_CONVD_LAUNCH(true, false);
-        else if (a.x16) DETR_CONVD_LAUNCH(false, true);
-        else DETR_CONVD_LAUNCH(false, false);
-    } else if (compute == 2) {
-        if (dgrad) hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, true, true, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, false, true, 2>), grid, block, 0, s, a);
-    } else {
-        if (dgrad) hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, true, false, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_kernel<64, 64, 2, 2, false, false, 2>), grid, block, 0, s, a);
-    }
-#undef DETR_CONVD_LAUNCH
+void conv_dilated_tiles(const ConvArgs &a, bool dgrad, int compute, hipStream_t s) {
+    ConvKernel k;
+    if (compute == 1) k = conv_bf16c_for<64, 64, 2>(a, dgrad);
+    else if (compute == 2) k = dgrad ? conv3x3_kernel<64, 64, 2, 2, true, true, 2> : conv3x3_kernel<64, 64, 2, 2, false, true, 2>;
+    else k = dgrad ? conv3x3_kernel<64, 64, 2, 2, true, false, 2> : conv3x3_kernel<64, 64, 2, 2, false, false, 2>;
+    launch_conv_tiles(k, 64, 64, a, s);
 }
 
-static int conv_dilated_wgrad_tile(int Ci, int Co) { return (Ci >= 128 && Co >= 128) ? 128 : 64; }
+static WgradPlan conv_dilated_wgrad_plan(int N, int H, int W, int Ci, int Co, bool s16, int compute, int split) {
+    return wgrad_plan(N, H, W, Ci, Co, 1, 2, s16, compute, 2, split);
+}
 
 void conv_dilated_wgrad_tiles(const ConvWgradArgs &a, int compute, int split, float *ws, long long ws_bytes, hipStream_t s) {
-    const bool bf = compute == 1, s3 = compute == 2;
-    if (conv_dilated_wgrad_tile(a.Ci, a.Co) == 128) launch_wgrad<128, 128, 2, 2>(a, split, ws, ws_bytes, s, bf, s3);
-    else launch_wgrad<64, 64, 2, 2>(a, split, ws, ws_bytes, s, bf, s3);
+    launch_wgrad_plan(a, conv_dilated_wgrad_plan(a.N, a.Ho, a.Wo, a.Ci, a.Co, a.s16, compute, split), ws, ws_bytes, s, compute == 1, compute == 2);
 }
 
-// row splits launch_wgrad will use for that call (the scratch-size query)
-int conv_dilated_wgrad_splits(int M, int Ci, int Co, int compute, int split) {
-    const int t = conv_dilated_wgrad_tile(Ci, Co), tiles = cdiv(Ci, t) * cdiv(Co, t);
-    if (compute == 2 && split <= 0 && tune(T_X3_CONV) != 2) split = wgrad_x3_split(M, tiles, t);
-    int rps;
-    return wgrad_split_plan(M, tiles, split, rps);
+// row splits that call will use (the scratch-size query)
+int conv_dilated_wgrad_splits(int N, int H, int W, int Ci, int Co, int compute, int split) {
+    return conv_dilated_wgrad_plan(N, H, W, Ci, Co, false, compute, split).split;
 }
 
 }  // namespace detr
 
 using namespace detr;
 
-static bool wgrad_is_fused(const detr_conv3x3_desc *d) {
-    const bool bf = d->compute == 1 && d->Ci % 32 == 0 && d->Co % 32 == 0;
-    // stride 2 (round 5): bf16-stored tensors only, and only up to 128 channels -- measured (scripts/micro_conv.py, profiles/r05_micro_conv_dma.txt;
-    // nine-tap | per-tap, us): 200x334x128 -> 100x167 100.1 | 115.9, 100x167x256 -> 50x84 96.7 | 90.5, 50x84x512 -> 25x42 116.0 | 105.0: the stride-2
-    // patch is twice the bytes per MFMA of the stride-1 one and every (ci, co) tile re-fetches it.  DETR_HIP_WGRAD_FUSED = 3: per-tap kernel for all
-    // stride-2 convolutions, 4: nine-tap kernel for all (A/B).
-    const int fmode = tune(T_WGRAD_FUSED);
-    const bool s_ok = d->stride == 1 || (d->stride == 2 && d->x_dtype == 1 && d->w_dtype == 1 && fmode != 3 && (fmode == 4 || (d->Ci <= 128 && d->Co <= 128)));
-    return bf && s_ok && d->pad == 1 && d->Ci % 64 == 0 && d->Co % 64 == 0 && tune(T_WGRAD_FUSED) != 2;
+static WgradPlan wgrad_plan(const detr_conv3x3_desc *d) {
+    return wgrad_plan(d->N, d->Ho, d->Wo, d->Ci, d->Co, d->stride, d->pad, d->x_dtype == 1 && d->w_dtype == 1, d->compute, 1, d->split);
+}
+
+// The halo-staged kernels (conv_halo.h) take stride-1 convolutions on all-bf16 tensors with the epilogues they have (DETR_HIP_CONV_HALO=2 =
+// off) and, in their class form, the stride-2 input gradient (dgrad_classes; DETR_HIP_DGRAD_S2_CLASSES = 3: tile kernel).  With 4-row tiles
+// they also take the 512-channel convs of layer4 (25 x 42 maps: 92.9 -> 64.5 us forward, 103.2 -> 65.5 us input gradient against the
+// 64x64 implicit-GEMM tiles; with 8-row tiles -- 64 workgroups x 4 channel slices, half of every tile padding -- it lost).
+static bool halo_eligible(const detr_conv3x3_desc *d, const ConvArgs &a, const EpiArgs &e, bool dgrad_classes) {
+    if (!(d->compute == 1 && d->pad == 1 && a.w16 && a.x16 && e.c16 && a.Cs % 32 == 0 && a.Cd % 64 == 0 && a.Cd <= 512 &&
+          (!d->mask || e.m16) && !d->residual && !d->scale && d->alpha == 1.0f && tune(T_CONV_HALO) != 2)) return false;
+    if (dgrad_classes) return d->stride == 2 && !d->bias && d->act == 0 && tune(T_DGRAD_S2_CLASSES) != 3;
+    return d->stride == 1 && (d->act == 0 || d->act == 1);
 }
 
 extern "C" int64_t detr_hip_workspace_bytes_conv3x3(const detr_conv3x3_desc *d, int32_t mode) {
     if (!d || d->N <= 0 || d->Ci <= 0 || d->Co <= 0) return -1;
     if (mode != 2) return 0;                       // forward / input gradient: no scratch
-    const long long part = 9LL * d->Ci * d->Co;
-    int split, aux;
-    if (wgrad_is_fused(d)) {
-        split = wgrad_fused_split_plan(d->N * d->Ho * cdiv(d->Wo, 32), (d->Ci / 64) * (d->Co / 64), d->split, aux);
-    } else {
-        const bool bf = d->compute == 1 && d->Ci % 32 == 0 && d->Co % 32 == 0;
-        const int wforce = bf ? 0 : tune(T_WGRAD_TILE);
-        const int t = (wforce == 3) ? 64 : ((wforce == 1 || (d->Ci >= 128 && d->Co >= 128)) ? 128 : 64);
-        int ask = d->split;
-        if (d->compute == 2 && ask <= 0 && tune(T_X3_CONV) != 2) ask = wgrad_x3_split(d->N * d->Ho * d->Wo, cdiv(d->Ci, t) * cdiv(d->Co, t), t);      // (the launch's plan)
-        split = wgrad_split_plan(d->N * d->Ho * d->Wo, cdiv(d->Ci, t) * cdiv(d->Co, t), ask, aux);
-    }
-    return split > 1 ? (int64_t)split * part * 4 : 0;
+    return wgrad_plan(d).bytes;
 }
 
 extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, void *stream) {
@@ -1380,24 +1041,9 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
         e.atomic = 1; e.ldr = 0; e.ldmask = 0;
         a.e = e;
         const bool bf = d->compute == 1 && d->Ci % 32 == 0 && d->Co % 32 == 0;
-        if (wgrad_is_fused(d)) {
-            launch_wgrad_fused(a, d->split, d->workspace, d->workspace_bytes, s);
-            DETR_LAUNCH_CHECK("conv3x3 wgrad bf16 (fused taps)");
-            return 0;
-        }
-        if (bf) {
-            if (d->Ci >= 128 && d->Co >= 128) launch_wgrad<128, 128, 2, 2>(a, d->split, d->workspace, d->workspace_bytes, s, true);
-            else launch_wgrad<64, 64, 2, 2>(a, d->split, d->workspace, d->workspace_bytes, s, true);
-            DETR_LAUNCH_CHECK("conv3x3 wgrad bf16");
-            return 0;
-        }
-        const int wforce = tune(T_WGRAD_TILE);
-        const bool s3 = d->compute == 2;
-        if (wforce == 3) launch_wgrad<64, 64, 2, 2>(a, d->split, d->workspace, d->workspace_bytes, s, false, s3);
-        else if (wforce == 1) launch_wgrad<128, 128, 2, 2>(a, d->split, d->workspace, d->workspace_bytes, s, false, s3);
-        else if (d->Ci >= 128 && d->Co >= 128) launch_wgrad<128, 128, 2, 2>(a, d->split, d->workspace, d->workspace_bytes, s, false, s3);
-        else launch_wgrad<64, 64, 2, 2>(a, d->split, d->workspace, d->workspace_bytes, s, false, s3);
-        DETR_LAUNCH_CHECK("conv3x3 wgrad");
+        const WgradPlan p = wgrad_plan(d);
+        launch_wgrad_plan(a, p, d->workspace, d->workspace_bytes, s, bf, !bf && d->compute == 2);
+        DETR_LAUNCH_CHECK(p.fused ? "conv3x3 wgrad bf16 (fused taps)" : (bf ? "conv3x3 wgrad bf16" : "conv3x3 wgrad"));
         return 0;
     }
     ConvArgs a;
@@ -1428,13 +1074,9 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
     a.par_on = 0; a.Hp = a.Wp = a.ph = a.pw = a.kh0 = a.kw0 = 0; a.nth = a.ntw = 3;
     a.cls_mix = 0;
     const bool dgrad = mode == 1;
-    // stride-1 convs on bf16 tensors: the halo-staged kernel (conv_halo.h; DETR_HIP_CONV_HALO=2 = off), for 128-channel panels on 4-row tiles
-    // its LDS-DMA form (conv_halo_dma.h: bit-identical, 5-10 % faster; DETR_HIP_CONV_DMA=2 = off).  With 4-row tiles it also
-    // takes the 512-channel convs of layer4 (25 x 42 maps: 92.9 -> 64.5 us forward, 103.2 -> 65.5 us input gradient against the
-    // 64x64 implicit-GEMM tiles; with 8-row tiles -- 64 workgroups x 4 channel slices, half of every tile padding -- it lost).
-    if (d->compute == 1 && d->stride == 1 && d->pad == 1 && a.w16 && a.x16 && e.c16 && a.Cs % 32 == 0 && a.Cd % 64 == 0 &&
-        a.Cd <= 512 && (!d->mask || e.m16) && !d->residual && !d->scale && d->alpha == 1.0f && (d->act == 0 || d->act == 1) &&
-        tune(T_CONV_HALO) != 2) {
+    // stride-1 convs on bf16 tensors: the halo-staged kernel, for 128-channel panels on 4-row tiles its LDS-DMA form
+    // (conv_halo_dma.h: bit-identical, 5-10 % faster; DETR_HIP_CONV_DMA=2 = off)
+    if (halo_eligible(d, a, e, false)) {
         if (a.Cd >= 128 && a.Cd % 128 == 0 && tune(T_CONV_DMA) != 2 && tune(T_CONV_HALO) != 4) { if (launch_conv_halo_dma(a, dgrad, s)) return -1; }
         // (the halo epilogue has no column guard: a 128-channel tile needs Cd % 128 == 0; 192 / 320 / 448 channels take 64-channel tiles)
         else if (a.Cd % 128 == 0) { if (launch_conv_halo<128>(a, dgrad, s)) return -1; }
@@ -1449,8 +1091,8 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
             // measured: profiles/tune_bf16_r1d.txt; round 3 (scripts/micro_conv.py, with the wide epilogue): the stride-2 forward at 128
             // channels 83 -> 72 us (cold 113 -> 97) and its input-gradient classes 173 -> 165 us on 128x128 tiles
             if (force == 3 || (force == 0 && (c.Cd < 128 || big < 256)))
-                launch_conv_bf16<64, 64, 2, 2>(c, dgrad, s);
-            else launch_conv_bf16<128, 128, 2, 2>(c, dgrad, s);
+                launch_conv_tiles(conv_bf16c_for<64, 64, 1>(c, dgrad), 64, 64, c, s);
+            else launch_conv_tiles(conv_bf16c_for<128, 128, 1>(c, dgrad), 128, 128, c, s);
         } else if (d->compute == 2) {
             // f32x3: 64 x 64 wave tiles (128 x 128 workgroup tiles) are matrix-pipe bound, 32 x 32 ones VALU bound (see gemm_pick_tile)
             const int lim = tune(T_SPLIT3_T128) > 0 ? tune(T_SPLIT3_T128) : 192;
@@ -1458,24 +1100,23 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
             // rounds, 350 tiles of 192 rows one round of 1.5 x the work (the rule of gemm_pick_tile's tile 8; DETR_HIP_X3_T192 = 2: never, 1: always)
             const long long t192 = (long long)cdiv(c.M, 192) * cdiv(c.Cd, 128);
             const long long r128 = (big + 511) / 512, r192 = (t192 + 511) / 512;
-            const bool x3form = c.Cs % 32 == 0 && tune(T_X3_CONV) != 2 && (!c.par_on || tune(T_X3_CONV) == 1);
-            if (force == 3 || (force == 0 && (c.Cd < 128 || big < lim))) launch_conv<64, 64, 2, 2>(c, dgrad, s, true);
-            else if (force == 0 && x3form && tune(T_X3_T192) != 2 && tune(T_X3_T192) != 3 && (tune(T_X3_T192) == 1 || 3 * r192 < 2 * r128)) launch_conv_x3_192(c, dgrad, s);
+            const bool x3form = x3_form(c);
+            if (force == 3 || (force == 0 && (c.Cd < 128 || big < lim))) launch_conv<64, 64>(c, dgrad, s, true);
+            else if (force == 0 && x3form && tune(T_X3_T192) != 2 && tune(T_X3_T192) != 3 && (tune(T_X3_T192) == 1 || 3 * r192 < 2 * r128)) 
+                launch_conv_tiles(dgrad ? conv3x3_x3_kernel<192, 128, true> : conv3x3_x3_kernel<192, 128, false>, 192, 128, c, s);
             // 128 x 64 tiles, three workgroups per CU: one 128-channel panel (layer2: 1044 tiles of 128 x 128 = 2.04 rounds -> 290 vs 275 us) and grids
             // that leave CUs with a single 128 x 128 workgroup (layer4: 264 tiles -> 357 vs 338 us); DETR_HIP_X3_T192 = 3: wherever 128 x 128 would run
-            else if (force == 0 && x3form && tune(T_X3_T192) != 2 && (tune(T_X3_T192) == 3 || c.Cd == 128 || big <= 384)) launch_conv_x3_128x64(c, dgrad, s);
-            else launch_conv<128, 128, 2, 2>(c, dgrad, s, true);
-        } else if (force == 1) launch_conv<128, 128, 2, 2>(c, dgrad, s);
-        else if (force == 2) launch_conv<128, 64, 2, 2>(c, dgrad, s);
-        else launch_conv<64, 64, 2, 2>(c, dgrad, s);   // 64x64 measured best on every backbone shape (profiles/tune_r1.txt)
+            else if (force == 0 && x3form && tune(T_X3_T192) != 2 && (tune(T_X3_T192) == 3 || c.Cd == 128 || big <= 384)) 
+                launch_conv_tiles(dgrad ? conv3x3_x3_kernel<128, 64, true> : conv3x3_x3_kernel<128, 64, false>, 128, 64, c, s);
+            else launch_conv<128, 128>(c, dgrad, s, true);
+        } else if (force == 1) launch_conv<128, 128>(c, dgrad, s);
+        else if (force == 2) launch_conv<128, 64>(c, dgrad, s);
+        else launch_conv<64, 64>(c, dgrad, s);   // 64x64 measured best on every backbone shape (profiles/tune_r1.txt)
     };
     if (dgrad && d->stride == 2 && tune(T_DGRAD_S2_CLASSES) != 2) {
         // one launch per destination-pixel parity class: 1 + 2 + 2 + 4 tap-GEMMs instead of 9 with 3/4 of the rows masked
-        // all-bf16 tensors: the class form of the halo-staged kernel (conv_halo.h; DETR_HIP_DGRAD_S2_CLASSES = 3: tile kernel)
-        const bool halo_cls = d->compute == 1 && d->pad == 1 && a.w16 && a.x16 && e.c16 && a.Cs % 32 == 0 && a.Cd % 64 == 0 &&
-                              a.Cd <= 512 && (!d->mask || e.m16) && !d->residual && !d->scale && !d->bias && d->alpha == 1.0f &&
-                              d->act == 0 && tune(T_DGRAD_S2_CLASSES) != 3 && tune(T_CONV_HALO) != 2;
-        if (halo_cls) {
+        // all-bf16 tensors: the class form of the halo-staged kernel
+        if (halo_eligible(d, a, e, true)) {
             if (a.Cd % 128 == 0) { if (launch_conv_halo_s2classes<128>(a, s)) return -1; }
             else if (launch_conv_halo_s2classes<64>(a, s)) return -1;
             DETR_LAUNCH_CHECK("conv3x3 (halo, stride-2 classes)");
@@ -1485,7 +1126,6 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
             for (int pw = 0; pw < 2; ++pw) {
                 ConvArgs c = a;
                 c.par_on = 1; c.ph = ph; c.pw = pw;
-
                 c.Hp = (a.Hd + 1 - ph) / 2;
                 c.Wp = (a.Wd + 1 - pw) / 2;
                 c.M = d->N * c.Hp * c.Wp;
@@ -1500,87 +1140,5 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
         launch(a);
     }
     DETR_LAUNCH_CHECK("conv3x3");
-    return 0;
-}
-
-extern "C" int detr_hip_maxpool3x3s2_fwd_f32(const float *x, float *y, uint8_t *argmax, int32_t N, int32_t H, int32_t W,
-                                             int32_t C, int32_t Ho, int32_t Wo, void *stream) {
-    DETR_REQUIRE(x && y && argmax, "maxpool fwd: null operand");
-    DETR_REQUIRE(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1, "maxpool fwd: bad output size");
-    const long long total = (long long)N * Ho * Wo * C;
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, argmax, N,
-                       H, W, C, Ho, Wo, total);
-    DETR_LAUNCH_CHECK("maxpool fwd");
-    return 0;
-}
-
-extern "C" int detr_hip_maxpool3x3s2_bwd_f32(const float *dy, const uint8_t *argmax, const float *x, float *dx, int32_t N,
-                                             int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, void *stream) {
-    DETR_REQUIRE(dy && argmax && x && dx, "maxpool bwd: null operand");
-    DETR_REQUIRE(C % 4 == 0 && aligned16(dy) && aligned16(x) && aligned16(dx) && ((uintptr_t)argmax % 4 == 0),
-                 "maxpool bwd: C must be a multiple of 4 and the tensors 16-byte aligned");
-    const long long total = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, argmax, x,
-                       dx, N, H, W, C, Ho, Wo, total);
-    DETR_LAUNCH_CHECK("maxpool bwd");
-    return 0;
-}
-
-extern "C" int detr_hip_subsample2_fwd_f32(const float *x, float *y, int32_t N, int32_t H, int32_t W, int32_t C,
-                                           int32_t Ho, int32_t Wo, void *stream) {
-    DETR_REQUIRE(x && y && C % 4 == 0 && aligned16(x) && aligned16(y), "subsample2 fwd: bad operands");
-    DETR_REQUIRE(Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "subsample2 fwd: bad output size");
-    const long long total = (long long)N * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(subsample2_fwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float4 *)x, (float4 *)y, H, W, C / 4, Ho, Wo, total);
-    DETR_LAUNCH_CHECK("subsample2 fwd");
-    return 0;
-}
-
-extern "C" int detr_hip_subsample2_bwd_f32(const float *dy, float *dx, int32_t N, int32_t H, int32_t W, int32_t C,
-                                           int32_t Ho, int32_t Wo, void *stream) {
-    DETR_REQUIRE(dy && dx && C % 4 == 0 && aligned16(dy) && aligned16(dx), "subsample2 bwd: bad operands");
-    const long long total = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(subsample2_bwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float4 *)dy, (float4 *)dx, H, W, C / 4, Ho, Wo, total);
-    DETR_LAUNCH_CHECK("subsample2 bwd");
-    return 0;
-}
-
-extern "C" int detr_hip_maxpool3x3s2_fwd_bf16(const uint16_t *x, uint16_t *y, uint8_t *argmax, int32_t N, int32_t H, int32_t W,
-                                              int32_t C, int32_t Ho, int32_t Wo, void *stream) {
-    DETR_REQUIRE(x && y && argmax && C % 4 == 0, "maxpool fwd bf16: bad operands");
-    DETR_REQUIRE(((uintptr_t)x % 8 == 0) && ((uintptr_t)y % 8 == 0) && ((uintptr_t)argmax % 4 == 0), "maxpool fwd bf16: alignment");
-    DETR_REQUIRE(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1, "maxpool fwd: bad output size");
-    if (C % 8 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((uintptr_t)argmax % 8 == 0)) {
-        const long long total8 = (long long)N * Ho * Wo * (C / 8);
-        hipLaunchKernelGGL(maxpool_fwd_bf16x8_kernel, dim3(ew_grid(total8, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)x,
-                           (uint4 *)y, (uint2 *)argmax, N, H, W, C / 8, Ho, Wo, total8);
-        DETR_LAUNCH_CHECK("maxpool fwd bf16 (8 channels per lane)");
-        return 0;
-    }
-    const long long total = (long long)N * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(maxpool_fwd_bf16_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, (const uint2 *)x,
-                       (uint2 *)y, (uint32_t *)argmax, N, H, W, C / 4, Ho, Wo, total);
-    DETR_LAUNCH_CHECK("maxpool fwd bf16");
-    return 0;
-}
-
-extern "C" int detr_hip_maxpool3x3s2_bwd_bf16(const uint16_t *dy, const uint8_t *argmax, const uint16_t *x, uint16_t *dx, int32_t N,
-                                              int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, void *stream) {
-    DETR_REQUIRE(dy && argmax && x && dx && C % 4 == 0, "maxpool bwd bf16: bad operands");
-    DETR_REQUIRE(((uintptr_t)dy % 8 == 0) && ((uintptr_t)x % 8 == 0) && ((uintptr_t)dx % 8 == 0) && ((uintptr_t)argmax % 4 == 0),
-                 "maxpool bwd bf16: alignment");
-    if (C % 8 == 0 && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)dx % 16 == 0) && ((uintptr_t)argmax % 8 == 0)) {
-        const long long total8 = (long long)N * H * W * (C / 8);
-        hipLaunchKernelGGL(maxpool_bwd_bf16x8_kernel, dim3(ew_grid(total8, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)dy,
-                           (const uint2 *)argmax, (const uint4 *)x, (uint4 *)dx, N, H, W, C / 8, Ho, Wo, total8);
-        DETR_LAUNCH_CHECK("maxpool bwd bf16 (8 channels per lane)");
-        return 0;
-    }
-    const long long total = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, (const uint2 *)dy,
-                       (const uint32_t *)argmax, (const uint2 *)x, (uint2 *)dx, N, H, W, C / 4, Ho, Wo, total);
-    DETR_LAUNCH_CHECK("maxpool bwd bf16");
     return 0;
 }
