@@ -129,6 +129,22 @@ class MapMatchDesc(Structure):
                 ("rec_score", c_void_p), ("rec_class", c_void_p), ("rec_flags", c_void_p), ("num_gt", c_void_p), ("status", c_void_p)]
 
 
+COCO_MAX_THR, COCO_MAX_AREA = 10, 4                                            # DETR_COCO_MAX_THR, DETR_COCO_MAX_AREA
+COCO_BAD = dict(MAP_BAD)
+COCO_BAD[16] = "a non-positive image size"                                     # DETR_COCO_BAD_SIZE
+
+
+class CocoMatchDesc(Structure):
+    """detr_coco_match_desc (appended entry point, ABI version unchanged)."""
+    _fields_ = [("B", c_int32), ("Q", c_int32), ("R", c_int32), ("nb_class", c_int32), ("n_thr", c_int32), ("n_area", c_int32),
+                ("boxes", c_void_p), ("labels", c_void_p), ("scores", c_void_p), ("counts", c_void_p), ("sD_b", c_int64),
+                ("t_bbox", c_void_p), ("sT_b", c_int64), ("t_class", c_void_p), ("sC_b", c_int64),
+                ("t_crowd", c_void_p), ("t_area", c_void_p), ("sM_b", c_int64), ("sizes", c_void_p),
+                ("thresholds", ctypes.c_double * COCO_MAX_THR), ("area_ranges", ctypes.c_double * (2 * COCO_MAX_AREA)),
+                ("rec_score", c_void_p), ("rec_class", c_void_p), ("rec_rank", c_void_p), ("rec_flags", c_void_p),
+                ("npig", c_void_p), ("status", c_void_p)]
+
+
 class SetLossDesc(Structure):
     _fields_ = [("levels", c_int32), ("B", c_int32), ("Q", c_int32), ("C", c_int32), ("R", c_int32),
                 ("logits", c_void_p), ("sL_l", c_int64), ("sL_b", c_int64), ("sL_q", c_int64),
@@ -207,6 +223,7 @@ _SIGNATURES = {
     "detr_hip_adamw_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, f32p, c_int32, c_int32, c_void_p],
     "detr_hip_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32, c_void_p],
     "detr_hip_detect": [POINTER(DetectDesc), c_void_p],
+    "detr_hip_coco_match": [POINTER(CocoMatchDesc), c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {

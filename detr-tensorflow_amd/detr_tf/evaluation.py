@@ -4,12 +4,16 @@ targets converted to [y1, x1, y2, x2] (bbox.py:186-196), the vectorised COCO-sty
 
 accumulate="device" keeps the per-image matching on the device as well (loss/compute_map.py: DeviceAPAccumulator, one more
 launch per batch): nothing is read back per batch, so the loop enqueues batch i+1 while batch i still runs; the result is the
-same to the last bit."""
+same to the last bit.
+
+protocol="coco" evaluates by the COCO protocol instead (loss/coco_eval.py: crowd regions, area ranges, maxDets, AP and AR): the
+loader must yield 4-tuples (images, t_bbox, t_class, meta), as DetectionDataset(with_meta=True) does; accumulate keeps its meaning."""
 import numpy as np
 import torch
 
 from . import bbox
 from .inference import get_model_inference_batched
+from .loss.coco_eval import COCOAccumulator, DeviceCOCOAccumulator, check_meta
 from .loss.compute_map import APAccumulator, DeviceAPAccumulator
 
 
@@ -26,9 +30,52 @@ def _add_batch_host(acc, model, m_outputs, target_bbox, target_class, background
         acc.add_image(p_bbox.cpu().numpy(), p_labels.cpu().numpy(), p_scores.cpu().numpy(), t_bbox.numpy(), t_class.numpy())
 
 
-def eval_model(model, config, class_names, valid_dt, max_batches=None, print_result=True, accumulate="host"):
+def _host(x):
+    return (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).cpu()
+
+
+def _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, background_class):
+    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx")
+    if getattr(model, "engine", None) is not None:
+        model.engine.check_mask_status()
+    tb, tc = _host(target_bbox).float(), _host(target_class)
+    crowd, area, size = _host(meta["crowd"]).numpy(), _host(meta["area"]).numpy(), _host(meta["size"]).numpy()
+    for b, (p_bbox, p_labels, p_scores) in enumerate(dets):
+        n = int(tb[b, 0, 0])
+        t_bbox = bbox.xcycwh_to_yx_min_yx_max(tb[b, 1:1 + n])
+        acc.add_image(p_bbox.cpu().numpy(), p_labels.cpu().numpy(), p_scores.cpu().numpy(), t_bbox.numpy(), tc[b, 1:1 + n].reshape(-1).numpy(),
+                      crowd[b, 1:1 + n], area[b, 1:1 + n], size[b])
+
+
+def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate):
+    acc = COCOAccumulator(len(class_names))
+    for it, batch in enumerate(valid_dt):
+        if not isinstance(batch, (tuple, list)) or len(batch) != 4:
+            raise TypeError('eval_model: protocol="coco" takes (images, t_bbox, t_class, meta) batches -- build the loader with '
+                            f"with_meta=True (and keep_crowd=True); got a batch of {len(batch) if isinstance(batch, (tuple, list)) else type(batch).__name__}")
+        images, target_bbox, target_class, meta = batch
+        check_meta(meta, "eval_model")
+        m_outputs = model(images, training=False)
+        if accumulate == "device":
+            if it == 0:
+                acc = DeviceCOCOAccumulator(len(class_names), device=m_outputs["pred_logits"].device)
+            acc.add_batch(m_outputs, target_bbox, target_class, meta, config.background_class)
+            if getattr(model, "engine", None) is not None:
+                model.engine.check_mask_status()
+        else:
+            _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, config.background_class)
+        if max_batches is not None and it + 1 >= max_batches:
+            break
+    return acc.result(class_names, print_result=print_result)
+
+
+def eval_model(model, config, class_names, valid_dt, max_batches=None, print_result=True, accumulate="host", *, protocol="reference"):
     if accumulate not in ("host", "device"):
         raise ValueError(f"eval_model: accumulate must be 'host' or 'device', got {accumulate!r}")
+    if protocol not in ("reference", "coco"):
+        raise ValueError(f"eval_model: protocol must be 'reference' or 'coco', got {protocol!r}")
+    if protocol == "coco":
+        return _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate)
     acc = APAccumulator(len(class_names))
     for it, (images, target_bbox, target_class) in enumerate(valid_dt):
         m_outputs = model(images, training=False)

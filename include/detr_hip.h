@@ -713,6 +713,60 @@ typedef struct {
 } detr_detect_desc;
 int detr_hip_detect(const detr_detect_desc *d, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO-protocol evaluation, per-image half, appended (the ABI version is unchanged):
+ *   restates COCOeval's bbIou / evaluateImg for boxes (crowd regions, area ranges, ignore flags); the accumulate / summarize half
+ *   is detr_tf/loss/coco_eval.py: COCOAccumulator.result.  One launch per batch, one workgroup per image (csrc/coco_match.hip).
+ * Inputs: the detections and padded targets of detr_hip_map_match (same layout, conversion and clip), plus per target row
+ * t_crowd[b][r] (iscrowd) and t_area[b][r] (the annotation's area in pixels^2 of the original image) -- rows line up with t_bbox,
+ * row 0 (the header) is unused -- and sizes[b] = (H_b, W_b), the ORIGINAL size of image b.
+ * Semantics, all in fp64 on the fp32 inputs (the file is compiled with -ffp-contract=off), boxes y1, x1, y2, x2 normalised:
+ *   IoU(d, g): w = min(dx2, gx2) - max(dx1, gx1), h = min(dy2, gy2) - max(dy1, gy1); 0 unless w > 0 and h > 0; i = w * h;
+ *     u = area_d when g is a crowd, else area_d + area_g - i (area = (x2 - x1) * (y2 - y1)); IoU = i / u.
+ *   ignore(g, a) = t_crowd[g] or t_area[g] < lo_a or t_area[g] > hi_a, with area_ranges[2 a] = lo_a, area_ranges[2 a + 1] = hi_a.
+ *   Detections are visited per class by descending score (stable, NaN last).  For every (area range a, threshold t) the bound starts
+ *   at cur = min(thresholds[t], 1 - 1e-10).  Phase 1 walks the class's ground truths with ignore(g, a) false in index order, skips
+ *   one already matched at (a, t), and takes g when IoU >= cur, then cur = IoU (non-strict: the LATER index wins ties).  Phase 2 runs
+ *   only when phase 1 took nothing: the ground truths with ignore(g, a) true, in index order, skipping one already matched at (a, t)
+ *   unless it is a crowd, same rule.  A match consumes g at (a, t).  The detection is `ignored` at (a, t) when it matched an ignored
+ *   ground truth, or matched nothing and its pixel area ((y2 - y1) * H_b) * ((x2 - x1) * W_b) lies outside [lo_a, hi_a].
+ * Outputs, for image b in visiting order (descending score over all classes, as detr_hip_map_match):
+ *   rec_score[b][r], rec_class[b][r], rec_rank[b][r] = 0-based rank of the detection among the image's detections of its class,
+ *   rec_flags[a][b][r]: bit t = matched at (a, t), bit 16 + t = ignored at (a, t).  All Q slots are written: r >= counts[b] and
+ *   skipped detections get class -1, rank 0, flags 0 (a slot past counts[b] also score 0).
+ *   npig[c][a] += ground truths of class c with ignore(g, a) false (integer atomics; the caller zeroes it once per evaluation).
+ *   status |= DETR_MAP_BAD_* as detr_hip_map_match, DETR_COCO_BAD_SIZE for H_b <= 0 or W_b <= 0 (the size is used as it is: it only
+ *   enters the pixel area).  Nothing is accessed out of bounds.  No float atomics: a rerun is bit-identical.
+ * Limits: Q <= 1024, R <= 256, 1..DETR_COCO_MAX_THR finite thresholds, 1..DETR_COCO_MAX_AREA finite ranges lo <= hi; boxes 16-byte
+ * aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_COCO_MAX_THR 10
+#define DETR_COCO_MAX_AREA 4
+#define DETR_COCO_BAD_SIZE 16
+typedef struct {
+    int32_t B, Q, R, nb_class, n_thr, n_area;
+    const float *boxes;                          /* [B, Q, 4] y1, x1, y2, x2 */
+    const int64_t *labels;                       /* [B, Q] */
+    const float *scores;                         /* [B, Q] */
+    const int32_t *counts;                       /* [B] */
+    int64_t sD_b;                                /* rows between two images of boxes / labels / scores (>= Q) */
+    const float *t_bbox;  int64_t sT_b;          /* [B, R, 4]; floats between two images (>= 4 R) */
+    const int64_t *t_class; int64_t sC_b;        /* [B, R, 1]; elements between two images (>= R) */
+    const uint8_t *t_crowd;                      /* [B, R] */
+    const float *t_area;                         /* [B, R] */
+    int64_t sM_b;                                /* elements between two images of t_crowd / t_area (>= R) */
+    const int32_t *sizes;                        /* [B, 2] (height, width), DEVICE memory */
+    double thresholds[DETR_COCO_MAX_THR];
+    double area_ranges[2 * DETR_COCO_MAX_AREA];
+    float *rec_score;                            /* [B, Q] */
+    int32_t *rec_class;                          /* [B, Q] */
+    int32_t *rec_rank;                           /* [B, Q] */
+    uint32_t *rec_flags;                         /* [n_area, B, Q] */
+    int64_t *npig;                               /* [nb_class, n_area] */
+    int32_t *status;                             /* [1] */
+} detr_coco_match_desc;
+int detr_hip_coco_match(const detr_coco_match_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,9 @@ the same in both paths): about 18 % of the queries stay foreground, over many cl
 paths are warmed up (eager pass, graph capture, first replays), then timed alternately `rounds` times over `batches` batches
 each: host clock around eval_model, which ends in the read-back of the records (device path) or of the last image's
 detections (host path) -- and a device synchronise after it.  The two paths must return the same maps; the script fails if not.
+With --coco the same batches (plus the metadata a with_meta=True loader adds: one crowd per image, box areas, the image size) are
+also timed through protocol="coco" on the device (csrc/coco_match.hip) and on the host, alternating with the two reference-protocol
+loops in every round; the two COCO paths must return the same statistics.
 Prints one JSON line."""
 import argparse
 import json
@@ -68,6 +71,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--precision", choices=["fp32", "bf16", "fp32x3"], default="bf16")
     ap.add_argument("--configs", default="c1,b8", help="comma list of c1 (B=1, 480x640), b8 (B=8, 800x1333)")
+    ap.add_argument("--coco", action="store_true", help="also time protocol='coco' on the device and on the host")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.batches < 50:
@@ -90,18 +94,30 @@ def main():
         images = torch.from_numpy(np.random.default_rng(7).normal(size=(B, H, W, 3)).astype(np.float32)).to(dev)
         tb, tc = make_targets(model, images, cfg.background_class)
 
+        meta = None
+        if args.coco:                                                      # what a with_meta=True loader adds to a batch
+            crowd = torch.zeros(B, tb.shape[1], dtype=torch.uint8, device=dev)
+            crowd[:, 1] = (tb[:, 0, 0] > 0).to(torch.uint8)                # the first target of every image is a crowd
+            area = (tb[:, :, 2] * W * tb[:, :, 3] * H * 0.7).contiguous()
+            area[:, 0] = 0.0
+            meta = {"crowd": crowd, "area": area, "image_id": torch.arange(B, device=dev),
+                    "size": torch.tensor([[H, W]] * B, dtype=torch.int32, device=dev)}
+
         def run(how, n):
-            loader = ((images, tb, tc) for _ in range(n))
+            coco = how.startswith("coco_")
+            loader = ((images, tb, tc, meta) if coco else (images, tb, tc) for _ in range(n))
             torch.cuda.synchronize()
             t = time.perf_counter()
-            maps = eval_model(model, cfg, names, loader, print_result=False, accumulate=how)
+            maps = eval_model(model, cfg, names, loader, print_result=False, accumulate=how.replace("coco_", ""),
+                              protocol="coco" if coco else "reference")
             torch.cuda.synchronize()
             return time.perf_counter() - t, maps
 
-        maps = {how: run(how, args.warmup)[1] for how in ("host", "device")}
-        times = {"host": [], "device": []}
+        hows = ("host", "device") + (("coco_host", "coco_device") if args.coco else ())
+        maps = {how: run(how, args.warmup)[1] for how in hows}
+        times = {how: [] for how in hows}
         for _ in range(args.rounds):
-            for how in ("host", "device"):
+            for how in hows:
                 d, m = run(how, args.batches)
                 times[how].append(d)
                 maps[how] = m
@@ -117,6 +133,15 @@ def main():
             "host_median": round(med["host"], 2), "device_median": round(med["device"], 2),
             "host_ms_per_batch": round(1e3 * B / med["host"], 3), "device_ms_per_batch": round(1e3 * B / med["device"], 3),
             "device_over_host": round(med["device"] / med["host"], 4)}
+        if args.coco:
+            if maps["coco_host"] != maps["coco_device"]:
+                raise SystemExit(f"eval_throughput: the two COCO paths disagree at {key}")
+            result["configs"][key].update({
+                "coco_AP": maps["coco_host"]["AP"], "coco_AR100": maps["coco_host"]["AR100"],
+                "coco_host_images_per_s": [round(v, 2) for v in ips["coco_host"]], "coco_device_images_per_s": [round(v, 2) for v in ips["coco_device"]],
+                "coco_host_median": round(med["coco_host"], 2), "coco_device_median": round(med["coco_device"], 2),
+                "coco_device_ms_per_batch": round(1e3 * B / med["coco_device"], 3),
+                "coco_device_over_reference_device": round(med["coco_device"] / med["device"], 4)})
     line = json.dumps(result)
     print(line)
     if args.out:
