@@ -227,6 +227,19 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_detect_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_detect_desc, out_labels));
         DETR_PUT(DETR_OFF(detr_detect_desc, out_scores)); DETR_PUT(DETR_OFF(detr_detect_desc, out_query)); DETR_PUT(DETR_OFF(detr_detect_desc, counts));
         break;
+    case 200:   // detr_tile_merge_desc (the second appended list counts from 200, include/detr_hip.h)
+        DETR_PUT((int32_t)sizeof(detr_tile_merge_desc));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, B)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, N)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, Q));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, C)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, logits)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, sL_b));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, sL_q)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, boxes)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, sB_b));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, sB_q)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, tile_start)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, tile_start_host));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, windows)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, sizes)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, background_class));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, score_threshold)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, max_detections)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, bbox_format));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, clip)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, match)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, class_agnostic));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, edge_margin)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, nms_threshold)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_boxes));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_labels)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_scores)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_query));
+        DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_tile)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, counts)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, status));
+        break;
     default:
         detr::set_error("struct_layout: unknown struct %d", which);
         return -1;

@@ -116,6 +116,24 @@ class DetectDesc(Structure):
                 ("out_boxes", c_void_p), ("out_labels", c_void_p), ("out_scores", c_void_p), ("out_query", c_void_p), ("counts", c_void_p)]
 
 
+TILE_MAX_CAND = 2048                                                           # DETR_TILE_MAX_CAND
+TILE_BAD = {1: f"an image with more than {TILE_MAX_CAND} candidates (the cap of detr_hip_tile_merge: raise score_threshold or use fewer tiles)",
+            2: "a tile_start entry that is not monotone inside [0, N]"}          # DETR_TILE_OVER_CAP, DETR_TILE_BAD_START
+
+
+class TileMergeDesc(Structure):
+    """detr_tile_merge_desc (appended entry point, ABI version unchanged)."""
+    _fields_ = [("B", c_int32), ("N", c_int32), ("Q", c_int32), ("C", c_int32),
+                ("logits", c_void_p), ("sL_b", c_int64), ("sL_q", c_int64),
+                ("boxes", c_void_p), ("sB_b", c_int64), ("sB_q", c_int64),
+                ("tile_start", c_void_p), ("tile_start_host", c_void_p), ("windows", c_void_p), ("sizes", c_void_p),
+                ("background_class", c_int32), ("score_threshold", c_float), ("max_detections", c_int32),
+                ("bbox_format", c_int32), ("clip", c_int32), ("match", c_int32), ("class_agnostic", c_int32),
+                ("edge_margin", c_float), ("nms_threshold", ctypes.c_double),
+                ("out_boxes", c_void_p), ("out_labels", c_void_p), ("out_scores", c_void_p), ("out_query", c_void_p),
+                ("out_tile", c_void_p), ("counts", c_void_p), ("status", c_void_p)]
+
+
 MAP_MAX_THR = 16                                                               # DETR_MAP_MAX_THR
 MAP_BAD = {1: "a predicted label outside [0, nb_class)", 2: "a target class outside [0, nb_class)",
            4: "a target header count outside [0, R-1]", 8: "a detection count outside [0, Q]"}      # DETR_MAP_BAD_*
@@ -223,6 +241,7 @@ _SIGNATURES = {
     "detr_hip_adamw_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, f32p, c_int32, c_int32, c_void_p],
     "detr_hip_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32, c_void_p],
     "detr_hip_detect": [POINTER(DetectDesc), c_void_p],
+    "detr_hip_tile_merge": [POINTER(TileMergeDesc), c_void_p],
     "detr_hip_coco_match": [POINTER(CocoMatchDesc), c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
@@ -244,6 +263,8 @@ LAYOUT_STRUCTS = (ReduceDesc, GemmDesc, Conv3x3Desc, StemDesc, LayerNormDesc, At
                   MapMatchDesc)
 # descriptors appended after ABI 9: `which` -> mirror (numbered from 100, include/detr_hip.h)
 APPENDED_LAYOUT_STRUCTS = {100: DetectDesc}
+# the second appended list (numbered from 200: 101 stays the unknown id behind the first list)
+LATER_LAYOUT_STRUCTS = {200: TileMergeDesc}
 
 _lib = None
 
@@ -478,7 +499,7 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in list(enumerate(LAYOUT_STRUCTS)) + sorted(APPENDED_LAYOUT_STRUCTS.items()):
+    for which, S in list(enumerate(LAYOUT_STRUCTS)) + sorted(APPENDED_LAYOUT_STRUCTS.items()) + sorted(LATER_LAYOUT_STRUCTS.items()):
         want = struct_layout_mirror(S)
         buf = (c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)

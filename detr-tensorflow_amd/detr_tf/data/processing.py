@@ -203,6 +203,42 @@ class DeviceInputStage:
                    "detr_hip_augment_padded")
         return dst, mask.view(torch.bool)
 
+    def augmented_tiles(self, images_uint8, records_per_image, canvas=None, multiple=32):
+        """Sliced inference: a list of B uint8 images [h_i, w_i, 3] (host) and, per image, a LIST of transformation.PaddedRecord
+        (transformation.tile_records: windows of that image) -> (images float32 [N, H, W, 3], masks bool [N, H, W], tile_start int32
+        [B + 1]) with N the number of records, the tiles of image i at rows [tile_start[i], tile_start[i + 1]).  Every source image
+        is packed and crosses PCIe ONCE: all records of an image point at the same byte offset.  One launch of
+        csrc/augment_padded.hip; staging and canvas as in augmented_padded()."""
+        from . import transformation as T
+        srcs = [np.asarray(im) for im in images_uint8]
+        if not srcs or len(srcs) != len(records_per_image) or any(s.dtype != np.uint8 or s.ndim != 3 or s.shape[-1] != 3 for s in srcs):
+            raise TypeError("DeviceInputStage.augmented_tiles expects a non-empty list of uint8 images [h, w, 3] and one list of records per image")
+        counts = [len(recs) for recs in records_per_image]
+        records = [t for recs in records_per_image for t in recs]
+        if not records:
+            raise ValueError("augmented_tiles: no records")
+        tile_start = np.zeros(len(srcs) + 1, np.int32)
+        tile_start[1:] = np.cumsum(counts)
+        owner = np.repeat(np.arange(len(srcs)), counts)
+        if canvas is None:
+            m = max(1, int(multiple))
+            H, W = (-(-max(int(t.hd) for t in records) // m) * m, -(-max(int(t.wd) for t in records) // m) * m)
+        else:
+            H, W = int(canvas[0]), int(canvas[1])
+        for i, t in zip(owner, records):
+            if (t.h0, t.w0) != srcs[i].shape[:2]:
+                raise ValueError(f"padded record for a {t.h0} x {t.w0} image given a {srcs[i].shape[0]} x {srcs[i].shape[1]} image")
+            T.check_padded_record(t, (H, W))
+        src, total, rec, _ = self._upload_ragged(srcs, lambda offsets: (T.pack_padded_records(records, offsets[owner]),))
+        N = len(records)
+        dst = torch.empty(N, H, W, 3, dtype=torch.float32, device=self.device)
+        mask = torch.empty(N, H, W, dtype=torch.uint8, device=self.device)
+        perm = (ctypes.c_int32 * 3)(*self.perm)
+        hip._check(hip.load().detr_hip_augment_padded(src.data_ptr(), total, rec.data_ptr(), N, H, W, self.lut.data_ptr(),
+                                                      ctypes.cast(perm, ctypes.c_void_p), dst.data_ptr(), mask.data_ptr(), hip._stream()),
+                   "detr_hip_augment_padded")
+        return dst, mask.view(torch.bool), tile_start
+
     def targets(self, boxes_per_image, classes_per_image):
         """lists (one entry per image) of [n_i, 4] cx,cy,w,h boxes and [n_i] class ids -> (t_bbox [B,100,4] float32,
         t_class [B,100,1] int64) on the device, in the reference's padded layout."""

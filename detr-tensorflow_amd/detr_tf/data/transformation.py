@@ -220,6 +220,41 @@ def eval_record(h0, w0, short=800, max_size=MULTISCALE_MAX_SIZE, interp=LINEAR):
     return PaddedRecord(h0, w0, False, 0, 0, h0, w0, hd, wd, int(interp))
 
 
+def _tile_axis(length, n, num, den):
+    """(window size, origins) of n equal windows over `length` pixels: the first starts at 0, the last ends at `length`, the origins
+    are i * (length - size) // (n - 1), and `size` is the smallest one at which two neighbours share at least num * size // den
+    pixels (their largest distance is ceil((length - size) / (n - 1)))."""
+    if n == 1:
+        return length, [0]
+    size = -(-length // n)
+    while size - -(-(length - size) // (n - 1)) < num * size // den:        # size = length always passes: the distance is 0
+        size += 1
+    return size, [i * (length - size) // (n - 1) for i in range(n)]
+
+
+def tile_records(h0, w0, rows, cols, overlap=0.2, short=800, max_size=MULTISCALE_MAX_SIZE, interp=LINEAR, include_full=True):
+    """The records of sliced inference on an h0 x w0 image: rows x cols overlapping windows in row-major order, behind the whole
+    image (eval_record) when `include_full`.  All windows have ONE size (hc, wc) -- so one destination size,
+    target_size(hc, wc, short, max_size), and a uniform batch --, the first starts at 0, the last ends exactly at h0 / w0, the
+    origins are evenly spaced up to integer rounding and neighbours share at least floor(overlap * hc) rows and
+    floor(overlap * wc) columns.  Integer arithmetic only: `overlap` is read as the exact decimal fraction it prints as."""
+    from fractions import Fraction
+    h0, w0, rows, cols = int(h0), int(w0), int(rows), int(cols)
+    if h0 < 1 or w0 < 1:
+        raise ValueError(f"tile_records: bad image size {h0} x {w0}")
+    if not (1 <= rows <= h0 and 1 <= cols <= w0):
+        raise ValueError(f"tile_records: a {rows} x {cols} grid does not fit a {h0} x {w0} image (1 <= rows <= height, 1 <= cols <= width)")
+    if not (0.0 <= float(overlap) < 1.0):
+        raise ValueError(f"tile_records: overlap={overlap} must be in [0, 1)")
+    frac = Fraction(repr(float(overlap)))
+    hc, ys = _tile_axis(h0, rows, frac.numerator, frac.denominator)
+    wc, xs = _tile_axis(w0, cols, frac.numerator, frac.denominator)
+    hd, wd = target_size(hc, wc, short, max_size)
+    records = [eval_record(h0, w0, short, max_size, interp)] if include_full else []
+    records += [PaddedRecord(h0, w0, False, y, x, hc, wc, hd, wd, int(interp)) for y in ys for x in xs]
+    return records
+
+
 def check_padded_record(t, canvas=None):
     """Host validation of one padded record (the kernel also clamps, but a wrong record is a caller's bug)."""
     if t.h0 < 1 or t.w0 < 1:

@@ -9,6 +9,11 @@ eager fallback; tensors on the CPU are moved to the model's device first by the 
 `detect_batched` goes the rest of the way to what a user draws (webcam_inference.py:26-34, eval.py:41-55), in one launch of
 `detr_hip_detect` (csrc/detect.hip): score threshold, detections sorted by score with a top-k cap, boxes in PIXELS of each image's
 own original size.  `Detector` wraps the whole chain: raw uint8 images -> input stage -> model -> `detect_batched`.
+
+`merge_tiles` is the last step of SLICED inference (the model run on overlapping windows of a large image, plus the whole image):
+one launch of `detr_hip_tile_merge` (csrc/tile_merge.hip) maps every window's boxes back to image pixels and removes the duplicates
+the overlaps create with a class-wise greedy NMS.  `Detector(tiles=(rows, cols))` runs that chain; `Detector(nms_threshold=...)`
+alone puts the same NMS behind the single-pass outputs.
 """
 import math
 from ctypes import byref
@@ -152,6 +157,93 @@ def detect_batched(m_outputs: dict, sizes, background_class, *, score_threshold=
     return [Detections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k]) for b, k in enumerate(counts.tolist())]
 
 
+MATCH_MODES = {"iou": 0, "ios": 1}                   # ios: intersection over the SMALLER area
+
+
+class TiledDetections(NamedTuple):
+    """The merged detections of ONE image of sliced inference, best first: Detections' four fields plus tile [k] int32, the index
+    of the tile (within its image; 0 is the whole image with include_full) each came from -- (tile, query) names the model output row."""
+    boxes: torch.Tensor
+    labels: torch.Tensor
+    scores: torch.Tensor
+    query: torch.Tensor
+    tile: torch.Tensor
+
+
+def _check_merge_args(nms_threshold, match, edge_margin, max_detections):
+    if match not in MATCH_MODES:
+        raise ValueError(f"merge_tiles: match must be one of {tuple(MATCH_MODES)}, got {match!r}")
+    if not math.isfinite(float(nms_threshold)):
+        raise ValueError(f"merge_tiles: nms_threshold={nms_threshold} is not finite")
+    if not (math.isfinite(float(edge_margin)) and float(edge_margin) >= 0.0):
+        raise ValueError(f"merge_tiles: edge_margin={edge_margin} must be finite and >= 0")
+    if not 1 <= int(max_detections) <= hip.TILE_MAX_CAND:
+        raise ValueError(f"merge_tiles: max_detections={max_detections} must be in 1..{hip.TILE_MAX_CAND} (the candidate cap)")
+
+
+def merge_tiles(m_outputs: dict, tile_start, windows, sizes, background_class, *, score_threshold=0.0, max_detections=100,
+                bbox_format="xyxy", clip=True, nms_threshold=0.5, match="iou", class_agnostic=False, edge_margin=0.0):
+    """[TiledDetections] for every image of a sliced batch.  m_outputs holds pred_logits [N, Q, C] / pred_boxes [N, Q, 4] of all N
+    tiles, the tiles of image b at rows [tile_start[b], tile_start[b + 1]) (tile_start: host int array [B + 1], as
+    DeviceInputStage.augmented_tiles returns it); windows [N, 4] = (y0, x0, hc, wc) of every tile in pixels of its image (the fields
+    of its PaddedRecord); sizes [B, 2] = (height, width) of every ORIGINAL image.  Per image: candidates as detect_batched keeps
+    them (label != background_class, score >= score_threshold), boxes mapped to image pixels (x = x0 + x_tile * wc, ...), the edge
+    rule (edge_margin > 0: a box of a window that is not the whole image is dropped when a corner lies within edge_margin pixels of,
+    or beyond, a window edge interior to the image -- a truncated object another tile sees whole), then greedy NMS by descending
+    score (ties: lower tile, then lower query): a box is dropped when an earlier kept box of its label (any label with
+    class_agnostic) matches it by MORE than nms_threshold; match "iou", or "ios" = intersection over the smaller area, which also
+    removes a part-box lying inside the box of the whole object.  The first max_detections survivors are returned.  One launch of
+    detr_hip_tile_merge and ONE host synchronisation (counts + status).  An image with more than _hip.TILE_MAX_CAND candidates
+    raises ValueError.  CUDA inputs only."""
+    logits, boxes = m_outputs["pred_logits"], m_outputs["pred_boxes"]
+    if logits.dim() != 3 or boxes.dim() != 3 or boxes.shape[-1] != 4 or tuple(boxes.shape[:2]) != tuple(logits.shape[:2]):
+        raise RuntimeError(f"merge_tiles: expected pred_logits [N, Q, C] and pred_boxes [N, Q, 4], got {tuple(logits.shape)} and {tuple(boxes.shape)}")
+    N, Q, C = logits.shape
+    _check_detect_args(bbox_format, score_threshold, None)
+    _check_merge_args(nms_threshold, match, edge_margin, max_detections)
+    K = int(max_detections)
+    if not (logits.is_cuda and boxes.is_cuda):
+        raise RuntimeError("merge_tiles: the outputs must live on the GPU (the merge is a HIP kernel; no CPU fallback)")
+    logits, boxes = logits.float(), boxes.float()
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    if boxes.stride(-1) != 1:
+        boxes = boxes.contiguous()
+    dev = logits.device
+    start_h = np.ascontiguousarray(np.asarray(tile_start.cpu() if isinstance(tile_start, torch.Tensor) else tile_start), np.int32)
+    if start_h.ndim != 1 or start_h.shape[0] < 2:
+        raise RuntimeError(f"merge_tiles: tile_start must be [B + 1] offsets, got shape {tuple(start_h.shape)}")
+    B = start_h.shape[0] - 1
+    sizes = torch.as_tensor(sizes).to(device=dev, dtype=torch.int32).contiguous()
+    windows = torch.as_tensor(windows).to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(sizes.shape) != (B, 2) or tuple(windows.shape) != (N, 4):
+        raise RuntimeError(f"merge_tiles: sizes must be [B, 2] and windows [N, 4], got {tuple(sizes.shape)} and {tuple(windows.shape)} "
+                           f"for B={B}, N={N}")
+    start_d = torch.from_numpy(start_h).to(dev)
+    out_b = torch.empty(B, K, 4, dtype=torch.float32, device=dev)         # the kernel writes every row: detections, then zeros
+    out_l = torch.empty(B, K, dtype=torch.int64, device=dev)
+    out_s = torch.empty(B, K, dtype=torch.float32, device=dev)
+    out_q = torch.empty(B, K, dtype=torch.int32, device=dev)
+    out_t = torch.empty(B, K, dtype=torch.int32, device=dev)
+    tail = torch.zeros(B + 1, dtype=torch.int32, device=dev)              # counts [B], then the status word
+    d = hip.TileMergeDesc()
+    d.B, d.N, d.Q, d.C = B, N, Q, C
+    d.logits, d.sL_b, d.sL_q = logits.data_ptr(), logits.stride(0), logits.stride(1)
+    d.boxes, d.sB_b, d.sB_q = boxes.data_ptr(), boxes.stride(0), boxes.stride(1)
+    d.tile_start, d.tile_start_host, d.windows, d.sizes = start_d.data_ptr(), start_h.ctypes.data, windows.data_ptr(), sizes.data_ptr()
+    d.background_class, d.score_threshold = int(background_class), float(score_threshold)
+    d.max_detections, d.bbox_format, d.clip = K, DETECT_FORMATS[bbox_format], int(bool(clip))
+    d.match, d.class_agnostic, d.edge_margin, d.nms_threshold = MATCH_MODES[match], int(bool(class_agnostic)), float(edge_margin), float(nms_threshold)
+    d.out_boxes, d.out_labels, d.out_scores, d.out_query, d.out_tile = (out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), out_q.data_ptr(),
+                                                                        out_t.data_ptr())
+    d.counts, d.status = tail.data_ptr(), tail.data_ptr() + 4 * B
+    hip._check(hip.load().detr_hip_tile_merge(byref(d), hip._stream()), "detr_hip_tile_merge")
+    *counts, status = tail.tolist()
+    if status:
+        raise ValueError("merge_tiles: " + "; ".join(text for bit, text in hip.TILE_BAD.items() if status & bit))
+    return [TiledDetections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k], out_t[b, :k]) for b, k in enumerate(counts)]
+
+
 class Detector:
     """Raw images in, pixel-space detections out (what the reference's webcam_inference.py:26-34 and eval.py:41-55 assemble by hand).
 
@@ -166,12 +258,21 @@ class Detector:
     resize="fixed" (the reference's path): every image is resized to config.image_size (DeviceInputStage.images); the images of one
     call must then have one size.
     The boxes come back in pixels of each ORIGINAL image whichever way it was resized.  The remaining arguments are
-    detect_batched's; background_class defaults to config.background_class."""
+    detect_batched's; background_class defaults to config.background_class.
+
+    tiles=(rows, cols) turns on SLICED inference (resize="shortest_side" only): every image is cut into rows x cols windows that
+    overlap by `overlap` (transformation.tile_records; plus the whole image with include_full), each window is resized by the same
+    shortest-side rule, the model runs on all tiles of the call (in chunks of at most tile_batch; None: one batch) and ONE
+    merge_tiles launch maps the boxes back and removes the duplicates (nms_threshold, default 0.5 here; match, class_agnostic,
+    edge_margin: see merge_tiles).  The results are TiledDetections.  nms_threshold without tiles runs the same class-wise NMS behind
+    the single pass (one whole-image window per image).  With neither, the call is the plain path above."""
 
     RESIZE_MODES = ("shortest_side", "fixed")
 
     def __init__(self, model, config, *, background_class=None, score_threshold=0.7, max_detections=100, bbox_format="xyxy",
-                 resize="shortest_side", shortest_side=800, max_size=1333, canvas=None, interpolation="cubic"):
+                 resize="shortest_side", shortest_side=800, max_size=1333, canvas=None, interpolation="cubic",
+                 tiles=None, overlap=0.2, include_full=True, tile_batch=None, nms_threshold=None, match="iou", class_agnostic=False,
+                 edge_margin=0.0):
         from .data import processing, transformation
         if resize not in self.RESIZE_MODES:
             raise ValueError(f"Detector: resize must be one of {self.RESIZE_MODES}, got {resize!r}")
@@ -190,6 +291,22 @@ class Detector:
         self.bbox_format, self.resize, self.interpolation = bbox_format, resize, interpolation
         self.shortest_side, self.max_size = int(shortest_side), None if max_size is None else int(max_size)
         self.canvas = None if canvas is None else (int(canvas[0]), int(canvas[1]))
+        if tiles is not None:
+            if resize != "shortest_side":
+                raise ValueError(f"Detector: tiles needs resize='shortest_side', not {resize!r} (every window is resized by the shortest-side rule)")
+            tiles = (int(tiles[0]), int(tiles[1]))
+            if tiles[0] < 1 or tiles[1] < 1 or not (0.0 <= float(overlap) < 1.0):
+                raise ValueError(f"Detector: bad tiles={tiles} / overlap={overlap} (a grid of at least 1 x 1, overlap in [0, 1))")
+            if tile_batch is not None and int(tile_batch) < 1:
+                raise ValueError(f"Detector: tile_batch={tile_batch} must be positive")
+            if nms_threshold is None:
+                nms_threshold = 0.5
+        if nms_threshold is not None:
+            _check_merge_args(nms_threshold, match, edge_margin, max_detections)
+        self.tiles, self.overlap, self.include_full = tiles, float(overlap), bool(include_full)
+        self.tile_batch = None if tile_batch is None else int(tile_batch)
+        self.nms_threshold = None if nms_threshold is None else float(nms_threshold)
+        self.match, self.class_agnostic, self.edge_margin = match, bool(class_agnostic), float(edge_margin)
         self._stage = None
 
     def stage(self):
@@ -205,14 +322,50 @@ class Detector:
         interp = T.INTERP_NAMES.index(self.interpolation)
         return [T.eval_record(im.shape[0], im.shape[1], self.shortest_side, self.max_size, interp) for im in images]
 
+    def tile_records(self, images):
+        """Per image, the PaddedRecords of its tiles (tiles=(rows, cols)): transformation.tile_records."""
+        from .data import transformation as T
+        interp = T.INTERP_NAMES.index(self.interpolation)
+        return [T.tile_records(im.shape[0], im.shape[1], self.tiles[0], self.tiles[1], self.overlap, self.shortest_side, self.max_size,
+                               interp, self.include_full) for im in images]
+
+    def _merge(self, m_outputs, tile_start, windows, sizes):
+        return merge_tiles(m_outputs, tile_start, windows, sizes, self.background_class, score_threshold=self.score_threshold,
+                           max_detections=self.max_detections, bbox_format=self.bbox_format, nms_threshold=self.nms_threshold,
+                           match=self.match, class_agnostic=self.class_agnostic, edge_margin=self.edge_margin)
+
+    def _tiled(self, srcs, sizes):
+        """Sliced inference: one upload per image, the model on chunks of tiles, one merge launch."""
+        recs = self.tile_records(srcs)
+        images, masks, tile_start = self.stage().augmented_tiles(srcs, recs, canvas=self.canvas)
+        N = images.shape[0]
+        step = N if self.tile_batch is None else self.tile_batch
+        logits = boxes = None
+        for at in range(0, N, step):
+            out = self.model((images[at:at + step], masks[at:at + step]), training=False)
+            if logits is None:
+                logits = torch.empty((N,) + tuple(out["pred_logits"].shape[1:]), dtype=torch.float32, device=images.device)
+                boxes = torch.empty((N,) + tuple(out["pred_boxes"].shape[1:]), dtype=torch.float32, device=images.device)
+            logits[at:at + step] = out["pred_logits"]                  # a replayed graph reuses its output buffers: copy out
+            boxes[at:at + step] = out["pred_boxes"]
+        windows = np.array([(t.y0, t.x0, t.hc, t.wc) for r in recs for t in r], np.int32)
+        return self._merge({"pred_logits": logits, "pred_boxes": boxes}, tile_start, windows, sizes)
+
     def __call__(self, images, need_weights=None):
-        """images: one uint8 [h, w, 3] array -> Detections, or a list of them -> [Detections].  With need_weights (DetrModel.__call__)
-        the result is (detections, maps), maps as get_attention_maps returns them."""
+        """images: one uint8 [h, w, 3] array -> Detections, or a list of them -> [Detections] (TiledDetections with tiles or
+        nms_threshold).  With need_weights (DetrModel.__call__) the result is (detections, maps), maps as get_attention_maps returns
+        them; not with tiles."""
         single = not isinstance(images, (list, tuple))
         srcs = [np.asarray(im) for im in ([images] if single else images)]
         if not srcs or any(s.dtype != np.uint8 or s.ndim != 3 or s.shape[-1] != 3 for s in srcs):
             raise TypeError("Detector expects a uint8 image [h, w, 3] or a non-empty list of them")
         sizes = np.array([s.shape[:2] for s in srcs], np.int32)
+        if self.tiles is not None:
+            if need_weights:
+                raise NotImplementedError("Detector: need_weights with tiles: there is one attention map per tile and no single image to "
+                                          "overlay it on; call the model on DeviceInputStage.augmented_tiles yourself")
+            detections = self._tiled(srcs, sizes)
+            return detections[0] if single else detections
         if self.resize == "fixed":
             if (sizes != sizes[0]).any():
                 raise ValueError(f"Detector: resize='fixed' takes images of ONE size per call, got {sorted(set(map(tuple, sizes.tolist())))}; "
@@ -223,8 +376,12 @@ class Detector:
             inputs = self.stage().augmented_padded(srcs, self.records(srcs), canvas=self.canvas)
             shape = inputs[0].shape
         m_outputs = self.model(inputs, training=False, need_weights=need_weights)
-        detections = detect_batched(m_outputs, sizes, self.background_class, score_threshold=self.score_threshold,
-                                    max_detections=self.max_detections, bbox_format=self.bbox_format)
+        if self.nms_threshold is not None:                              # one whole-image window per image
+            windows = np.concatenate([np.zeros_like(sizes), sizes], 1)
+            detections = self._merge(m_outputs, np.arange(len(srcs) + 1, dtype=np.int32), windows, sizes)
+        else:
+            detections = detect_batched(m_outputs, sizes, self.background_class, score_threshold=self.score_threshold,
+                                        max_detections=self.max_detections, bbox_format=self.bbox_format)
         detections = detections[0] if single else detections
         if "attn" in m_outputs:
             return detections, _feature_maps(self.model, shape, m_outputs["attn"])
@@ -236,7 +393,7 @@ class Detector:
         sequence indexed by label; None: the label itself).  One copy to the host for the whole list."""
         if self.bbox_format != "xywh":
             raise ValueError(f"to_coco_results: COCO boxes are [x, y, w, h]: build the Detector with bbox_format='xywh', not {self.bbox_format!r}")
-        if isinstance(detections, Detections):
+        if isinstance(detections, (Detections, TiledDetections)):
             detections, image_ids = [detections], [image_ids]
         if len(detections) != len(image_ids):
             raise ValueError(f"to_coco_results: {len(detections)} images of detections, {len(image_ids)} image ids")

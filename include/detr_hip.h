@@ -40,7 +40,8 @@ int detr_hip_reload_tuning(void);
  * (0 detr_reduce_desc, 1 detr_gemm_desc, 2 detr_conv3x3_desc, 3 detr_stem_desc, 4 detr_layernorm_desc, 5 detr_attn_desc,
  * 6 detr_setloss_desc, 7 detr_input_desc, 8 detr_postprocess_desc, 9 detr_map_match_desc) writes out[0] = sizeof, out[1..] = offsetof of every field in
  * declaration order, and returns the number of values (negative: unknown struct).  Descriptors appended after ABI 9 are numbered
- * from 100 (100 detr_detect_desc): binders probe the id behind the last one they know to find the end of the first list. */
+ * from 100 (100 detr_detect_desc): binders probe the id behind the last one they know to find the end of the first list.  A second
+ * appended list counts from 200 (200 detr_tile_merge_desc), so that 101 stays the unknown id behind the first one. */
 int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap);
 /* zero fill of accumulators (an ordinary kernel: a captured hipMemsetAsync node did not replay reliably) */
 int detr_hip_memset_zero(void *ptr, size_t bytes, void *stream);
@@ -766,6 +767,63 @@ typedef struct {
     int32_t *status;                             /* [1] */
 } detr_coco_match_desc;
 int detr_hip_coco_match(const detr_coco_match_desc *d, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Cross-tile merge of sliced inference, appended (the ABI version is unchanged):
+ *   replaces: the host loop a user of get_model_inference writes to run a model on overlapping windows of a large image -- boxes
+ *             of every window mapped back to the image, sorted, duplicates removed by a class-wise greedy NMS.
+ * One launch per batch, one workgroup per image (csrc/tile_merge.hip), Q <= 1024.  The N rows of logits / boxes are the tiles of
+ * all B images, the tiles of image b at rows [tile_start[b], tile_start[b + 1]); windows[n] = (y0, x0, hc, wc) is tile n's window
+ * in pixels of its image, sizes[b] = (H_b, W_b).  Per image, in this order:
+ *   1. candidates: score / label per query as detr_hip_detect (bit-identical); kept when label != background_class and
+ *      score >= score_threshold; ordered by (tile, query).
+ *   2. mapping, every operation ONE fp32 rounding: cx = x0 + bx * wc, cy = y0 + by * hc, w = bw * wc, h = bh * hc, corners
+ *      c -+ size * 0.5; clip = 1 clamps the corners to [0, W_b] x [0, H_b].  A window that is the whole image gives
+ *      detr_hip_detect's bits.
+ *   3. edge rule (edge_margin > 0): a candidate of a window that is not the whole image is dropped when an UNCLIPPED corner lies
+ *      within edge_margin pixels of -- or beyond -- a window edge that is interior to the image: x_lo - x0 <= edge_margin with
+ *      x0 > 0, (x0 + wc) - x_hi <= edge_margin with x0 + wc < W_b, and the same in y (differences in fp32).
+ *   4. order: descending score, ties by lower tile, then lower query.
+ *   5. greedy suppression in that order: a candidate is dropped when an earlier KEPT candidate of the same label (any label with
+ *      class_agnostic) matches it by more than nms_threshold (strict).  The measure is fp64 on the fp32 corners of step 2:
+ *      inter = max(0, min(x1) - max(x0)) * max(0, min(y1) - max(y0)), area = (x1 - x0) * (y1 - y0);
+ *      match 0: inter / (area_i + area_j - inter), match 1: inter / min(area_i, area_j); a zero denominator gives 0.
+ *   6. the first max_detections survivors are written at rows [b * max_detections, ...) in bbox_format (as detr_hip_detect;
+ *      format 0 is cx, cy, w, h of step 2), with out_tile the tile's index within its image; counts[b] of them, then zeros.
+ * An image with more than DETR_TILE_MAX_CAND candidates after step 3 sets DETR_TILE_OVER_CAP in *status (the caller zeroes it) and
+ * gets counts[b] = 0 and zero rows; a device tile_start entry that is not monotone inside [0, N] sets DETR_TILE_BAD_START, same
+ * outcome.  Nothing is accessed out of bounds.  No float atomics: a rerun is bit-identical.  out_boxes 16-byte aligned.
+ * tile_start_host is the HOST copy of tile_start: it is what this entry point validates (monotone, [0] == 0, [B] == N).
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_TILE_MAX_CAND 2048
+#define DETR_TILE_OVER_CAP 1
+#define DETR_TILE_BAD_START 2
+typedef struct {
+    int32_t B, N, Q, C;
+    const float *logits; int64_t sL_b, sL_q;     /* [N, Q, C], unit class stride */
+    const float *boxes;  int64_t sB_b, sB_q;     /* [N, Q, 4] cx, cy, w, h normalised to the tile */
+    const int32_t *tile_start;                   /* [B + 1], DEVICE memory */
+    const int32_t *tile_start_host;              /* [B + 1], HOST memory, the same values */
+    const int32_t *windows;                      /* [N, 4] (y0, x0, hc, wc), DEVICE memory */
+    const int32_t *sizes;                        /* [B, 2] (height, width), DEVICE memory */
+    int32_t background_class;
+    float score_threshold;                       /* finite */
+    int32_t max_detections;                      /* 1..DETR_TILE_MAX_CAND */
+    int32_t bbox_format;                         /* 0..3, as detr_detect_desc */
+    int32_t clip;                                /* 0 | 1 */
+    int32_t match;                               /* 0 IoU | 1 intersection over the smaller area */
+    int32_t class_agnostic;                      /* 0 | 1 */
+    float edge_margin;                           /* pixels, finite, >= 0 */
+    double nms_threshold;                        /* finite */
+    float *out_boxes;                            /* [B, max_detections, 4] */
+    int64_t *out_labels;                         /* [B, max_detections] */
+    float *out_scores;                           /* [B, max_detections] */
+    int32_t *out_query;                          /* [B, max_detections] */
+    int32_t *out_tile;                           /* [B, max_detections] */
+    int32_t *counts;                             /* [B] */
+    int32_t *status;                             /* [1] */
+} detr_tile_merge_desc;
+int detr_hip_tile_merge(const detr_tile_merge_desc *d, void *stream);
 
 #ifdef __cplusplus
 }
