@@ -613,9 +613,23 @@ extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int3
     DETR_REQUIRE(P > 0 && Q > 0 && Q <= SL_MAXQ && R > 1 && R <= SL_MAXR && ldc >= R - 1 && B > 0 && P % B == 0,
                  "assign: bad shape P=%d Q=%d ldc=%d B=%d R=%d", P, Q, ldc, B, R);
     const int nmax = (R + 1) & ~1;
-    const bool cd = Q <= 128 && (size_t)nmax * 12 + (size_t)(R - 1) * 129 * 8 <= 150 * 1024;   // cost tile as doubles, row stride 129
+    // cost tile as doubles, row stride 129, whenever the columns fit two slots: with R <= SL_MAXR that tile and the row state
+    // take at most 128 * 12 + 127 * 129 * 8 = 132 600 bytes, so Q <= 128 never needs the float tile
+    const bool cd = Q <= 128;
     const size_t tile = (size_t)(R - 1) * (size_t)(cd ? 129 : (Q + 63) / 64 * 64 + 1);
     const size_t smem = (size_t)nmax * 8 + (size_t)nmax * 4 + tile * (cd ? 8 : 4);
+    // the shape check above admits more than a workgroup's LDS holds (Q = 512, R = 128: 262 140 bytes): refused here, before
+    // any attribute call or launch
+    static int lds_limit = 0;                   // per-workgroup LDS of the current device, queried once
+    if (lds_limit == 0) {
+        int dev = 0, v = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+        DETR_REQUIRE(e == hipSuccess && v > 0, "assign: cannot query the LDS size: %s", hipGetErrorString(e));
+        lds_limit = v;
+    }
+    DETR_REQUIRE(smem <= (size_t)lds_limit, "assign: Q=%d R=%d needs %zu bytes of LDS, the device has %d per workgroup", Q, R,
+                 smem, lds_limit);
     hipStream_t s = (hipStream_t)stream;
     const int cpl = (Q + 63) / 64;
 #define DETR_ASSIGN_LAUNCH(MC, CD)                                                                                   \
@@ -628,8 +642,7 @@ extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int3
         hipLaunchKernelGGL((assign_kernel<MC, CD>), dim3(P), dim3(64), smem, s, cost, Q, ldc, t_bbox, B, R,          \
                            tgt_for_pred, pred_for_tgt, status);                                                      \
     } while (0)
-    if (cpl <= 2 && cd) DETR_ASSIGN_LAUNCH(2, true);
-    else if (cpl <= 2) DETR_ASSIGN_LAUNCH(2, false);
+    if (cd) DETR_ASSIGN_LAUNCH(2, true);
     else if (cpl <= 5) DETR_ASSIGN_LAUNCH(5, false);
     else DETR_ASSIGN_LAUNCH(8, false);
 #undef DETR_ASSIGN_LAUNCH
