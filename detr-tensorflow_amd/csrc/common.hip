@@ -240,6 +240,24 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_labels)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_scores)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_query));
         DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_tile)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, counts)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, status));
         break;
+    case 300:   // detr_overlay_desc (the third appended list counts from 300, include/detr_hip.h)
+        DETR_PUT((int32_t)sizeof(detr_overlay_desc));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, B)); DETR_PUT(DETR_OFF(detr_overlay_desc, D)); DETR_PUT(DETR_OFF(detr_overlay_desc, src));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, src_off)); DETR_PUT(DETR_OFF(detr_overlay_desc, dst)); DETR_PUT(DETR_OFF(detr_overlay_desc, dst_off));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, sizes)); DETR_PUT(DETR_OFF(detr_overlay_desc, sizes_host)); DETR_PUT(DETR_OFF(detr_overlay_desc, boxes));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, labels)); DETR_PUT(DETR_OFF(detr_overlay_desc, scores)); DETR_PUT(DETR_OFF(detr_overlay_desc, counts));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, thickness)); DETR_PUT(DETR_OFF(detr_overlay_desc, label_alpha)); DETR_PUT(DETR_OFF(detr_overlay_desc, fill_alpha));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, colors)); DETR_PUT(DETR_OFF(detr_overlay_desc, n_colors)); DETR_PUT(DETR_OFF(detr_overlay_desc, names));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, name_len)); DETR_PUT(DETR_OFF(detr_overlay_desc, n_names)); DETR_PUT(DETR_OFF(detr_overlay_desc, name_cap));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, atlas)); DETR_PUT(DETR_OFF(detr_overlay_desc, n_glyph)); DETR_PUT(DETR_OFF(detr_overlay_desc, gh));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, gw)); DETR_PUT(DETR_OFF(detr_overlay_desc, glyph_digit0)); DETR_PUT(DETR_OFF(detr_overlay_desc, glyph_colon));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, glyph_dot)); DETR_PUT(DETR_OFF(detr_overlay_desc, scale)); DETR_PUT(DETR_OFF(detr_overlay_desc, heat));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, sH_b)); DETR_PUT(DETR_OFF(detr_overlay_desc, sH_y)); DETR_PUT(DETR_OFF(detr_overlay_desc, sH_x));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, Hf)); DETR_PUT(DETR_OFF(detr_overlay_desc, Wf)); DETR_PUT(DETR_OFF(detr_overlay_desc, map_step));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, map_valid)); DETR_PUT(DETR_OFF(detr_overlay_desc, map_scale)); DETR_PUT(DETR_OFF(detr_overlay_desc, lut));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, heat_alpha)); DETR_PUT(DETR_OFF(detr_overlay_desc, workspace)); DETR_PUT(DETR_OFF(detr_overlay_desc, workspace_bytes));
+        DETR_PUT(DETR_OFF(detr_overlay_desc, status));
+        break;
     default:
         detr::set_error("struct_layout: unknown struct %d", which);
         return -1;

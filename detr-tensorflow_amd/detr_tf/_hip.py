@@ -134,6 +134,28 @@ class TileMergeDesc(Structure):
                 ("out_tile", c_void_p), ("counts", c_void_p), ("status", c_void_p)]
 
 
+OVERLAY_MAX_SCALE, OVERLAY_MAX_GLYPH, OVERLAY_MAX_NAME = 64, 64, 251             # DETR_OVERLAY_MAX_SCALE / _GLYPH / _NAME
+OVERLAY_MAX_SIDE, OVERLAY_MAX_THICKNESS = 32768, 1024                          # DETR_OVERLAY_MAX_SIDE / _THICKNESS
+OVERLAY_BAD = {1: "a detection count outside [0, D]"}                          # DETR_OVERLAY_BAD_COUNT
+
+
+class OverlayDesc(Structure):
+    """detr_overlay_desc (appended entry point, ABI version unchanged)."""
+    _fields_ = [("B", c_int32), ("D", c_int32),
+                ("src", c_void_p), ("src_off", c_void_p), ("dst", c_void_p), ("dst_off", c_void_p),
+                ("sizes", c_void_p), ("sizes_host", c_void_p),
+                ("boxes", c_void_p), ("labels", c_void_p), ("scores", c_void_p), ("counts", c_void_p),
+                ("thickness", c_int32), ("label_alpha", c_int32), ("fill_alpha", c_int32),
+                ("colors", c_void_p), ("n_colors", c_int32),
+                ("names", c_void_p), ("name_len", c_void_p), ("n_names", c_int32), ("name_cap", c_int32),
+                ("atlas", c_void_p), ("n_glyph", c_int32), ("gh", c_int32), ("gw", c_int32),
+                ("glyph_digit0", c_int32), ("glyph_colon", c_int32), ("glyph_dot", c_int32),
+                ("scale", c_void_p),
+                ("heat", c_void_p), ("sH_b", c_int64), ("sH_y", c_int64), ("sH_x", c_int64), ("Hf", c_int32), ("Wf", c_int32),
+                ("map_step", c_void_p), ("map_valid", c_void_p), ("map_scale", c_void_p), ("lut", c_void_p), ("heat_alpha", c_int32),
+                ("workspace", c_void_p), ("workspace_bytes", c_int64), ("status", c_void_p)]
+
+
 MAP_MAX_THR = 16                                                               # DETR_MAP_MAX_THR
 MAP_BAD = {1: "a predicted label outside [0, nb_class)", 2: "a target class outside [0, nb_class)",
            4: "a target header count outside [0, R-1]", 8: "a detection count outside [0, Q]"}      # DETR_MAP_BAD_*
@@ -244,6 +266,10 @@ _SIGNATURES = {
     "detr_hip_tile_merge": [POINTER(TileMergeDesc), c_void_p],
     "detr_hip_coco_match": [POINTER(CocoMatchDesc), c_void_p],
 }
+# entry points appended behind detr_hip_coco_match (its test pins it as the last of the table above)
+_SIGNATURES_LATER = {
+    "detr_hip_overlay": [POINTER(OverlayDesc), c_void_p],
+}
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
     "detr_hip_attention_dropmask_words": [c_int32, c_int32, c_int32, c_int32],
@@ -255,8 +281,9 @@ _SIGNATURES_I64 = {
     "detr_hip_workspace_bytes_stem": [POINTER(StemDesc), c_int32],
     "detr_hip_workspace_bytes_layernorm": [POINTER(LayerNormDesc)],
     "detr_hip_workspace_bytes_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32],
+    "detr_hip_workspace_bytes_overlay": [POINTER(OverlayDesc)],
 }
-EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
+EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_LATER) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
 # order of detr_hip_struct_layout's `which`
 LAYOUT_STRUCTS = (ReduceDesc, GemmDesc, Conv3x3Desc, StemDesc, LayerNormDesc, AttnDesc, SetLossDesc, InputDesc, PostprocessDesc,
@@ -265,6 +292,8 @@ LAYOUT_STRUCTS = (ReduceDesc, GemmDesc, Conv3x3Desc, StemDesc, LayerNormDesc, At
 APPENDED_LAYOUT_STRUCTS = {100: DetectDesc}
 # the second appended list (numbered from 200: 101 stays the unknown id behind the first list)
 LATER_LAYOUT_STRUCTS = {200: TileMergeDesc}
+# the third one (numbered from 300; the two above are pinned by their tests, so a new descriptor gets a registry of its own)
+EXTRA_LAYOUT_STRUCTS = {300: OverlayDesc}
 
 _lib = None
 
@@ -474,7 +503,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or `make -C detr-tensorflow_amd`) first; there is no CPU/eager fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in list(_SIGNATURES.items()) + list(_SIGNATURES_LATER.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_int32
@@ -499,7 +528,8 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in list(enumerate(LAYOUT_STRUCTS)) + sorted(APPENDED_LAYOUT_STRUCTS.items()) + sorted(LATER_LAYOUT_STRUCTS.items()):
+    for which, S in (list(enumerate(LAYOUT_STRUCTS)) + sorted(APPENDED_LAYOUT_STRUCTS.items()) + sorted(LATER_LAYOUT_STRUCTS.items())
+                     + sorted(EXTRA_LAYOUT_STRUCTS.items())):
         want = struct_layout_mirror(S)
         buf = (c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)

@@ -74,6 +74,7 @@ class DeviceInputStage:
         self.lut = torch.from_numpy(lut).to(self.device)
         self.interpolation = INTERPOLATIONS[interpolation]
         self._aug_img = self._aug_rec = self._aug_event = None         # augmented(): pinned staging buffers, last copy's event
+        self.last_upload = None                                        # overlay.RaggedFrames of the last ragged batch: its frames stay on the device
         hip.load()
 
     def images(self, batch_uint8, out=None):
@@ -148,6 +149,8 @@ class DeviceInputStage:
         rec = self._aug_rec[:rec_bytes].to(self.device, non_blocking=True)
         self._aug_event = torch.cuda.Event()
         self._aug_event.record()
+        from ..overlay import RaggedFrames
+        self.last_upload = RaggedFrames(src, offsets, [s.shape[:2] for s in srcs])      # Detector.draw(images=None) draws on these
         return src, total, rec, recs
 
     def augmented(self, images_uint8, records):

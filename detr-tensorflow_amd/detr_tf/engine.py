@@ -120,6 +120,11 @@ def feature_size(H, W, replace_stride_with_dilation=None):
     return H, W
 
 
+def backbone_stride(replace_stride_with_dilation=None):
+    """Input pixels per feature-map cell: 4 for the stem and the max-pool, times 2 for every stage of layer2..4 that keeps its stride."""
+    return 4 * 2 ** sum(1 for f in dilation_flags(replace_stride_with_dilation) if not f)
+
+
 class DetrEngine:
     def __init__(self, device="cuda:0", blocks=RESNET50_BLOCKS, num_enc=6, num_dec=6, num_queries=100,
                  num_classes=92, nb_class=None, seed=0, tf_backbone=False, replace_stride_with_dilation=(False, False, False)):

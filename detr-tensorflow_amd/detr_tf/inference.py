@@ -14,6 +14,9 @@ own original size.  `Detector` wraps the whole chain: raw uint8 images -> input 
 one launch of `detr_hip_tile_merge` (csrc/tile_merge.hip) maps every window's boxes back to image pixels and removes the duplicates
 the overlaps create with a class-wise greedy NMS.  `Detector(tiles=(rows, cols))` runs that chain; `Detector(nms_threshold=...)`
 alone puts the same NMS behind the single-pass outputs.
+
+`draw_detections` / `numpy_bbox_to_image` (detr_tf/overlay.py; reference inference.py:10-65) draw boxes, labels and an attention heat map
+onto the frames in one call of `detr_hip_overlay` (csrc/overlay.hip); `Detector.draw` feeds it the detector's own frames and maps.
 """
 import math
 from ctypes import byref
@@ -23,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _hip as hip
+from .overlay import class_palette, draw_detections, numpy_bbox_to_image  # noqa: F401  (the reference keeps them in inference.py)
 
 BBOX_FORMATS = {"xy_center": 0, "xyxy": 1, "yxyx": 2}
 DETECT_FORMATS = {"xy_center": 0, "xyxy": 1, "yxyx": 2, "xywh": 3}       # xywh: top-left + width / height, the COCO results form
@@ -308,6 +312,7 @@ class Detector:
         self.nms_threshold = None if nms_threshold is None else float(nms_threshold)
         self.match, self.class_agnostic, self.edge_margin = match, bool(class_agnostic), float(edge_margin)
         self._stage = None
+        self._last_frames = None                     # the frames of the last call: draw(images=None) draws on them
 
     def stage(self):
         if self._stage is None:
@@ -365,6 +370,7 @@ class Detector:
                 raise NotImplementedError("Detector: need_weights with tiles: there is one attention map per tile and no single image to "
                                           "overlay it on; call the model on DeviceInputStage.augmented_tiles yourself")
             detections = self._tiled(srcs, sizes)
+            self._last_frames = self.stage().last_upload
             return detections[0] if single else detections
         if self.resize == "fixed":
             if (sizes != sizes[0]).any():
@@ -372,9 +378,11 @@ class Detector:
                                  "resize='shortest_side' batches mixed sizes")
             inputs = self.stage().images(np.stack(srcs))
             shape = inputs.shape
+            self._last_frames = srcs                                    # (this path uploads one dense batch: kept on the host)
         else:
             inputs = self.stage().augmented_padded(srcs, self.records(srcs), canvas=self.canvas)
             shape = inputs[0].shape
+            self._last_frames = self.stage().last_upload                # already on the device: they cross PCIe once
         m_outputs = self.model(inputs, training=False, need_weights=need_weights)
         if self.nms_threshold is not None:                              # one whole-image window per image
             windows = np.concatenate([np.zeros_like(sizes), sizes], 1)
@@ -386,6 +394,62 @@ class Detector:
         if "attn" in m_outputs:
             return detections, _feature_maps(self.model, shape, m_outputs["attn"])
         return detections
+
+    def attention_site(self, site="dec"):
+        """The key of `maps` a site names: "dec" = the last decoder cross-attention (one row per object query), "enc" = the last
+        encoder self-attention; anything else is taken as the key itself."""
+        sites = self.model.default_attn_sites()
+        for name in sites:
+            if (site == "dec" and "/decoder/" in name) or (site == "enc" and "/encoder/" in name):
+                return name
+        return site
+
+    def heat_map(self, detections, maps, sizes, site="dec"):
+        """(heat [B, Hf, Wf], heat_scale [B], heat_extent [B, 2]) for draw_detections: per image the sum of the rows
+        Detections.query of maps[site] [B, Q, Hf, Wf], 1 / its maximum (0 for an all-zero map) -- both computed on the device, nothing
+        is read back -- and the part of the map the image covers: its resized hd x wd inside the canvas divided by the backbone's
+        total stride (engine.backbone_stride); the whole map with resize="fixed".  sizes [B, 2]: (height, width) of the frames."""
+        from .engine import backbone_stride
+        m = maps[self.attention_site(site)]
+        if m.dim() != 4 or m.shape[0] != len(detections):
+            raise ValueError(f"Detector.heat_map: maps[{site!r}] must be [B={len(detections)}, Q, Hf, Wf], got {tuple(m.shape)}")
+        heat = torch.stack([m[b].index_select(0, d.query.to(torch.int64)).sum(0) for b, d in enumerate(detections)]).float().contiguous()
+        peak = heat.amax(dim=(1, 2))
+        scale = torch.where(peak > 0, 1.0 / peak, torch.zeros_like(peak))
+        Hf, Wf = int(m.shape[2]), int(m.shape[3])
+        if self.resize == "fixed":
+            extent = [(Hf, Wf)] * len(detections)
+        else:
+            from .data import transformation as T
+            stride = backbone_stride(self.model.engine.dilate)
+            interp = T.INTERP_NAMES.index(self.interpolation)
+            recs = [T.eval_record(int(h), int(w), self.shortest_side, self.max_size, interp) for h, w in np.asarray(sizes).tolist()]
+            extent = [(r.hd / stride, r.wd / stride) for r in recs]
+        return heat, scale, extent
+
+    def draw(self, images, detections, class_names, maps=None, site="dec", **kw):
+        """The frames with `detections` (this detector's own output) drawn on them: draw_detections' list of uint8 device tensors.
+        images=None draws on the frames of the detector's last call, which are still on the device.  maps (the second value of a
+        call with need_weights) puts the attention of the drawn detections under the boxes as a heat map: heat_map(..., site).  Tiled
+        results draw like plain ones; maps with tiles stays refused.  Further keywords are draw_detections'."""
+        if self.bbox_format != "xyxy":
+            raise ValueError(f"Detector.draw: boxes must be 'xyxy' pixels: build the Detector with bbox_format='xyxy', not {self.bbox_format!r}")
+        if maps is not None and self.tiles is not None:
+            raise NotImplementedError("Detector.draw: maps with tiles: there is one attention map per tile and no single image to overlay it on")
+        if images is None:
+            images = self._last_frames
+            if images is None:
+                raise ValueError("Detector.draw: images=None draws on the frames of the last call, and there has been none")
+        elif isinstance(images, np.ndarray) and images.ndim == 3:
+            images = [images]
+        single = isinstance(detections, (Detections, TiledDetections))
+        dets = [detections] if single else list(detections)
+        if maps is not None:
+            sizes = images.sizes if hasattr(images, "sizes") else [im.shape[:2] for im in images]
+            heat, scale, extent = self.heat_map(dets, maps, sizes, site)
+            kw = dict(kw, heat=heat, heat_scale=scale, heat_extent=extent)
+        out = draw_detections(images, dets, class_names, **kw)
+        return out[0] if single else out
 
     def to_coco_results(self, detections, image_ids, category_ids=None):
         """COCO results records [{"image_id", "category_id", "bbox": [x, y, w, h], "score"}] (Python numbers) of the detections

@@ -825,6 +825,94 @@ typedef struct {
 } detr_tile_merge_desc;
 int detr_hip_tile_merge(const detr_tile_merge_desc *d, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Detections and attention heat maps drawn onto frames, appended (the ABI version is unchanged):
+ *   replaces: numpy_bbox_to_image (detr_tf/inference.py:10-65) -- cv2.rectangle / cv2.putText per box on the host -- and the
+ *             matplotlib overlay of an attention map the notebooks do.  Deviations: a bitmap font passed as an atlas, colours from a
+ *             table, outlines that grow inwards.  Pixel parity with OpenCV is not claimed.
+ * One call annotates a ragged batch of uint8 RGB frames in at most two launches (csrc/overlay.hip: a preparation launch, one workgroup
+ * per image, writes an ordered command list into `workspace`; a raster launch, one workgroup per run of 1024 pixels, applies it), no
+ * host synchronisation, no atomics except the integer OR on *status, vector stores only: a rerun is bit-identical.
+ * Frames: image b is [H_b, W_b, 3] bytes at src + src_off[b] (any alignment) and is written to dst + dst_off[b] (any alignment; a
+ *   4-byte aligned image is stored a dword at a time).  sizes[b] = (H_b, W_b) in DEVICE memory; sizes_host holds the same values in
+ *   HOST memory and is what this entry point validates and sizes its grid with.  dst == src with dst_off == src_off is allowed: every
+ *   output pixel depends on its own source pixel only.  Any other overlap of the two is the caller's error.
+ * Detections: what detr_hip_detect / detr_hip_tile_merge write with bbox_format 1: boxes [B, D, 4] fp32 x0, y0, x1, y1 in pixels,
+ *   labels [B, D] int64, scores [B, D] fp32 or NULL, counts [B] int32 (DEVICE; a value outside [0, D] is clamped and sets
+ *   DETR_OVERLAY_BAD_COUNT in *status, which the caller zeroes).  D <= DETR_TILE_MAX_CAND.
+ * Geometry, all integer: x1 = clamp(floor(bx0), 0, W - 1), x2 = clamp(floor(bx1), 0, W - 1), y1, y2 likewise with H.  A box with a
+ *   non-finite corner, with bx1 < bx0 or by1 < by0, or with a negative label is skipped.  Paint order: descending integer area
+ *   (x2 - x1) * (y2 - y1), ties by ascending detection index; the smallest box is painted last and ends up on top.
+ * Per box, with t = thickness, s = clamp(scale[b], 1, DETR_OVERLAY_MAX_SCALE) and colour = colors[label % n_colors], in this order:
+ *   1. interior tint: colour blended with fill_alpha over [x1, x2] x [y1, y2];
+ *   2. label background: colour blended with label_alpha over the label rectangle;
+ *   3. label text, opaque: black when 299 R + 587 G + 114 B >= 128000 for the colour, else white;
+ *   4. outline, opaque colour: the pixels of [x1, x2] x [y1, y2] outside [x1 + t, x2 - t] x [y1 + t, y2 - t] (a box thinner than
+ *      2 t is all outline; the outline never leaves the image).
+ *   blend(c, p, a) = (c * a + p * (255 - a) + 127) / 255 in integers, per channel.
+ * Label text: the glyph indices names[label][0 .. name_len[label]) when 0 <= label < n_names (name_len clamped to [0, name_cap]),
+ *   then, with scores, glyph_colon (only behind a name) and d.dd: q = rint((double)score * 100.0) (half to even; the product is
+ *   exact), clamped to [0, 999], NaN -> 0; the digits q / 100, glyph_dot, q / 10 % 10, q % 10, each digit as glyph_digit0 + digit.
+ *   A label outside [0, n_names) without scores has no label rectangle.  Label rectangle: pad = t + s, width = n_chars * gw * s +
+ *   2 pad, height = gh * s + 2 pad, origin (max(0, min(x1, W - width)), max(0, min(y1, H - height))), cut by the image; text origin =
+ *   origin + (pad, pad).  Font: atlas [n_glyph, gh, gw] bytes, non-zero = ink, every font pixel an s x s block; a glyph index
+ *   >= n_glyph draws nothing.
+ * Heat map (all of heat, map_step, map_valid, map_scale, lut given, or none), applied to the source pixel before any box.  For pixel
+ *   (y, x) of image b, with (sy, sx) = map_step[b], (vh, vw) = map_valid[b] clamped to [1, Hf] x [1, Wf], every fp32 operation
+ *   rounded once, in this order (the file is compiled with -ffp-contract=off):
+ *     fy = ((float)y + 0.5f) * sy - 0.5f; fy = min(max(fy, 0), (float)(vh - 1)); y0 = (int)floorf(fy); wy = fy - (float)y0;
+ *     y1 = min(y0 + 1, vh - 1); the same in x;  m_rc = heat[b][y_r][x_c];
+ *     top = m00 + wx * (m01 - m00); bot = m10 + wx * (m11 - m10); m = top + wy * (bot - top);
+ *     v = m * map_scale[b]; v = v > 0 ? min(v, 1) : 0 (NaN -> 0);
+ *     pixel = blend(lut[(int)(v * 255.0f + 0.5f)], pixel, (int)(v * (float)heat_alpha + 0.5f)).   v = 0 leaves the bytes unchanged.
+ * workspace: detr_hip_workspace_bytes_overlay(d) bytes (reads B, D, name_cap only; negative = malformed), 16-byte aligned.
+ * Limits: B 1..65535, D 1..DETR_TILE_MAX_CAND, H_b, W_b 1..DETR_OVERLAY_MAX_SIDE, thickness 1..DETR_OVERLAY_MAX_THICKNESS,
+ *   gw, gh 1..DETR_OVERLAY_MAX_GLYPH, name_cap 1..DETR_OVERLAY_MAX_NAME, n_colors >= 1, n_glyph >= 1, alphas 0..255.
+ * Nothing is read or written out of bounds for any label, score, count, glyph index or scale.
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_OVERLAY_BAD_COUNT 1
+#define DETR_OVERLAY_MAX_SCALE 64
+#define DETR_OVERLAY_MAX_GLYPH 64
+#define DETR_OVERLAY_MAX_NAME 251
+#define DETR_OVERLAY_MAX_SIDE 32768
+#define DETR_OVERLAY_MAX_THICKNESS 1024
+typedef struct {
+    int32_t B, D;
+    const uint8_t *src;                          /* packed frames */
+    const int64_t *src_off;                      /* [B] byte offsets, DEVICE memory */
+    uint8_t *dst;
+    const int64_t *dst_off;                      /* [B] byte offsets, DEVICE memory */
+    const int32_t *sizes;                        /* [B, 2] (height, width), DEVICE memory */
+    const int32_t *sizes_host;                   /* [B, 2], HOST memory, the same values */
+    const float *boxes;                          /* [B, D, 4] x0, y0, x1, y1 in pixels */
+    const int64_t *labels;                       /* [B, D] */
+    const float *scores;                         /* [B, D] or NULL */
+    const int32_t *counts;                       /* [B], DEVICE memory */
+    int32_t thickness, label_alpha, fill_alpha;
+    const uint8_t *colors;                       /* [n_colors, 3] */
+    int32_t n_colors;
+    const uint8_t *names;                        /* [n_names, name_cap] glyph indices (NULL with n_names == 0) */
+    const int32_t *name_len;                     /* [n_names] */
+    int32_t n_names, name_cap;
+    const uint8_t *atlas;                        /* [n_glyph, gh, gw] */
+    int32_t n_glyph, gh, gw;
+    int32_t glyph_digit0, glyph_colon, glyph_dot;
+    const int32_t *scale;                        /* [B], DEVICE memory */
+    const float *heat;                           /* [B, Hf, Wf] or NULL */
+    int64_t sH_b, sH_y, sH_x;                    /* its strides in elements */
+    int32_t Hf, Wf;
+    const float *map_step;                       /* [B, 2] (sy, sx), DEVICE memory */
+    const int32_t *map_valid;                    /* [B, 2] (vh, vw), DEVICE memory */
+    const float *map_scale;                      /* [B], DEVICE memory */
+    const uint8_t *lut;                          /* [256, 3] */
+    int32_t heat_alpha;
+    void *workspace;
+    int64_t workspace_bytes;
+    int32_t *status;                             /* [1] */
+} detr_overlay_desc;
+int detr_hip_overlay(const detr_overlay_desc *d, void *stream);
+int64_t detr_hip_workspace_bytes_overlay(const detr_overlay_desc *d);
+
 #ifdef __cplusplus
 }
 #endif
