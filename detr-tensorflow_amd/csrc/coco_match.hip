@@ -19,14 +19,12 @@
 // A label or target class outside [0, nb_class), a header count outside [0, R-1], a detection count outside [0, Q] or a
 // non-positive image size sets the status word; the first three skip the item / clamp the count as map_match.hip does, the size
 // only enters the pixel area.  Nothing is read or written out of bounds.
-#include "common.h"
+#include "detections.h"
 
 namespace detr {
 
-constexpr int CM_MAXQ = 1024;     // = MM_MAXQ of map_match.hip
-constexpr int CM_MAXR = 256;      // rows of the padded targets incl. the header
-constexpr int CM_WAVES = 4;
-constexpr int CM_CHUNKS = CM_MAXR / 64;
+constexpr int CM_WAVES = DET_THREADS / 64;
+constexpr int CM_CHUNKS = DET_MAXR / 64;
 
 struct CocoArgs {
     const float *boxes; const long long *labels; const float *scores; const int *counts; long long sd_b;
@@ -43,81 +41,49 @@ struct CocoArgs {
     int *status;
 };
 
-// (the two helpers of map_match.hip, which stays as it is)
-__device__ __forceinline__ float cm_clip01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
-
-// does detection (sa, ia) come before (sb, ib) in np.argsort(-scores, kind="stable")?
-__device__ __forceinline__ bool cm_det_before(float sa, int ia, float sb, int ib) {
-    const bool na = sa != sa, nb = sb != sb;
-    if (na || nb) return na == nb ? ia < ib : nb;
-    return sa > sb || (sa == sb && ia < ib);
-}
-
-__global__ __launch_bounds__(CM_WAVES * 64) void coco_match_kernel(CocoArgs a) {
-    __shared__ float s_score[CM_MAXQ];
-    __shared__ int s_label[CM_MAXQ];             // -1: label out of range, the detection is skipped
-    __shared__ int s_order[CM_MAXQ];             // s_order[rank] = position among the image's detections
-    __shared__ int s_crank[CM_MAXQ];             // rank among the detections of the same class
-    __shared__ float s_box[CM_MAXQ][4];
-    __shared__ float s_gt[CM_MAXR][4];
-    __shared__ int s_gcls[CM_MAXR];              // -1: class out of range, the ground truth is skipped
-    __shared__ int s_gcrowd[CM_MAXR];
-    __shared__ float s_garea[CM_MAXR];
-    __shared__ uint32_t s_used[CM_MAXR][2];      // bit (a * n_thr + t): consumed at that pair
-    __shared__ double s_iou[CM_WAVES][CM_MAXR];  // wave-private: the IoUs of the detection the wave is on
+__global__ __launch_bounds__(DET_THREADS) void coco_match_kernel(CocoArgs a) {
+    __shared__ float s_score[PP_MAXQ];
+    __shared__ int s_label[PP_MAXQ];             // -1: label out of range, the detection is skipped
+    __shared__ int s_order[PP_MAXQ];             // s_order[rank] = position among the image's detections
+    __shared__ int s_crank[PP_MAXQ];             // rank among the detections of the same class
+    __shared__ float s_box[PP_MAXQ][4];
+    __shared__ float s_gt[DET_MAXR][4];
+    __shared__ int s_gcls[DET_MAXR];             // -1: class out of range, the ground truth is skipped
+    __shared__ int s_gcrowd[DET_MAXR];
+    __shared__ float s_garea[DET_MAXR];
+    __shared__ uint32_t s_used[DET_MAXR][2];     // bit (a * n_thr + t): consumed at that pair
+    __shared__ double s_iou[CM_WAVES][DET_MAXR]; // wave-private: the IoUs of the detection the wave is on
     __shared__ double s_cur0[DETR_COCO_MAX_THR], s_lo[DETR_COCO_MAX_AREA], s_hi[DETR_COCO_MAX_AREA];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
-    int bad = 0;
-
-    int n = a.counts[b];
-    if (n < 0 || n > a.Q) { bad |= DETR_MAP_BAD_COUNT; n = n < 0 ? 0 : a.Q; }
-    const float head = a.t_bbox[b * a.st_b];
-    int G = 0;
-    if (head > -1.f && head < (float)a.R) G = (int)head;          // int(t_bbox[b, 0, 0]); NaN fails both comparisons
-    else bad |= DETR_MAP_BAD_HEADER;
+    int n, G;
+    int bad = stage_detections(a.boxes + b * a.sd_b * 4, a.labels + b * a.sd_b, a.scores + b * a.sd_b, a.counts[b], a.Q, a.nb_class, s_score, s_label,
+                               s_box, &n);
+    bad |= stage_targets(a.t_bbox + b * a.st_b, a.t_class + b * a.sc_b, a.R, a.nb_class, s_gt, s_gcls, &G);
     const int H = a.sizes[2 * b], W = a.sizes[2 * b + 1];
     if (H <= 0 || W <= 0) bad |= DETR_COCO_BAD_SIZE;
 
     if (tid < DETR_COCO_MAX_THR) s_cur0[tid] = tid < a.n_thr ? a.cur0[tid] : INFINITY;
     if (tid < DETR_COCO_MAX_AREA) { s_lo[tid] = tid < a.n_area ? a.lo[tid] : 0.0; s_hi[tid] = tid < a.n_area ? a.hi[tid] : 0.0; }
-    for (int i = tid; i < n; i += blockDim.x) {
-        const long long row = b * a.sd_b + i;
-        const long long l = a.labels[row];
-        const bool ok = l >= 0 && l < a.nb_class;
-        if (!ok) bad |= DETR_MAP_BAD_LABEL;
-        s_label[i] = ok ? (int)l : -1;
-        s_score[i] = a.scores[row];
-        const float4 bx = *reinterpret_cast<const float4 *>(a.boxes + row * 4);
-        s_box[i][0] = bx.x; s_box[i][1] = bx.y; s_box[i][2] = bx.z; s_box[i][3] = bx.w;
-    }
-    for (int j = tid; j < G; j += blockDim.x) {
-        const float *t = a.t_bbox + b * a.st_b + (long long)(j + 1) * 4;
-        const float cx = t[0], cy = t[1], w = t[2], h = t[3];
-        s_gt[j][0] = cm_clip01(cy - h / 2); s_gt[j][1] = cm_clip01(cx - w / 2);
-        s_gt[j][2] = cm_clip01(cy + h / 2); s_gt[j][3] = cm_clip01(cx + w / 2);
-        const long long c = a.t_class[b * a.sc_b + j + 1];
-        const bool ok = c >= 0 && c < a.nb_class;
-        if (!ok) bad |= DETR_MAP_BAD_TARGET_CLASS;
-        s_gcls[j] = ok ? (int)c : -1;
+    for (int j = tid; j < G; j += DET_THREADS) {                   // the thread that staged row j: its crowd flag and area
         const bool crowd = a.t_crowd[b * a.sm_b + j + 1] != 0;
         const float ga = a.t_area[b * a.sm_b + j + 1];
         s_gcrowd[j] = crowd ? 1 : 0;
         s_garea[j] = ga;
         s_used[j][0] = 0u; s_used[j][1] = 0u;
-        if (ok)
+        if (s_gcls[j] >= 0)
             for (int ar = 0; ar < a.n_area; ++ar)
-                if (!(crowd || (double)ga < a.lo[ar] || (double)ga > a.hi[ar])) atomicAdd(a.npig + c * a.n_area + ar, 1ull);
+                if (!(crowd || (double)ga < a.lo[ar] || (double)ga > a.hi[ar])) atomicAdd(a.npig + s_gcls[j] * a.n_area + ar, 1ull);
     }
     if (bad) atomicOr(a.status, bad);
     __syncthreads();
 
-    for (int i = tid; i < n; i += blockDim.x) {
+    for (int i = tid; i < n; i += DET_THREADS) {
         const float si = s_score[i];
         const int li = s_label[i];
         int rank = 0, crank = 0;
         for (int j = 0; j < n; ++j) {
-            const bool before = cm_det_before(s_score[j], j, si, i);
+            const bool before = det_before(s_score[j], j, si, i);
             rank += before ? 1 : 0;
             crank += (before && s_label[j] == li) ? 1 : 0;
         }
@@ -127,7 +93,7 @@ __global__ __launch_bounds__(CM_WAVES * 64) void coco_match_kernel(CocoArgs a) {
     __syncthreads();
 
     const long long rec = (long long)b * a.Q, plane = (long long)a.B * a.Q;
-    for (int r = tid; r < a.Q; r += blockDim.x) {
+    for (int r = tid; r < a.Q; r += DET_THREADS) {
         const int i = r < n ? s_order[r] : -1;
         const int c = i >= 0 ? s_label[i] : -1;
         a.rec_score[rec + r] = i >= 0 ? s_score[i] : 0.f;
@@ -235,8 +201,8 @@ extern "C" int detr_hip_coco_match(const detr_coco_match_desc *d, void *stream) 
                  "coco_match: null operand (boxes, labels, scores, counts, t_bbox, t_class, t_crowd, t_area, sizes)");
     DETR_REQUIRE(d->rec_score && d->rec_class && d->rec_rank && d->rec_flags && d->npig && d->status,
                  "coco_match: null operand (rec_score, rec_class, rec_rank, rec_flags, npig, status)");
-    DETR_REQUIRE(d->B > 0 && d->B <= 65535 && d->Q > 0 && d->Q <= CM_MAXQ && d->R >= 1 && d->R <= CM_MAXR,
-                 "coco_match: bad shape B=%d Q=%d R=%d (B 1..65535, Q 1..%d, R 1..%d)", d->B, d->Q, d->R, CM_MAXQ, CM_MAXR);
+    DETR_REQUIRE(d->B > 0 && d->B <= 65535 && d->Q > 0 && d->Q <= PP_MAXQ && d->R >= 1 && d->R <= DET_MAXR,
+                 "coco_match: bad shape B=%d Q=%d R=%d (B 1..65535, Q 1..%d, R 1..%d)", d->B, d->Q, d->R, PP_MAXQ, DET_MAXR);
     DETR_REQUIRE(d->nb_class > 0, "coco_match: nb_class=%d must be positive", d->nb_class);
     DETR_REQUIRE(d->n_thr >= 1 && d->n_thr <= DETR_COCO_MAX_THR, "coco_match: n_thr=%d thresholds, 1..%d are supported", d->n_thr, DETR_COCO_MAX_THR);
     DETR_REQUIRE(d->n_area >= 1 && d->n_area <= DETR_COCO_MAX_AREA, "coco_match: n_area=%d area ranges, 1..%d are supported", d->n_area,
@@ -271,7 +237,7 @@ extern "C" int detr_hip_coco_match(const detr_coco_match_desc *d, void *stream) 
     a.rec_score = d->rec_score; a.rec_class = d->rec_class; a.rec_rank = d->rec_rank; a.rec_flags = d->rec_flags;
     a.npig = reinterpret_cast<unsigned long long *>(d->npig);
     a.status = d->status;
-    hipLaunchKernelGGL(coco_match_kernel, dim3(d->B), dim3(CM_WAVES * 64), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(coco_match_kernel, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
     DETR_LAUNCH_CHECK("coco_match");
     return 0;
 }

@@ -3,7 +3,7 @@
 // The reference takes get_model_inference (inference.py:68-95: background queries dropped, boxes normalised, query order) back to
 // the host and rescales there with the numpy helpers of bbox.py:230-294; thresholding and ordering are left to the caller.  Here ONE
 // launch serves the batch, one workgroup per image, everything in LDS:
-//   1. score = max softmax probability and label = first arg-max per query -- query_scores_labels of postprocess_score.h, the code
+//   1. score = max softmax probability and label = first arg-max per query -- query_scores_labels of detections.h, the code
 //      postprocess_kernel runs, so both entry points give the same bits;
 //   2. a query is kept when label != background and score >= score_threshold (a NaN score fails the comparison); the kept queries
 //      are compacted in query order (ballot prefix count, as postprocess_kernel does);
@@ -14,7 +14,7 @@
 //      height are the differences of the (clipped) corners.  Products, sums and differences are single fp32 roundings (no
 //      contraction), so a rerun and a rebuild give the same bits.
 // Rows [counts[b], max_detections) of every output are zero.  No atomics.
-#include "postprocess_score.h"
+#include "detections.h"
 
 namespace detr {
 
@@ -31,70 +31,39 @@ struct DetectArgs {
     int *counts;                                    // [B]
 };
 
-__device__ __forceinline__ float clip_to(float x, float hi) { return fminf(fmaxf(x, 0.f), hi); }
-
-__global__ __launch_bounds__(256) void detect_kernel(DetectArgs a) {
+__global__ __launch_bounds__(DET_THREADS) void detect_kernel(DetectArgs a) {
     __shared__ float s_score[PP_MAXQ];
     __shared__ int s_label[PP_MAXQ];
     __shared__ int s_kept[PP_MAXQ];              // s_kept[i] = query of the i-th kept detection, ascending
-    __shared__ int s_order[PP_MAXQ];             // s_order[rank] = query
+    __shared__ int s_order[PP_MAXQ];             // s_order[rank] = position in s_kept
     __shared__ int s_wave_cnt[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
     query_scores_labels(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label);
     __syncthreads();
 
     int n = 0;
-    for (int q0 = 0; q0 < a.Q; q0 += 256) {
+    for (int q0 = 0; q0 < a.Q; q0 += DET_THREADS) {
         const int q = q0 + tid;
         const bool keep = q < a.Q && s_label[q] != a.background && s_score[q] >= a.thr;
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) s_wave_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int off = n;
-        for (int w = 0; w < wave; ++w) off += s_wave_cnt[w];
-        if (keep) s_kept[off + __popcll(m & ((1ull << lane) - 1ull))] = q;
-        n += s_wave_cnt[0] + s_wave_cnt[1] + s_wave_cnt[2] + s_wave_cnt[3];
-        __syncthreads();
+        n = compact_pass(keep, n, s_wave_cnt, [&](int i, int) { s_kept[i] = q; });
     }
-
-    for (int i = tid; i < n; i += 256) {
-        const int q = s_kept[i];
-        const float si = s_score[q];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            const float sj = s_score[s_kept[j]];
-            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
-        }
-        s_order[rank] = q;
-    }
-    __syncthreads();
+    rank_sort(n, [&](int i) { return s_score[s_kept[i]]; }, s_order);      // a kept score passed >= thr: never NaN, plain descending order
 
     const int cnt = n < a.max_det ? n : a.max_det;
     const float H = (float)a.sizes[2 * b], W = (float)a.sizes[2 * b + 1];
-    for (int r = tid; r < a.max_det; r += 256) {
+    for (int r = tid; r < a.max_det; r += DET_THREADS) {
         const long long row = (long long)b * a.max_det + r;
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         long long label = 0;
         float score = 0.f;
         int query = 0;
         if (r < cnt) {
-#pragma clang fp contract(off)                      // every product, sum and difference below is rounded on its own
-            query = s_order[r];
+            query = s_kept[s_order[r]];
             label = s_label[query];
             score = s_score[query];
+            // the whole image is the window; the origin -0 adds nothing, not even to a -0 product
             const float *bx = a.boxes + b * a.sb_b + query * a.sb_q;
-            const float cx = bx[0] * W, cy = bx[1] * H, w = bx[2] * W, h = bx[3] * H;
-            if (a.fmt == 0) {
-                o = make_float4(cx, cy, w, h);
-            } else {
-                float x0 = cx - w * 0.5f, y0 = cy - h * 0.5f;
-                float x1 = cx + w * 0.5f, y1 = cy + h * 0.5f;
-                if (a.clip) { x0 = clip_to(x0, W); x1 = clip_to(x1, W); y0 = clip_to(y0, H); y1 = clip_to(y1, H); }
-                if (a.fmt == 1) o = make_float4(x0, y0, x1, y1);
-                else if (a.fmt == 2) o = make_float4(y0, x0, y1, x1);
-                else o = make_float4(x0, y0, x1 - x0, y1 - y0);
-            }
+            o = emit_pixel_box(a.fmt, decode_pixel_box(bx, -0.f, -0.f, W, H, W, H, a.clip), bx, -0.f, -0.f, W, H);
         }
         *reinterpret_cast<float4 *>(a.out_boxes + row * 4) = o;
         a.out_labels[row] = label;
@@ -114,14 +83,8 @@ extern "C" int detr_hip_detect(const detr_detect_desc *d, void *stream) {
     DETR_REQUIRE(d->out_boxes && d->out_labels && d->out_scores && d->out_query && d->counts,
                  "detect: null operand (out_boxes, out_labels, out_scores, out_query, counts)");
     DETR_REQUIRE(d->B > 0 && d->Q > 0 && d->Q <= PP_MAXQ && d->C > 0, "detect: bad shape B=%d Q=%d C=%d (Q 1..%d)", d->B, d->Q, d->C, PP_MAXQ);
-    DETR_REQUIRE(d->sL_q >= d->C && d->sL_b >= 0 && d->sB_q >= 4 && d->sB_b >= 0,
-                 "detect: strides sL_b=%lld sL_q=%lld (>= C) sB_b=%lld sB_q=%lld (>= 4) are too small", (long long)d->sL_b, (long long)d->sL_q,
-                 (long long)d->sB_b, (long long)d->sB_q);
+    if (check_model_outputs("detect", d)) return -1;
     DETR_REQUIRE(d->max_detections >= 1 && d->max_detections <= d->Q, "detect: max_detections=%d must be in 1..Q=%d", d->max_detections, d->Q);
-    DETR_REQUIRE(d->bbox_format >= 0 && d->bbox_format <= 3, "detect: bbox_format must be 0 (xy_center), 1 (xyxy), 2 (yxyx) or 3 (xywh)");
-    DETR_REQUIRE(d->clip == 0 || d->clip == 1, "detect: clip=%d must be 0 or 1", d->clip);
-    DETR_REQUIRE(d->score_threshold - d->score_threshold == 0.f, "detect: score_threshold is not finite");
-    DETR_REQUIRE(aligned16(d->out_boxes), "detect: out_boxes must be 16-byte aligned");
     DetectArgs a;
     a.logits = d->logits; a.sl_b = d->sL_b; a.sl_q = d->sL_q;
     a.boxes = d->boxes; a.sb_b = d->sB_b; a.sb_q = d->sB_q;
@@ -130,7 +93,7 @@ extern "C" int detr_hip_detect(const detr_detect_desc *d, void *stream) {
     a.thr = d->score_threshold;
     a.out_boxes = d->out_boxes; a.out_labels = reinterpret_cast<long long *>(d->out_labels); a.out_scores = d->out_scores;
     a.out_query = d->out_query; a.counts = d->counts;
-    hipLaunchKernelGGL(detect_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(detect_kernel, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
     DETR_LAUNCH_CHECK("detect");
     return 0;
 }

@@ -19,13 +19,11 @@
 // A label or target class outside [0, nb_class), a header count outside [0, R-1] or a detection count outside [0, Q] sets the
 // status word and the item is skipped (the image is treated as having no targets / the count is clamped): nothing is read or
 // written out of bounds.
-#include "common.h"
+#include "detections.h"
 
 namespace detr {
 
-constexpr int MM_MAXQ = 1024;     // = PP_MAXQ of postprocess.hip
-constexpr int MM_MAXR = 256;      // rows of the padded targets incl. the header (the loaders ship 100)
-constexpr int MM_WAVES = 4;
+constexpr int MM_WAVES = DET_THREADS / 64;
 
 struct MapArgs {
     const float *boxes; const long long *labels; const float *scores; const int *counts; long long sd_b;
@@ -39,71 +37,32 @@ struct MapArgs {
     int *status;
 };
 
-__device__ __forceinline__ float clip01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
-
-// does detection (sa, ia) come before (sb, ib) in np.argsort(-scores, kind="stable")?
-__device__ __forceinline__ bool det_before(float sa, int ia, float sb, int ib) {
-    const bool na = sa != sa, nb = sb != sb;
-    if (na || nb) return na == nb ? ia < ib : nb;
-    return sa > sb || (sa == sb && ia < ib);
-}
-
-__global__ __launch_bounds__(MM_WAVES * 64) void map_match_kernel(MapArgs a) {
-    __shared__ float s_score[MM_MAXQ];
-    __shared__ int s_label[MM_MAXQ];             // -1: label out of range, the detection is skipped
-    __shared__ int s_order[MM_MAXQ];             // s_order[rank] = position among the image's detections
-    __shared__ float s_box[MM_MAXQ][4];
-    __shared__ float s_gt[MM_MAXR][4];
-    __shared__ int s_gcls[MM_MAXR];              // -1: class out of range, the ground truth is skipped
-    __shared__ uint32_t s_used[MM_MAXR];         // bit t: consumed at threshold t
+__global__ __launch_bounds__(DET_THREADS) void map_match_kernel(MapArgs a) {
+    __shared__ float s_score[PP_MAXQ];
+    __shared__ int s_label[PP_MAXQ];             // -1: label out of range, the detection is skipped
+    __shared__ int s_order[PP_MAXQ];             // s_order[rank] = position among the image's detections
+    __shared__ float s_box[PP_MAXQ][4];
+    __shared__ float s_gt[DET_MAXR][4];
+    __shared__ int s_gcls[DET_MAXR];             // -1: class out of range, the ground truth is skipped
+    __shared__ uint32_t s_used[DET_MAXR];        // bit t: consumed at threshold t
     __shared__ double s_thr[DETR_MAP_MAX_THR];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
-    int bad = 0;
-
-    int n = a.counts[b];
-    if (n < 0 || n > a.Q) { bad |= DETR_MAP_BAD_COUNT; n = n < 0 ? 0 : a.Q; }
-    const float head = a.t_bbox[b * a.st_b];
-    int G = 0;
-    if (head > -1.f && head < (float)a.R) G = (int)head;          // int(t_bbox[b, 0, 0]); NaN fails both comparisons
-    else bad |= DETR_MAP_BAD_HEADER;
-
+    int n, G;
+    int bad = stage_detections(a.boxes + b * a.sd_b * 4, a.labels + b * a.sd_b, a.scores + b * a.sd_b, a.counts[b], a.Q, a.nb_class, s_score, s_label,
+                               s_box, &n);
+    bad |= stage_targets(a.t_bbox + b * a.st_b, a.t_class + b * a.sc_b, a.R, a.nb_class, s_gt, s_gcls, &G);
     if (tid < DETR_MAP_MAX_THR) s_thr[tid] = tid < a.n_thr ? a.thr[tid] : INFINITY;
-    for (int i = tid; i < n; i += blockDim.x) {
-        const long long row = b * a.sd_b + i;
-        const long long l = a.labels[row];
-        const bool ok = l >= 0 && l < a.nb_class;
-        if (!ok) bad |= DETR_MAP_BAD_LABEL;
-        s_label[i] = ok ? (int)l : -1;
-        s_score[i] = a.scores[row];
-        const float4 bx = *reinterpret_cast<const float4 *>(a.boxes + row * 4);
-        s_box[i][0] = bx.x; s_box[i][1] = bx.y; s_box[i][2] = bx.z; s_box[i][3] = bx.w;
-    }
-    for (int j = tid; j < G; j += blockDim.x) {
-        const float *t = a.t_bbox + b * a.st_b + (long long)(j + 1) * 4;
-        const float cx = t[0], cy = t[1], w = t[2], h = t[3];
-        s_gt[j][0] = clip01(cy - h / 2); s_gt[j][1] = clip01(cx - w / 2);
-        s_gt[j][2] = clip01(cy + h / 2); s_gt[j][3] = clip01(cx + w / 2);
-        const long long c = a.t_class[b * a.sc_b + j + 1];
-        const bool ok = c >= 0 && c < a.nb_class;
-        if (!ok) bad |= DETR_MAP_BAD_TARGET_CLASS;
-        s_gcls[j] = ok ? (int)c : -1;
+    for (int j = tid; j < G; j += DET_THREADS) {                   // the thread that staged row j
         s_used[j] = 0u;
-        if (ok) atomicAdd(a.num_gt + c, 1ull);
+        if (s_gcls[j] >= 0) atomicAdd(a.num_gt + s_gcls[j], 1ull);
     }
     if (bad) atomicOr(a.status, bad);
     __syncthreads();
-
-    for (int i = tid; i < n; i += blockDim.x) {
-        const float si = s_score[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += det_before(s_score[j], j, si, i) ? 1 : 0;
-        s_order[rank] = i;
-    }
-    __syncthreads();
+    rank_sort(n, [&](int i) { return s_score[i]; }, s_order);
 
     const long long rec = (long long)b * a.Q;
-    for (int r = tid; r < a.Q; r += blockDim.x) {
+    for (int r = tid; r < a.Q; r += DET_THREADS) {
         const int i = r < n ? s_order[r] : -1;
         const int c = i >= 0 ? s_label[i] : -1;
         a.rec_score[rec + r] = i >= 0 ? s_score[i] : 0.f;
@@ -160,8 +119,8 @@ extern "C" int detr_hip_map_match(const detr_map_match_desc *d, void *stream) {
     DETR_REQUIRE(d, "map_match: null descriptor");
     DETR_REQUIRE(d->boxes && d->labels && d->scores && d->counts && d->t_bbox && d->t_class, "map_match: null operand (boxes, labels, scores, counts, t_bbox, t_class)");
     DETR_REQUIRE(d->rec_score && d->rec_class && d->rec_flags && d->num_gt && d->status, "map_match: null operand (rec_score, rec_class, rec_flags, num_gt, status)");
-    DETR_REQUIRE(d->B > 0 && d->B <= 65535 && d->Q > 0 && d->Q <= MM_MAXQ && d->R >= 1 && d->R <= MM_MAXR,
-                 "map_match: bad shape B=%d Q=%d R=%d (B 1..65535, Q 1..%d, R 1..%d)", d->B, d->Q, d->R, MM_MAXQ, MM_MAXR);
+    DETR_REQUIRE(d->B > 0 && d->B <= 65535 && d->Q > 0 && d->Q <= PP_MAXQ && d->R >= 1 && d->R <= DET_MAXR,
+                 "map_match: bad shape B=%d Q=%d R=%d (B 1..65535, Q 1..%d, R 1..%d)", d->B, d->Q, d->R, PP_MAXQ, DET_MAXR);
     DETR_REQUIRE(d->nb_class > 0, "map_match: nb_class=%d must be positive", d->nb_class);
     DETR_REQUIRE(d->n_thr >= 1 && d->n_thr <= DETR_MAP_MAX_THR, "map_match: n_thr=%d thresholds, 1..%d are supported", d->n_thr, DETR_MAP_MAX_THR);
     for (int t = 0; t < d->n_thr; ++t)
@@ -183,7 +142,7 @@ extern "C" int detr_hip_map_match(const detr_map_match_desc *d, void *stream) {
     a.rec_score = d->rec_score; a.rec_class = d->rec_class; a.rec_flags = d->rec_flags;
     a.num_gt = reinterpret_cast<unsigned long long *>(d->num_gt);
     a.status = d->status;
-    hipLaunchKernelGGL(map_match_kernel, dim3(d->B), dim3(MM_WAVES * 64), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(map_match_kernel, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
     DETR_LAUNCH_CHECK("map_match");
     return 0;
 }

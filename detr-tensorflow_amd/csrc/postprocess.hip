@@ -6,7 +6,7 @@
 // statistics (score = max probability, label = first arg-max, inference.py:73-75), drops the background queries
 // (:78-83, order preserved like tf.where) by an in-workgroup prefix count, converts the boxes (:86-93, bbox.py:171-196
 // incl. the clip to [0, 1]) and writes the kept detections compacted per image.
-#include "postprocess_score.h"
+#include "detections.h"
 
 namespace detr {
 
@@ -20,26 +20,19 @@ struct PostArgs {
     int *counts;                                    // [B]
 };
 
-__global__ __launch_bounds__(256) void postprocess_kernel(PostArgs a) {
+__global__ __launch_bounds__(DET_THREADS) void postprocess_kernel(PostArgs a) {
     __shared__ float s_score[PP_MAXQ];
     __shared__ int s_label[PP_MAXQ];
     __shared__ int s_wave_cnt[4];
     const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    query_scores_labels(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label);      // postprocess_score.h, shared with detect.hip
+    query_scores_labels(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label);      // detections.h, shared with detect.hip
     __syncthreads();
     // order-preserving compaction: 256 queries per pass
     int base = 0;
-    for (int q0 = 0; q0 < a.Q; q0 += 256) {
+    for (int q0 = 0; q0 < a.Q; q0 += DET_THREADS) {
         const int q = q0 + threadIdx.x;
         const bool keep = q < a.Q && s_label[q] != a.background;
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) s_wave_cnt[wave] = __popcll(m);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; ++w) off += s_wave_cnt[w];
-        const int pos = off + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep) {
+        base = compact_pass(keep, base, s_wave_cnt, [&](int pos, int) {
             const float *bx = a.boxes + b * a.sb_b + q * a.sb_q;
             const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
             float o0 = cx, o1 = cy, o2 = w, o3 = h;
@@ -53,9 +46,7 @@ __global__ __launch_bounds__(256) void postprocess_kernel(PostArgs a) {
             ob[0] = o0; ob[1] = o1; ob[2] = o2; ob[3] = o3;
             a.out_labels[(long long)b * a.Q + pos] = s_label[q];
             a.out_scores[(long long)b * a.Q + pos] = s_score[q];
-        }
-        base += s_wave_cnt[0] + s_wave_cnt[1] + s_wave_cnt[2] + s_wave_cnt[3];
-        __syncthreads();
+        });
     }
     if (threadIdx.x == 0) a.counts[b] = base;
 }
@@ -73,7 +64,7 @@ extern "C" int detr_hip_postprocess(const detr_postprocess_desc *d, void *stream
     a.boxes = d->boxes; a.sb_b = d->sB_b; a.sb_q = d->sB_q;
     a.B = d->B; a.Q = d->Q; a.C = d->C; a.background = d->background_class; a.fmt = d->bbox_format;
     a.out_boxes = d->out_boxes; a.out_labels = reinterpret_cast<long long *>(d->out_labels); a.out_scores = d->out_scores; a.counts = d->counts;
-    hipLaunchKernelGGL(postprocess_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(postprocess_kernel, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
     DETR_LAUNCH_CHECK("postprocess");
     return 0;
 }

@@ -2,11 +2,11 @@
 // image; this kernel maps every tile's boxes back to the image and removes the duplicates the overlaps create, by a class-wise
 // greedy non-maximum suppression.  The reference has nothing of the kind: a user of get_model_inference (inference.py:68-95) writes
 // this as a NumPy loop per image.  Here ONE launch serves the batch, one workgroup per image, everything in LDS:
-//   1. per tile, score = max softmax probability and label = first arg-max per query -- query_scores_labels of postprocess_score.h,
+//   1. per tile, score = max softmax probability and label = first arg-max per query -- query_scores_labels of detections.h,
 //      the code detect_kernel and postprocess_kernel run, so the bits agree; a query is kept when label != background and
 //      score >= score_threshold (a NaN score fails the comparison);
 //   2. its box is mapped to image pixels: cx = x0 + bx * wc, cy = y0 + by * hc, w = bw * wc, h = bh * hc, corners c -+ size * 0.5,
-//      every operation one fp32 rounding (the file is compiled with -ffp-contract=off), clipped to the image when `clip` is set;
+//      every operation one fp32 rounding (decode_pixel_box of detections.h), clipped to the image when `clip` is set;
 //      with the whole image as the window these are detect_kernel's bits;
 //   3. the edge rule: an unclipped corner within edge_margin pixels of (or beyond) a window edge that is interior to the image
 //      drops the candidate -- the object is probably truncated and another tile, or the full view, sees it whole;
@@ -19,12 +19,11 @@
 //   6. the kept boxes are written in bbox_format; rows [counts[b], max_detections) are zero.
 // An image with more than TM_MAXC candidates sets DETR_TILE_OVER_CAP in the status word and gets no detections: nothing is
 // truncated silently, nothing is read or written out of bounds.  No atomics except the integer OR on the status word.
-#include "postprocess_score.h"
+#include "detections.h"
 
 namespace detr {
 
 constexpr int TM_MAXC = DETR_TILE_MAX_CAND;      // candidates of one image held in LDS
-constexpr int TM_THREADS = 256;                  // 4 waves: query_scores_labels' shape
 
 struct TileMergeArgs {
     const float *logits; long long sl_b, sl_q;      // [N, Q, C]
@@ -43,8 +42,6 @@ struct TileMergeArgs {
     int *status;                                    // [1]
 };
 
-__device__ __forceinline__ float tm_clip(float x, float hi) { return fminf(fmaxf(x, 0.f), hi); }
-
 // the match measure of two boxes (x0, y0, x1, y1), fp64 on fp32 corners; a zero (or NaN) denominator gives 0
 __device__ __forceinline__ double tm_measure(const float4 p, const float4 g, int match) {
     const double px0 = p.x, py0 = p.y, px1 = p.z, py1 = p.w, gx0 = g.x, gy0 = g.y, gx1 = g.z, gy1 = g.w;
@@ -56,7 +53,7 @@ __device__ __forceinline__ double tm_measure(const float4 p, const float4 g, int
     return den == 0.0 ? 0.0 : inter / den;
 }
 
-__global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(TileMergeArgs a) {
+__global__ __launch_bounds__(DET_THREADS) void tile_merge_kernel(TileMergeArgs a) {
     __shared__ float s_score[PP_MAXQ];             // the tile being staged
     __shared__ int s_label[PP_MAXQ];
     __shared__ float4 c_box[TM_MAXC];              // candidates in (tile, query) order: corners x0, y0, x1, y1 of step 2
@@ -69,7 +66,6 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(TileMergeArgs a)
     __shared__ unsigned char s_dead[TM_MAXC];      // by rank
     __shared__ int s_wave_cnt[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
     const float H = (float)a.sizes[2 * b], W = (float)a.sizes[2 * b + 1];
     const int Hi = a.sizes[2 * b], Wi = a.sizes[2 * b + 1];
 
@@ -89,38 +85,24 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(TileMergeArgs a)
         const bool in_l = wx0 > 0, in_t = wy0 > 0;                      // which window edges are interior to the image
         const bool in_r = (long long)wx0 + wwc < Wi, in_b = (long long)wy0 + whc < Hi;
         const float ex1 = (float)((long long)wx0 + wwc), ey1 = (float)((long long)wy0 + whc);
-        for (int q0 = 0; q0 < a.Q; q0 += TM_THREADS) {
+        for (int q0 = 0; q0 < a.Q; q0 += DET_THREADS) {
             const int q = q0 + tid;
             bool keep = q < a.Q && s_label[q] != a.background && s_score[q] >= a.thr;
             float4 box = make_float4(0.f, 0.f, 0.f, 0.f);
             if (keep) {
-                const float *bx = a.boxes + t * a.sb_b + q * a.sb_q;
-                const float cx = fx0 + bx[0] * fwc, cy = fy0 + bx[1] * fhc, w = bx[2] * fwc, h = bx[3] * fhc;
-                float x0 = cx - w * 0.5f, y0 = cy - h * 0.5f;
-                float x1 = cx + w * 0.5f, y1 = cy + h * 0.5f;
+                box = decode_pixel_box(a.boxes + t * a.sb_b + q * a.sb_q, fx0, fy0, fwc, fhc, W, H, 0);
                 if (edges) {
-                    const bool drop = (in_l && x0 - fx0 <= a.margin) || (in_r && ex1 - x1 <= a.margin) ||
-                                      (in_t && y0 - fy0 <= a.margin) || (in_b && ey1 - y1 <= a.margin);
+                    const bool drop = (in_l && box.x - fx0 <= a.margin) || (in_r && ex1 - box.z <= a.margin) ||
+                                      (in_t && box.y - fy0 <= a.margin) || (in_b && ey1 - box.w <= a.margin);
                     keep = !drop;
                 }
-                if (a.clip) { x0 = tm_clip(x0, W); x1 = tm_clip(x1, W); y0 = tm_clip(y0, H); y1 = tm_clip(y1, H); }
-                box = make_float4(x0, y0, x1, y1);
+                if (a.clip) box = clip_pixel_box(box, W, H);
             }
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) s_wave_cnt[wave] = __popcll(m);
-            __syncthreads();
-            int off = n;
-            for (int w = 0; w < wave; ++w) off += s_wave_cnt[w];
-            const int add = s_wave_cnt[0] + s_wave_cnt[1] + s_wave_cnt[2] + s_wave_cnt[3];
-            if (n + add > TM_MAXC) {                                    // uniform: nothing of this pass is stored
-                bad |= DETR_TILE_OVER_CAP;
-            } else if (keep) {
-                const int i = off + __popcll(m & ((1ull << lane) - 1ull));
+            n = compact_pass(keep, n, s_wave_cnt, [&](int i, int total) {
+                if (total > TM_MAXC) return;                            // uniform: nothing of this pass is stored
                 c_box[i] = box; c_score[i] = s_score[q]; c_label[i] = s_label[q]; c_tile[i] = t - ts; c_query[i] = q;
-            }
-            n += add;
-            __syncthreads();
-            if (bad & DETR_TILE_OVER_CAP) break;                        // uniform
+            });
+            if (n > TM_MAXC) { bad |= DETR_TILE_OVER_CAP; break; }      // uniform
         }
     }
     if (bad) {
@@ -129,17 +111,8 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(TileMergeArgs a)
     }
 
     // ---- 4: rank sort, descending score, ties by position
-    for (int i = tid; i < n; i += TM_THREADS) {
-        const float si = c_score[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            const float sj = c_score[j];
-            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
-        }
-        s_order[rank] = i;
-        s_dead[i] = 0;
-    }
-    __syncthreads();
+    for (int i = tid; i < n; i += DET_THREADS) s_dead[i] = 0;
+    rank_sort(n, [&](int i) { return c_score[i]; }, s_order);           // a candidate's score passed >= thr: never NaN
 
     // ---- 5: greedy suppression, one barrier per kept box
     int kept = 0;
@@ -150,7 +123,7 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(TileMergeArgs a)
         ++kept;
         const float4 bi = c_box[i];
         const int li = c_label[i];
-        for (int rj = r + 1 + tid; rj < n; rj += TM_THREADS) {
+        for (int rj = r + 1 + tid; rj < n; rj += DET_THREADS) {
             if (s_dead[rj]) continue;
             const int j = s_order[rj];
             if (!a.agnostic && c_label[j] != li) continue;
@@ -161,7 +134,7 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(TileMergeArgs a)
     __syncthreads();                                                    // s_keep of thread 0 (n == 0 or no suppression pass ran last)
 
     // ---- 6: output
-    for (int r = tid; r < a.max_det; r += TM_THREADS) {
+    for (int r = tid; r < a.max_det; r += DET_THREADS) {
         const long long row = (long long)b * a.max_det + r;
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         long long label = 0;
@@ -170,16 +143,10 @@ __global__ __launch_bounds__(TM_THREADS) void tile_merge_kernel(TileMergeArgs a)
         if (r < kept) {
             const int i = s_order[s_keep[r]];
             label = c_label[i]; score = c_score[i]; query = c_query[i]; tile = c_tile[i];
-            const float4 c = c_box[i];
-            if (a.fmt == 0) {                                           // cx, cy, w, h of step 2, recomputed: the same operations
-                const int t = ts + tile;
-                const float *bx = a.boxes + t * a.sb_b + query * a.sb_q;
-                const float fx0 = (float)a.windows[4 * t + 1], fy0 = (float)a.windows[4 * t];
-                const float fwc = (float)a.windows[4 * t + 3], fhc = (float)a.windows[4 * t + 2];
-                o = make_float4(fx0 + bx[0] * fwc, fy0 + bx[1] * fhc, bx[2] * fwc, bx[3] * fhc);
-            } else if (a.fmt == 1) o = c;
-            else if (a.fmt == 2) o = make_float4(c.y, c.x, c.w, c.z);
-            else o = make_float4(c.x, c.y, c.z - c.x, c.w - c.y);
+            const int t = ts + tile;
+            float wx = 0.f, wy = 0.f, ww = 0.f, wh = 0.f;               // only format 0 reads the window again: cx, cy, w, h of step 2 recomputed
+            if (a.fmt == 0) { wx = (float)a.windows[4 * t + 1]; wy = (float)a.windows[4 * t]; ww = (float)a.windows[4 * t + 3]; wh = (float)a.windows[4 * t + 2]; }
+            o = emit_pixel_box(a.fmt, c_box[i], a.boxes + t * a.sb_b + query * a.sb_q, wx, wy, ww, wh);
         }
         *reinterpret_cast<float4 *>(a.out_boxes + row * 4) = o;
         a.out_labels[row] = label;
@@ -202,9 +169,7 @@ extern "C" int detr_hip_tile_merge(const detr_tile_merge_desc *d, void *stream) 
                  "tile_merge: null operand (out_boxes, out_labels, out_scores, out_query, out_tile, counts, status)");
     DETR_REQUIRE(d->B > 0 && d->B <= 65535 && d->N > 0 && d->Q > 0 && d->Q <= PP_MAXQ && d->C > 0,
                  "tile_merge: bad shape B=%d N=%d Q=%d C=%d (B 1..65535, N >= 1, Q 1..%d)", d->B, d->N, d->Q, d->C, PP_MAXQ);
-    DETR_REQUIRE(d->sL_q >= d->C && d->sL_b >= 0 && d->sB_q >= 4 && d->sB_b >= 0,
-                 "tile_merge: strides sL_b=%lld sL_q=%lld (>= C) sB_b=%lld sB_q=%lld (>= 4) are too small", (long long)d->sL_b, (long long)d->sL_q,
-                 (long long)d->sB_b, (long long)d->sB_q);
+    if (check_model_outputs("tile_merge", d)) return -1;
     DETR_REQUIRE(d->tile_start_host[0] == 0 && d->tile_start_host[d->B] == d->N,
                  "tile_merge: tile_start must run from 0 to N=%d, got %d .. %d", d->N, d->tile_start_host[0], d->tile_start_host[d->B]);
     for (int b = 0; b < d->B; ++b)
@@ -212,14 +177,10 @@ extern "C" int detr_hip_tile_merge(const detr_tile_merge_desc *d, void *stream) 
                      d->tile_start_host[b], d->tile_start_host[b + 1]);
     DETR_REQUIRE(d->max_detections >= 1 && d->max_detections <= TM_MAXC, "tile_merge: max_detections=%d must be in 1..%d (the candidate cap)",
                  d->max_detections, TM_MAXC);
-    DETR_REQUIRE(d->bbox_format >= 0 && d->bbox_format <= 3, "tile_merge: bbox_format must be 0 (xy_center), 1 (xyxy), 2 (yxyx) or 3 (xywh)");
-    DETR_REQUIRE(d->clip == 0 || d->clip == 1, "tile_merge: clip=%d must be 0 or 1", d->clip);
     DETR_REQUIRE(d->match == 0 || d->match == 1, "tile_merge: match=%d must be 0 (IoU) or 1 (intersection over the smaller area)", d->match);
     DETR_REQUIRE(d->class_agnostic == 0 || d->class_agnostic == 1, "tile_merge: class_agnostic=%d must be 0 or 1", d->class_agnostic);
-    DETR_REQUIRE(d->score_threshold - d->score_threshold == 0.f, "tile_merge: score_threshold is not finite");
     DETR_REQUIRE(d->nms_threshold - d->nms_threshold == 0.0, "tile_merge: nms_threshold is not finite");
     DETR_REQUIRE(d->edge_margin - d->edge_margin == 0.f && d->edge_margin >= 0.f, "tile_merge: edge_margin must be finite and >= 0");
-    DETR_REQUIRE(aligned16(d->out_boxes), "tile_merge: out_boxes must be 16-byte aligned");
     TileMergeArgs a;
     a.logits = d->logits; a.sl_b = d->sL_b; a.sl_q = d->sL_q;
     a.boxes = d->boxes; a.sb_b = d->sB_b; a.sb_q = d->sB_q;
@@ -229,7 +190,7 @@ extern "C" int detr_hip_tile_merge(const detr_tile_merge_desc *d, void *stream) 
     a.thr = d->score_threshold; a.margin = d->edge_margin; a.nms = d->nms_threshold;
     a.out_boxes = d->out_boxes; a.out_labels = reinterpret_cast<long long *>(d->out_labels); a.out_scores = d->out_scores;
     a.out_query = d->out_query; a.out_tile = d->out_tile; a.counts = d->counts; a.status = d->status;
-    hipLaunchKernelGGL(tile_merge_kernel, dim3(d->B), dim3(TM_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tile_merge_kernel, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
     DETR_LAUNCH_CHECK("tile_merge");
     return 0;
 }

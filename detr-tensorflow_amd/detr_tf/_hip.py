@@ -265,9 +265,6 @@ _SIGNATURES = {
     "detr_hip_detect": [POINTER(DetectDesc), c_void_p],
     "detr_hip_tile_merge": [POINTER(TileMergeDesc), c_void_p],
     "detr_hip_coco_match": [POINTER(CocoMatchDesc), c_void_p],
-}
-# entry points appended behind detr_hip_coco_match (its test pins it as the last of the table above)
-_SIGNATURES_LATER = {
     "detr_hip_overlay": [POINTER(OverlayDesc), c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
@@ -283,17 +280,12 @@ _SIGNATURES_I64 = {
     "detr_hip_workspace_bytes_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32],
     "detr_hip_workspace_bytes_overlay": [POINTER(OverlayDesc)],
 }
-EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_LATER) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
+EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
-# order of detr_hip_struct_layout's `which`
-LAYOUT_STRUCTS = (ReduceDesc, GemmDesc, Conv3x3Desc, StemDesc, LayerNormDesc, AttnDesc, SetLossDesc, InputDesc, PostprocessDesc,
-                  MapMatchDesc)
-# descriptors appended after ABI 9: `which` -> mirror (numbered from 100, include/detr_hip.h)
-APPENDED_LAYOUT_STRUCTS = {100: DetectDesc}
-# the second appended list (numbered from 200: 101 stays the unknown id behind the first list)
-LATER_LAYOUT_STRUCTS = {200: TileMergeDesc}
-# the third one (numbered from 300; the two above are pinned by their tests, so a new descriptor gets a registry of its own)
-EXTRA_LAYOUT_STRUCTS = {300: OverlayDesc}
+# detr_hip_struct_layout's `which` -> mirror: 0..9 are the descriptors of ABI 9, the ones appended since are numbered 100, 200, 300
+# (include/detr_hip.h), so the id behind each of them stays unknown to the library
+LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: LayerNormDesc, 5: AttnDesc, 6: SetLossDesc, 7: InputDesc,
+                  8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc}
 
 _lib = None
 
@@ -503,7 +495,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or `make -C detr-tensorflow_amd`) first; there is no CPU/eager fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(_SIGNATURES.items()) + list(_SIGNATURES_LATER.items()):
+    for name, argtypes in _SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_int32
@@ -528,8 +520,7 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in (list(enumerate(LAYOUT_STRUCTS)) + sorted(APPENDED_LAYOUT_STRUCTS.items()) + sorted(LATER_LAYOUT_STRUCTS.items())
-                     + sorted(EXTRA_LAYOUT_STRUCTS.items())):
+    for which, S in sorted(LAYOUT_STRUCTS.items()):
         want = struct_layout_mirror(S)
         buf = (c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)

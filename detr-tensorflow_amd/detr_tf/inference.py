@@ -32,27 +32,40 @@ BBOX_FORMATS = {"xy_center": 0, "xyxy": 1, "yxyx": 2}
 DETECT_FORMATS = {"xy_center": 0, "xyxy": 1, "yxyx": 2, "xywh": 3}       # xywh: top-left + width / height, the COCO results form
 
 
+def _check_model_outputs(who, lead, logits, boxes):
+    if logits.dim() != 3 or boxes.dim() != 3 or boxes.shape[-1] != 4 or tuple(boxes.shape[:2]) != tuple(logits.shape[:2]):
+        raise RuntimeError(f"{who}: expected pred_logits [{lead}, Q, C] and pred_boxes [{lead}, Q, 4], got {tuple(logits.shape)} and {tuple(boxes.shape)}")
+
+
+def _model_outputs(who, step, logits, boxes):
+    """pred_logits and pred_boxes as the kernels read them: on the GPU, float32, last stride 1.  `step` names the work in the message."""
+    if not (logits.is_cuda and boxes.is_cuda):
+        raise RuntimeError(f"{who}: the outputs must live on the GPU (the {step} is a HIP kernel; no CPU fallback)")
+    logits, boxes = logits.float(), boxes.float()
+    return (logits if logits.stride(-1) == 1 else logits.contiguous()), (boxes if boxes.stride(-1) == 1 else boxes.contiguous())
+
+
+def _fill_model_outputs(d, logits, boxes, background_class):
+    """The descriptor fields detr_hip_postprocess, detr_hip_detect and detr_hip_tile_merge share."""
+    d.Q, d.C = logits.shape[1:]
+    d.logits, d.sL_b, d.sL_q = logits.data_ptr(), logits.stride(0), logits.stride(1)
+    d.boxes, d.sB_b, d.sB_q = boxes.data_ptr(), boxes.stride(0), boxes.stride(1)
+    d.background_class = int(background_class)
+
+
 def _post(logits, boxes, background_class, bbox_format):
     if bbox_format not in BBOX_FORMATS:
         raise NotImplementedError()                                     # inference.py:92-93
-    if not (logits.is_cuda and boxes.is_cuda):
-        raise RuntimeError("get_model_inference: the outputs must live on the GPU (the post-processing is a HIP kernel; no CPU fallback)")
-    logits, boxes = logits.float(), boxes.float()
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    if boxes.stride(-1) != 1:
-        boxes = boxes.contiguous()
-    B, Q, C = logits.shape
+    logits, boxes = _model_outputs("get_model_inference", "post-processing", logits, boxes)
+    B, Q, _ = logits.shape
     dev = logits.device
     out_b = torch.zeros(B, Q, 4, dtype=torch.float32, device=dev)
     out_l = torch.zeros(B, Q, dtype=torch.int64, device=dev)
     out_s = torch.zeros(B, Q, dtype=torch.float32, device=dev)
     counts = torch.zeros(B, dtype=torch.int32, device=dev)
     d = hip.PostprocessDesc()
-    d.B, d.Q, d.C = B, Q, C
-    d.logits, d.sL_b, d.sL_q = logits.data_ptr(), logits.stride(0), logits.stride(1)
-    d.boxes, d.sB_b, d.sB_q = boxes.data_ptr(), boxes.stride(0), boxes.stride(1)
-    d.background_class, d.bbox_format = int(background_class), BBOX_FORMATS[bbox_format]
+    _fill_model_outputs(d, logits, boxes, background_class)
+    d.B, d.bbox_format = B, BBOX_FORMATS[bbox_format]
     d.out_boxes, d.out_labels, d.out_scores, d.counts = out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), counts.data_ptr()
     hip._check(hip.load().detr_hip_postprocess(byref(d), hip._stream()), "detr_hip_postprocess")
     return out_b, out_l, out_s, counts
@@ -114,33 +127,27 @@ def _check_detect_args(bbox_format, score_threshold, max_detections, Q=None):
         raise RuntimeError(f"detect: max_detections={max_detections} must be in 1..Q" + ("" if Q is None else f"={Q} (the number of queries)"))
 
 
+def _ranked_rows(B, K, dev, n_index):
+    """boxes, labels, scores and n_index int32 columns of K rows per image; the kernels write every row: detections, then zeros."""
+    return (torch.empty(B, K, 4, dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.int64, device=dev),
+            torch.empty(B, K, dtype=torch.float32, device=dev), *(torch.empty(B, K, dtype=torch.int32, device=dev) for _ in range(n_index)))
+
+
 def _detect(logits, boxes, sizes, background_class, score_threshold, max_detections, bbox_format, clip):
-    if logits.dim() != 3 or boxes.dim() != 3 or boxes.shape[-1] != 4 or tuple(boxes.shape[:2]) != tuple(logits.shape[:2]):
-        raise RuntimeError(f"detect: expected pred_logits [B, Q, C] and pred_boxes [B, Q, 4], got {tuple(logits.shape)} and {tuple(boxes.shape)}")
-    B, Q, C = logits.shape
+    _check_model_outputs("detect", "B", logits, boxes)
+    B, Q, _ = logits.shape
     _check_detect_args(bbox_format, score_threshold, max_detections, Q)
+    logits, boxes = _model_outputs("detect_batched", "post-processing", logits, boxes)
     K = Q if max_detections is None else int(max_detections)
-    if not (logits.is_cuda and boxes.is_cuda):
-        raise RuntimeError("detect_batched: the outputs must live on the GPU (the post-processing is a HIP kernel; no CPU fallback)")
-    logits, boxes = logits.float(), boxes.float()
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    if boxes.stride(-1) != 1:
-        boxes = boxes.contiguous()
     dev = logits.device
     sizes = torch.as_tensor(sizes).to(device=dev, dtype=torch.int32).contiguous()
     if tuple(sizes.shape) != (B, 2):
         raise RuntimeError(f"detect: sizes must be [B, 2] = (height, width) of every image, got {tuple(sizes.shape)} for B={B}")
-    out_b = torch.empty(B, K, 4, dtype=torch.float32, device=dev)         # the kernel writes every row: detections, then zeros
-    out_l = torch.empty(B, K, dtype=torch.int64, device=dev)
-    out_s = torch.empty(B, K, dtype=torch.float32, device=dev)
-    out_q = torch.empty(B, K, dtype=torch.int32, device=dev)
+    out_b, out_l, out_s, out_q = _ranked_rows(B, K, dev, 1)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     d = hip.DetectDesc()
-    d.B, d.Q, d.C = B, Q, C
-    d.logits, d.sL_b, d.sL_q = logits.data_ptr(), logits.stride(0), logits.stride(1)
-    d.boxes, d.sB_b, d.sB_q = boxes.data_ptr(), boxes.stride(0), boxes.stride(1)
-    d.sizes, d.background_class, d.score_threshold = sizes.data_ptr(), int(background_class), float(score_threshold)
+    _fill_model_outputs(d, logits, boxes, background_class)
+    d.B, d.sizes, d.score_threshold = B, sizes.data_ptr(), float(score_threshold)
     d.max_detections, d.bbox_format, d.clip = K, DETECT_FORMATS[bbox_format], int(bool(clip))
     d.out_boxes, d.out_labels, d.out_scores, d.out_query, d.counts = (out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), out_q.data_ptr(),
                                                                       counts.data_ptr())
@@ -199,20 +206,11 @@ def merge_tiles(m_outputs: dict, tile_start, windows, sizes, background_class, *
     removes a part-box lying inside the box of the whole object.  The first max_detections survivors are returned.  One launch of
     detr_hip_tile_merge and ONE host synchronisation (counts + status).  An image with more than _hip.TILE_MAX_CAND candidates
     raises ValueError.  CUDA inputs only."""
-    logits, boxes = m_outputs["pred_logits"], m_outputs["pred_boxes"]
-    if logits.dim() != 3 or boxes.dim() != 3 or boxes.shape[-1] != 4 or tuple(boxes.shape[:2]) != tuple(logits.shape[:2]):
-        raise RuntimeError(f"merge_tiles: expected pred_logits [N, Q, C] and pred_boxes [N, Q, 4], got {tuple(logits.shape)} and {tuple(boxes.shape)}")
-    N, Q, C = logits.shape
+    _check_model_outputs("merge_tiles", "N", m_outputs["pred_logits"], m_outputs["pred_boxes"])
     _check_detect_args(bbox_format, score_threshold, None)
     _check_merge_args(nms_threshold, match, edge_margin, max_detections)
-    K = int(max_detections)
-    if not (logits.is_cuda and boxes.is_cuda):
-        raise RuntimeError("merge_tiles: the outputs must live on the GPU (the merge is a HIP kernel; no CPU fallback)")
-    logits, boxes = logits.float(), boxes.float()
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    if boxes.stride(-1) != 1:
-        boxes = boxes.contiguous()
+    logits, boxes = _model_outputs("merge_tiles", "merge", m_outputs["pred_logits"], m_outputs["pred_boxes"])
+    N, K = logits.shape[0], int(max_detections)
     dev = logits.device
     start_h = np.ascontiguousarray(np.asarray(tile_start.cpu() if isinstance(tile_start, torch.Tensor) else tile_start), np.int32)
     if start_h.ndim != 1 or start_h.shape[0] < 2:
@@ -224,18 +222,12 @@ def merge_tiles(m_outputs: dict, tile_start, windows, sizes, background_class, *
         raise RuntimeError(f"merge_tiles: sizes must be [B, 2] and windows [N, 4], got {tuple(sizes.shape)} and {tuple(windows.shape)} "
                            f"for B={B}, N={N}")
     start_d = torch.from_numpy(start_h).to(dev)
-    out_b = torch.empty(B, K, 4, dtype=torch.float32, device=dev)         # the kernel writes every row: detections, then zeros
-    out_l = torch.empty(B, K, dtype=torch.int64, device=dev)
-    out_s = torch.empty(B, K, dtype=torch.float32, device=dev)
-    out_q = torch.empty(B, K, dtype=torch.int32, device=dev)
-    out_t = torch.empty(B, K, dtype=torch.int32, device=dev)
+    out_b, out_l, out_s, out_q, out_t = _ranked_rows(B, K, dev, 2)
     tail = torch.zeros(B + 1, dtype=torch.int32, device=dev)              # counts [B], then the status word
     d = hip.TileMergeDesc()
-    d.B, d.N, d.Q, d.C = B, N, Q, C
-    d.logits, d.sL_b, d.sL_q = logits.data_ptr(), logits.stride(0), logits.stride(1)
-    d.boxes, d.sB_b, d.sB_q = boxes.data_ptr(), boxes.stride(0), boxes.stride(1)
+    _fill_model_outputs(d, logits, boxes, background_class)
+    d.B, d.N, d.score_threshold = B, N, float(score_threshold)
     d.tile_start, d.tile_start_host, d.windows, d.sizes = start_d.data_ptr(), start_h.ctypes.data, windows.data_ptr(), sizes.data_ptr()
-    d.background_class, d.score_threshold = int(background_class), float(score_threshold)
     d.max_detections, d.bbox_format, d.clip = K, DETECT_FORMATS[bbox_format], int(bool(clip))
     d.match, d.class_agnostic, d.edge_margin, d.nms_threshold = MATCH_MODES[match], int(bool(class_agnostic)), float(edge_margin), float(nms_threshold)
     d.out_boxes, d.out_labels, d.out_scores, d.out_query, d.out_tile = (out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), out_q.data_ptr(),

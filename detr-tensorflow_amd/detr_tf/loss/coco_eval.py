@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _hip as hip
+from .compute_map import _DeviceAccumulator
 
 IOU_THRESHOLDS = np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1)
 RECALL_THRESHOLDS = np.linspace(0.0, 1.0, 101)
@@ -232,37 +233,25 @@ def check_meta(meta, who):
     return meta
 
 
-class DeviceCOCOAccumulator:
+class DeviceCOCOAccumulator(_DeviceAccumulator):
     """COCOAccumulator whose per-image work runs on the device: one detr_hip_coco_match launch per batch (after the one of
     detr_hip_postprocess), no host synchronisation until `to_host()`.  Records and counts are the host path's exactly."""
+    BAD = hip.COCO_BAD
 
     def __init__(self, nb_class, iou_thresholds=None, area_ranges=None, max_dets=MAX_DETS, device=None):
         self._host = COCOAccumulator(nb_class, iou_thresholds, area_ranges, max_dets)       # (validates; never filled)
         self.thresholds, self.area_ranges, self.max_dets = self._host.thresholds, self._host.area_ranges, self._host.max_dets
         self.nb_class = self._host.nb_class
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("DeviceCOCOAccumulator: the matching is a HIP kernel; there is no CPU fallback (use COCOAccumulator)")
+        self._open(device, "COCOAccumulator")    # records per batch: int32 [3 + n_area, B, Q] = score bits, class, rank, flag words
         self._npig = torch.zeros(self.nb_class * len(self.area_ranges), dtype=torch.int64, device=self.device)
-        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._records = []                        # per batch: int32 [3 + n_area, B, Q] = score bits, class, rank, flag words
-
-    def _device(self, x, dtype):
-        if torch.is_tensor(x) and x.is_cuda:
-            return x.to(device=self.device, dtype=dtype)
-        t = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(dtype)
-        return t.pin_memory().to(self.device, non_blocking=True)      # pinned + asynchronous: the upload does not block the host
 
     def add_detections(self, boxes, labels, scores, counts, t_bbox, t_class, t_crowd, t_area, sizes):
         """Device tensors: what detr_hip_postprocess wrote in "yxyx" format (boxes [B, Q, 4] fp32, labels [B, Q] int64, scores
         [B, Q] fp32, counts [B] int32), the padded targets t_bbox [B, R, 4] fp32 (header row 0), t_class [B, R, 1] int64, and the
         loader's metadata t_crowd [B, R] uint8, t_area [B, R] fp32, sizes [B, 2] int32."""
-        want = (("boxes", boxes, torch.float32, 3), ("labels", labels, torch.int64, 2), ("scores", scores, torch.float32, 2),
-                ("counts", counts, torch.int32, 1), ("t_bbox", t_bbox, torch.float32, 3), ("t_class", t_class, torch.int64, None),
-                ("t_crowd", t_crowd, torch.uint8, 2), ("t_area", t_area, torch.float32, 2), ("sizes", sizes, torch.int32, 2))
-        for name, t, dt, nd in want:
-            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dt and (nd is None or t.dim() == nd)):
-                raise TypeError(f"add_detections: {name} must be a {dt} tensor on {self.device}" + (f" with {nd} dimensions" if nd else ""))
+        self._check_tensors((("boxes", boxes, torch.float32, 3), ("labels", labels, torch.int64, 2), ("scores", scores, torch.float32, 2),
+                             ("counts", counts, torch.int32, 1), ("t_bbox", t_bbox, torch.float32, 3), ("t_class", t_class, torch.int64, None),
+                             ("t_crowd", t_crowd, torch.uint8, 2), ("t_area", t_area, torch.float32, 2), ("sizes", sizes, torch.int32, 2)))
         B, Q = labels.shape
         R = t_bbox.shape[1]
         if tuple(boxes.shape) != (B, Q, 4) or tuple(scores.shape) != (B, Q) or tuple(counts.shape) != (B,) or \
@@ -299,23 +288,11 @@ class DeviceCOCOAccumulator:
                             self._device(meta["size"], torch.int32))
 
     def to_host(self):
-        """One synchronisation, one device-to-host copy (status word, counts and every batch's records in one buffer) -> the
-        COCOAccumulator the host path would hold.  ValueError when the kernel flagged an input."""
-        na = len(self.area_ranges)
-        shapes = [tuple(r.shape[1:]) for r in self._records]
-        buf = torch.cat([self._status, self._npig.view(torch.int32)] + [r.reshape(-1) for r in self._records]).cpu().numpy()
-        n_words = 2 * self.nb_class * na
-        status, npig = int(buf[0]), buf[1:1 + n_words].copy().view(np.int64)
-        if status:
-            raise ValueError("DeviceCOCOAccumulator: " + "; ".join(text for bit, text in hip.COCO_BAD.items() if status & bit))
+        """One synchronisation, one device-to-host copy -> the COCOAccumulator the host path would hold.  ValueError when the kernel
+        flagged an input."""
+        npig, recs = self._unpack(self._npig)
         acc = COCOAccumulator(self.nb_class, self.thresholds, self.area_ranges, self.max_dets)
-        off = 1 + n_words
-        for B, Q in shapes:
-            rec = np.ascontiguousarray(buf[off:off + (3 + na) * B * Q].reshape(3 + na, B * Q))
-            off += (3 + na) * B * Q
+        for rec in recs:
             acc.add_records(rec[0].view(np.float32), rec[1], rec[2], rec[3:].view(np.uint32))
-        acc.npig = npig.reshape(self.nb_class, na).astype(np.int64)
+        acc.npig = npig.reshape(self.nb_class, len(self.area_ranges)).astype(np.int64)
         return acc
-
-    def result(self, class_names=None, print_result=False):
-        return self.to_host().result(class_names, print_result=print_result)

@@ -146,10 +146,54 @@ def group_records(rec_score, rec_class, rec_flags, nb_class, n_thr):
     return scores, flags
 
 
-class DeviceAPAccumulator:
+class _DeviceAccumulator:
+    """What DeviceAPAccumulator and coco_eval.DeviceCOCOAccumulator share: the device and its status word, the upload and the checks of
+    the tensors a batch brings, and the one copy that brings status, counters and records back.  A subclass sets BAD (status bit ->
+    text), fills its descriptor in add_detections and appends one int32 [width, B, Q] record block per batch to self._records."""
+    BAD = {}
+
+    def _open(self, device, host_class):
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__}: the matching is a HIP kernel; there is no CPU fallback (use {host_class})")
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._records = []
+
+    def _device(self, x, dtype):
+        if torch.is_tensor(x) and x.is_cuda:
+            return x.to(device=self.device, dtype=dtype)
+        t = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(dtype)
+        return t.pin_memory().to(self.device, non_blocking=True)      # pinned + asynchronous: the upload does not block the host
+
+    def _check_tensors(self, want):
+        """want: (name, tensor, dtype, number of dimensions or None) of every argument of add_detections."""
+        for name, t, dt, nd in want:
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dt and (nd is None or t.dim() == nd)):
+                raise TypeError(f"add_detections: {name} must be a {dt} tensor on {self.device}" + (f" with {nd} dimensions" if nd else ""))
+
+    def _unpack(self, counters):
+        """One synchronisation, one device-to-host copy (status word, the int64 counters and every batch's records in one buffer)
+        -> (counters, [records int32 [width, B * Q] per batch]).  ValueError when the kernel flagged an input."""
+        shapes = [tuple(r.shape) for r in self._records]
+        buf = torch.cat([self._status, counters.view(torch.int32)] + [r.reshape(-1) for r in self._records]).cpu().numpy()
+        status, off = int(buf[0]), 1 + 2 * counters.numel()
+        if status:
+            raise ValueError(f"{type(self).__name__}: " + "; ".join(text for bit, text in self.BAD.items() if status & bit))
+        recs = []
+        for width, B, Q in shapes:
+            recs.append(np.ascontiguousarray(buf[off:off + width * B * Q].reshape(width, B * Q)))
+            off += width * B * Q
+        return buf[1:1 + 2 * counters.numel()].copy().view(np.int64), recs
+
+    def result(self, class_names=None, print_result=False):
+        return self.to_host().result(class_names, print_result=print_result)
+
+
+class DeviceAPAccumulator(_DeviceAccumulator):
     """APAccumulator whose per-image work runs on the device: one detr_hip_map_match launch per batch (after the one of
     detr_hip_postprocess), no host synchronisation until `to_host()`.  The flags, scores and ground-truth counts are the host
     path's exactly (same fp64 IoU arithmetic, same visiting order, same tie rules)."""
+    BAD = hip.MAP_BAD
 
     def __init__(self, nb_class, iou_thresholds=None, device=None):
         self.thresholds = list(IOU_THRESHOLDS if iou_thresholds is None else iou_thresholds)
@@ -158,27 +202,14 @@ class DeviceAPAccumulator:
             raise ValueError(f"DeviceAPAccumulator: {len(self.thresholds)} thresholds, 1..{hip.MAP_MAX_THR} are supported")
         if self.nb_class <= 0:
             raise ValueError("DeviceAPAccumulator: nb_class must be positive")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("DeviceAPAccumulator: the matching is a HIP kernel; there is no CPU fallback (use APAccumulator)")
+        self._open(device, "APAccumulator")                # records per batch: int32 [3, B, Q] = score bits, class, flag word
         self._num_gt = torch.zeros(self.nb_class, dtype=torch.int64, device=self.device)
-        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._records = []                        # per batch: int32 [3, B, Q] = score bits, class, flag word
-
-    def _device(self, x, dtype):
-        if torch.is_tensor(x) and x.is_cuda:
-            return x.to(device=self.device, dtype=dtype)
-        t = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(dtype)
-        return t.pin_memory().to(self.device, non_blocking=True)      # pinned + asynchronous: the upload does not block the host
 
     def add_detections(self, boxes, labels, scores, counts, t_bbox, t_class):
         """Device tensors: what detr_hip_postprocess wrote in "yxyx" format (boxes [B, Q, 4] fp32, labels [B, Q] int64, scores
         [B, Q] fp32, counts [B] int32) and the padded targets t_bbox [B, R, 4] fp32 (header row 0), t_class [B, R, 1] int64."""
-        want = (("boxes", boxes, torch.float32, 3), ("labels", labels, torch.int64, 2), ("scores", scores, torch.float32, 2),
-                ("counts", counts, torch.int32, 1), ("t_bbox", t_bbox, torch.float32, 3), ("t_class", t_class, torch.int64, None))
-        for name, t, dt, nd in want:
-            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dt and (nd is None or t.dim() == nd)):
-                raise TypeError(f"add_detections: {name} must be a {dt} tensor on {self.device}" + (f" with {nd} dimensions" if nd else ""))
+        self._check_tensors((("boxes", boxes, torch.float32, 3), ("labels", labels, torch.int64, 2), ("scores", scores, torch.float32, 2),
+                             ("counts", counts, torch.int32, 1), ("t_bbox", t_bbox, torch.float32, 3), ("t_class", t_class, torch.int64, None)))
         B, Q = labels.shape
         R = t_bbox.shape[1]
         if tuple(boxes.shape) != (B, Q, 4) or tuple(scores.shape) != (B, Q) or tuple(counts.shape) != (B,) or \
@@ -207,26 +238,15 @@ class DeviceAPAccumulator:
         self.add_detections(out_b, out_l, out_s, counts, self._device(t_bbox, torch.float32), self._device(t_class, torch.int64))
 
     def to_host(self):
-        """One synchronisation, one device-to-host copy (status word, ground-truth counts and every batch's records in one
-        buffer) -> the APAccumulator the host path would hold.  ValueError when the kernel flagged an input."""
-        shapes = [tuple(r.shape[1:]) for r in self._records]
-        buf = torch.cat([self._status, self._num_gt.view(torch.int32)] + [r.reshape(-1) for r in self._records]).cpu().numpy()
-        status, num_gt = int(buf[0]), buf[1:1 + 2 * self.nb_class].copy().view(np.int64)
-        if status:
-            raise ValueError("DeviceAPAccumulator: " + "; ".join(text for bit, text in hip.MAP_BAD.items() if status & bit))
-        off, parts = 1 + 2 * self.nb_class, []
-        for B, Q in shapes:
-            parts.append(buf[off:off + 3 * B * Q].reshape(3, B * Q))
-            off += 3 * B * Q
+        """One synchronisation, one device-to-host copy -> the APAccumulator the host path would hold.  ValueError when the kernel
+        flagged an input."""
+        num_gt, parts = self._unpack(self._num_gt)
         rec = np.concatenate(parts, 1) if parts else np.zeros((3, 0), np.int32)
         acc = APAccumulator(self.nb_class, self.thresholds)
         acc.scores, acc.flags = group_records(np.ascontiguousarray(rec[0]).view(np.float32), rec[1], np.ascontiguousarray(rec[2]).view(np.uint32),
                                               self.nb_class, len(self.thresholds))
         acc.num_gt = num_gt.astype(np.int64)
         return acc
-
-    def result(self, class_names=None, print_result=False):
-        return self.to_host().result(class_names, print_result=print_result)
 
 
 def print_maps(all_maps):

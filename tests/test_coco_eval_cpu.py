@@ -36,7 +36,8 @@ def test_coco_match_symbol_declared_exported_appended():
     assert _hip.ABI_VERSION == 9 and lib.detr_hip_abi_version() == 9 and "#define DETR_HIP_ABI_VERSION 9" in hdr
     assert hdr.index("detr_coco_match_desc;") > hdr.index("int detr_hip_detect(")               # appended, behind the newest entry
     assert hdr.index("int detr_hip_coco_match(") > hdr.index("detr_coco_match_desc;")
-    assert list(_hip._SIGNATURES)[-1] == name
+    order = list(_hip._SIGNATURES)                                          # appended in this order
+    assert order.index("detr_hip_detect") < order.index(name) < order.index("detr_hip_overlay")
     assert (_hip.COCO_MAX_THR, _hip.COCO_MAX_AREA) == (10, 4) and "#define DETR_COCO_MAX_THR 10" in hdr and "#define DETR_COCO_MAX_AREA 4" in hdr
     assert set(_hip.COCO_BAD) == {1, 2, 4, 8, 16} and "#define DETR_COCO_BAD_SIZE 16" in hdr
 

@@ -183,7 +183,7 @@ def test_detect_desc_layout_matches_the_header():
             item = item.strip()
             fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
     assert fields == list(_hip.DetectDesc._fields_)                            # names, order and types of the C declaration
-    assert _hip.APPENDED_LAYOUT_STRUCTS == {100: _hip.DetectDesc}
+    assert {w: S for w, S in _hip.LAYOUT_STRUCTS.items() if 100 <= w < 200} == {100: _hip.DetectDesc}
     buf = (ctypes.c_int32 * 96)()
     n = lib.detr_hip_struct_layout(100, buf, 96)
     want = _hip.struct_layout_mirror(_hip.DetectDesc)
@@ -193,14 +193,12 @@ def test_detect_desc_layout_matches_the_header():
 
     class Drifted(ctypes.Structure):                                           # score_threshold widened: every later offset moves
         _fields_ = [(f, (ctypes.c_double if f == "score_threshold" else t)) for f, t in _hip.DetectDesc._fields_]
-    saved = dict(_hip.APPENDED_LAYOUT_STRUCTS)
     try:
-        _hip.APPENDED_LAYOUT_STRUCTS[100] = Drifted
+        _hip.LAYOUT_STRUCTS[100] = Drifted
         with pytest.raises(RuntimeError, match="Drifted"):
             _hip.check_struct_layouts(lib)
     finally:
-        _hip.APPENDED_LAYOUT_STRUCTS.clear()
-        _hip.APPENDED_LAYOUT_STRUCTS.update(saved)
+        _hip.LAYOUT_STRUCTS[100] = _hip.DetectDesc
 
 
 def test_detect_rejects_bad_arguments_without_a_gpu():

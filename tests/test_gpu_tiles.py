@@ -264,20 +264,30 @@ def test_nan_logits(hip):
 
 
 # ---- whole-image windows: detect's bits ------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def whole_image_cases():
+    """(case, score_threshold, K, candidates): three images of Q = 100, C = 92; and B = 2 of Q = 300, C = 4 with every query foreground and
+    the threshold at 0 -- 300 candidates per image, so the compaction of a tile takes a second pass of 256 (under the cap of 2048)."""
+    sizes = [(480, 640), (1333, 800), (1, 1)]
+    first = make_case(7, (1, 1, 1), sizes, 100, 92, [(0, 0, h, w) for h, w in sizes], box_lo=0.0, box_hi=1.0)
+    second = make_case(8, (1, 1), sizes[:2], 300, 4, [(0, 0, h, w) for h, w in sizes[:2]], fg=1.0, box_lo=0.0, box_hi=1.0)
+    return (first, 0.5, 100, None), (second, 0.0, 300, 300)
+
+
 @pytest.mark.parametrize("fmt", FORMATS)
 @pytest.mark.parametrize("clip", (True, False))
 def test_whole_image_windows_equal_detect(hip, fmt, clip):
     from detr_tf.inference import detect_batched
-    sizes = [(480, 640), (1333, 800), (1, 1)]
-    case = make_case(7, (1, 1, 1), sizes, 100, 92, [(0, 0, h, w) for h, w in sizes], box_lo=0.0, box_hi=1.0)
-    out = {"pred_logits": torch.from_numpy(case["logits"].copy()).to(DEV), "pred_boxes": torch.from_numpy(case["boxes"].copy()).to(DEV)}
-    want = detect_batched(out, case["sizes"], case["bg"], score_threshold=0.5, max_detections=100, bbox_format=fmt, clip=clip)
-    got = run(case, score_threshold=0.5, max_detections=100, bbox_format=fmt, clip=clip, nms_threshold=1.0, edge_margin=4.0)
-    assert sum(int(w.scores.shape[0]) for w in want) > 100
-    for g, w in zip(got, want):
-        assert not g.tile.any()
-        for a, b in zip(g[:4], w):
-            assert a.dtype == b.dtype and a.shape == b.shape and a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+    for case, thr, K, candidates in whole_image_cases():
+        out = {"pred_logits": torch.from_numpy(case["logits"].copy()).to(DEV), "pred_boxes": torch.from_numpy(case["boxes"].copy()).to(DEV)}
+        want = detect_batched(out, case["sizes"], case["bg"], score_threshold=thr, max_detections=K, bbox_format=fmt, clip=clip)
+        got = run(case, score_threshold=thr, max_detections=K, bbox_format=fmt, clip=clip, nms_threshold=1.0, edge_margin=4.0)
+        assert sum(int(w.scores.shape[0]) for w in want) > 100
+        assert candidates is None or [int(w.scores.shape[0]) for w in want] == [candidates] * len(want)
+        for g, w in zip(got, want):
+            assert not g.tile.any()
+            for a, b in zip(g[:4], w):
+                assert a.dtype == b.dtype and a.shape == b.shape and a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
 
 
 # ---- the candidate cap -----------------------------------------------------------------------------------------------------------

@@ -196,7 +196,8 @@ def test_ctypes_mirrors_match_the_library_struct_layouts():
     field offsets the library was compiled with (detr_hip_struct_layout); a deliberately drifted mirror is caught."""
     import ctypes
     _hip, lib = _hip_lib()
-    for which, S in enumerate(_hip.LAYOUT_STRUCTS):
+    assert sorted(_hip.LAYOUT_STRUCTS)[:10] == list(range(10))
+    for which, S in sorted(_hip.LAYOUT_STRUCTS.items()):
         buf = (ctypes.c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)
         assert n == 1 + len(S._fields_), (S.__name__, n)

@@ -52,9 +52,8 @@ def test_overlay_desc_layout_matches_the_header():
             item = item.strip()
             fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
     assert fields == list(_hip.OverlayDesc._fields_)                            # names, order and types of the C declaration
-    assert _hip.EXTRA_LAYOUT_STRUCTS == {300: _hip.OverlayDesc}
-    assert _hip.APPENDED_LAYOUT_STRUCTS == {100: _hip.DetectDesc} and _hip.LATER_LAYOUT_STRUCTS == {200: _hip.TileMergeDesc}      # untouched
-    assert len(_hip.LAYOUT_STRUCTS) == 10
+    assert {w: S for w, S in _hip.LAYOUT_STRUCTS.items() if w >= 100} == {100: _hip.DetectDesc, 200: _hip.TileMergeDesc, 300: _hip.OverlayDesc}
+    assert sorted(w for w in _hip.LAYOUT_STRUCTS if w < 100) == list(range(10))
     buf = (ctypes.c_int32 * 96)()
     n = lib.detr_hip_struct_layout(300, buf, 96)
     want = _hip.struct_layout_mirror(_hip.OverlayDesc)
@@ -65,14 +64,12 @@ def test_overlay_desc_layout_matches_the_header():
 
     class Drifted(ctypes.Structure):                                            # thickness widened: every later offset moves
         _fields_ = [(f, (ctypes.c_int64 if f == "thickness" else t)) for f, t in _hip.OverlayDesc._fields_]
-    saved = dict(_hip.EXTRA_LAYOUT_STRUCTS)
     try:
-        _hip.EXTRA_LAYOUT_STRUCTS[300] = Drifted
+        _hip.LAYOUT_STRUCTS[300] = Drifted
         with pytest.raises(RuntimeError, match="Drifted"):
             _hip.check_struct_layouts(lib)
     finally:
-        _hip.EXTRA_LAYOUT_STRUCTS.clear()
-        _hip.EXTRA_LAYOUT_STRUCTS.update(saved)
+        _hip.LAYOUT_STRUCTS[300] = _hip.OverlayDesc
 
 
 def test_overlay_rejects_bad_arguments_without_a_gpu():

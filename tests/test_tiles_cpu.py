@@ -206,7 +206,7 @@ def test_tile_merge_desc_layout_matches_the_header():
             item = item.strip()
             fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
     assert fields == list(_hip.TileMergeDesc._fields_)                          # names, order and types of the C declaration
-    assert _hip.LATER_LAYOUT_STRUCTS == {200: _hip.TileMergeDesc}
+    assert {w: S for w, S in _hip.LAYOUT_STRUCTS.items() if 200 <= w < 300} == {200: _hip.TileMergeDesc}
     buf = (ctypes.c_int32 * 96)()
     n = lib.detr_hip_struct_layout(200, buf, 96)
     want = _hip.struct_layout_mirror(_hip.TileMergeDesc)
@@ -216,14 +216,12 @@ def test_tile_merge_desc_layout_matches_the_header():
 
     class Drifted(ctypes.Structure):                                            # edge_margin widened: every later offset moves
         _fields_ = [(f, (ctypes.c_double if f == "edge_margin" else t)) for f, t in _hip.TileMergeDesc._fields_]
-    saved = dict(_hip.LATER_LAYOUT_STRUCTS)
     try:
-        _hip.LATER_LAYOUT_STRUCTS[200] = Drifted
+        _hip.LAYOUT_STRUCTS[200] = Drifted
         with pytest.raises(RuntimeError, match="Drifted"):
             _hip.check_struct_layouts(lib)
     finally:
-        _hip.LATER_LAYOUT_STRUCTS.clear()
-        _hip.LATER_LAYOUT_STRUCTS.update(saved)
+        _hip.LAYOUT_STRUCTS[200] = _hip.TileMergeDesc
 
 
 def test_tile_merge_rejects_bad_arguments_without_a_gpu():
