@@ -258,6 +258,18 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_overlay_desc, heat_alpha)); DETR_PUT(DETR_OFF(detr_overlay_desc, workspace)); DETR_PUT(DETR_OFF(detr_overlay_desc, workspace_bytes));
         DETR_PUT(DETR_OFF(detr_overlay_desc, status));
         break;
+    case 400:   // detr_track_desc (the fourth appended list counts from 400, include/detr_hip.h)
+        DETR_PUT((int32_t)sizeof(detr_track_desc));
+        DETR_PUT(DETR_OFF(detr_track_desc, S)); DETR_PUT(DETR_OFF(detr_track_desc, D)); DETR_PUT(DETR_OFF(detr_track_desc, state));
+        DETR_PUT(DETR_OFF(detr_track_desc, state_bytes)); DETR_PUT(DETR_OFF(detr_track_desc, boxes)); DETR_PUT(DETR_OFF(detr_track_desc, labels));
+        DETR_PUT(DETR_OFF(detr_track_desc, scores)); DETR_PUT(DETR_OFF(detr_track_desc, query)); DETR_PUT(DETR_OFF(detr_track_desc, counts));
+        DETR_PUT(DETR_OFF(detr_track_desc, active)); DETR_PUT(DETR_OFF(detr_track_desc, track_threshold)); DETR_PUT(DETR_OFF(detr_track_desc, new_threshold));
+        DETR_PUT(DETR_OFF(detr_track_desc, match_threshold)); DETR_PUT(DETR_OFF(detr_track_desc, low_match_threshold)); DETR_PUT(DETR_OFF(detr_track_desc, max_age));
+        DETR_PUT(DETR_OFF(detr_track_desc, min_hits)); DETR_PUT(DETR_OFF(detr_track_desc, alpha)); DETR_PUT(DETR_OFF(detr_track_desc, beta));
+        DETR_PUT(DETR_OFF(detr_track_desc, class_agnostic)); DETR_PUT(DETR_OFF(detr_track_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_track_desc, out_labels));
+        DETR_PUT(DETR_OFF(detr_track_desc, out_scores)); DETR_PUT(DETR_OFF(detr_track_desc, out_query)); DETR_PUT(DETR_OFF(detr_track_desc, out_ids));
+        DETR_PUT(DETR_OFF(detr_track_desc, out_hits)); DETR_PUT(DETR_OFF(detr_track_desc, out_counts)); DETR_PUT(DETR_OFF(detr_track_desc, status));
+        break;
     default:
         detr::set_error("struct_layout: unknown struct %d", which);
         return -1;

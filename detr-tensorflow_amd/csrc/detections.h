@@ -1,4 +1,4 @@
-// detections.h -- the primitives of the post-model kernels (postprocess.hip, detect.hip, tile_merge.hip, map_match.hip,
+// detections.h -- the primitives of the post-model kernels (postprocess.hip, detect.hip, tile_merge.hip, track.hip, map_match.hip,
 // coco_match.hip): each algorithm is written once here, so two entry points that promise the same bits run the same code.
 // Every kernel of the family is one workgroup of DET_THREADS threads (4 waves) per image; the helpers take pointers to the
 // caller's __shared__ arrays and own no LDS.
@@ -109,6 +109,20 @@ __device__ __forceinline__ float4 emit_pixel_box(int fmt, float4 c, const float 
     if (fmt == 1) return c;
     if (fmt == 2) return make_float4(c.y, c.x, c.w, c.z);
     return make_float4(c.x, c.y, c.z - c.x, c.w - c.y);
+}
+
+// the match measure of two boxes (x0, y0, x1, y1), fp64 on fp32 corners, every operation one rounding: match 0 = IoU, 1 = intersection
+// over the smaller area; a zero denominator gives 0 (a NaN one NaN, which no threshold comparison accepts).  The suppression of
+// tile_merge.hip and the association of track.hip run this one definition.
+__device__ __forceinline__ double match_measure(const float4 p, const float4 g, int match) {
+#pragma clang fp contract(off)
+    const double px0 = p.x, py0 = p.y, px1 = p.z, py1 = p.w, gx0 = g.x, gy0 = g.y, gx1 = g.z, gy1 = g.w;
+    const double ix = (px1 < gx1 ? px1 : gx1) - (px0 > gx0 ? px0 : gx0);
+    const double iy = (py1 < gy1 ? py1 : gy1) - (py0 > gy0 ? py0 : gy0);
+    const double inter = (ix > 0.0 ? ix : 0.0) * (iy > 0.0 ? iy : 0.0);
+    const double ap = (px1 - px0) * (py1 - py0), ag = (gx1 - gx0) * (gy1 - gy0);
+    const double den = match == 0 ? ap + ag - inter : (ap < ag ? ap : ag);
+    return den == 0.0 ? 0.0 : inter / den;
 }
 
 // ---- staging for the matchers (map_match.hip, coco_match.hip).  Both return the DETR_MAP_BAD_* bits THIS THREAD found; thread

@@ -42,17 +42,6 @@ struct TileMergeArgs {
     int *status;                                    // [1]
 };
 
-// the match measure of two boxes (x0, y0, x1, y1), fp64 on fp32 corners; a zero (or NaN) denominator gives 0
-__device__ __forceinline__ double tm_measure(const float4 p, const float4 g, int match) {
-    const double px0 = p.x, py0 = p.y, px1 = p.z, py1 = p.w, gx0 = g.x, gy0 = g.y, gx1 = g.z, gy1 = g.w;
-    const double ix = (px1 < gx1 ? px1 : gx1) - (px0 > gx0 ? px0 : gx0);
-    const double iy = (py1 < gy1 ? py1 : gy1) - (py0 > gy0 ? py0 : gy0);
-    const double inter = (ix > 0.0 ? ix : 0.0) * (iy > 0.0 ? iy : 0.0);
-    const double ap = (px1 - px0) * (py1 - py0), ag = (gx1 - gx0) * (gy1 - gy0);
-    const double den = match == 0 ? ap + ag - inter : (ap < ag ? ap : ag);
-    return den == 0.0 ? 0.0 : inter / den;
-}
-
 __global__ __launch_bounds__(DET_THREADS) void tile_merge_kernel(TileMergeArgs a) {
     __shared__ float s_score[PP_MAXQ];             // the tile being staged
     __shared__ int s_label[PP_MAXQ];
@@ -127,7 +116,7 @@ __global__ __launch_bounds__(DET_THREADS) void tile_merge_kernel(TileMergeArgs a
             if (s_dead[rj]) continue;
             const int j = s_order[rj];
             if (!a.agnostic && c_label[j] != li) continue;
-            if (tm_measure(bi, c_box[j], a.match) > a.nms) s_dead[rj] = 1;
+            if (match_measure(bi, c_box[j], a.match) > a.nms) s_dead[rj] = 1;
         }
         __syncthreads();
     }

@@ -156,6 +156,23 @@ class OverlayDesc(Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_int64), ("status", c_void_p)]
 
 
+TRACK_MAX = 256                                                                # DETR_TRACK_MAX: track slots per stream
+TRACK_BAD = {1: f"more than {TRACK_MAX} live tracks in one stream (the slots of detr_hip_track are full: the detections behind them are "
+                "not tracked; raise new_threshold or lower max_age)",
+             2: "a detection count outside [0, D]"}                            # DETR_TRACK_FULL, DETR_TRACK_BAD_COUNT
+
+
+class TrackDesc(Structure):
+    """detr_track_desc (appended entry point, ABI version unchanged)."""
+    _fields_ = [("S", c_int32), ("D", c_int32), ("state", c_void_p), ("state_bytes", c_int64),
+                ("boxes", c_void_p), ("labels", c_void_p), ("scores", c_void_p), ("query", c_void_p), ("counts", c_void_p), ("active", c_void_p),
+                ("track_threshold", c_float), ("new_threshold", c_float),
+                ("match_threshold", ctypes.c_double), ("low_match_threshold", ctypes.c_double),
+                ("max_age", c_int32), ("min_hits", c_int32), ("alpha", c_float), ("beta", c_float), ("class_agnostic", c_int32),
+                ("out_boxes", c_void_p), ("out_labels", c_void_p), ("out_scores", c_void_p),
+                ("out_query", c_void_p), ("out_ids", c_void_p), ("out_hits", c_void_p), ("out_counts", c_void_p), ("status", c_void_p)]
+
+
 MAP_MAX_THR = 16                                                               # DETR_MAP_MAX_THR
 MAP_BAD = {1: "a predicted label outside [0, nb_class)", 2: "a target class outside [0, nb_class)",
            4: "a target header count outside [0, R-1]", 8: "a detection count outside [0, Q]"}      # DETR_MAP_BAD_*
@@ -266,6 +283,7 @@ _SIGNATURES = {
     "detr_hip_tile_merge": [POINTER(TileMergeDesc), c_void_p],
     "detr_hip_coco_match": [POINTER(CocoMatchDesc), c_void_p],
     "detr_hip_overlay": [POINTER(OverlayDesc), c_void_p],
+    "detr_hip_track": [POINTER(TrackDesc), c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
@@ -279,6 +297,7 @@ _SIGNATURES_I64 = {
     "detr_hip_workspace_bytes_layernorm": [POINTER(LayerNormDesc)],
     "detr_hip_workspace_bytes_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32],
     "detr_hip_workspace_bytes_overlay": [POINTER(OverlayDesc)],
+    "detr_hip_track_state_bytes": [c_int32],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
@@ -286,6 +305,8 @@ ABI_VERSION = 9
 # (include/detr_hip.h), so the id behind each of them stays unknown to the library
 LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: LayerNormDesc, 5: AttnDesc, 6: SetLossDesc, 7: InputDesc,
                   8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc}
+# the descriptors appended after detr_overlay_desc, by the same numbering; check_struct_layouts walks both tables
+LAYOUT_STRUCTS_APPENDED = {400: TrackDesc}
 
 _lib = None
 
@@ -520,7 +541,7 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in sorted(LAYOUT_STRUCTS.items()):
+    for which, S in sorted({**LAYOUT_STRUCTS, **LAYOUT_STRUCTS_APPENDED}.items()):
         want = struct_layout_mirror(S)
         buf = (c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)

@@ -17,6 +17,9 @@ alone puts the same NMS behind the single-pass outputs.
 
 `draw_detections` / `numpy_bbox_to_image` (detr_tf/overlay.py; reference inference.py:10-65) draw boxes, labels and an attention heat map
 onto the frames in one call of `detr_hip_overlay` (csrc/overlay.hip); `Detector.draw` feeds it the detector's own frames and maps.
+
+`Tracker` carries detections across the frames of a video: its tracks live on the device and one launch of `detr_hip_track`
+(csrc/track.hip) per batch of frames associates, updates, spawns and emits -- `Detector.track` feeds it the detector's raw rows.
 """
 import math
 from ctypes import byref
@@ -240,6 +243,179 @@ def merge_tiles(m_outputs: dict, tile_start, windows, sizes, background_class, *
     return [TiledDetections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k], out_t[b, :k]) for b, k in enumerate(counts)]
 
 
+class TrackedDetections(NamedTuple):
+    """The detections of ONE frame that belong to a confirmed track, in the detector's order: Detections' four fields, copied bit for
+    bit, plus ids [k] int32, the track each belongs to (>= 1, never reused within a stream), and hits [k] int32, the number of frames
+    that track has been matched in."""
+    boxes: torch.Tensor
+    labels: torch.Tensor
+    scores: torch.Tensor
+    query: torch.Tensor
+    ids: torch.Tensor
+    hits: torch.Tensor
+
+
+_T = hip.TRACK_MAX
+# one stream of the device state (include/detr_hip.h: detr_track_desc); detr_hip_track_state_bytes is what sizes the buffer
+TRACK_STATE = np.dtype([("x", "<f4", (_T, 4)), ("v", "<f4", (_T, 4)), ("label", "<i8", (_T,)), ("score", "<f4", (_T,)), ("id", "<i4", (_T,)),
+                        ("hits", "<i4", (_T,)), ("miss", "<i4", (_T,)), ("confirmed", "<i4", (_T,)), ("frame", "<i4"), ("next_id", "<i4"),
+                        ("pad", "<i4", (2,))])
+TRACK_STATE_KEYS = ("x", "v", "label", "id", "hits", "miss", "confirmed", "score", "frame", "next_id")
+
+
+class Tracker:
+    """Multi-object tracking whose state lives on the device: `streams` independent videos, at most _hip.TRACK_MAX tracks each.
+
+        tracker = Tracker()                                  # one stream
+        for frame in video:
+            tracked = detector.track(frame, tracker)         # TrackedDetections: the detector's rows plus ids and hits
+
+    Per frame and stream (include/detr_hip.h: detr_track_desc is the normative text): every track is moved by its velocity; the
+    detections with score >= track_threshold are associated with the tracks of their label (any label with class_agnostic) by greedy
+    descending IoU above match_threshold (ties: lower id, then lower detection); the tracks left over that are confirmed and were
+    matched in the frame before get a second chance against the low-score detections above low_match_threshold; a matched track moves
+    to prediction + alpha * residual and its velocity by beta * residual; an unmatched one coasts, and is dropped when it is not yet
+    confirmed or has missed more than max_age frames; an unmatched detection with score >= new_threshold (None: track_threshold)
+    starts a track, confirmed after min_hits matched frames; only detections of confirmed tracks are returned.
+    The defaults are ByteTrack's and SORT's conventions carried over; nobody has tuned them for DETR outputs.  The association is
+    greedy, not Hungarian; there is no Kalman covariance, no re-identification feature and no camera-motion compensation."""
+
+    def __init__(self, streams=1, device=None, *, track_threshold=0.7, new_threshold=None, match_threshold=0.3, low_match_threshold=0.5,
+                 max_age=30, min_hits=3, alpha=0.75, beta=0.25, class_agnostic=False):
+        if new_threshold is None:
+            new_threshold = track_threshold
+        if not 1 <= int(streams) <= 65535:
+            raise ValueError(f"Tracker: streams={streams} must be in 1..65535")
+        for name, value in (("track_threshold", track_threshold), ("new_threshold", new_threshold), ("match_threshold", match_threshold),
+                            ("low_match_threshold", low_match_threshold), ("alpha", alpha), ("beta", beta)):
+            if not math.isfinite(float(value)):
+                raise ValueError(f"Tracker: {name}={value} is not finite")
+        if int(max_age) < 0 or int(min_hits) < 1:
+            raise ValueError(f"Tracker: max_age={max_age} must be >= 0 and min_hits={min_hits} >= 1")
+        self.streams = int(streams)
+        self.track_threshold, self.new_threshold = float(track_threshold), float(new_threshold)
+        self.match_threshold, self.low_match_threshold = float(match_threshold), float(low_match_threshold)
+        self.max_age, self.min_hits, self.alpha, self.beta = int(max_age), int(min_hits), float(alpha), float(beta)
+        self.class_agnostic = bool(class_agnostic)
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"Tracker: the state lives on the GPU (the tracker is a HIP kernel; no CPU fallback), not on {self.device}")
+        nbytes = int(hip.load().detr_hip_track_state_bytes(self.streams))
+        if nbytes != self.streams * TRACK_STATE.itemsize:
+            raise RuntimeError(f"Tracker: the library's state is {nbytes} bytes for {self.streams} streams, this binding lays out "
+                               f"{self.streams * TRACK_STATE.itemsize}: rebuild the library")
+        self._state = torch.empty(self.streams, TRACK_STATE.itemsize, dtype=torch.uint8, device=self.device)
+        self._all_active = torch.ones(self.streams, dtype=torch.int32, device=self.device)
+        self.reset()
+
+    # ---- state
+    def reset(self, stream=None):
+        """Forget every track of `stream` (None: of all streams); its ids start at 1 again."""
+        fresh = np.zeros(1, TRACK_STATE)
+        fresh["next_id"] = 1
+        row = torch.from_numpy(fresh.view(np.uint8).reshape(1, -1)).to(self.device)
+        if stream is None:
+            self._state.copy_(row.expand(self.streams, -1))
+        else:
+            if not 0 <= int(stream) < self.streams:
+                raise ValueError(f"Tracker.reset: stream={stream} outside 0..{self.streams - 1}")
+            self._state[int(stream)].copy_(row[0])
+
+    def state_dict(self):
+        """The whole state as named host arrays, leading axis = stream: x, v float32 [S, T, 4]; label int64, id, hits, miss int32,
+        confirmed bool, score float32 [S, T]; frame, next_id int32 [S] (T = _hip.TRACK_MAX; a free slot is all zeros).  One copy to the
+        host."""
+        raw = self._state.cpu().numpy().reshape(-1).view(TRACK_STATE)
+        out = {k: np.ascontiguousarray(raw[k]) for k in TRACK_STATE_KEYS}
+        out["confirmed"] = out["confirmed"] != 0
+        return out
+
+    def load_state_dict(self, state):
+        """Take over a state_dict(): the video goes on bit-identically."""
+        missing = [k for k in TRACK_STATE_KEYS if k not in state]
+        if missing:
+            raise ValueError(f"Tracker.load_state_dict: missing {missing}")
+        raw = np.zeros(self.streams, TRACK_STATE)
+        for k in TRACK_STATE_KEYS:
+            value = np.asarray(state[k])
+            if value.shape != raw[k].shape:
+                raise ValueError(f"Tracker.load_state_dict: {k} has shape {value.shape}, expected {raw[k].shape} ({self.streams} streams)")
+            raw[k] = value
+        self._state.copy_(torch.from_numpy(raw.view(np.uint8).reshape(self.streams, -1)))
+
+    # ---- frames
+    def _launch(self, boxes, labels, scores, query, counts, active):
+        S = self.streams
+        if boxes.dim() != 3 or boxes.shape[0] != S or boxes.shape[2] != 4 or not 1 <= boxes.shape[1] <= 1024:
+            raise ValueError(f"Tracker: boxes must be [S={S}, D, 4] with D in 1..1024, got {tuple(boxes.shape)}")
+        D = int(boxes.shape[1])
+        for name, t, dtype, shape in (("boxes", boxes, torch.float32, (S, D, 4)), ("labels", labels, torch.int64, (S, D)),
+                                      ("scores", scores, torch.float32, (S, D)), ("query", query, torch.int32, (S, D)),
+                                      ("counts", counts, torch.int32, (S,)), ("active", active, torch.int32, (S,))):
+            if t is None and name == "query":
+                continue
+            if t.device != self._state.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"Tracker: {name} must be a contiguous {dtype} tensor {shape} on {self._state.device}, got {t.dtype} "
+                                 f"{tuple(t.shape)} on {t.device}")
+        out_b, out_l, out_s, out_q, out_i, out_h = _ranked_rows(S, D, self.device, 3)
+        tail = torch.zeros(S + 1, dtype=torch.int32, device=self.device)       # counts [S], then the status word
+        d = hip.TrackDesc()
+        d.S, d.D, d.state, d.state_bytes = S, D, self._state.data_ptr(), self._state.numel()
+        d.boxes, d.labels, d.scores, d.query = boxes.data_ptr(), labels.data_ptr(), scores.data_ptr(), hip.ptr(query)
+        d.counts, d.active = counts.data_ptr(), active.data_ptr()
+        d.track_threshold, d.new_threshold = self.track_threshold, self.new_threshold
+        d.match_threshold, d.low_match_threshold = self.match_threshold, self.low_match_threshold
+        d.max_age, d.min_hits, d.alpha, d.beta, d.class_agnostic = self.max_age, self.min_hits, self.alpha, self.beta, int(self.class_agnostic)
+        d.out_boxes, d.out_labels, d.out_scores = out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr()
+        d.out_query, d.out_ids, d.out_hits = out_q.data_ptr(), out_i.data_ptr(), out_h.data_ptr()
+        d.out_counts, d.status = tail.data_ptr(), tail.data_ptr() + 4 * S
+        with torch.cuda.device(self.device):
+            hip._check(hip.load().detr_hip_track(byref(d), hip._stream()), "detr_hip_track")
+        return (out_b, out_l, out_s, out_q, out_i, out_h), tail
+
+    def _active(self, active):
+        if active is None:
+            return self._all_active
+        flags = np.asarray(active.cpu() if isinstance(active, torch.Tensor) else active).astype(bool)
+        if flags.shape != (self.streams,):
+            raise ValueError(f"Tracker: active must hold one flag per stream ({self.streams}), got shape {flags.shape}")
+        return torch.from_numpy(flags.astype(np.int32)).to(self.device)
+
+    def update_rows(self, boxes, labels, scores, query, counts, active=None):
+        """One frame per stream from padded DEVICE rows, as detr_hip_detect / detr_hip_tile_merge write them with bbox_format "xyxy":
+        boxes [S, D, 4] float32, labels [S, D] int64, scores [S, D] float32, query [S, D] int32 or None, counts [S] int32 -- D <= 1024;
+        rows behind counts[s] are not read.  active: one flag per stream (None: all); a stream whose flag is 0 keeps its state and
+        returns nothing, e.g. a video that delivered no frame.  No packing and no synchronisation before the launch; ONE host
+        synchronisation after it (the emitted counts and the status word).  -> [TrackedDetections], one per stream.  A stream with more
+        than _hip.TRACK_MAX live tracks raises ValueError AFTER the state has been updated: the state stays valid, the detections
+        that found no slot are not tracked."""
+        rows, tail = self._launch(boxes, labels, scores, query, counts, self._active(active))
+        *n, status = tail.tolist()
+        if status:
+            raise ValueError("Tracker: " + "; ".join(text for bit, text in hip.TRACK_BAD.items() if status & bit))
+        return [TrackedDetections(*(r[s, :k] for r in rows)) for s, k in enumerate(n)]
+
+    def update(self, detections, active=None):
+        """One frame per stream: `detections` holds, per stream, a Detections / TiledDetections with boxes in "xyxy" pixels, or a
+        (boxes [k, 4], labels [k], scores [k]) triple (its query is 0); a single one is taken as the frame of a one-stream tracker.
+        They are packed into padded rows (as draw_detections packs them) and go through update_rows."""
+        if isinstance(detections, (Detections, TiledDetections)) or (isinstance(detections, tuple) and len(detections) == 3
+                                                                       and not isinstance(detections[0], (tuple, list))):
+            detections = [detections]
+        if len(detections) != self.streams:
+            raise ValueError(f"Tracker.update: {len(detections)} frames for {self.streams} streams")
+        from .overlay import _pack_detections
+        rows = [(torch.as_tensor(d[0]).reshape(-1, 4), torch.as_tensor(d[1]).reshape(-1), torch.as_tensor(d[2]).reshape(-1)) for d in detections]
+        if max(int(r[0].shape[0]) for r in rows) > 1024:
+            raise ValueError("Tracker.update: more than 1024 detections in one frame")
+        boxes, labels, scores, counts = _pack_detections(rows, True, self.device)
+        query = torch.zeros(labels.shape, dtype=torch.int32, device=self.device)
+        for s, d in enumerate(detections):
+            if hasattr(d, "query") and counts[s]:
+                query[s, :counts[s]] = d.query.to(self.device)
+        return self.update_rows(boxes, labels, scores, query, torch.from_numpy(counts).to(self.device), active)
+
+
 class Detector:
     """Raw images in, pixel-space detections out (what the reference's webcam_inference.py:26-34 and eval.py:41-55 assemble by hand).
 
@@ -348,6 +524,21 @@ class Detector:
         windows = np.array([(t.y0, t.x0, t.hc, t.wc) for r in recs for t in r], np.int32)
         return self._merge({"pred_logits": logits, "pred_boxes": boxes}, tile_start, windows, sizes)
 
+    def _forward(self, srcs, sizes, need_weights=None):
+        """The single pass: input stage and model on the frames `srcs` -> (m_outputs, the input's shape)."""
+        if self.resize == "fixed":
+            if (sizes != sizes[0]).any():
+                raise ValueError(f"Detector: resize='fixed' takes images of ONE size per call, got {sorted(set(map(tuple, sizes.tolist())))}; "
+                                 "resize='shortest_side' batches mixed sizes")
+            inputs = self.stage().images(np.stack(srcs))
+            shape = inputs.shape
+            self._last_frames = srcs                                    # (this path uploads one dense batch: kept on the host)
+        else:
+            inputs = self.stage().augmented_padded(srcs, self.records(srcs), canvas=self.canvas)
+            shape = inputs[0].shape
+            self._last_frames = self.stage().last_upload                # already on the device: they cross PCIe once
+        return self.model(inputs, training=False, need_weights=need_weights), shape
+
     def __call__(self, images, need_weights=None):
         """images: one uint8 [h, w, 3] array -> Detections, or a list of them -> [Detections] (TiledDetections with tiles or
         nms_threshold).  With need_weights (DetrModel.__call__) the result is (detections, maps), maps as get_attention_maps returns
@@ -364,18 +555,7 @@ class Detector:
             detections = self._tiled(srcs, sizes)
             self._last_frames = self.stage().last_upload
             return detections[0] if single else detections
-        if self.resize == "fixed":
-            if (sizes != sizes[0]).any():
-                raise ValueError(f"Detector: resize='fixed' takes images of ONE size per call, got {sorted(set(map(tuple, sizes.tolist())))}; "
-                                 "resize='shortest_side' batches mixed sizes")
-            inputs = self.stage().images(np.stack(srcs))
-            shape = inputs.shape
-            self._last_frames = srcs                                    # (this path uploads one dense batch: kept on the host)
-        else:
-            inputs = self.stage().augmented_padded(srcs, self.records(srcs), canvas=self.canvas)
-            shape = inputs[0].shape
-            self._last_frames = self.stage().last_upload                # already on the device: they cross PCIe once
-        m_outputs = self.model(inputs, training=False, need_weights=need_weights)
+        m_outputs, shape = self._forward(srcs, sizes, need_weights)
         if self.nms_threshold is not None:                              # one whole-image window per image
             windows = np.concatenate([np.zeros_like(sizes), sizes], 1)
             detections = self._merge(m_outputs, np.arange(len(srcs) + 1, dtype=np.int32), windows, sizes)
@@ -386,6 +566,32 @@ class Detector:
         if "attn" in m_outputs:
             return detections, _feature_maps(self.model, shape, m_outputs["attn"])
         return detections
+
+    def track(self, images, tracker, active=None):
+        """One video frame per stream of `tracker` (a Tracker with as many streams as there are images): the detections of __call__
+        that belong to a confirmed track, as TrackedDetections (a list for a list of images).  The plain path hands detr_hip_detect's
+        raw rows and device counts to Tracker.update_rows: one launch more than __call__ and ONE host synchronisation per frame, the
+        tracker's counts.  With tiles / nms_threshold the frame goes through merge_tiles first, which synchronises once itself: two per
+        frame.  Needs bbox_format="xyxy".  active: Tracker.update_rows'."""
+        if self.bbox_format != "xyxy":
+            raise ValueError(f"Detector.track: boxes must be 'xyxy' pixels: build the Detector with bbox_format='xyxy', not {self.bbox_format!r}")
+        if not isinstance(tracker, Tracker):
+            raise TypeError(f"Detector.track: tracker must be a Tracker, got {type(tracker).__name__}")
+        single = not isinstance(images, (list, tuple))
+        srcs = [np.asarray(im) for im in ([images] if single else images)]
+        if not srcs or any(s.dtype != np.uint8 or s.ndim != 3 or s.shape[-1] != 3 for s in srcs):
+            raise TypeError("Detector expects a uint8 image [h, w, 3] or a non-empty list of them")
+        if len(srcs) != tracker.streams:
+            raise ValueError(f"Detector.track: {len(srcs)} images for a tracker of {tracker.streams} streams")
+        if self.tiles is not None or self.nms_threshold is not None:
+            tracked = tracker.update(self(srcs), active)
+        else:
+            sizes = np.array([s.shape[:2] for s in srcs], np.int32)
+            m_outputs, _ = self._forward(srcs, sizes)
+            rows = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, self.background_class, self.score_threshold,
+                           self.max_detections, self.bbox_format, True)
+            tracked = tracker.update_rows(*rows, active)
+        return tracked[0] if single else tracked
 
     def attention_site(self, site="dec"):
         """The key of `maps` a site names: "dec" = the last decoder cross-attention (one row per object query), "enc" = the last

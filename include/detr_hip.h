@@ -913,6 +913,69 @@ typedef struct {
 int detr_hip_overlay(const detr_overlay_desc *d, void *stream);
 int64_t detr_hip_workspace_bytes_overlay(const detr_overlay_desc *d);
 
+/* ---------------------------------------------------------------------------------------------
+ * Multi-object tracking across video frames, appended (the ABI version is unchanged):
+ *   replaces: the host loop a user of the video program (webcam_inference.py:26-34) writes to tell that a detection of this frame is
+ *             the object of the last one -- detections read back every frame, an O(tracks x detections) IoU association in NumPy.
+ * One launch per batch of frames, one workgroup per video stream (csrc/track.hip); the tracks of a stream live in `state` on the
+ * device, DETR_TRACK_MAX slots per stream.  A live slot holds x = (cx, cy, w, h) fp32 pixels, v = its change per frame, label, id >= 1,
+ * hits, miss, confirmed and the last score; a free slot is all zeros (id 0).  The stream holds frame and next_id (1 in a fresh state).
+ * Input of stream s: counts[s] <= D detections, boxes "xyxy" pixels (bbox_format 1 of detr_hip_detect / detr_hip_tile_merge), labels,
+ * scores, optionally query, in the detector's order.  Every fp32 operation below is ONE rounding (no fused multiply-add); every IoU is
+ * the fp64 measure of detr_hip_tile_merge with match 0 on fp32 corners.  Per stream with active[s] != 0, in this order:
+ *   1. predict: for every live slot p = x + v; p.w, p.h below 0 become 0 (p.w < 0 ? 0 : p.w); corners p.c -+ p.size * 0.5f.
+ *   2. detections: z = ((x0 + x1) * 0.5f, (y0 + y1) * 0.5f, x1 - x0, y1 - y0); `high` when score >= track_threshold, else `low`.
+ *   3. stage 1: the pairs (live slot, high detection) of equal label (any label with class_agnostic) with
+ *      IoU(corners of p, detection) > match_threshold (strict; a NaN IoU is no pair) are walked by descending IoU, ties by lower
+ *      track id, then lower detection index; a pair is taken when both sides are still free.
+ *   4. stage 2: the same walk with > low_match_threshold over the slots still unmatched that are confirmed and came into the frame
+ *      with miss == 0, and the low detections.
+ *   5. a matched slot: r = z - p; x = p + alpha * r; v = v + beta * r; hits += 1; miss = 0; score = the detection's;
+ *      confirmed |= hits >= min_hits.  The label never changes.
+ *   6. an unmatched slot: x = p; miss += 1; it is freed (zeroed) when it is not confirmed or miss > max_age.
+ *   7. spawn: the unmatched high detections with score >= new_threshold, by ascending index, each take the lowest free slot (those of
+ *      step 6 included): id = next_id++, x = z, v = 0, hits = 1, miss = 0, confirmed = (min_hits <= 1), label and score the
+ *      detection's.  Without a free slot the detection is not tracked and DETR_TRACK_FULL is set in *status.
+ *   8. emit, by ascending detection index: every detection matched to (or spawned as) a confirmed track -- box, label, score and
+ *      query copied unchanged, plus the track's id and hits -- at rows [s * D, s * D + out_counts[s]); the rows behind are zero.
+ *      frame += 1.
+ * counts[s] outside [0, D] sets DETR_TRACK_BAD_COUNT and the stream is run with no detections.  active[s] == 0 leaves the state of
+ * stream s untouched: out_counts[s] = 0 and zero rows.  The caller zeroes *status.  Nothing is accessed out of bounds for any input.
+ * Integer atomics on *status only, no float atomics: a rerun from the same state is bit-identical.
+ * state: detr_hip_track_state_bytes(S) bytes (negative: S outside 1..65535), 16-byte aligned; stream s at byte s * (that / S), as
+ *   float x[DETR_TRACK_MAX][4]; float v[DETR_TRACK_MAX][4]; int64_t label[DETR_TRACK_MAX]; float score[DETR_TRACK_MAX];
+ *   int32_t id[DETR_TRACK_MAX], hits[DETR_TRACK_MAX], miss[DETR_TRACK_MAX], confirmed[DETR_TRACK_MAX]; int32_t frame, next_id, pad[2].
+ * Limits: S 1..65535, D 1..1024; thresholds, alpha, beta finite; max_age >= 0; min_hits >= 1; boxes, out_boxes, state 16-byte aligned.
+ * detr_hip_struct_layout knows detr_track_desc as 400 (a fourth appended list; 300 is detr_overlay_desc).
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_TRACK_MAX 256
+#define DETR_TRACK_FULL 1
+#define DETR_TRACK_BAD_COUNT 2
+typedef struct {
+    int32_t S, D;
+    void *state;                                 /* detr_hip_track_state_bytes(S) bytes, read and written */
+    int64_t state_bytes;
+    const float *boxes;                          /* [S, D, 4] x0, y0, x1, y1 in pixels */
+    const int64_t *labels;                       /* [S, D] */
+    const float *scores;                         /* [S, D] */
+    const int32_t *query;                        /* [S, D] or NULL (emitted as 0) */
+    const int32_t *counts;                       /* [S], DEVICE memory */
+    const int32_t *active;                       /* [S], DEVICE memory */
+    float track_threshold, new_threshold;        /* finite */
+    double match_threshold, low_match_threshold; /* finite */
+    int32_t max_age, min_hits;
+    float alpha, beta;                           /* finite */
+    int32_t class_agnostic;                      /* 0 | 1 */
+    float *out_boxes;                            /* [S, D, 4] */
+    int64_t *out_labels;                         /* [S, D] */
+    float *out_scores;                           /* [S, D] */
+    int32_t *out_query, *out_ids, *out_hits;     /* [S, D] */
+    int32_t *out_counts;                         /* [S] */
+    int32_t *status;                             /* [1] */
+} detr_track_desc;
+int detr_hip_track(const detr_track_desc *d, void *stream);
+int64_t detr_hip_track_state_bytes(int32_t streams);
+
 #ifdef __cplusplus
 }
 #endif
