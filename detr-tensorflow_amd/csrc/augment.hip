@@ -10,19 +10,16 @@
 // then the normalisation table of detr_hip_input_stage.  Stage B is fused into R: every tap of the final resize recomputes
 // the stage-B pixel it reads (rounded to uint8 first), so the result is that of the two stages applied one after the other.
 //
-// Nearest / linear / cubic are input_stage_kernel's fp32 formulas in the same operation order (bit-identical results).
-// Area is OpenCV's INTER_AREA restated from its documentation: for r = src / dst >= 1 on both axes the fractional-overlap
+// Every resize is image_resample.h's resample(), the one input_stage_kernel calls: a record without flip and stage B gives
+// detr_hip_input_stage's bits.  Area is OpenCV's INTER_AREA restated from its documentation: for r = src / dst >= 1 on both axes the fractional-overlap
 // box average of the source footprint divided by rx * ry, otherwise per axis the linear taps with OpenCV's area-mode
 // coefficient.  OpenCV's uint8 paths use fixed-point coefficients: parity with cv2 / imgaug is unpinned, as for cubic.
 //
 // Safety: every source index is clamped into its own image, and an image whose record does not fit in the `src_bytes`
 // bytes of `src` is read as a single pixel at offset 0, so no record can read outside src; writes depend on B, Hd, Wd only.
-#include "augment_resample.h"
+#include "image_resample.h"
 
 namespace detr {
-
-constexpr int AUG_THREADS = 256;
-constexpr int AUG_PIX = 4;               // output pixels per lane: 12 floats = three 16-byte stores
 
 struct AugArgs {
     const unsigned char *src; long long src_bytes;
@@ -66,15 +63,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(AugArgs a) {
     const int b = blockIdx.y;
     const int *ir = a.irec + (long long)b * DETR_AUG_IREC;
     const float *fr = a.frec + (long long)b * DETR_AUG_FREC;
-    AugImage m;
-    m.src = a.src;
-    long long off = (long long)(unsigned)ir[0] | ((long long)ir[1] << 32);
-    m.h0 = ir[2]; m.w0 = ir[3];
-    if (off < 0 || m.h0 < 1 || m.w0 < 1 || m.h0 > 65536 || m.w0 > 65536 || off + (long long)m.h0 * m.w0 * 3 > a.src_bytes) {
-        off = 0; m.h0 = 1; m.w0 = 1;                 // a record that does not fit: one pixel at offset 0
-    }
-    m.lo = off; m.hi = off + (long long)m.h0 * m.w0 * 3 - 3;
-    m.flip = ir[4] & 1;
+    AugImage m = aug_image(a.src, a.src_bytes, ir);
     const int kind = ir[5], ia = min(max(ir[6], 0), 3), ifin = min(max(ir[7], 0), 3);
     m.cy0 = kind == 2 ? min(max(ir[8], 0), m.h0) : 0;   // crop offset (stage B = crop only)
     m.cx0 = kind == 2 ? min(max(ir[9], 0), m.w0) : 0;
@@ -98,21 +87,9 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(AugArgs a) {
         } else {
             resample(FetchWindow{m}, m.h0, m.w0, Hd, Wd, ifin, y, x, v);
         }
-        out[3 * q + 0] = a.lut[(int)v[a.perm0]];
-        out[3 * q + 1] = a.lut[256 + (int)v[a.perm1]];
-        out[3 * q + 2] = a.lut[512 + (int)v[a.perm2]];
+        lut_pixel(a.lut, a.perm0, a.perm1, a.perm2, v, out + 3 * q);
     }
-    float *o = a.dst + ((long long)b * HW + p0) * 3;
-    if (a.vec && p0 + AUG_PIX <= HW) {
-        float4 *o4 = reinterpret_cast<float4 *>(o);
-        o4[0] = make_float4(out[0], out[1], out[2], out[3]);
-        o4[1] = make_float4(out[4], out[5], out[6], out[7]);
-        o4[2] = make_float4(out[8], out[9], out[10], out[11]);
-    } else {
-        for (int q = 0; q < AUG_PIX && p0 + q < HW; ++q) {
-            o[3 * q + 0] = out[3 * q + 0]; o[3 * q + 1] = out[3 * q + 1]; o[3 * q + 2] = out[3 * q + 2];
-        }
-    }
+    store_pixels(a.dst + ((long long)b * HW + p0) * 3, out, a.vec && p0 + AUG_PIX <= HW, HW - p0);
 }
 
 }  // namespace detr
@@ -125,7 +102,7 @@ extern "C" int detr_hip_augment(const uint8_t *src, int64_t src_bytes, const int
     DETR_REQUIRE(B > 0 && B <= 65535 && Hd > 0 && Wd > 0 && (long long)Hd * Wd <= (1ll << 30),
                  "augment: bad shape B=%d Hd=%d Wd=%d", B, Hd, Wd);
     DETR_REQUIRE(src_bytes >= 3, "augment: src_bytes must cover at least one pixel");
-    for (int c = 0; c < 3; ++c) DETR_REQUIRE(perm[c] >= 0 && perm[c] < 3, "augment: channel permutation out of range");
+    DETR_REQUIRE(check_perm(perm), "augment: channel permutation out of range");
     AugArgs a;
     a.src = src; a.src_bytes = src_bytes; a.irec = irec; a.frec = frec; a.dst = dst; a.lut = lut;
     a.B = B; a.Hd = Hd; a.Wd = Wd; a.perm0 = perm[0]; a.perm1 = perm[1]; a.perm2 = perm[2];

@@ -6,7 +6,7 @@
 // draw_multiscale / eval_record); the kernel applies it:
 //   F  horizontal flip (exact index mirror),
 //   W  the window (y0, x0, hc, wc) of F, in whole source pixels,
-//   R  resize of the window to (hd, wd) with augment.hip's formulas (augment_resample.h: same operation order, result rounded
+//   R  resize of the window to (hd, wd) by image_resample.h's resample() (as augment.hip and input_stage.hip; result rounded
 //      and saturated to uint8), then the normalisation table of detr_hip_input_stage,
 // written at the canvas's top-left; every canvas pixel outside hd x wd is 0.0f with mask 1, inside the mask is 0.  The resized
 // images never exist on the host and no intermediate image is written to HBM.
@@ -15,17 +15,14 @@
 // of that).  Measured (B = 8, 480 x 640 -> 800 x 1066 on an 800 x 1344 canvas, bilinear): 58 us against 26 us for a device
 // copy of the same bytes and 66 us for augment_kernel writing 800 x 1344; the padding part runs at the copy's rate, the valid
 // part is bound by the byte gather (4 to 16 taps of three byte loads per pixel), as in augment_kernel (NOTEBOOK 12).  One lane
-// owns AUGP_PIX = 4 consecutive pixels of a canvas row-major run: three 16-byte pixel stores and one 4-byte mask store.
+// owns AUG_PIX = 4 consecutive pixels of a canvas row-major run: three 16-byte pixel stores and one 4-byte mask store.
 //
 // Safety (augment.hip's rule): every source index is clamped into its own window and image, a record that does not fit in
 // the `src_bytes` bytes of `src` is read as a single pixel at offset 0, the window is clamped into the image and (hd, wd)
 // to the canvas, so no record can read outside src; writes depend on B, H, W only.
-#include "augment_resample.h"
+#include "image_resample.h"
 
 namespace detr {
-
-constexpr int AUGP_THREADS = 256;
-constexpr int AUGP_PIX = 4;
 
 struct AugPadArgs {
     const unsigned char *src; long long src_bytes;
@@ -36,19 +33,11 @@ struct AugPadArgs {
     int B, H, W, perm0, perm1, perm2, vec;
 };
 
-// grid = (ceil(H * W / (AUGP_THREADS * AUGP_PIX)), B): the image index is uniform per workgroup, so is its record
-__global__ __launch_bounds__(AUGP_THREADS) void augment_padded_kernel(AugPadArgs a) {
+// grid = (ceil(H * W / (AUG_THREADS * AUG_PIX)), B): the image index is uniform per workgroup, so is its record
+__global__ __launch_bounds__(AUG_THREADS) void augment_padded_kernel(AugPadArgs a) {
     const int b = blockIdx.y;
     const int *ir = a.irec + (long long)b * DETR_AUGP_IREC;
-    AugImage m;
-    m.src = a.src;
-    long long off = (long long)(unsigned)ir[0] | ((long long)ir[1] << 32);
-    m.h0 = ir[2]; m.w0 = ir[3];
-    if (off < 0 || m.h0 < 1 || m.w0 < 1 || m.h0 > 65536 || m.w0 > 65536 || off + (long long)m.h0 * m.w0 * 3 > a.src_bytes) {
-        off = 0; m.h0 = 1; m.w0 = 1;                 // a record that does not fit: one pixel at offset 0
-    }
-    m.lo = off; m.hi = off + (long long)m.h0 * m.w0 * 3 - 3;
-    m.flip = ir[4] & 1;
+    AugImage m = aug_image(a.src, a.src_bytes, ir);
     m.cy0 = min(max(ir[5], 0), m.h0 - 1);            // the window, clamped into the image and at least one pixel
     m.cx0 = min(max(ir[6], 0), m.w0 - 1);
     const int hc = min(max(ir[7], 1), m.h0 - m.cy0), wc = min(max(ir[8], 1), m.w0 - m.cx0);
@@ -56,20 +45,18 @@ __global__ __launch_bounds__(AUGP_THREADS) void augment_padded_kernel(AugPadArgs
     const int interp = min(max(ir[11], 0), 3);
     m.isx = m.isy = 1.0f;
     const int HW = a.H * a.W;                        // <= 2^30 (checked by the entry point)
-    const long long p0l = ((long long)blockIdx.x * AUGP_THREADS + threadIdx.x) * AUGP_PIX;
+    const long long p0l = ((long long)blockIdx.x * AUG_THREADS + threadIdx.x) * AUG_PIX;
     if (p0l >= HW) return;
     const int p0 = (int)p0l;
     int y = (int)((unsigned)p0 / (unsigned)a.W), x = p0 - y * a.W;
-    float out[AUGP_PIX * 3];
+    float out[AUG_PIX * 3];
     unsigned pad = 0;                                // byte q = mask of pixel q
 #pragma unroll
-    for (int q = 0; q < AUGP_PIX; ++q) {
+    for (int q = 0; q < AUG_PIX; ++q) {
         if (y < hd && x < wd) {                      // (a pixel past the canvas end has y >= H >= hd: padding, never stored)
             float v[3];
             resample(FetchWindow{m}, hc, wc, hd, wd, interp, y, x, v);
-            out[3 * q + 0] = a.lut[(int)v[a.perm0]];
-            out[3 * q + 1] = a.lut[256 + (int)v[a.perm1]];
-            out[3 * q + 2] = a.lut[512 + (int)v[a.perm2]];
+            lut_pixel(a.lut, a.perm0, a.perm1, a.perm2, v, out + 3 * q);
         } else {
             out[3 * q + 0] = 0.0f; out[3 * q + 1] = 0.0f; out[3 * q + 2] = 0.0f;
             pad |= 1u << (8 * q);
@@ -77,19 +64,13 @@ __global__ __launch_bounds__(AUGP_THREADS) void augment_padded_kernel(AugPadArgs
         if (++x >= a.W) { x = 0; ++y; }
     }
     const long long base = (long long)b * HW + p0;
-    float *o = a.dst + base * 3;
     unsigned char *mk = a.mask + base;
-    if (a.vec && p0 + AUGP_PIX <= HW) {
-        float4 *o4 = reinterpret_cast<float4 *>(o);
-        o4[0] = make_float4(out[0], out[1], out[2], out[3]);
-        o4[1] = make_float4(out[4], out[5], out[6], out[7]);
-        o4[2] = make_float4(out[8], out[9], out[10], out[11]);
+    const bool vec = a.vec && p0 + AUG_PIX <= HW;
+    store_pixels(a.dst + base * 3, out, vec, HW - p0);
+    if (vec) {
         *reinterpret_cast<unsigned *>(mk) = pad;
     } else {
-        for (int q = 0; q < AUGP_PIX && p0 + q < HW; ++q) {
-            o[3 * q + 0] = out[3 * q + 0]; o[3 * q + 1] = out[3 * q + 1]; o[3 * q + 2] = out[3 * q + 2];
-            mk[q] = (unsigned char)((pad >> (8 * q)) & 1u);
-        }
+        for (int q = 0; q < AUG_PIX && p0 + q < HW; ++q) mk[q] = (unsigned char)((pad >> (8 * q)) & 1u);
     }
 }
 
@@ -103,15 +84,15 @@ extern "C" int detr_hip_augment_padded(const uint8_t *src, int64_t src_bytes, co
     DETR_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W <= (1ll << 30),
                  "augment_padded: bad shape B=%d H=%d W=%d", B, H, W);
     DETR_REQUIRE(src_bytes >= 3, "augment_padded: src_bytes must cover at least one pixel");
-    for (int c = 0; c < 3; ++c) DETR_REQUIRE(perm[c] >= 0 && perm[c] < 3, "augment_padded: channel permutation out of range");
+    DETR_REQUIRE(check_perm(perm), "augment_padded: channel permutation out of range");
     AugPadArgs a;
     a.src = src; a.src_bytes = src_bytes; a.irec = irec; a.dst = dst; a.mask = mask; a.lut = lut;
     a.B = B; a.H = H; a.W = W; a.perm0 = perm[0]; a.perm1 = perm[1]; a.perm2 = perm[2];
     const long long HW = (long long)H * W;
     // every lane's 12 floats start on a 16-byte boundary and its 4 mask bytes on a 4-byte one
-    a.vec = aligned16(dst) && ((uintptr_t)mask & 3) == 0 && HW % AUGP_PIX == 0;
-    const long long groups = (HW + (long long)AUGP_THREADS * AUGP_PIX - 1) / ((long long)AUGP_THREADS * AUGP_PIX);
-    hipLaunchKernelGGL(augment_padded_kernel, dim3((unsigned)groups, (unsigned)B), dim3(AUGP_THREADS), 0, (hipStream_t)stream, a);
+    a.vec = aligned16(dst) && ((uintptr_t)mask & 3) == 0 && HW % AUG_PIX == 0;
+    const long long groups = (HW + (long long)AUG_THREADS * AUG_PIX - 1) / ((long long)AUG_THREADS * AUG_PIX);
+    hipLaunchKernelGGL(augment_padded_kernel, dim3((unsigned)groups, (unsigned)B), dim3(AUG_THREADS), 0, (hipStream_t)stream, a);
     DETR_LAUNCH_CHECK("augment_padded");
     return 0;
 }

@@ -100,6 +100,11 @@ int tune(TuneKey k);
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// grid of a grid-stride loop over `total` items: one lane each, at most `cap` workgroups, at least one
+static inline int capped_grid(long long total, int block, int cap) {
+    const long long g = (total + block - 1) / block;
+    return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
 
 // Counter-based dropout: element `idx` of dropout site `site` in training step `*step` is kept iff 16 bits of a
 // keyed 32-bit integer hash are >= thresh16 = p * 2^16.  Forward and backward kernels regenerate the same mask from

@@ -8,9 +8,10 @@
 //     builds sin / cos tables [n][c][128] per axis once per feature size with the float32 NumPy expressions of
 //     engine.position_embedding_sine_host, and the kernel gathers -- an all-False mask reproduces the unmasked constant bit for bit.
 //   * detr_hip_input_stage_padded: ragged uint8 images -> zero-padded float32 NHWC canvas + its mask, one launch, valid pixels
-//     through the normalisation table of detr_hip_input_stage (no resize: that stays the caller's job, as in the reference).
+//     through the normalisation table of detr_hip_input_stage (image_resample.h: lut_pixel; no resize: that stays the caller's job,
+//     as in the reference).
 // Everything runs on the device: a masked step adds no host synchronisation, and a captured graph re-reads the mask buffer.
-#include "common.h"
+#include "image_resample.h"
 
 namespace detr {
 
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void input_stage_padded_kernel(PadInputArgs a)
         if (y < h && x < w) {
             const unsigned char *p = a.src + a.offsets[b] + ((long long)y * w + x) * 3;
             const int v[3] = {p[0], p[1], p[2]};
-            o[0] = a.lut[v[a.perm0]]; o[1] = a.lut[256 + v[a.perm1]]; o[2] = a.lut[512 + v[a.perm2]];
+            lut_pixel(a.lut, a.perm0, a.perm1, a.perm2, v, o);
             a.mask[i] = 0;
         } else {
             o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
@@ -132,13 +133,12 @@ extern "C" int detr_hip_input_stage_padded(const uint8_t *src, const int64_t *of
                                            const float *lut, const int32_t *perm, float *dst, uint8_t *mask, void *stream) {
     DETR_REQUIRE(src && offsets && hw && lut && perm && dst && mask, "input_stage_padded: null operand");
     DETR_REQUIRE(B > 0 && H > 0 && W > 0, "input_stage_padded: bad shape B=%d H=%d W=%d", B, H, W);
-    for (int c = 0; c < 3; ++c) DETR_REQUIRE(perm[c] >= 0 && perm[c] < 3, "input_stage_padded: channel permutation out of range");
+    DETR_REQUIRE(check_perm(perm), "input_stage_padded: channel permutation out of range");
     PadInputArgs a;
     a.src = src; a.offsets = reinterpret_cast<const long long *>(offsets); a.hw = hw; a.dst = dst; a.mask = mask; a.lut = lut;
     a.B = B; a.H = H; a.W = W; a.perm0 = perm[0]; a.perm1 = perm[1]; a.perm2 = perm[2];
     const long long total = (long long)B * H * W;
-    const int grid = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
-    hipLaunchKernelGGL(input_stage_padded_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(input_stage_padded_kernel, dim3(capped_grid(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, a);
     DETR_LAUNCH_CHECK("input_stage_padded");
     return 0;
 }

@@ -1,55 +1,120 @@
 // pool.hip -- elementwise companions of the ResNet stem and of the stride-2 shortcuts (NHWC) for gfx950:
-//   * 3x3/s2 max pool over the zero-padded map + its backward, fp32 and bf16 storage (4 or 8 channels per lane);
+//   * 3x3/s2 max pool over the zero-padded map + its backward: ONE forward and ONE backward body (maxpool_*_kernel<T, V>) over the
+//     storage type T and the channels per lane V, instantiated as f32 x 1 (forward), f32 x 4 (backward), bf16 x 4 and bf16 x 8;
 //   * stride-2 subsample gather / scatter.
 // Reference: detr_tf/networks/resnet_backbone.py:11-32,98-137 (see include/detr_hip.h).
 #include "gemm_core.h"
 namespace detr {
 
-__global__ void maxpool_fwd_kernel(const float *__restrict__ x, float *__restrict__ y, uint8_t *__restrict__ amax,
-                                   int N, int H, int W, int C, int Ho, int Wo, long long total) {
+// What one lane holds of one pixel: V channels of storage type T (float, or uint16_t = bf16 bits) as one vector `vec`, and their V
+// argmax bytes (one per channel, kh * 3 + kw) as V / 4 32-bit words (V = 1: the byte itself).
+template <class T, int V> struct PoolLane;
+template <> struct PoolLane<float, 1> {
+    using vec = float;
+    using amax_t = uint8_t;
+    static __device__ __forceinline__ void to_f32(vec r, float (&o)[1]) { o[0] = r; }
+    static __device__ __forceinline__ vec from_f32(const float (&v)[1]) { return v[0]; }
+};
+template <> struct PoolLane<float, 4> {
+    using vec = float4;
+    using amax_t = uint32_t;
+    static __device__ __forceinline__ void to_f32(vec r, float (&o)[4]) { o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w; }
+    static __device__ __forceinline__ vec from_f32(const float (&v)[4]) { return make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <> struct PoolLane<uint16_t, 4> {
+    using vec = uint2;
+    using amax_t = uint32_t;
+    static __device__ __forceinline__ void to_f32(vec r, float (&o)[4]) {
+        o[0] = bf16_bits_to_f32(r.x & 0xFFFFu); o[1] = bf16_bits_to_f32(r.x >> 16);
+        o[2] = bf16_bits_to_f32(r.y & 0xFFFFu); o[3] = bf16_bits_to_f32(r.y >> 16);
+    }
+    static __device__ __forceinline__ vec from_f32(const float (&v)[4]) { return make_uint2(f32_to_bf16_pair(v[0], v[1]), f32_to_bf16_pair(v[2], v[3])); }
+};
+// 8 channels (16 bytes) per lane: half the memory instructions and half the index arithmetic per byte of the 4-channel form (which
+// stays for C % 8 != 0).  rocprofv3, stem map 8 x 400 x 667 x 64: backward 266 us at 2.3 TB/s with 8-byte accesses.
+template <> struct PoolLane<uint16_t, 8> {
+    using vec = uint4;
+    using amax_t = uint2;
+    static __device__ __forceinline__ void to_f32(vec r, float (&o)[8]) {
+        o[0] = __builtin_bit_cast(float, r.x << 16); o[1] = __builtin_bit_cast(float, r.x & 0xFFFF0000u);
+        o[2] = __builtin_bit_cast(float, r.y << 16); o[3] = __builtin_bit_cast(float, r.y & 0xFFFF0000u);
+        o[4] = __builtin_bit_cast(float, r.z << 16); o[5] = __builtin_bit_cast(float, r.z & 0xFFFF0000u);
+        o[6] = __builtin_bit_cast(float, r.w << 16); o[7] = __builtin_bit_cast(float, r.w & 0xFFFF0000u);
+    }
+    static __device__ __forceinline__ vec from_f32(const float (&v)[8]) {
+        return make_uint4(f32_to_bf16_pair(v[0], v[1]), f32_to_bf16_pair(v[2], v[3]), f32_to_bf16_pair(v[4], v[5]), f32_to_bf16_pair(v[6], v[7]));
+    }
+};
+__device__ __forceinline__ uint8_t pack_taps(const uint32_t (&t)[1]) { return (uint8_t)t[0]; }
+__device__ __forceinline__ uint32_t pack_taps(const uint32_t (&t)[4]) { return t[0] | (t[1] << 8) | (t[2] << 16) | (t[3] << 24); }
+__device__ __forceinline__ uint2 pack_taps(const uint32_t (&t)[8]) {
+    return make_uint2(t[0] | (t[1] << 8) | (t[2] << 16) | (t[3] << 24), t[4] | (t[5] << 8) | (t[6] << 16) | (t[7] << 24));
+}
+__device__ __forceinline__ uint32_t tap_of(uint32_t a, int e) { return (a >> (8 * e)) & 0xFFu; }
+__device__ __forceinline__ uint32_t tap_of(uint2 a, int e) { return ((e < 4 ? a.x : a.y) >> (8 * (e & 3))) & 0xFFu; }
+
+// pixel index -> (n, row, col) of an N x rows x cols map; every max-pool entry point checks that N * H * W fits in 31 bits
+__device__ __forceinline__ void pool_pixel(long long idx, int CV, int rows, int cols, int &cv, int &n, int &r, int &c) {
+    cv = (int)(idx % CV);
+    const unsigned pix = (unsigned)(idx / CV);
+    c = (int)(pix % (unsigned)cols);
+    const unsigned t = pix / (unsigned)cols;
+    r = (int)(t % (unsigned)rows);
+    n = (int)(t / (unsigned)rows);
+}
+
+// y[n,ho,wo,c] = max over the 3x3 / stride-2 window of the zero-padded map; the FIRST maximal tap wins (strict `>` in kh-major order)
+template <class T, int V>
+__global__ __launch_bounds__(256) void maxpool_fwd_kernel(const typename PoolLane<T, V>::vec *__restrict__ x,
+                                                          typename PoolLane<T, V>::vec *__restrict__ y,
+                                                          typename PoolLane<T, V>::amax_t *__restrict__ amax, int N, int H, int W, int CV,
+                                                          int Ho, int Wo, long long total) {
+    using L = PoolLane<T, V>;
     for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C);
-        long long t = idx / C;
-        const int wo = (int)(t % Wo);
-        t /= Wo;
-        const int ho = (int)(t % Ho);
-        const int n = (int)(t / Ho);
-        float best = -INFINITY;
-        int bi = 0;
+        int cv, n, ho, wo;
+        pool_pixel(idx, CV, Ho, Wo, cv, n, ho, wo);
+        float best[V];
+        uint32_t bi[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) { best[e] = -INFINITY; bi[e] = 0; }
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int hi = 2 * ho - 1 + kh, wi = 2 * wo - 1 + kw;
-                float v = 0.0f;  // the explicit ZeroPadding2D(1) takes part in the max
-                if (hi >= 0 && wi >= 0 && hi < H && wi < W) v = x[(((long long)n * H + hi) * W + wi) * C + c];
-                if (v > best) {
-                    best = v;
-                    bi = kh * 3 + kw;
-                }
+                // the explicit ZeroPadding2D(1) takes part in the max.  Select the raw vector, convert after: converting under the
+                // branch into a zeroed float[V] costs the 8-channel form 31 VGPRs.
+                typename L::vec raw = {};
+                if (hi >= 0 && wi >= 0 && hi < H && wi < W) raw = x[((long long)(n * H + hi) * W + wi) * CV + cv];
+                float v[V];
+                L::to_f32(raw, v);
+#pragma unroll
+                for (int e = 0; e < V; ++e)
+                    if (v[e] > best[e]) { best[e] = v[e]; bi[e] = (uint32_t)(kh * 3 + kw); }
             }
-        y[idx] = best;
-        amax[idx] = (uint8_t)bi;
+        y[idx] = L::from_f32(best);                  // exact: inputs are bf16
+        amax[idx] = pack_taps(bi);
     }
 }
 
-// dx[n,h,w,c] = (x > 0) * sum over the (<= 4) pooling windows that contain (h,w) and selected it.
-// Four channels per thread: float4 x / dy / dx accesses, one 32-bit load of the four argmax bytes.
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float *__restrict__ dy, const uint8_t *__restrict__ amax,
-                                                          const float *__restrict__ x, float *__restrict__ dx, int N, int H,
-                                                          int W, int C, int Ho, int Wo, long long total4) {
-    const int C4 = C >> 2;
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total4;
+// dx[n,h,w,c] = (x > 0) * sum over the (<= 4) pooling windows that contain (h,w) and selected it: only taps of the parity of
+// (h + 1, w + 1) can reach the pixel.  One vector access of x / dy / dx and one load of the V argmax bytes per window.
+template <class T, int V>
+__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const typename PoolLane<T, V>::vec *__restrict__ dy,
+                                                          const typename PoolLane<T, V>::amax_t *__restrict__ amax,
+                                                          const typename PoolLane<T, V>::vec *__restrict__ x,
+                                                          typename PoolLane<T, V>::vec *__restrict__ dx, int N, int H, int W, int CV,
+                                                          int Ho, int Wo, long long total) {
+    using L = PoolLane<T, V>;
+    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % C4);
-        const unsigned pix = (unsigned)(idx / C4);
-        const int w = (int)(pix % (unsigned)W);
-        const unsigned t = pix / (unsigned)W;
-        const int h = (int)(t % (unsigned)H);
-        const int n = (int)(t / (unsigned)H);
-        const float4 xv = reinterpret_cast<const float4 *>(x)[idx];
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        int cv, n, h, w;
+        pool_pixel(idx, CV, H, W, cv, n, h, w);
+        const typename L::vec xraw = x[idx];
+        float g[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) g[e] = 0.0f;
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
             const int th = h + 1 - kh;
@@ -62,193 +127,23 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float *__restric
                 if (tw < 0 || (tw & 1)) continue;
                 const int wo = tw >> 1;
                 if (wo >= Wo) continue;
-                const long long o4 = ((long long)(n * Ho + ho) * Wo + wo) * C4 + c4;
-                const uint32_t am = reinterpret_cast<const uint32_t *>(amax)[o4];
-                const float4 d = reinterpret_cast<const float4 *>(dy)[o4];
-                const uint32_t tap = (uint32_t)(kh * 3 + kw);
-                if ((am & 0xFFu) == tap) g.x += d.x;
-                if (((am >> 8) & 0xFFu) == tap) g.y += d.y;
-                if (((am >> 16) & 0xFFu) == tap) g.z += d.z;
-                if ((am >> 24) == tap) g.w += d.w;
-            }
-        }
-        g.x = xv.x > 0.0f ? g.x : 0.0f;
-        g.y = xv.y > 0.0f ? g.y : 0.0f;
-        g.z = xv.z > 0.0f ? g.z : 0.0f;
-        g.w = xv.w > 0.0f ? g.w : 0.0f;
-        reinterpret_cast<float4 *>(dx)[idx] = g;
-    }
-}
-
-// bf16-storage twins of the two pooling kernels (4 channels = 8 bytes per thread)
-__device__ __forceinline__ float4 bf4_to_f4(uint2 v) {
-    return make_float4(bf16_bits_to_f32(v.x & 0xFFFFu), bf16_bits_to_f32(v.x >> 16), bf16_bits_to_f32(v.y & 0xFFFFu), bf16_bits_to_f32(v.y >> 16));
-}
-__global__ __launch_bounds__(256) void maxpool_fwd_bf16_kernel(const uint2 *__restrict__ x, uint2 *__restrict__ y,
-                                                               uint32_t *__restrict__ amax, int N, int H, int W, int C4,
-                                                               int Ho, int Wo, long long total4) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total4;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % C4);
-        const unsigned pix = (unsigned)(idx / C4);
-        const int wo = (int)(pix % (unsigned)Wo);
-        const unsigned t = pix / (unsigned)Wo;
-        const int ho = (int)(t % (unsigned)Ho);
-        const int n = (int)(t / (unsigned)Ho);
-        float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        uint32_t bi[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int hi = 2 * ho - 1 + kh, wi = 2 * wo - 1 + kw;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);   // the explicit ZeroPadding2D(1) takes part in the max
-                if (hi >= 0 && wi >= 0 && hi < H && wi < W) v = bf4_to_f4(x[((long long)(n * H + hi) * W + wi) * C4 + c4]);
-                const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (vv[e] > best[e]) { best[e] = vv[e]; bi[e] = (uint32_t)(kh * 3 + kw); }
-            }
-        y[idx] = make_uint2(f32_to_bf16_pair(best[0], best[1]), f32_to_bf16_pair(best[2], best[3]));   // exact: inputs are bf16
-        amax[idx] = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
-    }
-}
-
-__global__ __launch_bounds__(256) void maxpool_bwd_bf16_kernel(const uint2 *__restrict__ dy, const uint32_t *__restrict__ amax,
-                                                               const uint2 *__restrict__ x, uint2 *__restrict__ dx, int N, int H,
-                                                               int W, int C4, int Ho, int Wo, long long total4) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total4;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % C4);
-        const unsigned pix = (unsigned)(idx / C4);
-        const int w = (int)(pix % (unsigned)W);
-        const unsigned t = pix / (unsigned)W;
-        const int h = (int)(t % (unsigned)H);
-        const int n = (int)(t / (unsigned)H);
-        const float4 xv = bf4_to_f4(x[idx]);
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int th = h + 1 - kh;
-            if (th < 0 || (th & 1)) continue;
-            const int ho = th >> 1;
-            if (ho >= Ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int tw = w + 1 - kw;
-                if (tw < 0 || (tw & 1)) continue;
-                const int wo = tw >> 1;
-                if (wo >= Wo) continue;
-                const long long o4 = ((long long)(n * Ho + ho) * Wo + wo) * C4 + c4;
-                const uint32_t am = amax[o4];
-                const float4 d = bf4_to_f4(dy[o4]);
-                const uint32_t tap = (uint32_t)(kh * 3 + kw);
-                if ((am & 0xFFu) == tap) g.x += d.x;
-                if (((am >> 8) & 0xFFu) == tap) g.y += d.y;
-                if (((am >> 16) & 0xFFu) == tap) g.z += d.z;
-                if ((am >> 24) == tap) g.w += d.w;
-            }
-        }
-        g.x = xv.x > 0.0f ? g.x : 0.0f;
-        g.y = xv.y > 0.0f ? g.y : 0.0f;
-        g.z = xv.z > 0.0f ? g.z : 0.0f;
-        g.w = xv.w > 0.0f ? g.w : 0.0f;
-        dx[idx] = make_uint2(f32_to_bf16_pair(g.x, g.y), f32_to_bf16_pair(g.z, g.w));
-    }
-}
-// 8-channel (16-byte) forms of the two bf16 pooling kernels: half the memory instructions and half the index arithmetic per
-// byte of the 4-channel forms above (which stay for C % 8 != 0).  rocprofv3, stem map 8 x 400 x 667 x 64: backward 266 us
-// at 2.3 TB/s with 8-byte accesses.
-__device__ __forceinline__ void bf8_to_f8(uint4 v, float (&o)[8]) {
-    o[0] = __builtin_bit_cast(float, v.x << 16); o[1] = __builtin_bit_cast(float, v.x & 0xFFFF0000u);
-    o[2] = __builtin_bit_cast(float, v.y << 16); o[3] = __builtin_bit_cast(float, v.y & 0xFFFF0000u);
-    o[4] = __builtin_bit_cast(float, v.z << 16); o[5] = __builtin_bit_cast(float, v.z & 0xFFFF0000u);
-    o[6] = __builtin_bit_cast(float, v.w << 16); o[7] = __builtin_bit_cast(float, v.w & 0xFFFF0000u);
-}
-
-__global__ __launch_bounds__(256) void maxpool_fwd_bf16x8_kernel(const uint4 *__restrict__ x, uint4 *__restrict__ y,
-                                                                 uint2 *__restrict__ amax, int N, int H, int W, int C8,
-                                                                 int Ho, int Wo, long long total8) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total8;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c8 = (int)(idx % C8);
-        const unsigned pix = (unsigned)(idx / C8);
-        const int wo = (int)(pix % (unsigned)Wo);
-        const unsigned t = pix / (unsigned)Wo;
-        const int ho = (int)(t % (unsigned)Ho);
-        const int n = (int)(t / (unsigned)Ho);
-        // bf16 values compare like their bit patterns moved to the high half of a float: keep the raw winners, no re-rounding
-        float best[8];
-        uint32_t bi[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int hi = 2 * ho - 1 + kh, wi = 2 * wo - 1 + kw;
-                uint4 raw = make_uint4(0u, 0u, 0u, 0u);       // the explicit ZeroPadding2D(1) takes part in the max
-                if (hi >= 0 && wi >= 0 && hi < H && wi < W) raw = x[((long long)(n * H + hi) * W + wi) * C8 + c8];
-                float vv[8];
-                bf8_to_f8(raw, vv);
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (vv[e] > best[e]) { best[e] = vv[e]; bi[e] = (uint32_t)(kh * 3 + kw); }
-            }
-        y[idx] = make_uint4(f32_to_bf16_pair(best[0], best[1]), f32_to_bf16_pair(best[2], best[3]),
-                            f32_to_bf16_pair(best[4], best[5]), f32_to_bf16_pair(best[6], best[7]));      // exact: inputs are bf16
-        amax[idx] = make_uint2(bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24), bi[4] | (bi[5] << 8) | (bi[6] << 16) | (bi[7] << 24));
-    }
-}
-
-__global__ __launch_bounds__(256) void maxpool_bwd_bf16x8_kernel(const uint4 *__restrict__ dy, const uint2 *__restrict__ amax,
-                                                                 const uint4 *__restrict__ x, uint4 *__restrict__ dx, int N, int H,
-                                                                 int W, int C8, int Ho, int Wo, long long total8) {
-    for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total8;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const int c8 = (int)(idx % C8);
-        const unsigned pix = (unsigned)(idx / C8);
-        const int w = (int)(pix % (unsigned)W);
-        const unsigned t = pix / (unsigned)W;
-        const int h = (int)(t % (unsigned)H);
-        const int n = (int)(t / (unsigned)H);
-        const uint4 xraw = x[idx];
-        float g[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = 0.0f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int th = h + 1 - kh;
-            if (th < 0 || (th & 1)) continue;
-            const int ho = th >> 1;
-            if (ho >= Ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int tw = w + 1 - kw;
-                if (tw < 0 || (tw & 1)) continue;
-                const int wo = tw >> 1;
-                if (wo >= Wo) continue;
-                const long long o8 = ((long long)(n * Ho + ho) * Wo + wo) * C8 + c8;
-                const uint2 am = amax[o8];
-                float d[8];
-                bf8_to_f8(dy[o8], d);
+                const long long o = ((long long)(n * Ho + ho) * Wo + wo) * CV + cv;
+                const typename L::amax_t am = amax[o];
+                float d[V];
+                L::to_f32(dy[o], d);
                 const uint32_t tap = (uint32_t)(kh * 3 + kw);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (((am.x >> (8 * e)) & 0xFFu) == tap) g[e] += d[e];
-                    if (((am.y >> (8 * e)) & 0xFFu) == tap) g[4 + e] += d[4 + e];
-                }
+                for (int e = 0; e < V; ++e)
+                    if (tap_of(am, e) == tap) g[e] += d[e];
             }
         }
-        float xv[8];
-        bf8_to_f8(xraw, xv);
+        float xv[V];
+        L::to_f32(xraw, xv);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = xv[e] > 0.0f ? g[e] : 0.0f;
-        dx[idx] = make_uint4(f32_to_bf16_pair(g[0], g[1]), f32_to_bf16_pair(g[2], g[3]), f32_to_bf16_pair(g[4], g[5]), f32_to_bf16_pair(g[6], g[7]));
+        for (int e = 0; e < V; ++e) g[e] = xv[e] > 0.0f ? g[e] : 0.0f;
+        dx[idx] = L::from_f32(g);
     }
 }
-
-
 
 __global__ void subsample2_fwd_kernel(const float4 *__restrict__ x, float4 *__restrict__ y, int H, int W, int C4,
                                       int Ho, int Wo, long long total) {
@@ -281,9 +176,29 @@ __global__ void subsample2_bwd_kernel(const float4 *__restrict__ dy, float4 *__r
     }
 }
 
-static inline int ew_grid(long long total, int block) {
-    long long g = (total + block - 1) / block;
-    return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
+// V channels per lane need C % V == 0, every tensor aligned to its V * sizeof(T)-byte vector and the argmax buffer to its V bytes
+template <class T, int V>
+static bool pool_fits(int C, const void *argmax, const void *t0, const void *t1, const void *t2 = nullptr) {
+    const uintptr_t tensors = (uintptr_t)t0 | (uintptr_t)t1 | (uintptr_t)t2;
+    return C % V == 0 && tensors % (V * sizeof(T)) == 0 && (uintptr_t)argmax % V == 0;
+}
+
+template <class T, int V>
+static void maxpool_fwd_launch(const T *x, T *y, uint8_t *argmax, int N, int H, int W, int C, int Ho, int Wo, void *stream) {
+    using L = PoolLane<T, V>;
+    const long long total = (long long)N * Ho * Wo * (C / V);
+    hipLaunchKernelGGL((maxpool_fwd_kernel<T, V>), dim3(capped_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                       (const typename L::vec *)x, (typename L::vec *)y, (typename L::amax_t *)argmax, N, H, W, C / V, Ho, Wo, total);
+}
+
+template <class T, int V>
+static void maxpool_bwd_launch(const T *dy, const uint8_t *argmax, const T *x, T *dx, int N, int H, int W, int C, int Ho, int Wo,
+                               void *stream) {
+    using L = PoolLane<T, V>;
+    const long long total = (long long)N * H * W * (C / V);
+    hipLaunchKernelGGL((maxpool_bwd_kernel<T, V>), dim3(capped_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                       (const typename L::vec *)dy, (const typename L::amax_t *)argmax, (const typename L::vec *)x, (typename L::vec *)dx, N,
+                       H, W, C / V, Ho, Wo, total);
 }
 
 }  // namespace detr
@@ -293,10 +208,9 @@ using namespace detr;
 extern "C" int detr_hip_maxpool3x3s2_fwd_f32(const float *x, float *y, uint8_t *argmax, int32_t N, int32_t H, int32_t W,
                                              int32_t C, int32_t Ho, int32_t Wo, void *stream) {
     DETR_REQUIRE(x && y && argmax, "maxpool fwd: null operand");
+    DETR_REQUIRE((long long)N * H * W <= INT32_MAX, "maxpool fwd: N * H * W = %lld input pixels do not fit in 31 bits (the kernels index pixels in int)", (long long)N * H * W);
     DETR_REQUIRE(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1, "maxpool fwd: bad output size");
-    const long long total = (long long)N * Ho * Wo * C;
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, argmax, N,
-                       H, W, C, Ho, Wo, total);
+    maxpool_fwd_launch<float, 1>(x, y, argmax, N, H, W, C, Ho, Wo, stream);       // any C, no alignment demand
     DETR_LAUNCH_CHECK("maxpool fwd");
     return 0;
 }
@@ -304,11 +218,9 @@ extern "C" int detr_hip_maxpool3x3s2_fwd_f32(const float *x, float *y, uint8_t *
 extern "C" int detr_hip_maxpool3x3s2_bwd_f32(const float *dy, const uint8_t *argmax, const float *x, float *dx, int32_t N,
                                              int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, void *stream) {
     DETR_REQUIRE(dy && argmax && x && dx, "maxpool bwd: null operand");
-    DETR_REQUIRE(C % 4 == 0 && aligned16(dy) && aligned16(x) && aligned16(dx) && ((uintptr_t)argmax % 4 == 0),
-                 "maxpool bwd: C must be a multiple of 4 and the tensors 16-byte aligned");
-    const long long total = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, argmax, x,
-                       dx, N, H, W, C, Ho, Wo, total);
+    DETR_REQUIRE((long long)N * H * W <= INT32_MAX, "maxpool bwd: N * H * W = %lld input pixels do not fit in 31 bits (the kernels index pixels in int)", (long long)N * H * W);
+    DETR_REQUIRE((pool_fits<float, 4>(C, argmax, dy, x, dx)), "maxpool bwd: C must be a multiple of 4 and the tensors 16-byte aligned");
+    maxpool_bwd_launch<float, 4>(dy, argmax, x, dx, N, H, W, C, Ho, Wo, stream);
     DETR_LAUNCH_CHECK("maxpool bwd");
     return 0;
 }
@@ -318,7 +230,7 @@ extern "C" int detr_hip_subsample2_fwd_f32(const float *x, float *y, int32_t N, 
     DETR_REQUIRE(x && y && C % 4 == 0 && aligned16(x) && aligned16(y), "subsample2 fwd: bad operands");
     DETR_REQUIRE(Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "subsample2 fwd: bad output size");
     const long long total = (long long)N * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(subsample2_fwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(subsample2_fwd_kernel, dim3(capped_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                        (const float4 *)x, (float4 *)y, H, W, C / 4, Ho, Wo, total);
     DETR_LAUNCH_CHECK("subsample2 fwd");
     return 0;
@@ -328,7 +240,7 @@ extern "C" int detr_hip_subsample2_bwd_f32(const float *dy, float *dx, int32_t N
                                            int32_t Ho, int32_t Wo, void *stream) {
     DETR_REQUIRE(dy && dx && C % 4 == 0 && aligned16(dy) && aligned16(dx), "subsample2 bwd: bad operands");
     const long long total = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(subsample2_bwd_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(subsample2_bwd_kernel, dim3(capped_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                        (const float4 *)dy, (float4 *)dx, H, W, C / 4, Ho, Wo, total);
     DETR_LAUNCH_CHECK("subsample2 bwd");
     return 0;
@@ -337,18 +249,15 @@ extern "C" int detr_hip_subsample2_bwd_f32(const float *dy, float *dx, int32_t N
 extern "C" int detr_hip_maxpool3x3s2_fwd_bf16(const uint16_t *x, uint16_t *y, uint8_t *argmax, int32_t N, int32_t H, int32_t W,
                                               int32_t C, int32_t Ho, int32_t Wo, void *stream) {
     DETR_REQUIRE(x && y && argmax && C % 4 == 0, "maxpool fwd bf16: bad operands");
-    DETR_REQUIRE(((uintptr_t)x % 8 == 0) && ((uintptr_t)y % 8 == 0) && ((uintptr_t)argmax % 4 == 0), "maxpool fwd bf16: alignment");
+    DETR_REQUIRE((long long)N * H * W <= INT32_MAX, "maxpool fwd bf16: N * H * W = %lld input pixels do not fit in 31 bits (the kernels index pixels in int)", (long long)N * H * W);
+    DETR_REQUIRE((pool_fits<uint16_t, 4>(C, argmax, x, y)), "maxpool fwd bf16: alignment");
     DETR_REQUIRE(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1, "maxpool fwd: bad output size");
-    if (C % 8 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((uintptr_t)argmax % 8 == 0)) {
-        const long long total8 = (long long)N * Ho * Wo * (C / 8);
-        hipLaunchKernelGGL(maxpool_fwd_bf16x8_kernel, dim3(ew_grid(total8, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)x,
-                           (uint4 *)y, (uint2 *)argmax, N, H, W, C / 8, Ho, Wo, total8);
+    if (pool_fits<uint16_t, 8>(C, argmax, x, y)) {
+        maxpool_fwd_launch<uint16_t, 8>(x, y, argmax, N, H, W, C, Ho, Wo, stream);
         DETR_LAUNCH_CHECK("maxpool fwd bf16 (8 channels per lane)");
         return 0;
     }
-    const long long total = (long long)N * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(maxpool_fwd_bf16_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, (const uint2 *)x,
-                       (uint2 *)y, (uint32_t *)argmax, N, H, W, C / 4, Ho, Wo, total);
+    maxpool_fwd_launch<uint16_t, 4>(x, y, argmax, N, H, W, C, Ho, Wo, stream);
     DETR_LAUNCH_CHECK("maxpool fwd bf16");
     return 0;
 }
@@ -356,18 +265,14 @@ extern "C" int detr_hip_maxpool3x3s2_fwd_bf16(const uint16_t *x, uint16_t *y, ui
 extern "C" int detr_hip_maxpool3x3s2_bwd_bf16(const uint16_t *dy, const uint8_t *argmax, const uint16_t *x, uint16_t *dx, int32_t N,
                                               int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, void *stream) {
     DETR_REQUIRE(dy && argmax && x && dx && C % 4 == 0, "maxpool bwd bf16: bad operands");
-    DETR_REQUIRE(((uintptr_t)dy % 8 == 0) && ((uintptr_t)x % 8 == 0) && ((uintptr_t)dx % 8 == 0) && ((uintptr_t)argmax % 4 == 0),
-                 "maxpool bwd bf16: alignment");
-    if (C % 8 == 0 && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)dx % 16 == 0) && ((uintptr_t)argmax % 8 == 0)) {
-        const long long total8 = (long long)N * H * W * (C / 8);
-        hipLaunchKernelGGL(maxpool_bwd_bf16x8_kernel, dim3(ew_grid(total8, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4 *)dy,
-                           (const uint2 *)argmax, (const uint4 *)x, (uint4 *)dx, N, H, W, C / 8, Ho, Wo, total8);
+    DETR_REQUIRE((long long)N * H * W <= INT32_MAX, "maxpool bwd bf16: N * H * W = %lld input pixels do not fit in 31 bits (the kernels index pixels in int)", (long long)N * H * W);
+    DETR_REQUIRE((pool_fits<uint16_t, 4>(C, argmax, dy, x, dx)), "maxpool bwd bf16: alignment");
+    if (pool_fits<uint16_t, 8>(C, argmax, dy, x, dx)) {
+        maxpool_bwd_launch<uint16_t, 8>(dy, argmax, x, dx, N, H, W, C, Ho, Wo, stream);
         DETR_LAUNCH_CHECK("maxpool bwd bf16 (8 channels per lane)");
         return 0;
     }
-    const long long total = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, (const uint2 *)dy,
-                       (const uint32_t *)argmax, (const uint2 *)x, (uint2 *)dx, N, H, W, C / 4, Ho, Wo, total);
+    maxpool_bwd_launch<uint16_t, 4>(dy, argmax, x, dx, N, H, W, C, Ho, Wo, stream);
     DETR_LAUNCH_CHECK("maxpool bwd bf16");
     return 0;
 }

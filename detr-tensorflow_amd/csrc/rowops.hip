@@ -310,11 +310,6 @@ __global__ void axpy_kernel(float *__restrict__ acc, const float *__restrict__ g
         acc[i] += a * g[i];
 }
 
-static inline int ew_grid(long long total, int block) {
-    long long g = (total + block - 1) / block;
-    return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 }  // namespace detr
 
 using namespace detr;
@@ -500,7 +495,7 @@ extern "C" int detr_hip_add_bcast_f32(const float *x, const float *p, float *out
                                       void *stream) {
     DETR_REQUIRE(x && p && out && n > 0 && period > 0, "add_bcast: bad args");
     DETR_REQUIRE(n % 4 == 0 && period % 4 == 0 && aligned16(x) && aligned16(p) && aligned16(out), "add_bcast: alignment");
-    hipLaunchKernelGGL(add_bcast_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)x,
+    hipLaunchKernelGGL(add_bcast_kernel, dim3(capped_grid(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const float4 *)x,
                        (const float4 *)p, (float4 *)out, (long long)(n / 4), (long long)(period / 4));
     DETR_LAUNCH_CHECK("add_bcast");
     return 0;
@@ -508,14 +503,14 @@ extern "C" int detr_hip_add_bcast_f32(const float *x, const float *p, float *out
 
 extern "C" int detr_hip_add_f32(const float *a, const float *b, float *out, int64_t n, void *stream) {
     DETR_REQUIRE(a && b && out && n > 0, "add: bad args");
-    hipLaunchKernelGGL(add_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long long)n);
+    hipLaunchKernelGGL(add_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long long)n);
     DETR_LAUNCH_CHECK("add");
     return 0;
 }
 
 extern "C" int detr_hip_sigmoid_bwd_f32(const float *dy, const float *y, float *dz, int64_t n, void *stream) {
     DETR_REQUIRE(dy && y && dz && n > 0, "sigmoid_bwd: bad args");
-    hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, dy, y, dz,
+    hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, y, dz,
                        (long long)n);
     DETR_LAUNCH_CHECK("sigmoid_bwd");
     return 0;
@@ -524,7 +519,7 @@ extern "C" int detr_hip_sigmoid_bwd_f32(const float *dy, const float *y, float *
 extern "C" int detr_hip_dropout_f32(const float *x, float *out, int64_t n, float p, uint32_t site, const uint32_t *step,
                                     void *stream) {
     DETR_REQUIRE(x && out && n > 0 && p >= 0.0f && p < 1.0f, "dropout: bad args");
-    hipLaunchKernelGGL(dropout_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, x, out, (long long)n,
+    hipLaunchKernelGGL(dropout_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, out, (long long)n,
                        1.0f / (1.0f - p), drop_thresh16(p), site, step);
     DETR_LAUNCH_CHECK("dropout");
     return 0;
@@ -615,7 +610,7 @@ extern "C" int detr_hip_set_u32x8(uint32_t *dst, uint32_t v0, uint32_t v1, uint3
 
 extern "C" int detr_hip_relu_mask_f32(const float *g, const float *ref, float *out, int64_t n, void *stream) {
     DETR_REQUIRE(g && ref && out && n > 0, "relu_mask: bad args");
-    hipLaunchKernelGGL(relu_mask_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, g, ref, out,
+    hipLaunchKernelGGL(relu_mask_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, g, ref, out,
                        (long long)n);
     DETR_LAUNCH_CHECK("relu_mask");
     return 0;
@@ -625,7 +620,7 @@ extern "C" int detr_hip_scale_cols_f32(const float *w, const float *scale, float
                                        void *stream) {
     DETR_REQUIRE(w && scale && w_out && rows > 0 && cols > 0, "scale_cols: bad args");
     const long long n = (long long)rows * cols;
-    hipLaunchKernelGGL(scale_cols_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, w, scale, w_out, n,
+    hipLaunchKernelGGL(scale_cols_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, w, scale, w_out, n,
                        cols);
     DETR_LAUNCH_CHECK("scale_cols");
     return 0;
@@ -651,7 +646,7 @@ extern "C" int detr_hip_bn_fold_f32(const float *weight, const float *bias, cons
 
 extern "C" int detr_hip_axpy_f32(float *acc, const float *g, float a, int64_t n, void *stream) {
     DETR_REQUIRE(acc && g && n > 0, "axpy: bad args");
-    hipLaunchKernelGGL(axpy_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, acc, g, a, (long long)n);
+    hipLaunchKernelGGL(axpy_kernel, dim3(capped_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, acc, g, a, (long long)n);
     DETR_LAUNCH_CHECK("axpy");
     return 0;
 }

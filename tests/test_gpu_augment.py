@@ -62,6 +62,17 @@ def test_augment_bit_exact_anchors(hip):
     img = rng.integers(0, 256, (96, 128, 3)).astype(np.uint8)
     flipped = st.augmented([img], [T.Transform(96, 128, flip=True, iff=3)]).cpu().numpy()
     assert np.array_equal(flipped, st.images(np.ascontiguousarray(img[None, :, ::-1])).cpu().numpy())
+    # a plain record (no flip, no stage B) in every interpolation detr_hip_input_stage has: one resample() serves both kernels
+    from detr_tf.data.processing import INTERPOLATIONS
+    small = rng.integers(0, 256, (37, 53, 3)).astype(np.uint8)
+    same = rng.integers(0, 256, (64, 96, 3)).astype(np.uint8)
+    for name in ("nearest", "linear", "cubic"):
+        st2 = _stage("torch_resnet", (64, 96))
+        st2.interpolation = INTERPOLATIONS[name]
+        for im in (small, same):                                                    # 37 x 53 -> 64 x 96, and the identity
+            got = st2.augmented([im], [T.Transform(*im.shape[:2], iff=INTERPOLATIONS[name])]).cpu().numpy()
+            want = st2.images(im[None]).cpu().numpy()
+            assert np.array_equal(got, want), (name, im.shape, int((got != want).sum()))
     # a batch mixing both gives the same images as one at a time
     both = st.augmented([np.zeros((150, 210, 3), np.uint8) + 9, img], [T.Transform(150, 210), T.Transform(96, 128, flip=True)])
     assert np.array_equal(both[1].cpu().numpy(), flipped[0])

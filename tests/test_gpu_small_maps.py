@@ -350,15 +350,20 @@ def _pool_case(H, W, C):
     return _POOL_REF[(H, W, C)]
 
 
-def _pool_run(hip, x, dy, H, W, C, dt):
+def _pool_run(hip, x, dy, H, W, C, dt, shift=0, backward=True):
+    """shift: every tensor is a view `shift` elements into a larger buffer (its base is then less aligned than an allocation's)."""
     suffix = "bf16" if dt == torch.bfloat16 else "f32"
     Ho, Wo = dy.shape[1], dy.shape[2]
-    xd, dyd = g(x.float()).to(dt), g(dy.float()).to(dt)
-    pool = torch.full((N, Ho, Wo, C), 7.0, device=DEV, dtype=dt)
-    amax = torch.full((N, Ho, Wo, C), 0xAA, device=DEV, dtype=torch.uint8)
+
+    def dev(shape, fill, dtype=dt):
+        return torch.full((shift + math.prod(shape),), fill, device=DEV, dtype=dtype)[shift:].view(shape)
+    xd, dyd = dev(x.shape, 0.0).copy_(g(x.float())), dev(dy.shape, 0.0).copy_(g(dy.float()))
+    pool = dev((N, Ho, Wo, C), 7.0)
+    amax = dev((N, Ho, Wo, C), 0xAA, torch.uint8)
     hip.call(f"detr_hip_maxpool3x3s2_fwd_{suffix}", xd.data_ptr(), pool.data_ptr(), amax.data_ptr(), N, H, W, C, Ho, Wo)
-    dx = torch.full((N, H, W, C), 7.0, device=DEV, dtype=dt)
-    hip.call(f"detr_hip_maxpool3x3s2_bwd_{suffix}", dyd.data_ptr(), amax.data_ptr(), xd.data_ptr(), dx.data_ptr(), N, H, W, C, Ho, Wo)
+    dx = dev((N, H, W, C), 7.0)
+    if backward:
+        hip.call(f"detr_hip_maxpool3x3s2_bwd_{suffix}", dyd.data_ptr(), amax.data_ptr(), xd.data_ptr(), dx.data_ptr(), N, H, W, C, Ho, Wo)
     torch.cuda.synchronize()
     return pool.cpu().double(), amax.cpu(), dx.cpu().double()
 
@@ -381,6 +386,22 @@ def test_maxpool_small_maps_with_ties_exact(hip, H, W, C):
         outs[dt] = got
     for a, b in zip(outs[torch.float32], outs[torch.bfloat16]):
         assert torch.equal(a, b)
+
+
+@gpu
+@pytest.mark.parametrize("H,W", [(3, 3), (4, 6)])
+def test_maxpool_dispatch_corners_exact(hip, H, W):
+    """The two forms of the pooling dispatch that no other test reaches, against the same reference.
+    fp32 forward with C = 5: one channel per lane, on a channel count no vector form accepts (the fp32 backward needs C % 4 == 0: forward
+    only).  bf16 with C = 8 on tensors 4 elements into their buffers: 8-byte but not 16-byte aligned bases (argmax: 4-byte, not 8-byte),
+    so the 4-channel form runs although C % 8 == 0."""
+    x, dy, pooled, am, _, _ = _pool_case(H, W, 5)
+    got = _pool_run(hip, x, dy, H, W, 5, torch.float32, backward=False)
+    assert torch.equal(got[0], pooled) and torch.equal(got[1], am), f"maxpool f32 {H}x{W}x5 forward differs from the reference"
+    x, dy, pooled, am, dx, _ = _pool_case(H, W, 8)
+    got = _pool_run(hip, x, dy, H, W, 8, torch.bfloat16, shift=4)
+    for name, a, b in (("pooled", got[0], pooled), ("argmax", got[1], am), ("dx", got[2], dx)):
+        assert torch.equal(a, b), f"maxpool bf16 {H}x{W}x8, 8-byte aligned: {name} differs from the reference in {int((a != b).sum())} entries"
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

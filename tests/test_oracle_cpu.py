@@ -306,6 +306,31 @@ def test_fused_1x1_backward_sizing_and_rejections():
         assert what in msg, (bad, msg)
 
 
+def test_maxpool_rejects_pixel_counts_past_31_bits_without_a_gpu():
+    """The pooling kernels index input pixels in int: each of the four max-pool entry points REJECTS N * H * W >= 2^31 (N = 65536 and
+    N = 32768 maps of 256 x 256), and the largest shape class below (N = 32767: 2^31 - 65536 pixels) passes that check.  No GPU is needed
+    and none is touched: the pointers are never dereferenced, and the accepted shape carries one defect that a LATER check of the same
+    entry point names (output size, channel count or alignment), so no call here reaches a launch."""
+    _hip, lib = _hip_lib()
+    P = 1 << 20                                      # "pointers": 16-byte aligned, never touched
+    H = W = 256
+    Ho = Wo = 128
+    # (symbol, its pointers, the accepted shape's one defect, the message of the later check that names it)
+    entries = (("detr_hip_maxpool3x3s2_fwd_f32", (P, P, P), dict(C=64, Ho=Ho + 1), "bad output size"),
+               ("detr_hip_maxpool3x3s2_bwd_f32", (P, P, P, P), dict(C=6), "multiple of 4"),
+               ("detr_hip_maxpool3x3s2_fwd_bf16", (P, P, P), dict(C=64, Ho=Ho + 1), "bad output size"),
+               ("detr_hip_maxpool3x3s2_bwd_bf16", (P + 2, P, P, P), dict(C=64), "alignment"))
+    for name, ptrs, later, text in entries:
+        f = getattr(lib, name)
+        for n in (65536, 32768):
+            rc = f(*ptrs, n, H, W, 64, Ho, Wo, None)
+            msg = lib.detr_hip_last_error().decode()
+            assert rc < 0 and "31 bits" in msg and msg.startswith("maxpool"), (name, n, rc, msg)
+        rc = f(*ptrs, 32767, H, W, later["C"], later.get("Ho", Ho), Wo, None)
+        msg = lib.detr_hip_last_error().decode()
+        assert rc < 0 and text in msg and "31 bits" not in msg, (name, rc, msg)
+
+
 def test_host_side_of_the_c_abi_under_address_sanitizer():
     """SURVEY section 5 stance: the host side of the boundary (descriptor validation, planning, scratch-size queries, layout
     self-check) built with -fsanitize=address and driven by tests/host_abi_check.c (plain C, no GPU): every rejection path
