@@ -270,6 +270,23 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_track_desc, out_scores)); DETR_PUT(DETR_OFF(detr_track_desc, out_query)); DETR_PUT(DETR_OFF(detr_track_desc, out_ids));
         DETR_PUT(DETR_OFF(detr_track_desc, out_hits)); DETR_PUT(DETR_OFF(detr_track_desc, out_counts)); DETR_PUT(DETR_OFF(detr_track_desc, status));
         break;
+    case 500:   // detr_track_embed_desc (the fifth appended list counts from 500, include/detr_hip.h)
+        DETR_PUT((int32_t)sizeof(detr_track_embed_desc));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, S)); DETR_PUT(DETR_OFF(detr_track_embed_desc, D)); DETR_PUT(DETR_OFF(detr_track_embed_desc, state));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, state_bytes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, boxes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, labels));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, scores)); DETR_PUT(DETR_OFF(detr_track_embed_desc, query)); DETR_PUT(DETR_OFF(detr_track_embed_desc, counts));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, active)); DETR_PUT(DETR_OFF(detr_track_embed_desc, track_threshold)); DETR_PUT(DETR_OFF(detr_track_embed_desc, new_threshold));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, match_threshold)); DETR_PUT(DETR_OFF(detr_track_embed_desc, low_match_threshold)); DETR_PUT(DETR_OFF(detr_track_embed_desc, max_age));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, min_hits)); DETR_PUT(DETR_OFF(detr_track_embed_desc, alpha)); DETR_PUT(DETR_OFF(detr_track_embed_desc, beta));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, class_agnostic)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_labels));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, out_scores)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_query)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_ids));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, out_hits)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_counts)); DETR_PUT(DETR_OFF(detr_track_embed_desc, status));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, embed)); DETR_PUT(DETR_OFF(detr_track_embed_desc, sE_s)); DETR_PUT(DETR_OFF(detr_track_embed_desc, sE_r));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, R)); DETR_PUT(DETR_OFF(detr_track_embed_desc, E)); DETR_PUT(DETR_OFF(detr_track_embed_desc, embed_state));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, embed_state_bytes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, workspace)); DETR_PUT(DETR_OFF(detr_track_embed_desc, workspace_bytes));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, appearance_weight)); DETR_PUT(DETR_OFF(detr_track_embed_desc, reid)); DETR_PUT(DETR_OFF(detr_track_embed_desc, reid_threshold));
+        DETR_PUT(DETR_OFF(detr_track_embed_desc, momentum));
+        break;
     default:
         detr::set_error("struct_layout: unknown struct %d", which);
         return -1;

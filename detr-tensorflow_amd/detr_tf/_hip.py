@@ -173,6 +173,19 @@ class TrackDesc(Structure):
                 ("out_query", c_void_p), ("out_ids", c_void_p), ("out_hits", c_void_p), ("out_counts", c_void_p), ("status", c_void_p)]
 
 
+# detr_hip_track_embed reports detr_hip_track's bits and DETR_TRACK_BAD_EMBED
+TRACK_EMBED_BAD = dict(TRACK_BAD)
+TRACK_EMBED_BAD[4] = "an embedding row index outside [0, R) or a non-finite embedding (that detection was given the zero embedding)"
+
+
+class TrackEmbedDesc(Structure):
+    """detr_track_embed_desc (appended entry point, ABI version unchanged): detr_track_desc's fields, then the appearance ones."""
+    _fields_ = list(TrackDesc._fields_) + [
+        ("embed", c_void_p), ("sE_s", c_int64), ("sE_r", c_int64), ("R", c_int32), ("E", c_int32),
+        ("embed_state", c_void_p), ("embed_state_bytes", c_int64), ("workspace", c_void_p), ("workspace_bytes", c_int64),
+        ("appearance_weight", ctypes.c_double), ("reid", c_int32), ("reid_threshold", ctypes.c_double), ("momentum", c_float)]
+
+
 MAP_MAX_THR = 16                                                               # DETR_MAP_MAX_THR
 MAP_BAD = {1: "a predicted label outside [0, nb_class)", 2: "a target class outside [0, nb_class)",
            4: "a target header count outside [0, R-1]", 8: "a detection count outside [0, Q]"}      # DETR_MAP_BAD_*
@@ -284,6 +297,7 @@ _SIGNATURES = {
     "detr_hip_coco_match": [POINTER(CocoMatchDesc), c_void_p],
     "detr_hip_overlay": [POINTER(OverlayDesc), c_void_p],
     "detr_hip_track": [POINTER(TrackDesc), c_void_p],
+    "detr_hip_track_embed": [POINTER(TrackEmbedDesc), c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
@@ -298,6 +312,8 @@ _SIGNATURES_I64 = {
     "detr_hip_workspace_bytes_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32],
     "detr_hip_workspace_bytes_overlay": [POINTER(OverlayDesc)],
     "detr_hip_track_state_bytes": [c_int32],
+    "detr_hip_track_embed_state_bytes": [c_int32, c_int32],
+    "detr_hip_workspace_bytes_track_embed": [POINTER(TrackEmbedDesc)],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
@@ -307,6 +323,8 @@ LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: La
                   8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc}
 # the descriptors appended after detr_overlay_desc, by the same numbering; check_struct_layouts walks both tables
 LAYOUT_STRUCTS_APPENDED = {400: TrackDesc}
+# and the one behind detr_track_desc (a fifth list, 500), in a table of its own for the same reason
+LAYOUT_STRUCTS_APPENDED_500 = {500: TrackEmbedDesc}
 
 _lib = None
 
@@ -541,7 +559,7 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in sorted({**LAYOUT_STRUCTS, **LAYOUT_STRUCTS_APPENDED}.items()):
+    for which, S in sorted({**LAYOUT_STRUCTS, **LAYOUT_STRUCTS_APPENDED, **LAYOUT_STRUCTS_APPENDED_500}.items()):
         want = struct_layout_mirror(S)
         buf = (c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)

@@ -278,10 +278,21 @@ class Tracker:
     confirmed or has missed more than max_age frames; an unmatched detection with score >= new_threshold (None: track_threshold)
     starts a track, confirmed after min_hits matched frames; only detections of confirmed tracks are returned.
     The defaults are ByteTrack's and SORT's conventions carried over; nobody has tuned them for DETR outputs.  The association is
-    greedy, not Hungarian; there is no Kalman covariance, no re-identification feature and no camera-motion compensation."""
+    greedy, not Hungarian; there is no Kalman covariance and no camera-motion compensation.
+
+    embed_dim=E turns on tracking by APPEARANCE (include/detr_hip.h: detr_track_embed_desc; one launch as before): every frame also
+    hands in an embedding per detection, and every track keeps a unit embedding, an exponential average (momentum) of the detections it
+    was matched to.  The first association then walks its pairs -- still only those above match_threshold in IoU -- by
+    (1 - appearance_weight) * IoU + appearance_weight * cosine similarity, which keeps the ids of two objects of one class that pass
+    each other; and a confirmed track that was lost is found again, wherever it reappears, by a similarity above reid_threshold to an
+    unmatched detection that would otherwise start a track (None: no such stage).  Detector.track feeds the model's own descriptor
+    (DetrModel return_embeddings, E = 256); update_rows takes any [S, R, E] tensor.  appearance_weight, reid_threshold and momentum are
+    the conventions of BoT-SORT-like trackers carried over, UNTUNED: nobody has measured how well DETR's hidden states tell the objects
+    of a real video apart.  embed_dim=None (the default) is the tracker described above in every respect."""
 
     def __init__(self, streams=1, device=None, *, track_threshold=0.7, new_threshold=None, match_threshold=0.3, low_match_threshold=0.5,
-                 max_age=30, min_hits=3, alpha=0.75, beta=0.25, class_agnostic=False):
+                 max_age=30, min_hits=3, alpha=0.75, beta=0.25, class_agnostic=False, embed_dim=None, appearance_weight=0.5,
+                 reid_threshold=0.8, momentum=0.9):
         if new_threshold is None:
             new_threshold = track_threshold
         if not 1 <= int(streams) <= 65535:
@@ -292,6 +303,17 @@ class Tracker:
                 raise ValueError(f"Tracker: {name}={value} is not finite")
         if int(max_age) < 0 or int(min_hits) < 1:
             raise ValueError(f"Tracker: max_age={max_age} must be >= 0 and min_hits={min_hits} >= 1")
+        self.embed_dim = None if embed_dim is None else int(embed_dim)
+        if self.embed_dim is not None:
+            E = self.embed_dim
+            if E % 4 or not 4 <= E <= 512:
+                raise ValueError(f"Tracker: embed_dim={embed_dim} must be a multiple of 4 in 4..512")
+            if not 0.0 <= float(appearance_weight) <= 1.0 or not 0.0 <= float(momentum) <= 1.0:
+                raise ValueError(f"Tracker: appearance_weight={appearance_weight} and momentum={momentum} must be in [0, 1]")
+            if reid_threshold is not None and not math.isfinite(float(reid_threshold)):
+                raise ValueError(f"Tracker: reid_threshold={reid_threshold} is not finite")
+            self.appearance_weight, self.momentum = float(appearance_weight), float(momentum)
+            self.reid_threshold = None if reid_threshold is None else float(reid_threshold)
         self.streams = int(streams)
         self.track_threshold, self.new_threshold = float(track_threshold), float(new_threshold)
         self.match_threshold, self.low_match_threshold = float(match_threshold), float(low_match_threshold)
@@ -306,6 +328,14 @@ class Tracker:
                                f"{self.streams * TRACK_STATE.itemsize}: rebuild the library")
         self._state = torch.empty(self.streams, TRACK_STATE.itemsize, dtype=torch.uint8, device=self.device)
         self._all_active = torch.ones(self.streams, dtype=torch.int32, device=self.device)
+        if self.embed_dim is not None:
+            E = self.embed_dim
+            nbytes = int(hip.load().detr_hip_track_embed_state_bytes(self.streams, E))
+            if nbytes != self.streams * _T * E * 4:
+                raise RuntimeError(f"Tracker: the library's embedding bank is {nbytes} bytes, this binding lays out {self.streams * _T * E * 4}: "
+                                   "rebuild the library")
+            self._bank = torch.empty(self.streams, _T, E, dtype=torch.float32, device=self.device)
+            self._table = None                       # the kernel's scratch, sized by the widest frame seen
         self.reset()
 
     # ---- state
@@ -320,21 +350,29 @@ class Tracker:
             if not 0 <= int(stream) < self.streams:
                 raise ValueError(f"Tracker.reset: stream={stream} outside 0..{self.streams - 1}")
             self._state[int(stream)].copy_(row[0])
+        if self.embed_dim is not None:
+            (self._bank if stream is None else self._bank[int(stream)]).zero_()
 
     def state_dict(self):
         """The whole state as named host arrays, leading axis = stream: x, v float32 [S, T, 4]; label int64, id, hits, miss int32,
         confirmed bool, score float32 [S, T]; frame, next_id int32 [S] (T = _hip.TRACK_MAX; a free slot is all zeros).  One copy to the
-        host."""
+        host.  With embed_dim: plus embed float32 [S, T, E], the unit embedding of every slot (a second copy)."""
         raw = self._state.cpu().numpy().reshape(-1).view(TRACK_STATE)
         out = {k: np.ascontiguousarray(raw[k]) for k in TRACK_STATE_KEYS}
         out["confirmed"] = out["confirmed"] != 0
+        if self.embed_dim is not None:
+            out["embed"] = self._bank.cpu().numpy()
         return out
 
     def load_state_dict(self, state):
         """Take over a state_dict(): the video goes on bit-identically."""
-        missing = [k for k in TRACK_STATE_KEYS if k not in state]
+        missing = [k for k in TRACK_STATE_KEYS + (("embed",) if self.embed_dim is not None else ()) if k not in state]
         if missing:
             raise ValueError(f"Tracker.load_state_dict: missing {missing}")
+        if self.embed_dim is not None:
+            bank = np.asarray(state["embed"])
+            if bank.shape != tuple(self._bank.shape):
+                raise ValueError(f"Tracker.load_state_dict: embed has shape {bank.shape}, expected {tuple(self._bank.shape)}")
         raw = np.zeros(self.streams, TRACK_STATE)
         for k in TRACK_STATE_KEYS:
             value = np.asarray(state[k])
@@ -342,9 +380,11 @@ class Tracker:
                 raise ValueError(f"Tracker.load_state_dict: {k} has shape {value.shape}, expected {raw[k].shape} ({self.streams} streams)")
             raw[k] = value
         self._state.copy_(torch.from_numpy(raw.view(np.uint8).reshape(self.streams, -1)))
+        if self.embed_dim is not None:
+            self._bank.copy_(torch.from_numpy(np.ascontiguousarray(bank, np.float32)))
 
     # ---- frames
-    def _launch(self, boxes, labels, scores, query, counts, active):
+    def _launch(self, boxes, labels, scores, query, counts, active, embeddings=None):
         S = self.streams
         if boxes.dim() != 3 or boxes.shape[0] != S or boxes.shape[2] != 4 or not 1 <= boxes.shape[1] <= 1024:
             raise ValueError(f"Tracker: boxes must be [S={S}, D, 4] with D in 1..1024, got {tuple(boxes.shape)}")
@@ -357,9 +397,20 @@ class Tracker:
             if t.device != self._state.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
                 raise ValueError(f"Tracker: {name} must be a contiguous {dtype} tensor {shape} on {self._state.device}, got {t.dtype} "
                                  f"{tuple(t.shape)} on {t.device}")
+        if (embeddings is None) != (self.embed_dim is None):
+            raise ValueError("Tracker: embeddings= is mandatory with embed_dim and refused without: this tracker was built with "
+                             f"embed_dim={self.embed_dim}")
+        if embeddings is not None:
+            e = embeddings
+            if (not torch.is_tensor(e) or e.device != self._state.device or e.dtype != torch.float32 or e.dim() != 3 or e.shape[0] != S
+                    or e.shape[1] < 1 or e.shape[2] != self.embed_dim or e.stride(2) != 1 or e.stride(1) < self.embed_dim or e.stride(0) < 0
+                    or e.data_ptr() % 16):
+                raise ValueError(f"Tracker: embeddings must be a float32 tensor [S={S}, R, E={self.embed_dim}] on {self._state.device} with "
+                                 "contiguous, 16-byte aligned rows, got "
+                                 f"{(e.dtype, tuple(e.shape), e.stride(), e.device) if torch.is_tensor(e) else type(e).__name__}")
         out_b, out_l, out_s, out_q, out_i, out_h = _ranked_rows(S, D, self.device, 3)
         tail = torch.zeros(S + 1, dtype=torch.int32, device=self.device)       # counts [S], then the status word
-        d = hip.TrackDesc()
+        d = hip.TrackDesc() if embeddings is None else hip.TrackEmbedDesc()
         d.S, d.D, d.state, d.state_bytes = S, D, self._state.data_ptr(), self._state.numel()
         d.boxes, d.labels, d.scores, d.query = boxes.data_ptr(), labels.data_ptr(), scores.data_ptr(), hip.ptr(query)
         d.counts, d.active = counts.data_ptr(), active.data_ptr()
@@ -370,7 +421,18 @@ class Tracker:
         d.out_query, d.out_ids, d.out_hits = out_q.data_ptr(), out_i.data_ptr(), out_h.data_ptr()
         d.out_counts, d.status = tail.data_ptr(), tail.data_ptr() + 4 * S
         with torch.cuda.device(self.device):
-            hip._check(hip.load().detr_hip_track(byref(d), hip._stream()), "detr_hip_track")
+            if embeddings is None:
+                hip._check(hip.load().detr_hip_track(byref(d), hip._stream()), "detr_hip_track")
+                return (out_b, out_l, out_s, out_q, out_i, out_h), tail
+            d.embed, d.sE_s, d.sE_r, d.R, d.E = embeddings.data_ptr(), embeddings.stride(0), embeddings.stride(1), embeddings.shape[1], self.embed_dim
+            d.embed_state, d.embed_state_bytes = self._bank.data_ptr(), self._bank.numel() * 4
+            need = hip._ws_query("detr_hip_workspace_bytes_track_embed", ("track_embed", S, D), byref(d))
+            if self._table is None or self._table.numel() * 8 < need:
+                self._table = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+            d.workspace, d.workspace_bytes = self._table.data_ptr(), self._table.numel() * 8
+            d.appearance_weight, d.momentum = self.appearance_weight, self.momentum
+            d.reid, d.reid_threshold = int(self.reid_threshold is not None), 0.0 if self.reid_threshold is None else self.reid_threshold
+            hip._check(hip.load().detr_hip_track_embed(byref(d), hip._stream()), "detr_hip_track_embed")
         return (out_b, out_l, out_s, out_q, out_i, out_h), tail
 
     def _active(self, active):
@@ -381,24 +443,29 @@ class Tracker:
             raise ValueError(f"Tracker: active must hold one flag per stream ({self.streams}), got shape {flags.shape}")
         return torch.from_numpy(flags.astype(np.int32)).to(self.device)
 
-    def update_rows(self, boxes, labels, scores, query, counts, active=None):
+    def update_rows(self, boxes, labels, scores, query, counts, active=None, embeddings=None):
         """One frame per stream from padded DEVICE rows, as detr_hip_detect / detr_hip_tile_merge write them with bbox_format "xyxy":
         boxes [S, D, 4] float32, labels [S, D] int64, scores [S, D] float32, query [S, D] int32 or None, counts [S] int32 -- D <= 1024;
         rows behind counts[s] are not read.  active: one flag per stream (None: all); a stream whose flag is 0 keeps its state and
         returns nothing, e.g. a video that delivered no frame.  No packing and no synchronisation before the launch; ONE host
         synchronisation after it (the emitted counts and the status word).  -> [TrackedDetections], one per stream.  A stream with more
         than _hip.TRACK_MAX live tracks raises ValueError AFTER the state has been updated: the state stays valid, the detections
-        that found no slot are not tracked."""
-        rows, tail = self._launch(boxes, labels, scores, query, counts, self._active(active))
+        that found no slot are not tracked.
+        embeddings (mandatory with embed_dim, refused without): float32 [S, R, E] on the device, rows contiguous; the embedding of
+        detection d of stream s is row query[s, d] (row d with query None).  A row index outside [0, R) or a non-finite row raises
+        ValueError the same way: the frame has been tracked with the zero embedding for that detection."""
+        rows, tail = self._launch(boxes, labels, scores, query, counts, self._active(active), embeddings)
         *n, status = tail.tolist()
         if status:
-            raise ValueError("Tracker: " + "; ".join(text for bit, text in hip.TRACK_BAD.items() if status & bit))
+            raise ValueError("Tracker: " + "; ".join(text for bit, text in hip.TRACK_EMBED_BAD.items() if status & bit))
         return [TrackedDetections(*(r[s, :k] for r in rows)) for s, k in enumerate(n)]
 
-    def update(self, detections, active=None):
+    def update(self, detections, active=None, embeddings=None):
         """One frame per stream: `detections` holds, per stream, a Detections / TiledDetections with boxes in "xyxy" pixels, or a
         (boxes [k, 4], labels [k], scores [k]) triple (its query is 0); a single one is taken as the frame of a one-stream tracker.
-        They are packed into padded rows (as draw_detections packs them) and go through update_rows."""
+        They are packed into padded rows (as draw_detections packs them) and go through update_rows.  embeddings: update_rows'; the
+        rows are the detections' query, and for a triple, which has none, its k detections take the rows 0..k-1 (and are emitted with
+        those as query)."""
         if isinstance(detections, (Detections, TiledDetections)) or (isinstance(detections, tuple) and len(detections) == 3
                                                                        and not isinstance(detections[0], (tuple, list))):
             detections = [detections]
@@ -413,7 +480,9 @@ class Tracker:
         for s, d in enumerate(detections):
             if hasattr(d, "query") and counts[s]:
                 query[s, :counts[s]] = d.query.to(self.device)
-        return self.update_rows(boxes, labels, scores, query, torch.from_numpy(counts).to(self.device), active)
+            elif embeddings is not None and counts[s]:
+                query[s, :counts[s]] = torch.arange(int(counts[s]), dtype=torch.int32, device=self.device)
+        return self.update_rows(boxes, labels, scores, query, torch.from_numpy(counts).to(self.device), active, embeddings)
 
 
 class Detector:
@@ -524,8 +593,9 @@ class Detector:
         windows = np.array([(t.y0, t.x0, t.hc, t.wc) for r in recs for t in r], np.int32)
         return self._merge({"pred_logits": logits, "pred_boxes": boxes}, tile_start, windows, sizes)
 
-    def _forward(self, srcs, sizes, need_weights=None):
+    def _forward(self, srcs, sizes, need_weights=None, return_embeddings=False):
         """The single pass: input stage and model on the frames `srcs` -> (m_outputs, the input's shape)."""
+        extra = dict(return_embeddings=True) if return_embeddings else {}
         if self.resize == "fixed":
             if (sizes != sizes[0]).any():
                 raise ValueError(f"Detector: resize='fixed' takes images of ONE size per call, got {sorted(set(map(tuple, sizes.tolist())))}; "
@@ -537,7 +607,7 @@ class Detector:
             inputs = self.stage().augmented_padded(srcs, self.records(srcs), canvas=self.canvas)
             shape = inputs[0].shape
             self._last_frames = self.stage().last_upload                # already on the device: they cross PCIe once
-        return self.model(inputs, training=False, need_weights=need_weights), shape
+        return self.model(inputs, training=False, need_weights=need_weights, **extra), shape
 
     def __call__(self, images, need_weights=None):
         """images: one uint8 [h, w, 3] array -> Detections, or a list of them -> [Detections] (TiledDetections with tiles or
@@ -572,7 +642,10 @@ class Detector:
         that belong to a confirmed track, as TrackedDetections (a list for a list of images).  The plain path hands detr_hip_detect's
         raw rows and device counts to Tracker.update_rows: one launch more than __call__ and ONE host synchronisation per frame, the
         tracker's counts.  With tiles / nms_threshold the frame goes through merge_tiles first, which synchronises once itself: two per
-        frame.  Needs bbox_format="xyxy".  active: Tracker.update_rows'."""
+        frame.  Needs bbox_format="xyxy".  active: Tracker.update_rows'.
+        A tracker with embed_dim (it must be 256) tracks by appearance: the model is called with return_embeddings and its out["embed"]
+        goes to update_rows with detr_hip_detect's query rows -- one launch more (the copy of the embeddings), no further
+        synchronisation.  Not with tiles / nms_threshold: that path keeps no per-tile embeddings."""
         if self.bbox_format != "xyxy":
             raise ValueError(f"Detector.track: boxes must be 'xyxy' pixels: build the Detector with bbox_format='xyxy', not {self.bbox_format!r}")
         if not isinstance(tracker, Tracker):
@@ -583,14 +656,20 @@ class Detector:
             raise TypeError("Detector expects a uint8 image [h, w, 3] or a non-empty list of them")
         if len(srcs) != tracker.streams:
             raise ValueError(f"Detector.track: {len(srcs)} images for a tracker of {tracker.streams} streams")
+        appearance = tracker.embed_dim is not None
+        if appearance and tracker.embed_dim != 256:
+            raise ValueError(f"Detector.track: the model's embeddings have 256 elements, the tracker was built with embed_dim={tracker.embed_dim}")
         if self.tiles is not None or self.nms_threshold is not None:
+            if appearance:
+                raise NotImplementedError("Detector.track: tracking by appearance with tiles / nms_threshold: that path keeps no per-tile "
+                                          "embeddings; use a Tracker without embed_dim, or a Detector without tiles and nms_threshold")
             tracked = tracker.update(self(srcs), active)
         else:
             sizes = np.array([s.shape[:2] for s in srcs], np.int32)
-            m_outputs, _ = self._forward(srcs, sizes)
+            m_outputs, _ = self._forward(srcs, sizes, return_embeddings=appearance)
             rows = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, self.background_class, self.score_threshold,
                            self.max_detections, self.bbox_format, True)
-            tracked = tracker.update_rows(*rows, active)
+            tracked = tracker.update_rows(*rows, active, m_outputs["embed"] if appearance else None)
         return tracked[0] if single else tracked
 
     def attention_site(self, site="dec"):

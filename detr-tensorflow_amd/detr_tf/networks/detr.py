@@ -195,15 +195,26 @@ class DetrModel:
         graph.replay()
         return out
 
-    def __call__(self, images, training=False, masks=None, need_weights=None):
+    def __call__(self, images, training=False, masks=None, need_weights=None, return_embeddings=False):
         """images: [B, H, W, 3] float32, or the reference's `(images, masks)` pair (detr.py:65-72); masks: [B, H, W] bool, True =
         padding (a padded mixed-size batch).  Host masks are validated here (ValueError for an image without a
         valid feature position); device masks on the device (engine.check_mask_status).
         need_weights (the reference's MultiHeadAttention need_weights, transformer.py:285-286, 349-354; evaluation mode only): True
         = the head-averaged maps of the last encoder layer's self-attention [B, L, L] and of the last decoder layer's
         cross-attention [B, Q, L] (L = Hf * Wf); an iterable of site names (engine.attn_site_names()) = those.  The result gains
-        out["attn"] = {site name: fp32 tensor [B, T, S]}."""
+        out["attn"] = {site name: fp32 tensor [B, T, S]}.
+        return_embeddings (evaluation mode only, a model with a head): the result gains out["embed"], fp32 [B, Q, 256]: the last
+        decoder layer's normalised hidden state of every object query -- what the headless mode returns as hs[-1] --, the default
+        appearance descriptor of inference.Tracker(embed_dim=256).  A copy of the engine's buffer taken after the forward (or the
+        graph replay): no kernel of the model is added and the captured graph is the same one."""
         sites = self._need_weights_sites(need_weights, training)
+        if return_embeddings:
+            if training:
+                raise NotImplementedError("return_embeddings: the embeddings are returned in evaluation mode only; with training=True "
+                                          "the outputs are views of the engine's buffers")
+            if self.headless:
+                raise NotImplementedError("return_embeddings: the headless mode (include_top=False, nb_class=None) already returns the "
+                                          "hidden states themselves: take hs[-1]")
         if isinstance(images, (tuple, list)):
             if masks is not None or len(images) != 2:
                 raise TypeError("model((images, masks)): pass the mask once, either in the tuple or as masks=")
@@ -230,6 +241,9 @@ class DetrModel:
         out.levels_logits, out.levels_boxes, out.model = logits, boxes, self
         if sites:
             out["attn"] = {name: self.engine.attn_maps[name].clone() for name in sites}
+        if return_embeddings:
+            eng = self.engine
+            out["embed"] = eng._bufs["dec:hs"][eng.num_dec - 1].view(images.shape[0], eng.Q, 256).clone()
         if self.dp is not None:
             out.reduce_sums = self.dp.reduce_sums
         return out

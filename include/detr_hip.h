@@ -976,6 +976,83 @@ typedef struct {
 int detr_hip_track(const detr_track_desc *d, void *stream);
 int64_t detr_hip_track_state_bytes(int32_t streams);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tracking by appearance, appended (the ABI version is unchanged): detr_hip_track with an embedding per detection -- a fused
+ * IoU / similarity cost in stage 1 and a re-identification stage for tracks that were lost (csrc/track_embed.hip; the kernel body is
+ * the one of detr_hip_track, csrc/track_core.h).  Every field of detr_track_desc means what it means there; the steps 1..8 of
+ * detr_hip_track stand, with the changes below.  Still one launch per batch of frames and one workgroup per stream.
+ * Embeddings: embed is [S, R, E] fp32, row r of stream s at embed + s * sE_s + r * sE_r (strides in elements, sE_r >= E).  The RAW
+ *   embedding f of detection d of stream s is row query[s, d], or row d with query == NULL.  Any tensor will do; the default source
+ *   is the last decoder layer's hidden state of the model (DetrModel return_embeddings, E = 256, query = detr_hip_detect's out_query).
+ * dot64(a, b) of two fp32 vectors of length E, in this order: lane partials p[l] = sum over j ascending of (double)a[l + 64 j] *
+ *   (double)b[l + 64 j] for l = 0..63 (the products are exact in fp64), p[l] = 0 for l >= E; then for o = 32, 16, 8, 4, 2, 1:
+ *   p[l] = p[l] + p[l ^ o] for all l at once.  Every lane ends with the same value, which is the result.
+ * The unit embedding n of a detection: nrm = sqrt(dot64(f, f)) (fp64, correctly rounded), n[k] = (float)((double)f[k] / nrm); n is
+ *   all zeros when nrm is 0 or not finite, or when the row index is outside [0, R).  The last two cases -- an index outside [0, R),
+ *   a NaN or an infinity in the row -- set DETR_TRACK_BAD_EMBED in *status; they are looked for in all counts[s] detections of an
+ *   active stream.  n is recomputed from f wherever it is needed.
+ * The bank: embed_state holds float e[DETR_TRACK_MAX][E] per stream, the unit embedding of every slot (zeros for a free slot), in
+ *   detr_hip_track_embed_state_bytes(S, E) bytes; it is a second state buffer next to `state`, whose layout is detr_hip_track's.
+ *   sim(t, d) = dot64(e_t, n_d).
+ * Per stream with active[s] != 0:
+ *   3. stage 1 takes the same pairs by the same gate, IoU > match_threshold, but walks them by descending
+ *      m = (1 - w) * IoU + w * sim(t, d), w = appearance_weight: fp64, (1 - w), the two products and the sum one rounding each; ties by
+ *      lower track id, then lower detection index.  With w == 0 no similarity is computed and m is the IoU itself.  (A NaN m is no pair.)
+ *   4. stage 2 is unchanged: IoU only.
+ *   4b. with reid != 0, re-identification: the slots still unmatched that are confirmed and came into the frame with miss >= 1, against
+ *      the high detections still unmatched with score >= new_threshold, of equal label (any label with class_agnostic), with
+ *      sim(t, d) > reid_threshold (strict) and NO IoU gate, walked by descending sim, ties by lower id, then lower detection.
+ *      A slot matched here takes x = z, v = 0, hits += 1, miss = 0, score = the detection's; its detection does not spawn (step 7) and
+ *      is emitted with the slot's id (step 8).
+ *   5..8 are unchanged for every other slot.  Then the bank: a slot matched in stage 1 or 4b, in fp32 with one rounding per operation,
+ *      u[k] = momentum * e[k] + (1 - momentum) * n_d[k], then e[k] = (float)((double)u[k] / sqrt(dot64(u, u))) (zeros when that root
+ *      is 0 or not finite); a slot matched in stage 2 keeps e; a spawned slot takes e = n_d; a freed slot is zeroed.
+ * active[s] == 0 leaves both states of stream s untouched.  Nothing is read or written out of bounds for any count, query or embedding
+ * value.  Integer atomics on *status only, no float atomics: a rerun from the same two states is bit-identical.
+ * workspace: detr_hip_workspace_bytes_track_embed(d) bytes (reads S, D only; negative = malformed), 16-byte aligned: the fp64
+ *   similarities [S][DETR_TRACK_MAX][D] of the pairs that pass a walk's gate, filled by whole waves before the walk.
+ * Limits: those of detr_hip_track; R >= 1; E a multiple of 4 in 4..512; sE_r >= E, sE_s >= 0; embed, embed_state and workspace
+ *   16-byte aligned; appearance_weight in [0, 1]; reid 0 or 1; reid_threshold finite; momentum in [0, 1].
+ * detr_hip_struct_layout knows detr_track_embed_desc as 500 (a fifth appended list).
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_TRACK_BAD_EMBED 4
+typedef struct {
+    int32_t S, D;
+    void *state;                                 /* detr_hip_track_state_bytes(S) bytes, read and written */
+    int64_t state_bytes;
+    const float *boxes;                          /* [S, D, 4] x0, y0, x1, y1 in pixels */
+    const int64_t *labels;                       /* [S, D] */
+    const float *scores;                         /* [S, D] */
+    const int32_t *query;                        /* [S, D] or NULL (emitted as 0; the embedding of detection d is then row d) */
+    const int32_t *counts;                       /* [S], DEVICE memory */
+    const int32_t *active;                       /* [S], DEVICE memory */
+    float track_threshold, new_threshold;        /* finite */
+    double match_threshold, low_match_threshold; /* finite */
+    int32_t max_age, min_hits;
+    float alpha, beta;                           /* finite */
+    int32_t class_agnostic;                      /* 0 | 1 */
+    float *out_boxes;                            /* [S, D, 4] */
+    int64_t *out_labels;                         /* [S, D] */
+    float *out_scores;                           /* [S, D] */
+    int32_t *out_query, *out_ids, *out_hits;     /* [S, D] */
+    int32_t *out_counts;                         /* [S] */
+    int32_t *status;                             /* [1] */
+    const float *embed;                          /* [S, R, E] */
+    int64_t sE_s, sE_r;                          /* its stream and row strides in elements */
+    int32_t R, E;
+    void *embed_state;                           /* detr_hip_track_embed_state_bytes(S, E) bytes, read and written */
+    int64_t embed_state_bytes;
+    void *workspace;
+    int64_t workspace_bytes;
+    double appearance_weight;                    /* in [0, 1] */
+    int32_t reid;                                /* 0 | 1 */
+    double reid_threshold;                       /* finite */
+    float momentum;                              /* in [0, 1] */
+} detr_track_embed_desc;
+int detr_hip_track_embed(const detr_track_embed_desc *d, void *stream);
+int64_t detr_hip_track_embed_state_bytes(int32_t streams, int32_t embed_dim);
+int64_t detr_hip_workspace_bytes_track_embed(const detr_track_embed_desc *d);
+
 #ifdef __cplusplus
 }
 #endif
