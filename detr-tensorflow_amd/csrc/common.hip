@@ -132,6 +132,8 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_gemm_desc, ln_mean)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_rstd)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_add));
         DETR_PUT(DETR_OFF(detr_gemm_desc, ln_add_rows)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_y2)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_y16));
         DETR_PUT(DETR_OFF(detr_gemm_desc, ln_eps));
+        DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_h)); DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_w)); DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_ho));
+        DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_wo));
         break;
     case 2:   // detr_conv3x3_desc
         DETR_PUT((int32_t)sizeof(detr_conv3x3_desc));

@@ -55,7 +55,19 @@ struct EpiArgs {
     // [row * ldmask + n / 8], ldmask in BYTES); mbits_out != null -> the epilogue also writes those bytes for its own output
     unsigned char *mbits_out = nullptr;
     long long ld_mbits_out = 0;
+    // optional residual row map (wide16 / streaming epilogues only; detr_gemm_desc.res_sub_*): the output rows are the pixels of
+    // [.., res_sub_h, res_sub_w] maps and `residual` is the compact [.., res_sub_ho, res_sub_wo, N] tensor of their even pixels --
+    // pixel (n, y, x) takes row (n, y / 2, x / 2) when y and x are even and NO residual (zero, no request) otherwise.  C and the mask
+    // keep their rows.  res_sub_w == 0: identity.
+    int res_sub_w = 0, res_sub_h = 0, res_sub_wo = 0, res_sub_ho = 0;
 };
+// row of the compact residual for output row `row` (EpiArgs.res_sub_*), -1 for a pixel that was not sampled
+__device__ __forceinline__ long long res_sub_row(int row, int w, int h, int wo, int ho) {
+    const unsigned x = (unsigned)row % (unsigned)w, t = (unsigned)row / (unsigned)w;
+    const unsigned y = t % (unsigned)h, n = t / (unsigned)h;
+    if ((x | y) & 1u) return -1;
+    return ((long long)n * ho + (y >> 1)) * wo + (x >> 1);
+}
 // bit j of the result = (bf16 element j of the four packed pairs > 0)
 __device__ __forceinline__ unsigned bf16x8_gt0_bits(unsigned w0, unsigned w1, unsigned w2, unsigned w3) {
     const unsigned w[4] = {w0, w1, w2, w3};
@@ -518,7 +530,9 @@ __device__ __forceinline__ void epilogue_wide16(const f32x16 (&acc)[TileCfg<BM, 
             prow[p] = prow_of(row);
             rr[p] = make_uint4(0u, 0u, 0u, 0u);
             mm[p] = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-            if (ok && res16) rr[p] = epi_ld16(res16 + prow[p] * e.ldr + col);
+            long long rrow = prow[p];                  // (once per row of the strip: a lane owns one column chunk of it)
+            if (e.res_sub_w > 0) rrow = res_sub_row(row, e.res_sub_w, e.res_sub_h, e.res_sub_wo, e.res_sub_ho);
+            if (ok && res16 && rrow >= 0) rr[p] = epi_ld16(res16 + rrow * e.ldr + col);
             if (ok && msk16) {
                 if (e.m16 == 2) mm[p].x = reinterpret_cast<const unsigned char *>(e.mask)[prow[p] * e.ldmask + (col >> 3)];      // 8 mask bits
                 else mm[p] = epi_ld16(msk16 + prow[p] * e.ldmask + col);

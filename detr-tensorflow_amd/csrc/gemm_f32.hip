@@ -485,10 +485,19 @@ static int gemm_prepare(const detr_gemm_desc *d, GemmPlan &p) {
     g.e.wide16 = g.e.c16 && split == 1 && batch == 1 && (!d->residual || g.e.r16) && (!d->mask || g.e.m16) && d->N % 8 == 0 &&
                  d->ldc % 8 == 0 && aligned16(d->C) && (!d->residual || (d->ldr % 8 == 0 && aligned16(d->residual))) &&
                  (!d->mask || bits_in || (d->ldmask % 8 == 0 && aligned16(d->mask))) && (!d->scale || aligned16(d->scale)) &&
-                 (!d->bias || aligned16(d->bias)) && (tune(T_EPI_WIDE) != 2 || bits_in || bits_out);
+                 (!d->bias || aligned16(d->bias)) && (tune(T_EPI_WIDE) != 2 || bits_in || bits_out || d->res_sub_w > 0);
     // bit-packed masks live in the all-bf16 epilogues (8 columns per lane = one byte) of the tile engine and of the streaming kernel
     DETR_REQUIRE(!(bits_in || bits_out) || (bf16c && g.e.wide16 && (!bits_in || d->ldmask >= d->N / 8) && (!bits_out || d->ld_maskbits_out >= d->N / 8)),
                  "gemm: bit-packed masks need bf16 C / residual, N %% 8 == 0, 16-byte aligned rows, no split-K / batch, and a row pitch >= N / 8 bytes");
+    // the residual row map lives in the same epilogues (a launch that reaches any other one must fail, never ignore the map)
+    if (d->res_sub_h || d->res_sub_w || d->res_sub_ho || d->res_sub_wo) {
+        DETR_REQUIRE(d->res_sub_h > 0 && d->res_sub_w > 0 && d->res_sub_ho == (d->res_sub_h + 1) / 2 && d->res_sub_wo == (d->res_sub_w + 1) / 2 &&
+                     d->M % ((long long)d->res_sub_h * d->res_sub_w) == 0,
+                     "gemm: residual row map: M must be whole res_sub_h x res_sub_w maps and res_sub_ho / res_sub_wo their halves, rounded up");
+        DETR_REQUIRE(d->residual && bf16c && g.e.wide16 && !d->ln_y,
+                     "gemm: a residual row map needs a bf16 residual and bf16 C (compute = bf16), N %% 8 == 0, 16-byte aligned rows, no split-K / batch / LayerNorm");
+        g.e.res_sub_h = d->res_sub_h; g.e.res_sub_w = d->res_sub_w; g.e.res_sub_ho = d->res_sub_ho; g.e.res_sub_wo = d->res_sub_wo;
+    }
 
     const bool ak = d->a_kcontig != 0, bk = d->b_kcontig != 0;
     DETR_REQUIRE(!(bf16c && d->a_dtype == 1 && !ak) || (d->lda % 8 == 0 && d->M % 8 == 0 && aligned16(d->A)),
@@ -566,6 +575,7 @@ static bool gemm_stream_eligible(const GemmPlan &p) {
     if (d->mask && g.e.m16 != 2 && !(g.e.m16 && d->ldmask % 8 == 0 && aligned16(d->mask))) return false;
     if (!(d->lda % 8 == 0 && d->ldb % 8 == 0 && d->ldc % 8 == 0 && aligned16(d->A) && aligned16(d->B) && aligned16(d->C))) return false;
     const long long ldm_eff = g.e.m16 == 2 ? 0 : d->ldmask;
+    // (a mapped residual is the smaller compact tensor: bounding it by the M full-resolution rows is the safe side)
     long long pitch = d->ldr > ldm_eff ? d->ldr : ldm_eff;
     if (d->ldc > pitch) pitch = d->ldc;             // C is stored through a buffer descriptor as well (32-bit byte offsets)
     const long long span = (long long)(d->M - 1) * pitch + d->N;
@@ -590,6 +600,8 @@ static void gemm_stream_launch(const GemmPlan &p, hipStream_t s) {
     a.alpha = d->alpha;
     a.drop_scale = p.g.e.drop_scale; a.drop_thresh = p.g.e.drop_thresh; a.drop_seed = p.g.e.drop_seed; a.drop_step = p.g.e.drop_step;
     a.n_tiles = a.row_tiles = a.q = 0;
+    a.res_sub_h = p.g.e.res_sub_h; a.res_sub_w = p.g.e.res_sub_w; a.res_sub_ho = p.g.e.res_sub_ho; a.res_sub_wo = p.g.e.res_sub_wo;
+    a.res_rows = a.res_sub_w > 0 ? (long long)d->M / ((long long)a.res_sub_h * a.res_sub_w) * a.res_sub_ho * a.res_sub_wo : 0;
     const bool mb = d->mask && d->m_dtype == 2;
     if (d->K == 64) launch_gemm_stream<64>(a, p.bk, s, mb);
     else if (d->K == 128) launch_gemm_stream<128>(a, p.bk, s, mb);

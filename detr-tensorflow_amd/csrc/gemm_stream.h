@@ -45,6 +45,9 @@ struct StreamArgs {
     float drop_scale;                              // 1 / (1 - p), 0 = no dropout
     uint32_t drop_thresh, drop_seed;
     const uint32_t *drop_step;
+    // residual row map (gemm_core.h EpiArgs.res_sub_*; 0 = identity): `res` is the compact tensor of res_rows rows
+    int res_sub_w = 0, res_sub_h = 0, res_sub_wo = 0, res_sub_ho = 0;
+    long long res_rows = 0;
 };
 
 // Cache policy of the epilogue streams.  The residual and the mask are read exactly once by this kernel and by nobody
@@ -115,7 +118,7 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
         for (int i = 0; i < 8; ++i) bias[sw][i] = a.bias ? a.bias[n0 + sw * 64 + ecg * 8 + i] : 0.0f;
     BufSrc srcA, srcR, srcM;
     srcA.init_bytes(a.A, ((long long)(a.M - 1) * a.lda + K) * 2);
-    if (RES) srcR.init_bytes(a.res, ((long long)(a.M - 1) * a.ldr + a.N) * 2);
+    if (RES) srcR.init_bytes(a.res, ((long long)((a.res_sub_w > 0 ? a.res_rows : (long long)a.M) - 1) * a.ldr + a.N) * 2);
     if (MASK == 1) srcM.init_bytes(a.mask, ((long long)(a.M - 1) * a.ldm + a.N) * 2);
     if (MASK == 2) srcM.init_bytes(a.mask, (long long)(a.M - 1) * a.ldm + a.N / 8);
     BufSrc dstC, dstB;
@@ -175,6 +178,29 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
     auto strip = [&](const int rt, uint4 (&a_first)[KK], uint4 (&a_other)[KK]) {
         const int r0 = rt * 32;
         uint4 rres[NW][4], rmsk[NW][4];
+        unsigned roff[4];                          // byte offset of the residual row of item `it`, BUF_OOB: no residual for that row
+        if (RES) {
+            if (a.res_sub_w > 0) {
+                // one decomposition per strip (the row of item 0); items 1..3 are 8 rows further each: carried, not divided again
+                const unsigned sw_ = (unsigned)a.res_sub_w, sh_ = (unsigned)a.res_sub_h;
+                const unsigned row0 = (unsigned)(r0 + erow);
+                unsigned x = row0 % sw_, t = row0 / sw_;
+                unsigned y = t % sh_, n = t / sh_;
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {
+                    const bool live = (r0 + it * 8 + erow) < a.M && !((x | y) & 1u);
+                    roff[it] = live ? (unsigned)((n * (unsigned)a.res_sub_ho + (y >> 1)) * (unsigned)a.res_sub_wo + (x >> 1)) * ldr2 : BUF_OOB;
+                    x += 8u;
+                    while (x >= sw_) {
+                        x -= sw_;
+                        if (++y == sh_) { y = 0u; ++n; }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int it = 0; it < 4; ++it) roff[it] = (r0 + it * 8 + erow) < a.M ? (unsigned)(r0 + it * 8 + erow) * ldr2 : BUF_OOB;
+            }
+        }
 #pragma unroll
         for (int sw = 0; sw < NW; ++sw)
 #pragma unroll
@@ -182,7 +208,7 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
             const int row = r0 + it * 8 + erow;
             const unsigned colb = (unsigned)((n0 + sw * 64 + ecg * 8) * 2);
             // (byte offsets fit 32 bits: the host dispatch only sends tensors below 4 GB here)
-            if (RES) rres[sw][it] = stream_ld_ep(srcR, (row < a.M) ? (unsigned)row * ldr2 + colb : BUF_OOB);
+            if (RES) rres[sw][it] = stream_ld_ep(srcR, roff[it] != BUF_OOB ? roff[it] + colb : BUF_OOB);
             if (MASK == 1) rmsk[sw][it] = stream_ld_ep(srcM, (row < a.M) ? (unsigned)row * ldm2 + colb : BUF_OOB);
             if (MASK == 2)      // one byte = the 8 columns of this lane; the 8 lanes of a row read 8 consecutive bytes
                 rmsk[sw][it].x = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(srcM.rsrc, (row < a.M) ? (unsigned)row * ldm1 + (unsigned)(((n0 + sw * 64) >> 3) + ecg) : BUF_OOB, 0, 0);

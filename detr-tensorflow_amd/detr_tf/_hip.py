@@ -43,7 +43,8 @@ class GemmDesc(Structure):
                 ("dropout_step", c_void_p), ("defer_out", POINTER(ReduceDesc)),
                 ("maskbits_out", c_void_p), ("ld_maskbits_out", c_int64),          # ABI 5: bit-packed ReLU masks
                 ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_y", c_void_p), ("ln_mean", c_void_p), ("ln_rstd", c_void_p),
-                ("ln_add", c_void_p), ("ln_add_rows", c_int32), ("ln_y2", c_void_p), ("ln_y16", c_void_p), ("ln_eps", c_float)]
+                ("ln_add", c_void_p), ("ln_add_rows", c_int32), ("ln_y2", c_void_p), ("ln_y16", c_void_p), ("ln_eps", c_float),
+                ("res_sub_h", c_int32), ("res_sub_w", c_int32), ("res_sub_ho", c_int32), ("res_sub_wo", c_int32)]    # appended: residual row map
 
 
 class AttnDesc(Structure):
@@ -604,11 +605,19 @@ def _f32(t, name="tensor"):
 def _gemm_desc(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, *, alpha=1.0, scale=None, bias=None,
                residual=None, ldr=0, mask=None, ldmask=0, act=0, split_k=1, batch=1, batch_inner=1,
                sA=(0, 0), sB=(0, 0), sC=(0, 0), a_off=0, b_off=0, c_off=0, workspace=None, dropout_p=0.0, dropout_seed=0,
-               dropout_step=None, compute=None, rowsum_a=None, rowsum_alpha=1.0, ws_slice=None, maskbits_out=None, ln=None):
+               dropout_step=None, compute=None, rowsum_a=None, rowsum_alpha=1.0, ws_slice=None, maskbits_out=None, ln=None,
+               res_sub=None):
     """Fills a detr_gemm_desc; returns (desc, profiler info).  ws_slice = (index, count): this call's share of WORKSPACE.
-    ln: dict(gamma, beta, y, mean, rstd, eps[, add, y2][, y16]) -- the LayerNorm of the output rows from the same launch."""
+    ln: dict(gamma, beta, y, mean, rstd, eps[, add, y2][, y16]) -- the LayerNorm of the output rows from the same launch.
+    res_sub = (h, w): the output rows are pixels of h x w maps and `residual` is the compact tensor of their even pixels
+    (detr_gemm_desc.res_sub_*)."""
     d = GemmDesc()
     d.M, d.N, d.K = M, N, K
+    res_rows = M
+    if res_sub is not None:
+        d.res_sub_h, d.res_sub_w = res_sub
+        d.res_sub_ho, d.res_sub_wo = (d.res_sub_h + 1) // 2, (d.res_sub_w + 1) // 2
+        res_rows = M // max(1, d.res_sub_h * d.res_sub_w) * d.res_sub_ho * d.res_sub_wo
     if ln is not None:
         d.ln_gamma, d.ln_beta, d.ln_y = ln["gamma"].data_ptr(), ln["beta"].data_ptr(), ln["y"].data_ptr()
         d.ln_mean, d.ln_rstd, d.ln_eps = ln["mean"].data_ptr(), ln["rstd"].data_ptr(), float(ln["eps"])
@@ -672,7 +681,7 @@ def _gemm_desc(M, N, K, A, lda, a_kcontig, B, ldb, b_kcontig, C, ldc, *, alpha=1
     sig = (f"M{M} N{N} K{K} b{batch} ak{int(a_kcontig)} bk{int(b_kcontig)} a16{d.a_dtype} b16{d.b_dtype} sk{split_k}"
            f"{' res' if residual is not None else ''}{' mask' if mask is not None else ''}")
     nbytes = float(batch) * (A.element_size() * M * K + B.element_size() * K * N + C.element_size() * M * N
-                             + (residual.element_size() * M * N if residual is not None else 0)
+                             + (residual.element_size() * res_rows * N if residual is not None else 0)
                              + ((M * N // 8 if mask.dtype == torch.uint8 else mask.element_size() * M * N) if mask is not None else 0)
                              + (M * N // 8 if maskbits_out is not None else 0))     # algorithmic bytes at the stored widths
     return d, (fam, 2.0 * M * N * K * batch, sig, nbytes, rd)

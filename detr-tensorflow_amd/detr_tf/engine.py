@@ -1172,19 +1172,27 @@ class DetrEngine:
             # conv3: g is the gradient w.r.t. (bn3(conv3(y2)) + identity), already ReLU-masked
             strided = m["first"] and stride == 2
             wsd = self._bufs[f"{wk}:{n['down']}/kernel"] if m["first"] else None
-            idg, idg_ready = g, None
+            idg, idg_ready, idg_sub = g, None, None
             # layer1's 64 -> 256 convolutions on bf16 tensors: g (274 MB at B = 8, 800 x 1333) is read once per convolution, not twice
             fused_ok = BWD_FUSED and self.compute == 1 and adt == torch.bfloat16 and d2 == 256 and g.is_cuda
             fuse3, fuse_down = fused_ok and d1 == 64, False
             if m["first"] and not (tfb and strided):
-                # data gradient of the projection shortcut: only the block's last GEMM reads it (as its residual operand)
-                idg = self.buf(f"scratch:idg:{cin}:{h}", (B, h, w, cin), adt)
+                # data gradient of the projection shortcut: only the block's last GEMM reads it (as its residual operand).
+                # Stride 2, bf16 tensors: it stays the compact [B, ho, wo, cin] tensor and the GEMM's residual row map
+                # (detr_gemm_desc.res_sub_*) adds it at the even pixels -- no zero-filled full-resolution copy is written or read
+                sub_res = strided and adt == torch.bfloat16
+                if sub_res:
+                    idg, idg_sub = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt), (h, w)
+                else:
+                    idg = self.buf(f"scratch:idg:{cin}:{h}", (B, h, w, cin), adt)
 
                 # (layer1, bf16: the shortcut's input gradient and weight gradient in ONE pass over g -- csrc/bwd_fused.hip)
                 fuse_down = fused_ok and not strided and cin == 64
 
-                def dg_down(g=g, idg=idg):
-                    if strided:
+                def dg_down(g=g, idg=idg, sub_res=sub_res):
+                    if sub_res:
+                        hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, idg, cin)
+                    elif strided:
                         dxs = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt)
                         hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, dxs, cin)
                         hip.call("detr_hip_subsample2_bwd_f32", dxs.data_ptr(), idg.data_ptr(), B, h, w, cin // f32c, ho, wo)
@@ -1248,10 +1256,11 @@ class DetrEngine:
                 if idg_ready is not None:
                     main.wait_event(idg_ready)
                 if xbits is not None:
-                    hip.gemm(M_in, cin, d1, dz1, d1, 1, ws1, d1, 1, gx, cin, residual=idg, ldr=cin, mask=xbits, ldmask=xbits.stride(0))
+                    hip.gemm(M_in, cin, d1, dz1, d1, 1, ws1, d1, 1, gx, cin, residual=idg, ldr=cin, mask=xbits, ldmask=xbits.stride(0),
+                             res_sub=idg_sub)
                 else:
                     hip.gemm(M_in, cin, d1, dz1, d1, 1, ws1, d1, 1, gx, cin, residual=idg, ldr=cin, mask=mask,
-                             ldmask=(cin if mask is not None else 0))
+                             ldmask=(cin if mask is not None else 0), res_sub=idg_sub)
             g = gx
             if on_bucket:
                 if p == block_names(3, 0, tfb)["tag"]:

@@ -142,6 +142,14 @@ typedef struct {
      * K % 8 == 0, batch = split_k = 1, act = 0, no scale / mask; anything else is rejected. */
     const float *ln_gamma, *ln_beta; float *ln_y, *ln_mean, *ln_rstd; const float *ln_add; int32_t ln_add_rows; float *ln_y2;
     uint16_t *ln_y16; float ln_eps;
+    /* Optional residual row map (appended; all 0 = identity): the output rows are the pixels of [.., res_sub_h, res_sub_w] maps
+     * (M %% (res_sub_h * res_sub_w) == 0) and `residual` is the COMPACT [.., res_sub_ho, res_sub_wo, N] tensor of their even pixels
+     * (res_sub_ho = (res_sub_h + 1) / 2, res_sub_wo = (res_sub_w + 1) / 2): output pixel (n, y, x) adds residual row (n, y / 2, x / 2)
+     * when y and x are both even and nothing otherwise (an exact zero, no memory request).  C and the mask keep their own rows.
+     * This is the input gradient of a stride-2 1x1 convolution (the projection shortcut of a stage's first block) added without
+     * scattering it into a zero-filled full-resolution tensor first.  All-bf16 epilogues only: bf16 C and residual (c_dtype =
+     * r_dtype = 1), compute = 1, N %% 8 == 0, 16-byte aligned rows, no batch / split_k / fused LayerNorm; anything else is rejected. */
+    int32_t res_sub_h, res_sub_w, res_sub_ho, res_sub_wo;
 } detr_gemm_desc;
 int detr_hip_gemm_f32(const detr_gemm_desc *d, void *stream);
 /* the kernel family detr_hip_gemm_f32 would launch for this descriptor (no launch): 0 tile engine, 1 streaming kernel, 2 ring kernel (bf16),
