@@ -262,7 +262,10 @@ extern "C" int detr_hip_conv1x1_bwd_fused_bf16(const uint16_t *dy, int64_t ldg, 
     }
     hipLaunchKernelGGL(conv1x1_bwd_fused_bf16_kernel, dim3((unsigned)k.nwg), dim3(BF_THREADS), BF_SMEM, (hipStream_t)stream, k);
     DETR_LAUNCH_CHECK("conv1x1 bwd (fused)");
-    launch_splitk_reduce(workspace, k.nwg, (long long)BF_D1 * BF_D2, BF_D1, BF_D2, dw, lddw, alpha, scale, (hipStream_t)stream, nullptr, nullptr, 0.0f, 0, 0, 0);
+    detr_reduce_desc r = {};
+    r.ws = workspace; r.splits = k.nwg; r.part_stride = (long long)BF_D1 * BF_D2; r.rows = BF_D1; r.cols = BF_D2;
+    r.C = dw; r.ldc = lddw; r.alpha = alpha; r.scale = scale;
+    launch_splitk_reduce(r, (hipStream_t)stream);
     DETR_LAUNCH_CHECK("conv1x1 bwd (fused): reduction");
     return 0;
 }

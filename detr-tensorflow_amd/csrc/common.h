@@ -29,11 +29,9 @@ void set_error(const char *fmt, ...);
         }                                                                               \
     } while (0)
 
-// out[r*ldc + c] += alpha * scale[c] * sum_s ws[s*part_stride + r*cols + c]   (gemm_f32.hip)
-// ts_bm > 0: tile-ordered slabs (gemm_core.h: store_slab_ts), tiles of ts_bm x ts_bn, ts_tiles_n per tile row
-void launch_splitk_reduce(const float *ws, int splits, long long part_stride, int rows, int cols, float *C, long long ldc,
-                          float alpha, const float *scale, hipStream_t stream, const float *rs_ws = nullptr,
-                          float *rs_out = nullptr, float rs_alpha = 1.0f, int ts_bm = 0, int ts_bn = 0, int ts_tiles_n = 0);
+// One deterministic split-K reduction (gemm_f32.hip), described as in include/detr_hip.h:
+// C[r*ldc + c] += alpha * scale[c] * sum_s ws[s*part_stride + r*cols + c]; callers fill a zero-initialised record by field name
+void launch_splitk_reduce(const detr_reduce_desc &r, hipStream_t stream);
 
 // Minimum waves per SIMD requested for the 64x64-tile bf16 GEMM / conv kernels (second __launch_bounds__ argument).  Measured:
 // 6 (<= 64 VGPRs, 8 workgroups / CU instead of 5) buys the HBM-bound short-K GEMMs 1-2 % and costs the long-K ones 10-25 %
@@ -100,6 +98,11 @@ int tune(TuneKey k);
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// f32x3 (compute = 2) tile rules that the GEMM (gemm_pick_tile) and the 3x3 convolution (detr_hip_conv3x3_f32) share: 128 x 128 tiles from
+// this many of them on (DETR_HIP_SPLIT3_T128), and 192 x 128 tiles (1.5 x the work, the same two workgroups per CU = 512 slots) where they
+// need fewer rounds x 1.5 than the t128 tiles of 128 x 128 do
+static inline int x3_t128_threshold() { return tune(T_SPLIT3_T128) > 0 ? tune(T_SPLIT3_T128) : 192; }
+static inline bool x3_t192_fewer_rounds(long long t128, long long t192) { return 3 * ((t192 + 511) / 512) < 2 * ((t128 + 511) / 512); }
 // grid of a grid-stride loop over `total` items: one lane each, at most `cap` workgroups, at least one
 static inline int capped_grid(long long total, int block, int cap) {
     const long long g = (total + block - 1) / block;

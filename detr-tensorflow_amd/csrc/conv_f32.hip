@@ -916,8 +916,13 @@ static void wgrad_run(const ConvWgradArgs &a0, const WgradPlan &p, int taps_y, f
         a.e.atomic = 1;   // accumulate onto dw
     }
     launch(a, dim3((unsigned)(a.tiles_m * a.tiles_n), (unsigned)taps_y, (unsigned)p.split));
-    if (partial) launch_splitk_reduce(ws, p.split, part, 9 * a.Ci, a.Co, dw_final, a.Co, final_e.alpha, final_e.scale, s, nullptr, nullptr, 1.0f,
-                                      ts ? p.tile : 0, ts ? p.tile : 0, a.tiles_n);
+    if (partial) {
+        detr_reduce_desc r = {};
+        r.ws = ws; r.splits = p.split; r.part_stride = part; r.rows = 9 * a.Ci; r.cols = a.Co;
+        r.C = dw_final; r.ldc = a.Co; r.alpha = final_e.alpha; r.scale = final_e.scale; r.rs_alpha = 1.0f;
+        if (ts) { r.ts_bm = r.ts_bn = p.tile; r.ts_tiles_n = a.tiles_n; }
+        launch_splitk_reduce(r, s);
+    }
 }
 
 // per-tap weight gradient on BT x BT tiles (BT = plan.tile)
@@ -1095,14 +1100,12 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
             else launch_conv_tiles(conv_bf16c_for<128, 128, 1>(c, dgrad), 128, 128, c, s);
         } else if (d->compute == 2) {
             // f32x3: 64 x 64 wave tiles (128 x 128 workgroup tiles) are matrix-pipe bound, 32 x 32 ones VALU bound (see gemm_pick_tile)
-            const int lim = tune(T_SPLIT3_T128) > 0 ? tune(T_SPLIT3_T128) : 192;
             // 192 x 128 tiles where 128 x 128 ones overflow the 512 workgroup slots (two per CU) by a few: 256 channels at 50 x 84 are 526 tiles = two
-            // rounds, 350 tiles of 192 rows one round of 1.5 x the work (the rule of gemm_pick_tile's tile 8; DETR_HIP_X3_T192 = 2: never, 1: always)
+            // rounds, 350 tiles of 192 rows one round of 1.5 x the work (common.h: the rule gemm_pick_tile shares; DETR_HIP_X3_T192 = 2: never, 1: always)
             const long long t192 = (long long)cdiv(c.M, 192) * cdiv(c.Cd, 128);
-            const long long r128 = (big + 511) / 512, r192 = (t192 + 511) / 512;
             const bool x3form = x3_form(c);
-            if (force == 3 || (force == 0 && (c.Cd < 128 || big < lim))) launch_conv<64, 64>(c, dgrad, s, true);
-            else if (force == 0 && x3form && tune(T_X3_T192) != 2 && tune(T_X3_T192) != 3 && (tune(T_X3_T192) == 1 || 3 * r192 < 2 * r128)) 
+            if (force == 3 || (force == 0 && (c.Cd < 128 || big < x3_t128_threshold()))) launch_conv<64, 64>(c, dgrad, s, true);
+            else if (force == 0 && x3form && tune(T_X3_T192) != 2 && tune(T_X3_T192) != 3 && (tune(T_X3_T192) == 1 || x3_t192_fewer_rounds(big, t192)))
                 launch_conv_tiles(dgrad ? conv3x3_x3_kernel<192, 128, true> : conv3x3_x3_kernel<192, 128, false>, 192, 128, c, s);
             // 128 x 64 tiles, three workgroups per CU: one 128-channel panel (layer2: 1044 tiles of 128 x 128 = 2.04 rounds -> 290 vs 275 us) and grids
             // that leave CUs with a single 128 x 128 workgroup (layer4: 264 tiles -> 357 vs 338 us); DETR_HIP_X3_T192 = 3: wherever 128 x 128 would run

@@ -14,12 +14,11 @@ namespace detr {
 // Reduction of the split-K partial slabs: 256 threads = (256 / G) float4 outputs x G split groups (the groups stride the
 // split index), combined through LDS in a fixed order.  G = 4 for large outputs; G = 16 for small ones (a 256 x 256
 // weight gradient has only 16 K float4 outputs: with G = 4 the launch is 256 blocks and purely latency bound).
-struct ReduceOne {
-    const float *ws; int splits; long long part_stride; int rows, cols; float *C; long long ldc;
-    float alpha; const float *scale; int vec; const float *rs_ws; float *rs_out; float rs_alpha; int nblocks;
-    int ts_bm, ts_bn, ts_tn;     // tile-ordered slabs (0: row-major)
+// One planned reduction: the caller's record (ts_tiles_n >= 1 from reduce_plan on) plus what the launch adds.
+struct ReduceOne : detr_reduce_desc {
+    int vec;         // the row-major slabs and C take 16-byte accesses
+    int nblocks;     // workgroups this reduction uses (its grid-stride loops run over nblocks, not over the launch's grid)
 };
-struct ReduceGroupArgs { ReduceOne r[GEMM_MAX_GROUP]; };
 
 template <int G>
 __device__ __forceinline__ void splitk_reduce_body(const float *__restrict__ ws, int splits, long long part_stride,
@@ -137,36 +136,24 @@ __device__ __forceinline__ void splitk_reduce_body(const float *__restrict__ ws,
     }
 }
 
-template <int G>
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restrict__ ws, int splits, long long part_stride,
-                                                            int rows, int cols, float *__restrict__ C, long long ldc,
-                                                            float alpha, const float *__restrict__ scale, int vec,
-                                                            const float *__restrict__ rs_ws, float *__restrict__ rs_out,
-                                                            float rs_alpha, int ts_bm, int ts_bn, int ts_tn) {
-    splitk_reduce_body<G>(ws, splits, part_stride, rows, cols, C, ldc, alpha, scale, vec, rs_ws, rs_out, rs_alpha, blockIdx.x,
-                          gridDim.x, ts_bm, ts_bn, ts_tn);
-}
-template <int G>
-__global__ __launch_bounds__(256) void splitk_reduce_group_kernel(ReduceGroupArgs R) {
-    const ReduceOne &r = R.r[blockIdx.y];
-    if ((int)blockIdx.x >= r.nblocks) return;
-    splitk_reduce_body<G>(r.ws, r.splits, r.part_stride, r.rows, r.cols, r.C, r.ldc, r.alpha, r.scale, r.vec, r.rs_ws, r.rs_out,
-                          r.rs_alpha, blockIdx.x, r.nblocks, r.ts_bm, r.ts_bn, r.ts_tn);
-}
-
+// Up to NMAX reductions of one size class in one launch: entry blockIdx.y.  NMAX = 1: a single reduction; GEMM_MAX_GROUP: the members
+// of a grouped GEMM; REDUCE_MANY: the deferred reductions of a backward pass (detr_hip_splitk_reduce_many).
 constexpr int REDUCE_MANY = 16;
-struct ReduceManyArgs { ReduceOne r[REDUCE_MANY]; };
-template <int G>
-__global__ __launch_bounds__(256) void splitk_reduce_many_kernel(ReduceManyArgs R) {
-    const ReduceOne &r = R.r[blockIdx.y];
+template <int NMAX> struct ReduceArgs { ReduceOne r[NMAX]; };
+template <int G, int NMAX>
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(ReduceArgs<NMAX> R) {
+    const ReduceOne &r = R.r[NMAX == 1 ? 0 : blockIdx.y];
     if ((int)blockIdx.x >= r.nblocks) return;
     splitk_reduce_body<G>(r.ws, r.splits, r.part_stride, r.rows, r.cols, r.C, r.ldc, r.alpha, r.scale, r.vec, r.rs_ws, r.rs_out,
-                          r.rs_alpha, blockIdx.x, r.nblocks, r.ts_bm, r.ts_bn, r.ts_tn);
+                          r.rs_alpha, blockIdx.x, r.nblocks, r.ts_bm, r.ts_bn, r.ts_tiles_n);
 }
 
 // `small` (16 instead of 4 split groups per block) is a function of (rows, cols, splits) alone -- the summation order, and with it
 // the bits of the result, must not depend on the slab layout
-static void reduce_plan(ReduceOne &r, bool &small) {
+static ReduceOne reduce_plan(const detr_reduce_desc &d, bool &small) {
+    ReduceOne r;
+    static_cast<detr_reduce_desc &>(r) = d;
+    if (r.ts_tiles_n <= 0) r.ts_tiles_n = 1;
     r.vec = (r.cols % 4 == 0) && (r.ldc % 4 == 0) && (r.part_stride % 4 == 0) && aligned16(r.ws) && aligned16(r.C) &&
             (!r.scale || aligned16(r.scale));
     const bool ts = r.ts_bm > 0;
@@ -178,97 +165,101 @@ static void reduce_plan(ReduceOne &r, bool &small) {
     if (grid > 8192) grid = 8192;
     if (grid < 1) grid = 1;
     r.nblocks = (int)grid;
+    return r;
 }
 
-void launch_splitk_reduce(const float *ws, int splits, long long part_stride, int rows, int cols, float *C, long long ldc,
-                          float alpha, const float *scale, hipStream_t stream, const float *rs_ws, float *rs_out,
-                          float rs_alpha, int ts_bm, int ts_bn, int ts_tiles_n) {
-    ReduceOne r;
-    r.ws = ws; r.splits = splits; r.part_stride = part_stride; r.rows = rows; r.cols = cols; r.C = C; r.ldc = ldc;
-    r.alpha = alpha; r.scale = scale; r.rs_ws = rs_ws; r.rs_out = rs_out; r.rs_alpha = rs_alpha;
-    r.ts_bm = ts_bm; r.ts_bn = ts_bn; r.ts_tn = ts_tiles_n > 0 ? ts_tiles_n : 1;
+// One launch for the n <= NMAX planned reductions r[0..n), all of the size class `small`: grid.x is the largest of their block counts
+// (an entry's surplus blocks leave at once), the unused slots repeat entry 0.
+template <int NMAX>
+static void launch_reduce_list(const ReduceOne *r, int n, bool small, hipStream_t s) {
+    ReduceArgs<NMAX> R;
+    unsigned rx = 1;
+    for (int i = 0; i < NMAX; ++i) {
+        R.r[i] = r[i < n ? i : 0];
+        if ((unsigned)R.r[i].nblocks > rx) rx = (unsigned)R.r[i].nblocks;
+    }
+    const dim3 grid(rx, (unsigned)n), block(256);
+    if (small) hipLaunchKernelGGL((splitk_reduce_kernel<16, NMAX>), grid, block, 0, s, R);
+    else hipLaunchKernelGGL((splitk_reduce_kernel<4, NMAX>), grid, block, 0, s, R);
+}
+
+void launch_splitk_reduce(const detr_reduce_desc &d, hipStream_t stream) {
     bool small;
-    reduce_plan(r, small);
-    if (small)
-        hipLaunchKernelGGL(splitk_reduce_kernel<16>, dim3((unsigned)r.nblocks), dim3(256), 0, stream, ws, splits, part_stride, rows, cols,
-                           C, ldc, alpha, scale, r.vec, rs_ws, rs_out, rs_alpha, r.ts_bm, r.ts_bn, r.ts_tn);
-    else
-        hipLaunchKernelGGL(splitk_reduce_kernel<4>, dim3((unsigned)r.nblocks), dim3(256), 0, stream, ws, splits, part_stride, rows, cols,
-                           C, ldc, alpha, scale, r.vec, rs_ws, rs_out, rs_alpha, r.ts_bm, r.ts_bn, r.ts_tn);
+    const ReduceOne r = reduce_plan(d, small);
+    launch_reduce_list<1>(&r, 1, small, stream);
 }
 
-template <int BM, int BN, int WGM, int WGN>
-static int launch_cfg(const GemmArgs &g, int batch, hipStream_t s, bool ak, bool bk) {
-    GemmArgs a = g;
-    a.tiles_m = cdiv(g.M, BM);
-    a.tiles_n = cdiv(g.N, BN);
-    dim3 grid((unsigned)(a.tiles_m * a.tiles_n), 1, (unsigned)(batch * g.split_k));
-    dim3 block(GEMM_THREADS);
-    if (ak && bk) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WGM, WGN, true, true>), grid, block, 0, s, a);
-    else if (ak && !bk) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WGM, WGN, true, false>), grid, block, 0, s, a);
-    else if (!ak && bk) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WGM, WGN, false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WGM, WGN, false, false>), grid, block, 0, s, a);
-    return 0;
+// ---- kernel selection: a kernel family is a struct whose get<AK, BKC>() names one instantiation; by_layout picks the operand layouts ----
+typedef void (*GemmKernel)(GemmArgs);
+typedef void (*GemmGroupKernel)(GemmGroupArgs);
+
+template <class F>
+static auto by_layout(bool ak, bool bk) {
+    return ak ? (bk ? F::template get<true, true>() : F::template get<true, false>())
+              : (bk ? F::template get<false, true>() : F::template get<false, false>());
 }
+
+template <int BM, int BN, int WGM, int WGN> struct F32Kernels {
+    template <bool AK, bool BKC> static GemmKernel get() { return gemm_f32_kernel<BM, BN, WGM, WGN, AK, BKC>; }
+};
+template <int BM, int BN, bool DB> struct X3Kernels {
+    template <bool AK, bool BKC> static GemmKernel get() {
+        // 192 x 128: K-contiguous A only (the transpose-read image of an MN-contiguous operand needs a power-of-two block count)
+        if constexpr (BM == 192 && !AK) return nullptr;
+        else return gemm_x3_kernel<BM, BN, AK, BKC, DB>;
+    }
+};
+template <int BM, int BN, bool A16, bool B16> struct Bf16Kernels {
+    template <bool AK, bool BKC> static GemmKernel get() { return gemm_bf16c_kernel<BM, BN, 2, 2, AK, BKC, A16, B16>; }
+};
+template <int BM, int BN> struct Bf16K64Kernels {
+    template <bool AK, bool BKC> static GemmKernel get() { return gemm_bf16c_k64_kernel<BM, BN, 2, 2, AK, BKC>; }
+};
+struct GroupF32Kernels {
+    template <bool AK, bool BKC> static GemmGroupKernel get() { return gemm_f32_group_kernel<64, 64, 2, 2, AK, BKC>; }
+};
+struct GroupX3Kernels {
+    template <bool AK, bool BKC> static GemmGroupKernel get() { return gemm_x3_group_kernel<64, 64, AK, BKC>; }
+};
+template <bool A16, bool B16> struct GroupBf16Kernels {
+    template <bool AK, bool BKC> static GemmGroupKernel get() { return gemm_bf16c_group_kernel<64, 64, 2, 2, AK, BKC, A16, B16>; }
+};
 
 // compute = 2 on the shapes of gemm_split3_shape: the f32x3 kernel (gemm_x3.h)
+// DETR_HIP_X3_DB: 1 = double-buffered LDS (in-wave overlap); 0 / 2 = single-buffered, which measured faster on every shape of the step
+// (profiles/r06_micro_split3.txt: two workgroups per CU overlap better than one with two buffers); 192 x 128 is single-buffered only
 template <int BM, int BN>
-static int launch_x3(const GemmArgs &g, int batch, hipStream_t s, bool ak, bool bk) {
-    GemmArgs a = g;
-    a.tiles_m = cdiv(g.M, BM);
-    a.tiles_n = cdiv(g.N, BN);
-    dim3 grid((unsigned)(a.tiles_m * a.tiles_n), 1, (unsigned)(batch * g.split_k));
-    dim3 block(GEMM_THREADS);
-    // DETR_HIP_X3_DB: 1 = double-buffered LDS (in-wave overlap); 0 / 2 = single-buffered, which measured faster on every shape of the step
-    // (profiles/r06_micro_split3.txt: two workgroups per CU overlap better than one with two buffers)
-    const bool db = tune(T_X3_DB) == 1;
-    if constexpr (BM == 192) {       // (K-contiguous A only: the transpose-read image of an MN-contiguous operand needs a power-of-two block count)
-        if (bk) hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, true, true, false>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, true, false, false>), grid, block, 0, s, a);
-    } else {
-#define DETR_X3_LAUNCH(DB_)                                                                                              \
-    do {                                                                                                                 \
-        if (ak && bk) hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, true, true, DB_>), grid, block, 0, s, a);               \
-        else if (ak && !bk) hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, true, false, DB_>), grid, block, 0, s, a);        \
-        else if (!ak && bk) hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, false, true, DB_>), grid, block, 0, s, a);        \
-        else hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, false, false, DB_>), grid, block, 0, s, a);                      \
-    } while (0)
-        if (db) {
-            DETR_X3_LAUNCH(true);
-        } else DETR_X3_LAUNCH(false);
+static GemmKernel gemm_x3_for(bool ak, bool bk) {
+    if constexpr (BM != 192) {
+        if (tune(T_X3_DB) == 1) return by_layout<X3Kernels<BM, BN, true>>(ak, bk);
     }
-#undef DETR_X3_LAUNCH
-    return 0;
+    return by_layout<X3Kernels<BM, BN, false>>(ak, bk);
 }
 
-template <int BM, int BN, int WGM, int WGN>
-static int launch_cfg_bf16(const GemmArgs &g, int batch, hipStream_t s, bool ak, bool bk, int deep = 0) {
-    GemmArgs a = g;
-    a.tiles_m = cdiv(g.M, BM);
-    a.tiles_n = cdiv(g.N, BN);
-    dim3 grid((unsigned)(a.tiles_m * a.tiles_n), 1, (unsigned)(batch * g.split_k));
-    dim3 block(GEMM_THREADS);
+// k64: the 64-deep K tiles of the all-bf16 operands (64 x 64 and 128 x 128 tiles only)
+template <int BM, int BN>
+static GemmKernel gemm_bf16_for(bool ak, bool bk, bool a16, bool b16, bool k64) {
     if constexpr ((BM == 64 && BN == 64) || (BM == 128 && BN == 128)) {
-        if (deep && g.a16 && g.b16) {
-            if (ak && bk) hipLaunchKernelGGL((gemm_bf16c_k64_kernel<BM, BN, WGM, WGN, true, true>), grid, block, 0, s, a);
-            else if (ak && !bk) hipLaunchKernelGGL((gemm_bf16c_k64_kernel<BM, BN, WGM, WGN, true, false>), grid, block, 0, s, a);
-            else if (!ak && bk) hipLaunchKernelGGL((gemm_bf16c_k64_kernel<BM, BN, WGM, WGN, false, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((gemm_bf16c_k64_kernel<BM, BN, WGM, WGN, false, false>), grid, block, 0, s, a);
-            return 0;
-        }
+        if (k64 && a16 && b16) return by_layout<Bf16K64Kernels<BM, BN>>(ak, bk);
     }
-#define DETR_BF16_LAUNCH(A16_, B16_)                                                                                          \
-    do {                                                                                                                          \
-        if (ak && bk) hipLaunchKernelGGL((gemm_bf16c_kernel<BM, BN, WGM, WGN, true, true, A16_, B16_>), grid, block, 0, s, a);        \
-        else if (ak && !bk) hipLaunchKernelGGL((gemm_bf16c_kernel<BM, BN, WGM, WGN, true, false, A16_, B16_>), grid, block, 0, s, a); \
-        else if (!ak && bk) hipLaunchKernelGGL((gemm_bf16c_kernel<BM, BN, WGM, WGN, false, true, A16_, B16_>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((gemm_bf16c_kernel<BM, BN, WGM, WGN, false, false, A16_, B16_>), grid, block, 0, s, a);               \
-    } while (0)
-    if (g.a16 && g.b16) DETR_BF16_LAUNCH(true, true);
-    else if (g.a16) DETR_BF16_LAUNCH(true, false);
-    else if (g.b16) DETR_BF16_LAUNCH(false, true);
-    else DETR_BF16_LAUNCH(false, false);
-#undef DETR_BF16_LAUNCH
+    if (a16) return b16 ? by_layout<Bf16Kernels<BM, BN, true, true>>(ak, bk) : by_layout<Bf16Kernels<BM, BN, true, false>>(ak, bk);
+    return b16 ? by_layout<Bf16Kernels<BM, BN, false, true>>(ak, bk) : by_layout<Bf16Kernels<BM, BN, false, false>>(ak, bk);
+}
+
+static GemmGroupKernel gemm_group_for(bool bf16c, bool split3, bool ak, bool bk, bool a16, bool b16) {
+    if (!bf16c) return split3 ? by_layout<GroupX3Kernels>(ak, bk) : by_layout<GroupF32Kernels>(ak, bk);
+    if (a16) return b16 ? by_layout<GroupBf16Kernels<true, true>>(ak, bk) : by_layout<GroupBf16Kernels<true, false>>(ak, bk);
+    return b16 ? by_layout<GroupBf16Kernels<false, true>>(ak, bk) : by_layout<GroupBf16Kernels<false, false>>(ak, bk);
+}
+
+// one workgroup per (bm x bn tile, batch member x split)
+static int launch_gemm_tiles(GemmKernel kernel, int bm, int bn, const GemmArgs &g, int batch, hipStream_t s) {
+    DETR_REQUIRE(kernel != nullptr && bm > 0 && bn > 0, "gemm: no kernel for this tile, precision and operand layout");
+    GemmArgs a = g;
+    a.tiles_m = cdiv(g.M, bm);
+    a.tiles_n = cdiv(g.N, bn);
+    const dim3 grid((unsigned)(a.tiles_m * a.tiles_n), 1, (unsigned)(batch * g.split_k));
+    hipLaunchKernelGGL(kernel, grid, dim3(GEMM_THREADS), 0, s, a);
     return 0;
 }
 
@@ -276,23 +267,69 @@ static int launch_cfg_bf16(const GemmArgs &g, int batch, hipStream_t s, bool ak,
 
 using namespace detr;
 
+// Tile ids.  The values are the interface of DETR_HIP_GEMM_TILE (gemm_pick_tile maps `force` to them) and stay as they are.
+enum GemmTile {
+    TILE_64x64 = 0,
+    TILE_128x128 = 1,
+    TILE_128x64 = 2,
+    TILE_128x32 = 3,             // exact fp32 only (N <= 32)
+    TILE_WIDE = 4,               // 64 x 256 (exact fp32) / 64 x 128 (bf16)
+    TILE_256x64 = 5,             // exact fp32 only
+    TILE_RING_128x256 = 6,       // ring weight gradient only (bf16; DETR_HIP_RING_WTILE)
+    TILE_RING_256x128 = 7,
+    TILE_X3_192x128 = 8          // f32x3 only, unsplit
+};
+
 // Host side of one GEMM: validation + kernel arguments (gemm_prepare), then the launch(es) (gemm_launch).  The grouped entry
 // point prepares every member the same way and, when they share one kernel variant, issues ONE launch for all of them.
 struct GemmPlan {
     GemmArgs g;
     int batch, split;
     bool ak, bk, bf16c, partial;
-    bool split3;              // compute = 2: fp32 storage and accuracy on the bf16 matrix pipe (3-way operand split; 64x64 / 128x128 tiles)
-    int deep;                 // K-tile depth of the all-bf16 variants: 0 = 32, 1 = 64, 2 = 128 (64x64 tiles only)
-    int tile;                 // 0: 64x64, 1: 128x128, 2: 128x64, 3: 128x32, 4: 64x256 (fp32) / 64x128 (bf16), 5: 256x64
+    bool split3;              // compute = 2: fp32 storage and accuracy on the bf16 matrix pipe (3-way operand split; gemm_x3.h)
+    bool deep;                // the all-bf16 variants walk 64-deep K tiles instead of 32-deep ones (64x64 / 128x128 tiles only)
+    GemmTile tile;
     long long part;           // floats per split slab (row-major: M*N; tile-ordered: the padded tile grid)
     int ts_bm, ts_bn, ts_tn;  // tile-ordered slabs (0: row-major)
     EpiArgs final_e;
     const detr_gemm_desc *d;
 };
 
-// Tile shape of a GEMM: 0: 64x64, 1: 128x128, 2: 128x64, 3: 128x32, 4: 64x256 (fp32) / 64x128 (bf16), 5: 256x64.  Shared by the
-// launch path and by the scratch-size query (the tile-ordered split-K slabs are padded to whole tiles).
+// The one table of tile shapes: BM x BN and the wave grid of a tile id for a precision (bf16c: compute = 1; otherwise the exact fp32 and
+// the f32x3 kernels), shared by the launch path and by the scratch-size query.  slab_ts: the kernel can write tile-ordered split-K slabs
+// (store_slab_ts / slab_ts_unit: 2 x 2 wave grids; the 4 x 1 / 1 x 4 grids of the narrow fp32 tiles keep row-major slabs).  A tile the
+// precision does not have answers bm = bn = 0.
+struct TileDims { int bm, bn, wgm, wgn; bool slab_ts; };
+static TileDims gemm_tile_dims(bool bf16c, GemmTile tile) {
+    switch (tile) {
+        case TILE_64x64: return {64, 64, 2, 2, true};
+        case TILE_128x128: return {128, 128, 2, 2, true};
+        case TILE_128x64: return {128, 64, 2, 2, true};
+        case TILE_128x32: if (!bf16c) return {128, 32, 4, 1, false}; break;
+        case TILE_WIDE: if (bf16c) return {64, 128, 2, 2, true}; return {64, 256, 1, 4, false};
+        case TILE_256x64: if (!bf16c) return {256, 64, 4, 1, false}; break;
+        case TILE_RING_128x256: if (bf16c) return {128, 256, 2, 2, true}; break;
+        case TILE_RING_256x128: if (bf16c) return {256, 128, 2, 2, true}; break;
+        case TILE_X3_192x128: if (!bf16c) return {192, 128, 2, 2, true}; break;
+    }
+    return {0, 0, 0, 0, false};
+}
+// Split-K slab layout: tile-ordered when the reduce launch can keep its 16-byte form (the same conditions as its row-major
+// `vec` path: the summation order -- the bits of the result -- must not depend on the layout).  DETR_HIP_SLAB_TS=2: row-major.
+static bool gemm_slab_ts(const detr_gemm_desc *d, int split, int batch, GemmTile tile, int &bm, int &bn) {
+    const TileDims t = gemm_tile_dims(d->compute == 1, tile);
+    bm = t.bm; bn = t.bn;
+    return t.slab_ts && split > 1 && batch == 1 && d->N % 4 == 0 && d->ldc % 4 == 0 && aligned16(d->C) && (!d->scale || aligned16(d->scale)) &&
+           tune(T_SLAB_TS) != 2;
+}
+// The descriptor half of the ring weight gradient's predicate (gemm_ring.h: gemm_ring_wgrad_kernel): MN-contiguous bf16 operands in 16-byte
+// requests, no fused row sums; DETR_HIP_GEMM_RING = 2 / 3 switch the form off.  gemm_route adds what the plan decides (tile, split, slabs).
+static bool gemm_ring_wgrad_operands(const detr_gemm_desc *d) {
+    return d->compute == 1 && d->a_dtype == 1 && d->b_dtype == 1 && !d->a_kcontig && !d->b_kcontig && !d->rowsum_a && d->M % 8 == 0 &&
+           d->N % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && aligned16(d->A) && aligned16(d->B) && tune(T_GEMM_RING) != 2 &&
+           tune(T_GEMM_RING) != 3;
+}
+
 // compute = 2 (f32x3): the shapes whose products go through the split kernel (gemm_core.h: mma_ktile_split3).  The operand split is VALU work
 // per fragment, so the narrow (N <= 64: 0.77x) and the short-K (K <= 128: 0.92-0.96x) 1x1-convolution GEMMs and the 64-row weight gradients
 // (0.85x) keep the exact kernel (scripts/micro_split3.py, profiles/r06_micro_split3.txt) -- both are fp32-accurate, the mode only decides
@@ -300,10 +337,10 @@ struct GemmPlan {
 static bool gemm_split3_shape(const detr_gemm_desc *d) {
     return d->compute == 2 && d->N > 32 && (tune(T_SPLIT3_ALL) == 1 || (d->N >= 128 && d->K >= 256 && d->M >= 128));
 }
-static int gemm_pick_tile(const detr_gemm_desc *d, int split, int batch) {
+static GemmTile gemm_pick_tile(const detr_gemm_desc *d, int split, int batch) {
     const bool bf16c = d->compute == 1;
     const int force = tune(T_GEMM_TILE);     // tuning hook (scripts/tune_gemm.py); 0 = heuristic
-    int tile = 0;
+    GemmTile tile = TILE_64x64;
     if (bf16c) {
         // measured (profiles/tune_bf16_r1c.txt, buffer-descriptor loaders + transpose-read LDS images): the 64x64 tile
         // (7-8 waves/SIMD) wins every non-split shape and the short reductions; 128x128 (3 waves/SIMD, 4x the operand
@@ -322,75 +359,51 @@ static int gemm_pick_tile(const detr_gemm_desc *d, int split, int batch) {
         const bool big_plain = (d->K >= 1024 && t128 >= 512) || (d->K >= 512 && d->N >= 512 && t128 >= 1024) ||
                                (d->K >= 512 && d->N >= 256 && t128 >= 2048);
         const bool small = (split > 1) ? !big_split : !big_plain;
-        if (force == 2) tile = 2;
-        else if (force == 5) tile = 4;
-        else if (force == 3 || (force == 0 && small)) tile = 0;
-        else if (force == 0 && split > 1 && d->M <= 64) tile = 4;     // 64 output rows: half of a 128-row tile would be padding (M64 N256 K534400: 84 -> 74 us)
-        else tile = 1;
+        if (force == 2) tile = TILE_128x64;
+        else if (force == 5) tile = TILE_WIDE;
+        else if (force == 3 || (force == 0 && small)) tile = TILE_64x64;
+        else if (force == 0 && split > 1 && d->M <= 64) tile = TILE_WIDE;     // 64 output rows: half of a 128-row tile would be padding (M64 N256 K534400: 84 -> 74 us)
+        else tile = TILE_128x128;
         // ring weight gradient (gemm_ring.h) on wider tiles -- experiment hook DETR_HIP_RING_WTILE: 1 = 128 x 256, 2 = 256 x 128
-        // (the FULL predicate of the ring weight gradient in gemm_launch -- ADVICE r5: a tile only that kernel has must not be handed to a
-        //  launch the kernel will not take, nor size the slab scratch for it; the slab form itself is checked again there)
-        if (tile == 1 && split > 1 && batch == 1 && d->a_dtype == 1 && d->b_dtype == 1 && !d->a_kcontig && !d->b_kcontig && !d->rowsum_a &&
-            tune(T_GEMM_RING) != 2 && tune(T_GEMM_RING) != 3 && tune(T_SLAB_TS) != 2 && d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 &&
-            d->ldb % 8 == 0 && aligned16(d->A) && aligned16(d->B) && aligned16(d->C) && d->ldc % 4 == 0 && (!d->scale || aligned16(d->scale))) {
+        // (the FULL predicate of the ring weight gradient in gemm_route -- ADVICE r5: a tile only that kernel has must not be handed to a
+        //  launch the kernel will not take, nor size the slab scratch for it: the operands' half, and a split, unbatched output that can take
+        //  tile-ordered slabs; whether the workspace holds them is checked again there)
+        int bm, bn;
+        if (tile == TILE_128x128 && gemm_ring_wgrad_operands(d) && gemm_slab_ts(d, split, batch, tile, bm, bn)) {
             const int wt = tune(T_RING_WTILE);
-            if (wt == 1 && d->N >= 256) tile = 6;
-            else if (wt == 2 && d->M >= 256) tile = 7;
+            if (wt == 1 && d->N >= 256) tile = TILE_RING_128x256;
+            else if (wt == 2 && d->M >= 256) tile = TILE_RING_256x128;
         }
     } else if (gemm_split3_shape(d)) {
         // f32x3 (mma_ktile_split3): a wave's operand split costs VALU time per FRAGMENT, its 6 MFMAs per fragment PAIR -- 64 x 64 wave
         // tiles (128 x 128 workgroup tiles) are matrix-pipe bound where 32 x 32 ones are VALU bound; small grids keep the 64 x 64 tile
         const long long t128 = (long long)cdiv(d->M, 128) * cdiv(d->N, 128) * batch * split;
-        const int lim = tune(T_SPLIT3_T128) > 0 ? tune(T_SPLIT3_T128) : 192;
-        if (force == 1 || (force == 0 && t128 >= lim)) tile = 1;
-        else if (force == 2) tile = 2;        // (128 x 64: three workgroups per CU)
-        else tile = 0;
+        if (force == 1 || (force == 0 && t128 >= x3_t128_threshold())) tile = TILE_128x128;
+        else if (force == 2) tile = TILE_128x64;        // (128 x 64: three workgroups per CU)
+        else tile = TILE_64x64;
         // Tile-count quantisation (profiles/r06_ab_results.txt #9): two 128 x 128 workgroups fit a CU = 512 slots, and M33600 N256 is 526 tiles -- two
         // rounds, the second with 14 workgroups.  192 x 128 tiles (tile id 8: 1.5 x the work per workgroup, the same two per CU; K-contiguous A,
         // unsplit, no fused row sums) take the GEMM when they need fewer rounds x 1.5.  DETR_HIP_X3_T192 = 2: never, 1: wherever eligible.
-        if (tile == 1 && force == 0 && split == 1 && batch == 1 && d->a_kcontig && !d->rowsum_a && tune(T_X3_T192) != 2) {
-            const long long slots = 512;
+        if (tile == TILE_128x128 && force == 0 && split == 1 && batch == 1 && d->a_kcontig && !d->rowsum_a && tune(T_X3_T192) != 2) {
             const long long t192 = (long long)cdiv(d->M, 192) * cdiv(d->N, 128);
-            const long long r128 = (t128 + slots - 1) / slots, r192 = (t192 + slots - 1) / slots;
-            if (tune(T_X3_T192) == 1 || 3 * r192 < 2 * r128) tile = 8;
+            if (tune(T_X3_T192) == 1 || x3_t192_fewer_rounds(t128, t192)) tile = TILE_X3_192x128;
         }
         // 128 x 64 tiles (three workgroups per CU = 768 slots) where the 128 x 128 grid is just over a whole number of rounds (M8400 N2048: 1056 tiles = 2.06
         // rounds: 142 -> 135 us, 88.7 -> 77.9 us at K = 256) or a short-K grid fills half the chip (M8400 N512 K256: 34.7 -> 30.4 us)
-        if (tile == 1 && force == 0 && split == 1 && batch == 1 && tune(T_X3_T192) != 2 && d->M >= 4096) {
+        if (tile == TILE_128x128 && force == 0 && split == 1 && batch == 1 && tune(T_X3_T192) != 2 && d->M >= 4096) {
             const long long over = t128 % 512;
-            if ((t128 > 512 && over > 0 && over <= 128) || (t128 <= 384 && d->K <= 512)) tile = 2;
+            if ((t128 > 512 && over > 0 && over <= 128) || (t128 <= 384 && d->K <= 512)) tile = TILE_128x64;
         }
-    } else if (force == 1) tile = 1;
-    else if (force == 2) tile = 2;
-    else if (force == 3) tile = 0;
-    else if (force == 4) tile = 3;
-    else if (force == 5) tile = 4;
-    else if (force == 6) tile = 5;
-    else if (d->N <= 32) tile = 3;
-    else tile = 0;      // measured (profiles/tune_r1.txt): 64x64 (8 waves/SIMD) beats 128x64 by 2-10 % and 128x128 by 15-50 % in fp32
+    } else if (force == 1) tile = TILE_128x128;
+    else if (force == 2) tile = TILE_128x64;
+    else if (force == 3) tile = TILE_64x64;
+    else if (force == 4) tile = TILE_128x32;
+    else if (force == 5) tile = TILE_WIDE;
+    else if (force == 6) tile = TILE_256x64;
+    else if (d->N <= 32) tile = TILE_128x32;
+    else tile = TILE_64x64;      // measured (profiles/tune_r1.txt): 64x64 (8 waves/SIMD) beats 128x64 by 2-10 % and 128x128 by 15-50 % in fp32
     return tile;
 }
-// BM x BN of a tile id; ts_ok: the kernel runs a 2 x 2 wave grid (store_slab_ts / slab_ts_unit)
-static void gemm_tile_dims(bool bf16c, int tile, int &bm, int &bn, bool &ts_ok) {
-    ts_ok = true;
-    if (tile == 1) { bm = 128; bn = 128; }
-    else if (tile == 8 && !bf16c) { bm = 192; bn = 128; }         // (f32x3, unsplit only)
-    else if (tile == 6 && bf16c) { bm = 128; bn = 256; }         // (ring weight gradient only)
-    else if (tile == 7 && bf16c) { bm = 256; bn = 128; }
-    else if (tile == 2) { bm = 128; bn = 64; }
-    else if (tile == 4 && bf16c) { bm = 64; bn = 128; }
-    else if (tile == 0) { bm = 64; bn = 64; }
-    else { bm = bn = 0; ts_ok = false; }          // fp32 128x32 / 64x256 / 256x64: 4x1 / 1x4 wave grids keep row-major slabs
-}
-// Split-K slab layout: tile-ordered when the reduce launch can keep its 16-byte form (the same conditions as its row-major
-// `vec` path: the summation order -- the bits of the result -- must not depend on the layout).  DETR_HIP_SLAB_TS=2: row-major.
-static bool gemm_slab_ts(const detr_gemm_desc *d, int split, int batch, int tile, int &bm, int &bn) {
-    bool ok;
-    gemm_tile_dims(d->compute == 1, tile, bm, bn, ok);
-    return ok && split > 1 && batch == 1 && d->N % 4 == 0 && d->ldc % 4 == 0 && aligned16(d->C) && (!d->scale || aligned16(d->scale)) &&
-           tune(T_SLAB_TS) != 2;
-}
-
 // split count a GEMM really runs with: no empty splits (recomputed from the K tiles each split gets)
 static int gemm_effective_split(const detr_gemm_desc *d) {
     int split = d->split_k > 1 ? d->split_k : 1;
@@ -504,7 +517,7 @@ static int gemm_prepare(const detr_gemm_desc *d, GemmPlan &p) {
                  "gemm: an M-contiguous bf16 A operand needs lda %% 8 == 0, M %% 8 == 0 and a 16-byte aligned base (16-byte requests)");
     DETR_REQUIRE(!(bf16c && d->b_dtype == 1 && !bk) || (d->ldb % 8 == 0 && d->N % 8 == 0 && aligned16(d->B)),
                  "gemm: an N-contiguous bf16 B operand needs ldb %% 8 == 0, N %% 8 == 0 and a 16-byte aligned base (16-byte requests)");
-    const int tile = gemm_pick_tile(d, split, batch);
+    const GemmTile tile = gemm_pick_tile(d, split, batch);
     // deterministic split-K: partial slabs in the caller's workspace.  Tile-ordered slabs (whole tiles: a little more scratch than
     // split*M*N -- detr_hip_workspace_bytes_gemm reports it) when the workspace holds them, row-major slabs when it only holds
     // the documented split*M*N floats, fp32 atomics without a workspace.
@@ -551,11 +564,11 @@ static int gemm_prepare(const detr_gemm_desc *d, GemmPlan &p) {
     {
         const int k64 = tune(T_GEMM_K64);
         const int per_split = cdiv(d->K, split);
-        p.deep = (bf16c && g.a16 && g.b16 && (tile == 0 || tile == 1) && k64 != 2 &&
-                  (k64 == 1 || (per_split >= 512 && (tile == 0 || split > 1)))) ? 1 : 0;
+        p.deep = bf16c && g.a16 && g.b16 && (tile == TILE_64x64 || tile == TILE_128x128) && k64 != 2 &&
+                 (k64 == 1 || (per_split >= 512 && (tile == TILE_64x64 || split > 1)));
     }
     p.batch = batch; p.split = split; p.ak = ak; p.bk = bk; p.bf16c = bf16c; p.partial = partial; p.tile = tile;
-    p.split3 = gemm_split3_shape(d) && (tile == 0 || tile == 1 || tile == 2 || tile == 8);
+    p.split3 = gemm_split3_shape(d) && (tile == TILE_64x64 || tile == TILE_128x128 || tile == TILE_128x64 || tile == TILE_X3_192x128);
     p.part = part; p.final_e = final_e; p.d = d;
     return 0;
 }
@@ -674,71 +687,112 @@ static bool gemm_ring_f32_eligible(const GemmPlan &p, RingPlan &rp) {
     return gemm_ring_f32_plan(d->M, d->N, d->K, rp);
 }
 
-static int gemm_launch(const GemmPlan &p, hipStream_t s) {
-    const GemmArgs &g = p.g;
+// Split-K weight gradients of the backbone's 1x1 convolutions on 128 x 128 tiles (128 x 256 / 256 x 128: DETR_HIP_RING_WTILE): the 8-wave
+// ring form (gemm_ring.h; bit-identical slabs).  Needs the tile-ordered slabs, that is a workspace of detr_hip_workspace_bytes_gemm bytes.
+static bool gemm_ring_wgrad_eligible(const GemmPlan &p) {
+    return (p.tile == TILE_128x128 || p.tile == TILE_RING_128x256 || p.tile == TILE_RING_256x128) && p.batch == 1 && p.split > 1 &&
+           p.g.slab_ts && gemm_ring_wgrad_operands(p.d);
+}
+
+// The kernel family of a prepared GEMM; the values are what detr_hip_gemm_family promises (include/detr_hip.h).
+enum GemmRoute { ROUTE_TILE = 0, ROUTE_STREAM = 1, ROUTE_RING = 2, ROUTE_RING_F32 = 3, ROUTE_LN = 4, ROUTE_RING_WGRAD = 5 };
+
+// THE routing decision, in this order: fused LayerNorm; the ring kernel where it is eligible (in front of the streaming kernel, unless
+// DETR_HIP_GEMM_STREAM=3, which takes the ring kernel out so that the streaming kernel keeps its K = 256 shapes); the streaming kernel;
+// the fp32 ring kernel; the ring weight gradient; otherwise the 4-wave tile engine.  rp: the plan of the ring kernel that was chosen.
+static GemmRoute gemm_route(const GemmPlan &p, RingPlan &rp) {
+    if (p.d->ln_y) return ROUTE_LN;
+    const bool ring_first = tune(T_GEMM_STREAM) != 3 && gemm_ring_eligible(p, rp);
+    if (!ring_first && gemm_stream_eligible(p)) return ROUTE_STREAM;
+    if (ring_first) return ROUTE_RING;
+    if (gemm_ring_f32_eligible(p, rp)) return ROUTE_RING_F32;
+    if (gemm_ring_wgrad_eligible(p)) return ROUTE_RING_WGRAD;
+    return ROUTE_TILE;
+}
+
+// the deterministic split-K reduction a prepared GEMM (p.partial) leaves behind
+static detr_reduce_desc gemm_reduce_desc(const GemmPlan &p) {
     const detr_gemm_desc *d = p.d;
-    const int batch = p.batch;
+    detr_reduce_desc r = {};
+    r.ws = d->workspace; r.splits = p.split; r.part_stride = p.part; r.rows = d->M; r.cols = d->N;
+    r.C = d->C; r.ldc = d->ldc; r.alpha = p.final_e.alpha; r.scale = p.final_e.scale;
+    r.rs_ws = d->rowsum_a ? d->workspace + (long long)p.split * p.part : nullptr;
+    r.rs_out = d->rowsum_a; r.rs_alpha = d->rowsum_alpha;
+    r.ts_bm = p.ts_bm; r.ts_bn = p.ts_bn; r.ts_tiles_n = p.ts_tn;
+    return r;
+}
+
+// the tile engine's kernel for a plan: the compile-time half of the tile table (gemm_tile_dims has the numbers)
+static GemmKernel gemm_tile_kernel(const GemmPlan &p) {
     const bool ak = p.ak, bk = p.bk;
-    if (d->ln_y) return gemm_ln_launch(p, s);
-    {
-        RingPlan rp;
-        const bool ring_first = tune(T_GEMM_STREAM) != 3 && gemm_ring_eligible(p, rp);      // (DETR_HIP_GEMM_STREAM=3: the streaming kernel keeps its K = 256 shapes)
-        if (!ring_first && gemm_stream_eligible(p)) {
+    if (p.bf16c) {
+        const bool a16 = p.g.a16, b16 = p.g.b16;
+        switch (p.tile) {
+            case TILE_64x64: return gemm_bf16_for<64, 64>(ak, bk, a16, b16, p.deep);
+            case TILE_128x128: return gemm_bf16_for<128, 128>(ak, bk, a16, b16, p.deep);
+            case TILE_128x64: return gemm_bf16_for<128, 64>(ak, bk, a16, b16, false);
+            case TILE_WIDE: return gemm_bf16_for<64, 128>(ak, bk, a16, b16, false);
+            default: return nullptr;
+        }
+    }
+    if (p.split3) {
+        switch (p.tile) {
+            case TILE_64x64: return gemm_x3_for<64, 64>(ak, bk);
+            case TILE_128x128: return gemm_x3_for<128, 128>(ak, bk);
+            case TILE_128x64: return gemm_x3_for<128, 64>(ak, bk);
+            case TILE_X3_192x128: return gemm_x3_for<192, 128>(ak, bk);
+            default: return nullptr;
+        }
+    }
+    switch (p.tile) {
+        case TILE_64x64: return by_layout<F32Kernels<64, 64, 2, 2>>(ak, bk);
+        case TILE_128x128: return by_layout<F32Kernels<128, 128, 2, 2>>(ak, bk);
+        case TILE_128x64: return by_layout<F32Kernels<128, 64, 2, 2>>(ak, bk);
+        case TILE_128x32: return by_layout<F32Kernels<128, 32, 4, 1>>(ak, bk);
+        case TILE_WIDE: return by_layout<F32Kernels<64, 256, 1, 4>>(ak, bk);
+        case TILE_256x64: return by_layout<F32Kernels<256, 64, 4, 1>>(ak, bk);
+        default: return nullptr;
+    }
+}
+
+static int gemm_launch(const GemmPlan &p, hipStream_t s) {
+    const detr_gemm_desc *d = p.d;
+    RingPlan rp;
+    switch (gemm_route(p, rp)) {
+        case ROUTE_LN: return gemm_ln_launch(p, s);
+        case ROUTE_STREAM:
             gemm_stream_launch(p, s);
             DETR_LAUNCH_CHECK("gemm (stream)");
             return 0;
-        }
-        if (ring_first) {
-            if (gemm_ring_launch(g, bk, rp, s)) return -1;
+        case ROUTE_RING:
+            if (gemm_ring_launch(p.g, p.bk, rp, s)) return -1;
             DETR_LAUNCH_CHECK("gemm (ring)");
             if (d->defer_out) d->defer_out->splits = 0;
             return 0;
-        }
-        if (gemm_ring_f32_eligible(p, rp)) {
-            if (gemm_ring_f32_launch(g, bk, rp, s)) return -1;
+        case ROUTE_RING_F32:
+            if (gemm_ring_f32_launch(p.g, p.bk, rp, s)) return -1;
             DETR_LAUNCH_CHECK("gemm (ring, fp32)");
             if (d->defer_out) d->defer_out->splits = 0;
             return 0;
+        case ROUTE_RING_WGRAD:
+            if (gemm_ring_wgrad_launch(p.g, p.ts_bm, p.ts_bn, p.split, s)) return -1;
+            break;
+        case ROUTE_TILE: {
+            DETR_REQUIRE(p.tile != TILE_RING_128x256 && p.tile != TILE_RING_256x128, "gemm: the 128 x 256 / 256 x 128 tiles exist for the ring weight gradient only "
+                         "(tile-ordered slabs in a workspace of detr_hip_workspace_bytes_gemm bytes are required)");
+            const TileDims t = gemm_tile_dims(p.bf16c, p.tile);
+            if (launch_gemm_tiles(gemm_tile_kernel(p), t.bm, t.bn, p.g, p.batch, s)) return -1;
+            break;
         }
     }
-    // split-K weight gradients of the backbone's 1x1 convolutions on 128 x 128 tiles: the 8-wave ring form (gemm_ring.h; bit-identical slabs)
-    const bool ring_wgrad = p.bf16c && (p.tile == 1 || p.tile == 6 || p.tile == 7) && g.a16 && g.b16 && !ak && !bk && batch == 1 && p.split > 1 &&
-                            g.slab_ts && !g.rowsum && d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && aligned16(d->A) &&
-                            aligned16(d->B) && tune(T_GEMM_RING) != 2 && tune(T_GEMM_RING) != 3;
-    DETR_REQUIRE(ring_wgrad || (p.tile != 6 && p.tile != 7), "gemm: the 128 x 256 / 256 x 128 tiles exist for the ring weight gradient only "
-                 "(tile-ordered slabs in a workspace of detr_hip_workspace_bytes_gemm bytes are required)");
-    if (ring_wgrad) {
-        if (gemm_ring_wgrad_launch(g, p.ts_bm, p.ts_bn, p.split, s)) return -1;
-    } else if (p.bf16c) {
-        if (p.tile == 2) launch_cfg_bf16<128, 64, 2, 2>(g, batch, s, ak, bk);
-        else if (p.tile == 4) launch_cfg_bf16<64, 128, 2, 2>(g, batch, s, ak, bk);
-        else if (p.tile == 0) launch_cfg_bf16<64, 64, 2, 2>(g, batch, s, ak, bk, p.deep);
-        else launch_cfg_bf16<128, 128, 2, 2>(g, batch, s, ak, bk, p.deep);
-    } else if (p.split3 && p.tile == 8) launch_x3<192, 128>(g, batch, s, ak, bk);
-    else if (p.split3 && p.tile == 1) launch_x3<128, 128>(g, batch, s, ak, bk);
-    else if (p.split3 && p.tile == 2) launch_x3<128, 64>(g, batch, s, ak, bk);
-    else if (p.split3) launch_x3<64, 64>(g, batch, s, ak, bk);
-    else if (p.tile == 1) launch_cfg<128, 128, 2, 2>(g, batch, s, ak, bk);
-    else if (p.tile == 2) launch_cfg<128, 64, 2, 2>(g, batch, s, ak, bk);
-    else if (p.tile == 3) launch_cfg<128, 32, 4, 1>(g, batch, s, ak, bk);
-    else if (p.tile == 4) launch_cfg<64, 256, 1, 4>(g, batch, s, ak, bk);
-    else if (p.tile == 5) launch_cfg<256, 64, 4, 1>(g, batch, s, ak, bk);
-    else launch_cfg<64, 64, 2, 2>(g, batch, s, ak, bk);
     DETR_LAUNCH_CHECK("gemm");
-    if (p.partial && d->defer_out) {      // the caller reduces later, many slabs per launch (detr_hip_splitk_reduce_many)
-        detr_reduce_desc *o = d->defer_out;
-        o->ws = d->workspace; o->splits = p.split; o->part_stride = p.part; o->rows = d->M; o->cols = d->N;
-        o->C = d->C; o->ldc = d->ldc; o->alpha = p.final_e.alpha; o->scale = p.final_e.scale;
-        o->rs_ws = d->rowsum_a ? d->workspace + (long long)p.split * p.part : nullptr;
-        o->rs_out = d->rowsum_a; o->rs_alpha = d->rowsum_alpha;
-        o->ts_bm = p.ts_bm; o->ts_bn = p.ts_bn; o->ts_tiles_n = p.ts_tn;
+    if (d->defer_out) {      // the caller reduces later, many slabs per launch (detr_hip_splitk_reduce_many)
+        d->defer_out->splits = 0;
+        if (p.partial) *d->defer_out = gemm_reduce_desc(p);
         return 0;
     }
-    if (d->defer_out) d->defer_out->splits = 0;
     if (p.partial) {
-        launch_splitk_reduce(d->workspace, p.split, p.part, d->M, d->N, d->C, d->ldc, p.final_e.alpha, p.final_e.scale, s,
-                             d->rowsum_a ? d->workspace + (long long)p.split * p.part : nullptr, d->rowsum_a, d->rowsum_alpha,
-                             p.ts_bm, p.ts_bn, p.ts_tn);
+        launch_splitk_reduce(gemm_reduce_desc(p), s);
         DETR_LAUNCH_CHECK("gemm split-k reduce");
     }
     return 0;
@@ -746,22 +800,12 @@ static int gemm_launch(const GemmPlan &p, hipStream_t s) {
 
 // Which kernel family detr_hip_gemm_f32 would launch for this descriptor -- the decision of gemm_launch itself, for callers that bill launches
 // to roofline families (bench.py / scripts/pmc_summary.py through detr_tf/_hip.py; ADVICE r5: the Python copy of these rules had drifted).
-// 0 = tile engine (4-wave), 1 = streaming kernel, 2 = ring kernel (bf16), 3 = ring kernel (fp32), 4 = GEMM + LayerNorm, 5 = ring weight gradient;
-// negative: the descriptor is rejected (detr_hip_last_error).
+// Negative: the descriptor is rejected (detr_hip_last_error).
 extern "C" int detr_hip_gemm_family(const detr_gemm_desc *d) {
     GemmPlan p;
     if (gemm_prepare(d, p)) return -1;
-    if (d->ln_y) return 4;
     RingPlan rp;
-    const bool ring_first = tune(T_GEMM_STREAM) != 3 && gemm_ring_eligible(p, rp);
-    if (!ring_first && gemm_stream_eligible(p)) return 1;
-    if (ring_first) return 2;
-    if (gemm_ring_f32_eligible(p, rp)) return 3;
-    const GemmArgs &g = p.g;
-    const bool ring_wgrad = p.bf16c && (p.tile == 1 || p.tile == 6 || p.tile == 7) && g.a16 && g.b16 && !p.ak && !p.bk && p.batch == 1 && p.split > 1 &&
-                            g.slab_ts && !g.rowsum && d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && aligned16(d->A) &&
-                            aligned16(d->B) && tune(T_GEMM_RING) != 2 && tune(T_GEMM_RING) != 3;
-    return ring_wgrad ? 5 : 0;
+    return gemm_route(p, rp);
 }
 
 extern "C" int detr_hip_gemm_f32(const detr_gemm_desc *d, void *stream) {
@@ -771,16 +815,6 @@ extern "C" int detr_hip_gemm_f32(const detr_gemm_desc *d, void *stream) {
 }
 
 // ---- grouped launch ------------------------------------------------------------------------------
-template <bool AK, bool BKC>
-static void launch_group_f32(const GemmGroupArgs &G, dim3 grid, hipStream_t s, bool split3) {
-    if (split3) hipLaunchKernelGGL((gemm_x3_group_kernel<64, 64, AK, BKC>), grid, dim3(GEMM_THREADS), 0, s, G);
-    else hipLaunchKernelGGL((gemm_f32_group_kernel<64, 64, 2, 2, AK, BKC>), grid, dim3(GEMM_THREADS), 0, s, G);
-}
-template <bool AK, bool BKC, bool A16, bool B16>
-static void launch_group_bf16(const GemmGroupArgs &G, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((gemm_bf16c_group_kernel<64, 64, 2, 2, AK, BKC, A16, B16>), grid, dim3(GEMM_THREADS), 0, s, G);
-}
-
 extern "C" int detr_hip_gemm_group_f32(const detr_gemm_desc *descs, int32_t n, void *stream) {
     DETR_REQUIRE(descs != nullptr && n >= 1 && n <= 64, "gemm group: 1..64 descriptors");
     hipStream_t s = (hipStream_t)stream;
@@ -792,13 +826,14 @@ extern "C" int detr_hip_gemm_group_f32(const detr_gemm_desc *descs, int32_t n, v
             DETR_REQUIRE(!descs[done + i].ln_y, "gemm group: the fused LayerNorm (ln_y) exists for single launches only");
             if (gemm_prepare(descs + done + i, p[i])) return -1;
         }
-        // one launch needs ONE kernel variant: 64x64 tiles, same layouts / storage types, no batch; members may differ in shape
+        // one launch needs ONE kernel variant: the tile engine's 64x64 tiles, same layouts / storage types, no batch; members may differ in shape
         bool same = m > 1 && tune(T_GEMM_GROUP) != 2;
-        for (int i = 0; i < m && same; ++i)
-            same = p[i].tile == 0 && p[i].batch == 1 && p[i].bf16c == p[0].bf16c && p[i].split3 == p[0].split3 && p[i].ak == p[0].ak && p[i].bk == p[0].bk &&
-                   p[i].g.a16 == p[0].g.a16 && p[i].g.b16 == p[0].g.b16 && (p[i].split == 1 || p[i].partial) &&
-                   !gemm_stream_eligible(p[i]);
-        if (same) { RingPlan rp; for (int i = 0; i < m && same; ++i) same = !gemm_ring_eligible(p[i], rp) && !gemm_ring_f32_eligible(p[i], rp); }
+        for (int i = 0; i < m && same; ++i) {
+            RingPlan rp;
+            same = p[i].tile == TILE_64x64 && p[i].batch == 1 && p[i].bf16c == p[0].bf16c && p[i].split3 == p[0].split3 && p[i].ak == p[0].ak &&
+                   p[i].bk == p[0].bk && p[i].g.a16 == p[0].g.a16 && p[i].g.b16 == p[0].g.b16 && (p[i].split == 1 || p[i].partial) &&
+                   gemm_route(p[i], rp) == ROUTE_TILE;
+        }
         if (!same) {
             for (int i = 0; i < m; ++i)
                 if (gemm_launch(p[i], s)) return -1;
@@ -816,69 +851,27 @@ extern "C" int detr_hip_gemm_group_f32(const detr_gemm_desc *descs, int32_t n, v
         }
         for (int i = m; i < GEMM_MAX_GROUP; ++i) { G.g[i] = G.g[0]; G.work_off[i + 1] = G.work_off[m]; }
         const dim3 grid((unsigned)G.work_off[m]);      // exactly one workgroup per (member, split, tile): balanced over the XCDs
-        const bool ak = p[0].ak, bk = p[0].bk, a16 = p[0].g.a16 != 0, b16 = p[0].g.b16 != 0;
-#define DETR_GROUP_BF16(A16_, B16_)                                          \
-    do {                                                                     \
-        if (ak && bk) launch_group_bf16<true, true, A16_, B16_>(G, grid, s);    \
-        else if (ak) launch_group_bf16<true, false, A16_, B16_>(G, grid, s);    \
-        else if (bk) launch_group_bf16<false, true, A16_, B16_>(G, grid, s);    \
-        else launch_group_bf16<false, false, A16_, B16_>(G, grid, s);           \
-    } while (0)
-        if (p[0].bf16c) {
-            if (a16 && b16) DETR_GROUP_BF16(true, true);
-            else if (a16) DETR_GROUP_BF16(true, false);
-            else if (b16) DETR_GROUP_BF16(false, true);
-            else DETR_GROUP_BF16(false, false);
-        } else if (ak && bk) launch_group_f32<true, true>(G, grid, s, p[0].split3);
-        else if (ak) launch_group_f32<true, false>(G, grid, s, p[0].split3);
-        else if (bk) launch_group_f32<false, true>(G, grid, s, p[0].split3);
-        else launch_group_f32<false, false>(G, grid, s, p[0].split3);
-#undef DETR_GROUP_BF16
+        hipLaunchKernelGGL(gemm_group_for(p[0].bf16c, p[0].split3, p[0].ak, p[0].bk, p[0].g.a16 != 0, p[0].g.b16 != 0), grid, dim3(GEMM_THREADS), 0, s, G);
         DETR_LAUNCH_CHECK("gemm group");
         // the members' split-K reductions, again as one launch (or handed back to the caller: detr_gemm_desc.defer_out)
-        ReduceGroupArgs R;
-        int nr = 0;
-        unsigned rx = 1;
-        bool all_small = true, any_small = false;
+        ReduceOne r[GEMM_MAX_GROUP];
+        bool small[GEMM_MAX_GROUP];
+        int nr = 0, nsmall = 0;
         for (int i = 0; i < m; ++i) {
             const detr_gemm_desc *d = p[i].d;
             if (d->defer_out) {
-                detr_reduce_desc *o = d->defer_out;
-                o->splits = 0;
-                if (p[i].partial) {
-                    o->ws = d->workspace; o->splits = p[i].split; o->part_stride = p[i].part; o->rows = d->M; o->cols = d->N;
-                    o->C = d->C; o->ldc = d->ldc; o->alpha = p[i].final_e.alpha; o->scale = p[i].final_e.scale;
-                    o->rs_ws = d->rowsum_a ? d->workspace + (long long)p[i].split * p[i].part : nullptr;
-                    o->rs_out = d->rowsum_a; o->rs_alpha = d->rowsum_alpha;
-                    o->ts_bm = p[i].ts_bm; o->ts_bn = p[i].ts_bn; o->ts_tiles_n = p[i].ts_tn;
-                }
-                continue;
+                d->defer_out->splits = 0;
+                if (p[i].partial) *d->defer_out = gemm_reduce_desc(p[i]);
+            } else if (p[i].partial) {
+                r[nr] = reduce_plan(gemm_reduce_desc(p[i]), small[nr]);
+                nsmall += small[nr++];
             }
-            if (!p[i].partial) continue;
-            ReduceOne &r = R.r[nr];
-            r.ws = d->workspace; r.splits = p[i].split; r.part_stride = p[i].part; r.rows = d->M; r.cols = d->N;
-            r.C = d->C; r.ldc = d->ldc; r.alpha = p[i].final_e.alpha; r.scale = p[i].final_e.scale;
-            r.rs_ws = d->rowsum_a ? d->workspace + (long long)p[i].split * p[i].part : nullptr;
-            r.rs_out = d->rowsum_a; r.rs_alpha = d->rowsum_alpha;
-            r.ts_bm = p[i].ts_bm; r.ts_bn = p[i].ts_bn; r.ts_tn = p[i].ts_tn;
-            bool small;
-            reduce_plan(r, small);
-            all_small = all_small && small;
-            any_small = any_small || small;
-            rx = (unsigned)r.nblocks > rx ? (unsigned)r.nblocks : rx;
-            ++nr;
         }
-        if (nr > 0 && (all_small || !any_small)) {
-            for (int i = nr; i < GEMM_MAX_GROUP; ++i) R.r[i] = R.r[0];
-            if (all_small) hipLaunchKernelGGL(splitk_reduce_group_kernel<16>, dim3(rx, (unsigned)nr), dim3(256), 0, s, R);
-            else hipLaunchKernelGGL(splitk_reduce_group_kernel<4>, dim3(rx, (unsigned)nr), dim3(256), 0, s, R);
+        if (nr > 0 && (nsmall == 0 || nsmall == nr)) {
+            launch_reduce_list<GEMM_MAX_GROUP>(r, nr, nsmall > 0, s);
             DETR_LAUNCH_CHECK("gemm group split-k reduce");
-        } else if (nr > 0) {
-            for (int i = 0; i < nr; ++i) {
-                const ReduceOne &r = R.r[i];
-                launch_splitk_reduce(r.ws, r.splits, r.part_stride, r.rows, r.cols, r.C, r.ldc, r.alpha, r.scale, s, r.rs_ws, r.rs_out,
-                                     r.rs_alpha, r.ts_bm, r.ts_bn, r.ts_tn);
-            }
+        } else if (nr > 0) {      // mixed size classes: one launch each
+            for (int i = 0; i < nr; ++i) launch_reduce_list<1>(&r[i], 1, small[i], s);
             DETR_LAUNCH_CHECK("gemm group split-k reduce (sequential)");
         }
         done += m;
@@ -887,42 +880,31 @@ extern "C" int detr_hip_gemm_group_f32(const detr_gemm_desc *descs, int32_t n, v
 }
 
 
+
 // Deferred split-K reductions (detr_gemm_desc.defer_out): n slab sets reduced by ceil(n / 16) launches per size class instead of
 // one launch each -- the ~90 reductions of a training step were ~9 us latency-bound launches (rocprofv3: 0.9 ms per step).
 extern "C" int detr_hip_splitk_reduce_many(const detr_reduce_desc *descs, int32_t n, void *stream) {
     DETR_REQUIRE(descs != nullptr && n >= 1, "splitk_reduce_many: bad args");
     hipStream_t s = (hipStream_t)stream;
     for (int pass = 0; pass < 2; ++pass) {           // pass 0: small outputs (16 split groups per block), pass 1: large ones
-        ReduceManyArgs R;
+        ReduceOne r[REDUCE_MANY];
         int cnt = 0;
-        unsigned rx = 1;
-        auto flush = [&]() {
-            if (cnt == 0) return;
-            for (int i = cnt; i < REDUCE_MANY; ++i) R.r[i] = R.r[0];
-            if (pass == 0) hipLaunchKernelGGL(splitk_reduce_many_kernel<16>, dim3(rx, (unsigned)cnt), dim3(256), 0, s, R);
-            else hipLaunchKernelGGL(splitk_reduce_many_kernel<4>, dim3(rx, (unsigned)cnt), dim3(256), 0, s, R);
-            cnt = 0;
-            rx = 1;
-        };
         for (int i = 0; i < n; ++i) {
             const detr_reduce_desc &d = descs[i];
             if (d.splits <= 0) continue;
             DETR_REQUIRE(d.ws && d.C && d.rows > 0 && d.cols > 0, "splitk_reduce_many: entry %d is malformed", i);
-            ReduceOne r;
-            r.ws = d.ws; r.splits = d.splits; r.part_stride = d.part_stride; r.rows = d.rows; r.cols = d.cols; r.C = d.C; r.ldc = d.ldc;
-            r.alpha = d.alpha; r.scale = d.scale; r.rs_ws = d.rs_ws; r.rs_out = d.rs_out; r.rs_alpha = d.rs_alpha;
-            r.ts_bm = d.ts_bm; r.ts_bn = d.ts_bn; r.ts_tn = d.ts_tiles_n > 0 ? d.ts_tiles_n : 1;
             DETR_REQUIRE(d.ts_bm == 0 || ((d.ts_bm == 64 || d.ts_bm == 128 || d.ts_bm == 256) && (d.ts_bn == 64 || d.ts_bn == 128 || d.ts_bn == 256) && d.ts_tiles_n > 0 &&
                                           d.part_stride % ((long long)d.ts_bm * d.ts_bn) == 0),
                          "splitk_reduce_many: entry %d has a malformed tile-ordered slab description", i);
             bool small;
-            reduce_plan(r, small);
+            r[cnt] = reduce_plan(d, small);
             if (small != (pass == 0)) continue;
-            R.r[cnt++] = r;
-            rx = (unsigned)r.nblocks > rx ? (unsigned)r.nblocks : rx;
-            if (cnt == REDUCE_MANY) flush();
+            if (++cnt == REDUCE_MANY) {
+                launch_reduce_list<REDUCE_MANY>(r, cnt, pass == 0, s);
+                cnt = 0;
+            }
         }
-        flush();
+        if (cnt > 0) launch_reduce_list<REDUCE_MANY>(r, cnt, pass == 0, s);
     }
     DETR_LAUNCH_CHECK("splitk_reduce_many");
     return 0;

@@ -53,6 +53,19 @@ bool gemm_ring_plan(int M, int N, int K, RingPlan &p) {
     return p.lds_bytes <= 160 * 1024;
 }
 
+// kernel arguments of the two planned ring kernels: the GEMM's own with the plan's tile grid, and the plan's LDS layout
+static RingArgs ring_args(const GemmArgs &g, const RingPlan &p) {
+    RingArgs ra;
+    ra.g = g;
+    ra.g.tiles_m = p.tiles_m;
+    ra.g.tiles_n = p.tiles_n;
+    ra.tile_rows = p.tile_rows;
+    ra.a_rows8 = p.a_rows8;
+    ra.stage_bytes = p.stage_bytes;
+    ra.dump_off = p.dump_off;
+    return ra;
+}
+
 template <int TM, int TN, bool BKC, int NS>
 static int ring_launch_one(const RingArgs &ra, int wgs, int lds, hipStream_t s) {
     static int reserved = 0;                            // largest dynamic-LDS size this instantiation has been granted
@@ -73,14 +86,7 @@ static int ring_launch_tt(const RingArgs &ra, const RingPlan &p, bool bk, hipStr
 }
 
 int gemm_ring_launch(const GemmArgs &g, bool bk, const RingPlan &p, hipStream_t s) {
-    RingArgs ra;
-    ra.g = g;
-    ra.g.tiles_m = p.tiles_m;
-    ra.g.tiles_n = p.tiles_n;
-    ra.tile_rows = p.tile_rows;
-    ra.a_rows8 = p.a_rows8;
-    ra.stage_bytes = p.stage_bytes;
-    ra.dump_off = p.dump_off;
+    const RingArgs ra = ring_args(g, p);
     int rc = -1;
     switch (p.tm * 2 + (p.tn - 1)) {
         case 2: rc = ring_launch_tt<1, 1>(ra, p, bk, s); break;
@@ -142,14 +148,7 @@ static int ring_f32_launch_one(const RingArgs &ra, int wgs, int lds, hipStream_t
 }
 
 int gemm_ring_f32_launch(const GemmArgs &g, bool bk, const RingPlan &p, hipStream_t s) {
-    RingArgs ra;
-    ra.g = g;
-    ra.g.tiles_m = p.tiles_m;
-    ra.g.tiles_n = p.tiles_n;
-    ra.tile_rows = p.tile_rows;
-    ra.a_rows8 = p.a_rows8;
-    ra.stage_bytes = p.stage_bytes;
-    ra.dump_off = p.dump_off;
+    const RingArgs ra = ring_args(g, p);
     DETR_REQUIRE(p.tn == 1 && p.ns == 2 && p.tm >= 1 && p.tm <= 3, "gemm (ring, fp32): no instantiation for TM=%d TN=%d NS=%d", p.tm, p.tn, p.ns);
     if (p.tm == 1) return bk ? ring_f32_launch_one<1, true>(ra, p.wgs, p.lds_bytes, s) : ring_f32_launch_one<1, false>(ra, p.wgs, p.lds_bytes, s);
     if (p.tm == 2) return bk ? ring_f32_launch_one<2, true>(ra, p.wgs, p.lds_bytes, s) : ring_f32_launch_one<2, false>(ra, p.wgs, p.lds_bytes, s);

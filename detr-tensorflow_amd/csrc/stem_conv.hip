@@ -575,7 +575,10 @@ extern "C" int detr_hip_stem_conv7x7_f32(const detr_stem_desc *d, int32_t mode, 
             a.part_stride = part;
             hipLaunchKernelGGL(stem_wgrad_rows_bf16_kernel, dim3((unsigned)wgs), dim3(GEMM_THREADS), 0, s, a, chunks, nunits);
             DETR_LAUNCH_CHECK("stem conv wgrad (staged rows)");
-            launch_splitk_reduce(d->workspace, wgs, part, STEM_K, 64, d->y, 64, e.alpha, e.scale, s);
+            detr_reduce_desc r = {};
+            r.ws = d->workspace; r.splits = wgs; r.part_stride = part; r.rows = STEM_K; r.cols = 64;
+            r.C = d->y; r.ldc = 64; r.alpha = e.alpha; r.scale = e.scale;
+            launch_splitk_reduce(r, s);
             DETR_LAUNCH_CHECK("stem conv wgrad reduce");
             return 0;
         }
@@ -605,7 +608,10 @@ extern "C" int detr_hip_stem_conv7x7_f32(const detr_stem_desc *d, int32_t mode, 
     else hipLaunchKernelGGL((stem_wgrad_kernel<0, false>), grid, dim3(GEMM_THREADS), 0, s, a);
     DETR_LAUNCH_CHECK("stem conv wgrad");
     if (partial) {
-        launch_splitk_reduce(d->workspace, split, part, STEM_K, 64, d->y, 64, fin.alpha, fin.scale, s);
+        detr_reduce_desc r = {};
+        r.ws = d->workspace; r.splits = split; r.part_stride = part; r.rows = STEM_K; r.cols = 64;
+        r.C = d->y; r.ldc = 64; r.alpha = fin.alpha; r.scale = fin.scale;
+        launch_splitk_reduce(r, s);
         DETR_LAUNCH_CHECK("stem conv wgrad reduce");
     }
     return 0;

@@ -107,8 +107,9 @@ typedef struct {
      * matrix pipe: every fp32 operand value is split exactly into three bf16 values (x = h + m + l) and a product is the sum
      * of the six largest of the nine bf16 partial products, accumulated in fp32 (relative error of a product <= 2^-23, the
      * size of one fp32 rounding; csrc/gemm_core.h: mma_ktile_split3) -- 6 bf16 MFMAs instead of 8 fp32 MFMAs per 32x32x16
-     * block at 16x the instruction rate.  Operands, C, residual and mask must be fp32 (the *_dtype fields 0); tiles other
-     * than 64x64 / 128x128 (N <= 32) run the exact kernel. */
+     * block at 16x the instruction rate.  Operands, C, residual and mask must be fp32 (the *_dtype fields 0).  Both forms are
+     * fp32-accurate; the split kernel takes the shapes on which it is the faster one (csrc/gemm_f32.hip: gemm_split3_shape) --
+     * N > 32 and, unless DETR_HIP_SPLIT3_ALL=1, N >= 128, K >= 256 and M >= 128 -- and every other shape runs the exact kernel. */
     int32_t compute;
     /* optional fused bias gradient of a weight-gradient GEMM (dW = dy^T x): rowsum_a[m] += rowsum_alpha * sum_k A[m][k]
      * (A must be MN-contiguous, a_kcontig = 0; batch == 1; with split_k > 1 the deterministic workspace path is

@@ -1334,6 +1334,42 @@ def test_gemm_group_matches_individual_launches(hip, compute):
         hip.COMPUTE_BF16 = old
 
 
+def test_gemm_group_reductions_of_mixed_size_class(hip):
+    """A grouped split-K launch whose members' reductions fall into DIFFERENT size classes: the members still share one GEMM launch
+    (64x64 tiles, one kernel variant), but a reduce launch has one summation order -- 16 split groups per block for small outputs,
+    4 for large ones -- so the reductions are issued one after the other.  Bit-identical to the two GEMMs issued singly."""
+    torch.manual_seed(77)
+    hip.ensure_workspace(DEV)
+    K, split = 2048, 8
+    shapes = [(256, 256), (512, 1024)]
+    # the classing rule (gemm_f32.hip: reduce_plan): small = M * N / 4 <= 65536 float4 outputs and splits >= 8
+    small = [m * n // 4 <= 65536 and split >= 8 for m, n in shapes]
+    assert small == [True, False], "the two members must fall into different reduce classes"
+    # neither output is a big split (gemm_pick_tile): both keep 64x64 tiles and can share a launch
+    assert all(not ((n >= 128 and K >= 16384) or (m >= 512 and n >= 512 and K >= 4096) or K >= 4096) for m, n in shapes)
+    A = [g(torch.randn(K, m)).to(torch.bfloat16) for m, n in shapes]          # MN-contiguous bf16 operands: dW = A^T B
+    B = [g(torch.randn(K, n)).to(torch.bfloat16) for m, n in shapes]
+
+    def calls(dws, db):
+        return [((m, n, K, A[i], m, 0, B[i], n, 0, dws[i], n),
+                 dict(split_k=split, compute=1, alpha=(0.5 if i else 1.0), rowsum_a=(db if i == 0 else None), rowsum_alpha=1.0))
+                for i, (m, n) in enumerate(shapes)]
+    dw_s, dw_g = ([torch.zeros(m, n, device=DEV) for m, n in shapes] for _ in range(2))
+    db_s, db_g = (torch.zeros(shapes[0][0], device=DEV) for _ in range(2))
+    for a, kw in calls(dw_s, db_s):
+        hip.gemm(*a, **kw)
+    hip.gemm_group(calls(dw_g, db_g))
+    torch.cuda.synchronize()
+    for i in range(2):
+        assert torch.equal(dw_s[i], dw_g[i]), f"grouped member {i} differs from the single launch"
+        assert float(dw_s[i].abs().max()) > 0
+    assert torch.equal(db_s, db_g) and float(db_s.abs().max()) > 0
+    # and the right product: bf16 operands are exact, the fp32 sums of K terms err by at most K * 2^-24 * sum |a b| ~ 0.5 * 2048 * 6e-8 * 1300
+    # = 0.08, under 1e-3 of the largest of the 512 K outputs (~ 5 sigma of 0.5 * sqrt(2048))
+    ref = A[1].double().t() @ B[1].double() * 0.5
+    assert float((dw_g[1].double() - ref).abs().max()) <= 1e-3 * float(ref.abs().max())
+
+
 @pytest.mark.parametrize("compute", [0, 1])
 def test_deferred_split_k_reductions_match_immediate(hip, compute):
     """detr_gemm_desc.defer_out + detr_hip_splitk_reduce_many: 20 weight-gradient GEMMs (plain and grouped, with fused bias
