@@ -289,6 +289,14 @@ extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) 
         DETR_PUT(DETR_OFF(detr_track_embed_desc, appearance_weight)); DETR_PUT(DETR_OFF(detr_track_embed_desc, reid)); DETR_PUT(DETR_OFF(detr_track_embed_desc, reid_threshold));
         DETR_PUT(DETR_OFF(detr_track_embed_desc, momentum));
         break;
+    case 600:   // detr_track_motion_desc (the sixth appended list counts from 600, include/detr_hip.h)
+        DETR_PUT((int32_t)sizeof(detr_track_motion_desc));
+        DETR_PUT(DETR_OFF(detr_track_motion_desc, S)); DETR_PUT(DETR_OFF(detr_track_motion_desc, frames)); DETR_PUT(DETR_OFF(detr_track_motion_desc, frames_bytes));
+        DETR_PUT(DETR_OFF(detr_track_motion_desc, offsets)); DETR_PUT(DETR_OFF(detr_track_motion_desc, sizes)); DETR_PUT(DETR_OFF(detr_track_motion_desc, active));
+        DETR_PUT(DETR_OFF(detr_track_motion_desc, radius)); DETR_PUT(DETR_OFF(detr_track_motion_desc, motion_state)); DETR_PUT(DETR_OFF(detr_track_motion_desc, motion_state_bytes));
+        DETR_PUT(DETR_OFF(detr_track_motion_desc, state)); DETR_PUT(DETR_OFF(detr_track_motion_desc, state_bytes)); DETR_PUT(DETR_OFF(detr_track_motion_desc, workspace));
+        DETR_PUT(DETR_OFF(detr_track_motion_desc, workspace_bytes)); DETR_PUT(DETR_OFF(detr_track_motion_desc, out_motion)); DETR_PUT(DETR_OFF(detr_track_motion_desc, status));
+        break;
     default:
         detr::set_error("struct_layout: unknown struct %d", which);
         return -1;

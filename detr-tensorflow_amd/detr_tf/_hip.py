@@ -187,6 +187,21 @@ class TrackEmbedDesc(Structure):
         ("appearance_weight", ctypes.c_double), ("reid", c_int32), ("reid_threshold", ctypes.c_double), ("momentum", c_float)]
 
 
+# detr_hip_track_motion (camera-motion compensation in front of the trackers): the constants of include/detr_hip.h
+MOTION_SIDE, MOTION_BLOCK, MOTION_MIN_BLOCKS, MOTION_MIN_CONTRAST, MOTION_MAX_RADIUS = 384, 16, 4, 16, 16     # DETR_MOTION_*
+TRACK_MOTION_BAD = {8: "a frame with a side outside 1..32768, or one that does not lie inside the frames' buffer (that stream got no "
+                       "motion estimate)"}                                     # DETR_TRACK_BAD_FRAME
+TRACK_ALL_BAD = {**TRACK_EMBED_BAD, **TRACK_MOTION_BAD}                        # the bits share one status word
+
+
+class TrackMotionDesc(Structure):
+    """detr_track_motion_desc (appended entry point, ABI version unchanged)."""
+    _fields_ = [("S", c_int32), ("frames", c_void_p), ("frames_bytes", c_int64), ("offsets", c_void_p), ("sizes", c_void_p),
+                ("active", c_void_p), ("radius", c_int32), ("motion_state", c_void_p), ("motion_state_bytes", c_int64),
+                ("state", c_void_p), ("state_bytes", c_int64), ("workspace", c_void_p), ("workspace_bytes", c_int64),
+                ("out_motion", c_void_p), ("status", c_void_p)]
+
+
 MAP_MAX_THR = 16                                                               # DETR_MAP_MAX_THR
 MAP_BAD = {1: "a predicted label outside [0, nb_class)", 2: "a target class outside [0, nb_class)",
            4: "a target header count outside [0, R-1]", 8: "a detection count outside [0, Q]"}      # DETR_MAP_BAD_*
@@ -299,6 +314,7 @@ _SIGNATURES = {
     "detr_hip_overlay": [POINTER(OverlayDesc), c_void_p],
     "detr_hip_track": [POINTER(TrackDesc), c_void_p],
     "detr_hip_track_embed": [POINTER(TrackEmbedDesc), c_void_p],
+    "detr_hip_track_motion": [POINTER(TrackMotionDesc), c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
@@ -315,6 +331,8 @@ _SIGNATURES_I64 = {
     "detr_hip_track_state_bytes": [c_int32],
     "detr_hip_track_embed_state_bytes": [c_int32, c_int32],
     "detr_hip_workspace_bytes_track_embed": [POINTER(TrackEmbedDesc)],
+    "detr_hip_track_motion_state_bytes": [c_int32],
+    "detr_hip_workspace_bytes_track_motion": [POINTER(TrackMotionDesc)],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
@@ -326,6 +344,8 @@ LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: La
 LAYOUT_STRUCTS_APPENDED = {400: TrackDesc}
 # and the one behind detr_track_desc (a fifth list, 500), in a table of its own for the same reason
 LAYOUT_STRUCTS_APPENDED_500 = {500: TrackEmbedDesc}
+# and detr_track_motion_desc (a sixth list, 600)
+LAYOUT_STRUCTS_APPENDED_600 = {600: TrackMotionDesc}
 
 _lib = None
 
@@ -560,7 +580,7 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in sorted({**LAYOUT_STRUCTS, **LAYOUT_STRUCTS_APPENDED, **LAYOUT_STRUCTS_APPENDED_500}.items()):
+    for which, S in sorted({**LAYOUT_STRUCTS, **LAYOUT_STRUCTS_APPENDED, **LAYOUT_STRUCTS_APPENDED_500, **LAYOUT_STRUCTS_APPENDED_600}.items()):
         want = struct_layout_mirror(S)
         buf = (c_int32 * 96)()
         n = lib.detr_hip_struct_layout(which, buf, 96)

@@ -20,6 +20,8 @@ onto the frames in one call of `detr_hip_overlay` (csrc/overlay.hip); `Detector.
 
 `Tracker` carries detections across the frames of a video: its tracks live on the device and one launch of `detr_hip_track`
 (csrc/track.hip) per batch of frames associates, updates, spawns and emits -- `Detector.track` feeds it the detector's raw rows.
+`Tracker(motion=True)` puts `detr_hip_track_motion` (csrc/track_motion.hip) in front: a global shift per frame, estimated on the
+device from the frames themselves, moves the tracks with the camera before they are associated.
 """
 import math
 from ctypes import byref
@@ -261,6 +263,9 @@ TRACK_STATE = np.dtype([("x", "<f4", (_T, 4)), ("v", "<f4", (_T, 4)), ("label", 
                         ("hits", "<i4", (_T,)), ("miss", "<i4", (_T,)), ("confirmed", "<i4", (_T,)), ("frame", "<i4"), ("next_id", "<i4"),
                         ("pad", "<i4", (2,))])
 TRACK_STATE_KEYS = ("x", "v", "label", "id", "hits", "miss", "confirmed", "score", "frame", "next_id")
+# one stream of the motion state (include/detr_hip.h: detr_track_motion_desc); detr_hip_track_motion_state_bytes sizes the buffer
+MOTION_STATE = np.dtype([("head", "<i4", (16,)), ("thumb", "u1", (2, hip.MOTION_SIDE * hip.MOTION_SIDE))])
+MOTION_HEAD = ("h", "w", "f", "tw", "th", "valid", "slot", "estimated", "sx", "sy", "n", "agree")
 
 
 class Tracker:
@@ -278,7 +283,7 @@ class Tracker:
     confirmed or has missed more than max_age frames; an unmatched detection with score >= new_threshold (None: track_threshold)
     starts a track, confirmed after min_hits matched frames; only detections of confirmed tracks are returned.
     The defaults are ByteTrack's and SORT's conventions carried over; nobody has tuned them for DETR outputs.  The association is
-    greedy, not Hungarian; there is no Kalman covariance and no camera-motion compensation.
+    greedy, not Hungarian; there is no Kalman covariance.
 
     embed_dim=E turns on tracking by APPEARANCE (include/detr_hip.h: detr_track_embed_desc; one launch as before): every frame also
     hands in an embedding per detection, and every track keeps a unit embedding, an exponential average (momentum) of the detections it
@@ -288,11 +293,25 @@ class Tracker:
     unmatched detection that would otherwise start a track (None: no such stage).  Detector.track feeds the model's own descriptor
     (DetrModel return_embeddings, E = 256); update_rows takes any [S, R, E] tensor.  appearance_weight, reid_threshold and momentum are
     the conventions of BoT-SORT-like trackers carried over, UNTUNED: nobody has measured how well DETR's hidden states tell the objects
-    of a real video apart.  embed_dim=None (the default) is the tracker described above in every respect."""
+    of a real video apart.  embed_dim=None (the default) is the tracker described above in every respect.
+
+    motion=True compensates CAMERA MOTION (include/detr_hip.h: detr_track_motion_desc; at most three launches more, no read-back and no
+    further synchronisation): every call also hands in the frames (frames=; Detector.track passes the ones it has just uploaded).  Each
+    frame is reduced to a luma thumbnail of at most 384 x 384 pixels, its 16 x 16 blocks are matched against the previous frame's
+    thumbnail within +-motion_radius thumbnail pixels, and when the blocks' median displacement is one most of them agree on, every
+    track of the stream is moved by it before the association -- so a hand-held or vehicle-mounted camera, which moves every box at
+    once by more than the IoU gate forgives, no longer costs every track its id.  There is no estimate on the first frame, after a
+    change of frame size, on a frame too small or too flat, or when the blocks disagree (a scene cut, a frame filled by moving
+    foreground): the frame is then tracked as without motion.  last_motion holds the [S, 6] int32 device tensor (estimated, sx, sy, n,
+    agree, f) of the last call, not synchronised.  Translation only: zoom and roll are not modelled.  The shift is quantised to f
+    pixels, the thumbnail's reduction factor (4 for 800 x 1333, 5 for 1080p); the alpha-beta update absorbs the remainder.  The
+    defaults (radius 8, at least 4 textured blocks, half of them within one pixel of the median) are reasoned, not tuned: what the
+    compensation is worth on real hand-held video is UNMEASURED, there is no such video here.  motion=False (the default) launches and
+    returns exactly what the tracker above does."""
 
     def __init__(self, streams=1, device=None, *, track_threshold=0.7, new_threshold=None, match_threshold=0.3, low_match_threshold=0.5,
                  max_age=30, min_hits=3, alpha=0.75, beta=0.25, class_agnostic=False, embed_dim=None, appearance_weight=0.5,
-                 reid_threshold=0.8, momentum=0.9):
+                 reid_threshold=0.8, momentum=0.9, motion=False, motion_radius=8):
         if new_threshold is None:
             new_threshold = track_threshold
         if not 1 <= int(streams) <= 65535:
@@ -314,6 +333,10 @@ class Tracker:
                 raise ValueError(f"Tracker: reid_threshold={reid_threshold} is not finite")
             self.appearance_weight, self.momentum = float(appearance_weight), float(momentum)
             self.reid_threshold = None if reid_threshold is None else float(reid_threshold)
+        self.motion, self.motion_radius = bool(motion), int(motion_radius)
+        if self.motion and not 1 <= self.motion_radius <= hip.MOTION_MAX_RADIUS:
+            raise ValueError(f"Tracker: motion_radius={motion_radius} must be in 1..{hip.MOTION_MAX_RADIUS}")
+        self.last_motion = None                      # [S, 6] int32 on the device: what the last call estimated
         self.streams = int(streams)
         self.track_threshold, self.new_threshold = float(track_threshold), float(new_threshold)
         self.match_threshold, self.low_match_threshold = float(match_threshold), float(low_match_threshold)
@@ -336,11 +359,21 @@ class Tracker:
                                    "rebuild the library")
             self._bank = torch.empty(self.streams, _T, E, dtype=torch.float32, device=self.device)
             self._table = None                       # the kernel's scratch, sized by the widest frame seen
+        if self.motion:
+            nbytes = int(hip.load().detr_hip_track_motion_state_bytes(self.streams))
+            if nbytes != self.streams * MOTION_STATE.itemsize:
+                raise RuntimeError(f"Tracker: the library's motion state is {nbytes} bytes, this binding lays out "
+                                   f"{self.streams * MOTION_STATE.itemsize}: rebuild the library")
+            self._motion = torch.empty(self.streams, MOTION_STATE.itemsize, dtype=torch.uint8, device=self.device)
+            d = hip.TrackMotionDesc()
+            d.S = self.streams
+            self._votes = torch.empty(int(hip.load().detr_hip_workspace_bytes_track_motion(byref(d))), dtype=torch.uint8, device=self.device)
         self.reset()
 
     # ---- state
     def reset(self, stream=None):
-        """Forget every track of `stream` (None: of all streams); its ids start at 1 again."""
+        """Forget every track of `stream` (None: of all streams); its ids start at 1 again.  With motion its motion state is zeroed:
+        the next frame has no predecessor."""
         fresh = np.zeros(1, TRACK_STATE)
         fresh["next_id"] = 1
         row = torch.from_numpy(fresh.view(np.uint8).reshape(1, -1)).to(self.device)
@@ -352,27 +385,41 @@ class Tracker:
             self._state[int(stream)].copy_(row[0])
         if self.embed_dim is not None:
             (self._bank if stream is None else self._bank[int(stream)]).zero_()
+        if self.motion:
+            (self._motion if stream is None else self._motion[int(stream)]).zero_()
 
     def state_dict(self):
         """The whole state as named host arrays, leading axis = stream: x, v float32 [S, T, 4]; label int64, id, hits, miss int32,
         confirmed bool, score float32 [S, T]; frame, next_id int32 [S] (T = _hip.TRACK_MAX; a free slot is all zeros).  One copy to the
-        host.  With embed_dim: plus embed float32 [S, T, E], the unit embedding of every slot (a second copy)."""
+        host.  With embed_dim: plus embed float32 [S, T, E], the unit embedding of every slot (a second copy).  With motion: plus
+        motion_head int32 [S, 16] (MOTION_HEAD names the first twelve) and motion_thumb uint8 [S, 2, 384 * 384], the two thumbnail slots."""
         raw = self._state.cpu().numpy().reshape(-1).view(TRACK_STATE)
         out = {k: np.ascontiguousarray(raw[k]) for k in TRACK_STATE_KEYS}
         out["confirmed"] = out["confirmed"] != 0
         if self.embed_dim is not None:
             out["embed"] = self._bank.cpu().numpy()
+        if self.motion:
+            raw = self._motion.cpu().numpy().reshape(-1).view(MOTION_STATE)
+            out["motion_head"], out["motion_thumb"] = np.ascontiguousarray(raw["head"]), np.ascontiguousarray(raw["thumb"])
         return out
 
     def load_state_dict(self, state):
         """Take over a state_dict(): the video goes on bit-identically."""
-        missing = [k for k in TRACK_STATE_KEYS + (("embed",) if self.embed_dim is not None else ()) if k not in state]
+        missing = [k for k in TRACK_STATE_KEYS + (("embed",) if self.embed_dim is not None else ())
+                   + (("motion_head", "motion_thumb") if self.motion else ()) if k not in state]
         if missing:
             raise ValueError(f"Tracker.load_state_dict: missing {missing}")
         if self.embed_dim is not None:
             bank = np.asarray(state["embed"])
             if bank.shape != tuple(self._bank.shape):
                 raise ValueError(f"Tracker.load_state_dict: embed has shape {bank.shape}, expected {tuple(self._bank.shape)}")
+        if self.motion:
+            moved = np.zeros(self.streams, MOTION_STATE)
+            for k, name in (("head", "motion_head"), ("thumb", "motion_thumb")):
+                value = np.asarray(state[name])
+                if value.shape != moved[k].shape:
+                    raise ValueError(f"Tracker.load_state_dict: {name} has shape {value.shape}, expected {moved[k].shape}")
+                moved[k] = value
         raw = np.zeros(self.streams, TRACK_STATE)
         for k in TRACK_STATE_KEYS:
             value = np.asarray(state[k])
@@ -382,9 +429,49 @@ class Tracker:
         self._state.copy_(torch.from_numpy(raw.view(np.uint8).reshape(self.streams, -1)))
         if self.embed_dim is not None:
             self._bank.copy_(torch.from_numpy(np.ascontiguousarray(bank, np.float32)))
+        if self.motion:
+            self._motion.copy_(torch.from_numpy(moved.view(np.uint8).reshape(self.streams, -1)))
 
     # ---- frames
-    def _launch(self, boxes, labels, scores, query, counts, active, embeddings=None):
+    def _launch_motion(self, frames, active, status):
+        """detr_hip_track_motion on the current stream: the tracks of every stream move with its camera.  `status` is the device
+        address of the status word the tracker's launch behind it shares."""
+        from .overlay import RaggedFrames, _check_frames, _upload_frames
+        S = self.streams
+        if isinstance(frames, RaggedFrames):
+            sizes, offsets, buf = frames.sizes, frames.offsets, frames.buffer
+            if not (isinstance(buf, torch.Tensor) and buf.device == self._state.device and buf.dtype == torch.uint8 and buf.is_contiguous()):
+                raise ValueError(f"Tracker: frames.buffer must be a contiguous uint8 tensor on {self._state.device}")
+            keep, base, nbytes = [buf], buf.data_ptr(), buf.numel()
+        else:
+            try:
+                images, sizes, on_device = _check_frames(frames)
+            except (TypeError, ValueError) as e:
+                raise type(e)(str(e).replace("draw_detections", "Tracker: frames")) from None
+            if on_device and any(im.device != self._state.device for im in images):
+                raise ValueError(f"Tracker: frames on the device must be on {self._state.device}")
+            with torch.cuda.device(self.device):
+                keep, base, offsets = _upload_frames(images, on_device, self.device)
+            nbytes = int((offsets + sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3).max())
+        if sizes.shape[0] != S:
+            raise ValueError(f"Tracker: {sizes.shape[0]} frames for {S} streams")
+        # offsets (int64) | sizes (int32) in one transfer; the result behind them
+        meta = torch.from_numpy(np.concatenate([np.ascontiguousarray(offsets, np.int64).view(np.uint8),
+                                                np.ascontiguousarray(sizes, np.int32).reshape(-1).view(np.uint8)])).to(self.device)
+        out = torch.empty(S, 6, dtype=torch.int32, device=self.device)
+        d = hip.TrackMotionDesc()
+        d.S, d.frames, d.frames_bytes, d.offsets, d.sizes = S, base, nbytes, meta.data_ptr(), meta.data_ptr() + 8 * S
+        d.active, d.radius = active.data_ptr(), self.motion_radius
+        d.motion_state, d.motion_state_bytes = self._motion.data_ptr(), self._motion.numel()
+        d.state, d.state_bytes = self._state.data_ptr(), self._state.numel()
+        d.workspace, d.workspace_bytes = self._votes.data_ptr(), self._votes.numel()
+        d.out_motion, d.status = out.data_ptr(), status
+        with torch.cuda.device(self.device):
+            hip._check(hip.load().detr_hip_track_motion(byref(d), hip._stream()), "detr_hip_track_motion")
+        del keep                    # (freed blocks are reused in stream order: the launches above still own them)
+        self.last_motion = out
+
+    def _launch(self, boxes, labels, scores, query, counts, active, embeddings=None, frames=None):
         S = self.streams
         if boxes.dim() != 3 or boxes.shape[0] != S or boxes.shape[2] != 4 or not 1 <= boxes.shape[1] <= 1024:
             raise ValueError(f"Tracker: boxes must be [S={S}, D, 4] with D in 1..1024, got {tuple(boxes.shape)}")
@@ -408,8 +495,12 @@ class Tracker:
                 raise ValueError(f"Tracker: embeddings must be a float32 tensor [S={S}, R, E={self.embed_dim}] on {self._state.device} with "
                                  "contiguous, 16-byte aligned rows, got "
                                  f"{(e.dtype, tuple(e.shape), e.stride(), e.device) if torch.is_tensor(e) else type(e).__name__}")
+        if (frames is None) == self.motion:
+            raise ValueError(f"Tracker: frames= is mandatory with motion and refused without: this tracker was built with motion={self.motion}")
         out_b, out_l, out_s, out_q, out_i, out_h = _ranked_rows(S, D, self.device, 3)
         tail = torch.zeros(S + 1, dtype=torch.int32, device=self.device)       # counts [S], then the status word
+        if self.motion:
+            self._launch_motion(frames, active, tail.data_ptr() + 4 * S)
         d = hip.TrackDesc() if embeddings is None else hip.TrackEmbedDesc()
         d.S, d.D, d.state, d.state_bytes = S, D, self._state.data_ptr(), self._state.numel()
         d.boxes, d.labels, d.scores, d.query = boxes.data_ptr(), labels.data_ptr(), scores.data_ptr(), hip.ptr(query)
@@ -443,7 +534,7 @@ class Tracker:
             raise ValueError(f"Tracker: active must hold one flag per stream ({self.streams}), got shape {flags.shape}")
         return torch.from_numpy(flags.astype(np.int32)).to(self.device)
 
-    def update_rows(self, boxes, labels, scores, query, counts, active=None, embeddings=None):
+    def update_rows(self, boxes, labels, scores, query, counts, active=None, embeddings=None, frames=None):
         """One frame per stream from padded DEVICE rows, as detr_hip_detect / detr_hip_tile_merge write them with bbox_format "xyxy":
         boxes [S, D, 4] float32, labels [S, D] int64, scores [S, D] float32, query [S, D] int32 or None, counts [S] int32 -- D <= 1024;
         rows behind counts[s] are not read.  active: one flag per stream (None: all); a stream whose flag is 0 keeps its state and
@@ -453,19 +544,22 @@ class Tracker:
         that found no slot are not tracked.
         embeddings (mandatory with embed_dim, refused without): float32 [S, R, E] on the device, rows contiguous; the embedding of
         detection d of stream s is row query[s, d] (row d with query None).  A row index outside [0, R) or a non-finite row raises
-        ValueError the same way: the frame has been tracked with the zero embedding for that detection."""
-        rows, tail = self._launch(boxes, labels, scores, query, counts, self._active(active), embeddings)
+        ValueError the same way: the frame has been tracked with the zero embedding for that detection.
+        frames (mandatory with motion, refused without): the frame of every stream, as draw_detections takes them -- an
+        overlay.RaggedFrames (DeviceInputStage.last_upload), or a list of uint8 [h, w, 3] host arrays (uploaded once) or device tensors
+        (used where they are).  The tracks are moved by the estimated camera shift first (last_motion), then associated as above."""
+        rows, tail = self._launch(boxes, labels, scores, query, counts, self._active(active), embeddings, frames)
         *n, status = tail.tolist()
         if status:
-            raise ValueError("Tracker: " + "; ".join(text for bit, text in hip.TRACK_EMBED_BAD.items() if status & bit))
+            raise ValueError("Tracker: " + "; ".join(text for bit, text in hip.TRACK_ALL_BAD.items() if status & bit))
         return [TrackedDetections(*(r[s, :k] for r in rows)) for s, k in enumerate(n)]
 
-    def update(self, detections, active=None, embeddings=None):
+    def update(self, detections, active=None, embeddings=None, frames=None):
         """One frame per stream: `detections` holds, per stream, a Detections / TiledDetections with boxes in "xyxy" pixels, or a
         (boxes [k, 4], labels [k], scores [k]) triple (its query is 0); a single one is taken as the frame of a one-stream tracker.
         They are packed into padded rows (as draw_detections packs them) and go through update_rows.  embeddings: update_rows'; the
         rows are the detections' query, and for a triple, which has none, its k detections take the rows 0..k-1 (and are emitted with
-        those as query)."""
+        those as query).  frames: update_rows'."""
         if isinstance(detections, (Detections, TiledDetections)) or (isinstance(detections, tuple) and len(detections) == 3
                                                                        and not isinstance(detections[0], (tuple, list))):
             detections = [detections]
@@ -482,7 +576,7 @@ class Tracker:
                 query[s, :counts[s]] = d.query.to(self.device)
             elif embeddings is not None and counts[s]:
                 query[s, :counts[s]] = torch.arange(int(counts[s]), dtype=torch.int32, device=self.device)
-        return self.update_rows(boxes, labels, scores, query, torch.from_numpy(counts).to(self.device), active, embeddings)
+        return self.update_rows(boxes, labels, scores, query, torch.from_numpy(counts).to(self.device), active, embeddings, frames)
 
 
 class Detector:
@@ -645,7 +739,10 @@ class Detector:
         frame.  Needs bbox_format="xyxy".  active: Tracker.update_rows'.
         A tracker with embed_dim (it must be 256) tracks by appearance: the model is called with return_embeddings and its out["embed"]
         goes to update_rows with detr_hip_detect's query rows -- one launch more (the copy of the embeddings), no further
-        synchronisation.  Not with tiles / nms_threshold: that path keeps no per-tile embeddings."""
+        synchronisation.  Not with tiles / nms_threshold: that path keeps no per-tile embeddings.
+        A tracker with motion is handed the frames this call has just uploaded (DeviceInputStage.last_upload; the host frames with
+        resize="fixed", which uploads a dense batch) on every path -- with tiles they are the whole images --: at most three launches
+        more, no further synchronisation."""
         if self.bbox_format != "xyxy":
             raise ValueError(f"Detector.track: boxes must be 'xyxy' pixels: build the Detector with bbox_format='xyxy', not {self.bbox_format!r}")
         if not isinstance(tracker, Tracker):
@@ -663,13 +760,15 @@ class Detector:
             if appearance:
                 raise NotImplementedError("Detector.track: tracking by appearance with tiles / nms_threshold: that path keeps no per-tile "
                                           "embeddings; use a Tracker without embed_dim, or a Detector without tiles and nms_threshold")
-            tracked = tracker.update(self(srcs), active)
+            detections = self(srcs)
+            tracked = tracker.update(detections, active, frames=self._last_frames if tracker.motion else None)
         else:
             sizes = np.array([s.shape[:2] for s in srcs], np.int32)
             m_outputs, _ = self._forward(srcs, sizes, return_embeddings=appearance)
             rows = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, self.background_class, self.score_threshold,
                            self.max_detections, self.bbox_format, True)
-            tracked = tracker.update_rows(*rows, active, m_outputs["embed"] if appearance else None)
+            tracked = tracker.update_rows(*rows, active, m_outputs["embed"] if appearance else None,
+                                          self._last_frames if tracker.motion else None)
         return tracked[0] if single else tracked
 
     def attention_site(self, site="dec"):

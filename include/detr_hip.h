@@ -1062,6 +1062,76 @@ int detr_hip_track_embed(const detr_track_embed_desc *d, void *stream);
 int64_t detr_hip_track_embed_state_bytes(int32_t streams, int32_t embed_dim);
 int64_t detr_hip_workspace_bytes_track_embed(const detr_track_embed_desc *d);
 
+/* ---------------------------------------------------------------------------------------------
+ * Camera-motion compensation for the trackers, appended (the ABI version is unchanged): a global translation per stream and frame,
+ * estimated from the frames themselves and added to the track positions BEFORE detr_hip_track / detr_hip_track_embed run on the same
+ * `state` (csrc/track_motion.hip).  A hand-held or vehicle-mounted camera moves every box by tens of pixels between two frames;
+ * the alpha-beta velocity cannot learn jitter, so every IoU gate fails at once.  Three launches on the caller's stream (thumbnail:
+ * one workgroup per stream and thumbnail row; block matching: one workgroup per stream and block; finalise: one workgroup per
+ * stream), no read-back, no host synchronisation.  All arithmetic up to the shift is integer: the result is exact, and a rerun from
+ * the same states is bit-identical.  Translation only -- zoom and roll are not modelled --, quantised to f pixels (f = 4 for
+ * 800 x 1333, 5 for 1080p); the alpha-beta update of the tracker absorbs the remainder.
+ * Frames: stream s is [h, w, 3] uint8 RGB at frames + offsets[s] (any alignment), (h, w) = sizes[s], both in DEVICE memory.  A side
+ *   outside 1..DETR_OVERLAY_MAX_SIDE, a negative offset or offsets[s] + 3 h w > frames_bytes sets DETR_TRACK_BAD_FRAME in *status (which
+ *   the caller zeroes; the bit is apart from detr_hip_track's, so the word may be shared), and the stream is run as (h, w) = (0, 0):
+ *   no pixel is read, there is no estimate.
+ * With SIDE = DETR_MOTION_SIDE, R = radius, per stream with active[s] != 0:
+ *   1. thumbnail: f = max(1, ceil(w / SIDE), ceil(h / SIDE)), tw = w / f, th = h / f (integer division; the partial right and bottom
+ *      edges are dropped).  Luma y = (77 R + 150 G + 29 B + 128) >> 8; thumbnail pixel (j, i) = (sum of y over its f x f cell) / (f f),
+ *      integer division, stored as uint8 into thumb[1 - slot] (slot = the header's: where the previous frame's thumbnail is), dense with
+ *      row stride tw; the bytes behind th * tw keep what they held.
+ *   2. whether an estimate exists: none when the header's valid is 0 (the first frame after a reset), when (h, w) differs from the
+ *      header's, or when gx = (tw - 2 R) / 16 < 1 or gy = (th - 2 R) / 16 < 1 (tw == 0 and th == 0 fall under this).
+ *   3. block votes: block (bx, by), bx < gx, by < gy, is the 16 x 16 window of the current thumbnail at (R + 16 bx, R + 16 by); it is
+ *      valid when max - min of its pixels is >= DETR_MOTION_MIN_CONTRAST.  For every (dx, dy) in [-R, R]^2,
+ *      SAD = sum over the window of |cur(x, y) - prev(x - dx, y - dy)|; the block's vote is the displacement with the smallest key
+ *      (SAD, dx dx + dy dy, dy, dx), compared lexicographically.
+ *   4. global shift: n = number of valid blocks; no estimate when n < DETR_MOTION_MIN_BLOCKS.  dx*, dy* = the lower medians of the
+ *      votes' dx and of their dy, taken independently (index (n - 1) / 2 of the sorted list); agree = number of valid blocks with
+ *      |dx - dx*| <= 1 and |dy - dy*| <= 1; no estimate when 2 agree < n (a scene cut, or a frame dominated by moving foreground).
+ *      (sx, sy) = (dx* f, dy* f) pixels.
+ *   5. apply: with an estimate, every live slot (id >= 1) of the stream's track state gets x.cx = x.cx + (float)sx and
+ *      x.cy = x.cy + (float)sy, one fp32 rounding each; v, w, h and the free slots are not touched.
+ *   6. book-keeping, with or without an estimate: the header takes the new h, w, f, tw, th, valid = 1, slot = 1 - slot, and
+ *      estimated, sx, sy, n, agree as reported.  out_motion[s] = (estimated, sx, sy, n, agree, f): sx = sy = 0 without an estimate;
+ *      n = agree = 0 when step 2 found none; agree = 0 when n < DETR_MOTION_MIN_BLOCKS.
+ * active[s] == 0 leaves the motion state and the track state of stream s untouched: out_motion[s] is six zeros.
+ * motion_state: detr_hip_track_motion_state_bytes(S) bytes (negative: S outside 1..65535), 16-byte aligned; per stream
+ *   int32_t head[16] = h, w, f, tw, th, valid, slot, estimated, sx, sy, n, agree, 0, 0, 0, 0; uint8_t thumb[2][SIDE * SIDE].
+ *   A fresh state is all zeros.
+ * state: the track state of detr_hip_track.  workspace: detr_hip_workspace_bytes_track_motion(d) bytes (reads S only; negative =
+ *   malformed), 16-byte aligned: the votes.
+ * Limits: S 1..65535; radius 1..16; frames_bytes >= 1; motion_state, state and workspace 16-byte aligned, offsets 8-byte aligned.
+ * No float atomics; integer atomics on *status and inside a workgroup's LDS only.  Nothing is read or written out of bounds for any
+ * size or offset.  detr_hip_struct_layout knows detr_track_motion_desc as 600 (a sixth appended list).
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_MOTION_SIDE 384
+#define DETR_MOTION_BLOCK 16
+#define DETR_MOTION_MIN_BLOCKS 4
+#define DETR_MOTION_MIN_CONTRAST 16
+#define DETR_MOTION_MAX_RADIUS 16
+#define DETR_TRACK_BAD_FRAME 8
+typedef struct {
+    int32_t S;
+    const uint8_t *frames;                       /* base of the frames */
+    int64_t frames_bytes;                        /* bytes readable behind it */
+    const int64_t *offsets;                      /* [S] byte offsets, DEVICE memory */
+    const int32_t *sizes;                        /* [S, 2] (height, width), DEVICE memory */
+    const int32_t *active;                       /* [S], DEVICE memory */
+    int32_t radius;                              /* 1..DETR_MOTION_MAX_RADIUS */
+    void *motion_state;                          /* detr_hip_track_motion_state_bytes(S) bytes, read and written */
+    int64_t motion_state_bytes;
+    void *state;                                 /* detr_hip_track_state_bytes(S) bytes, read and written */
+    int64_t state_bytes;
+    void *workspace;
+    int64_t workspace_bytes;
+    int32_t *out_motion;                         /* [S, 6] estimated, sx, sy, n, agree, f */
+    int32_t *status;                             /* [1] */
+} detr_track_motion_desc;
+int detr_hip_track_motion(const detr_track_motion_desc *d, void *stream);
+int64_t detr_hip_track_motion_state_bytes(int32_t streams);
+int64_t detr_hip_workspace_bytes_track_motion(const detr_track_motion_desc *d);
+
 #ifdef __cplusplus
 }
 #endif
