@@ -97,210 +97,88 @@ extern "C" int detr_hip_memset_zero(void *ptr, size_t bytes, void *stream) {
 // A foreign binder mirrors the descriptor structs of include/detr_hip.h by hand (ctypes / cgo / JNI).  This entry point
 // reports what THIS build of the library sees: for struct `which`, out[0] = sizeof and out[1..] = offsetof of every field in
 // declaration order.  The binding compares them with its own mirror at load time (detr_tf/_hip.py: check_struct_layouts).
+// A new descriptor takes one field list and one line of DETR_LAYOUTS; a field appended to a struct is appended to its list (the
+// static_assert below fails the build until it is).
 #include <stddef.h>
-#define DETR_OFF(S, f) (int32_t)offsetof(S, f)
-extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) {
-    int n = 0;
-#define DETR_PUT(v) do { if (n < cap) out[n] = (v); ++n; } while (0)
-    switch (which) {
-    case 0:   // detr_reduce_desc
-        DETR_PUT((int32_t)sizeof(detr_reduce_desc));
-        DETR_PUT(DETR_OFF(detr_reduce_desc, ws)); DETR_PUT(DETR_OFF(detr_reduce_desc, splits)); DETR_PUT(DETR_OFF(detr_reduce_desc, part_stride));
-        DETR_PUT(DETR_OFF(detr_reduce_desc, rows)); DETR_PUT(DETR_OFF(detr_reduce_desc, cols)); DETR_PUT(DETR_OFF(detr_reduce_desc, C));
-        DETR_PUT(DETR_OFF(detr_reduce_desc, ldc)); DETR_PUT(DETR_OFF(detr_reduce_desc, alpha)); DETR_PUT(DETR_OFF(detr_reduce_desc, scale));
-        DETR_PUT(DETR_OFF(detr_reduce_desc, rs_ws)); DETR_PUT(DETR_OFF(detr_reduce_desc, rs_out)); DETR_PUT(DETR_OFF(detr_reduce_desc, rs_alpha));
-        DETR_PUT(DETR_OFF(detr_reduce_desc, ts_bm)); DETR_PUT(DETR_OFF(detr_reduce_desc, ts_bn)); DETR_PUT(DETR_OFF(detr_reduce_desc, ts_tiles_n));
-        break;
-    case 1:   // detr_gemm_desc
-        DETR_PUT((int32_t)sizeof(detr_gemm_desc));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, M)); DETR_PUT(DETR_OFF(detr_gemm_desc, N)); DETR_PUT(DETR_OFF(detr_gemm_desc, K));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, A)); DETR_PUT(DETR_OFF(detr_gemm_desc, lda)); DETR_PUT(DETR_OFF(detr_gemm_desc, a_kcontig));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, B)); DETR_PUT(DETR_OFF(detr_gemm_desc, ldb)); DETR_PUT(DETR_OFF(detr_gemm_desc, b_kcontig));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, C)); DETR_PUT(DETR_OFF(detr_gemm_desc, ldc)); DETR_PUT(DETR_OFF(detr_gemm_desc, batch));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, batch_inner)); DETR_PUT(DETR_OFF(detr_gemm_desc, sA0)); DETR_PUT(DETR_OFF(detr_gemm_desc, sA1));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, sB0)); DETR_PUT(DETR_OFF(detr_gemm_desc, sB1)); DETR_PUT(DETR_OFF(detr_gemm_desc, sC0));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, sC1)); DETR_PUT(DETR_OFF(detr_gemm_desc, alpha)); DETR_PUT(DETR_OFF(detr_gemm_desc, scale));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, bias)); DETR_PUT(DETR_OFF(detr_gemm_desc, residual)); DETR_PUT(DETR_OFF(detr_gemm_desc, ldr));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, mask)); DETR_PUT(DETR_OFF(detr_gemm_desc, ldmask)); DETR_PUT(DETR_OFF(detr_gemm_desc, act));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, split_k)); DETR_PUT(DETR_OFF(detr_gemm_desc, workspace)); DETR_PUT(DETR_OFF(detr_gemm_desc, workspace_bytes));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, dropout_p)); DETR_PUT(DETR_OFF(detr_gemm_desc, dropout_seed)); DETR_PUT(DETR_OFF(detr_gemm_desc, compute));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, rowsum_a)); DETR_PUT(DETR_OFF(detr_gemm_desc, rowsum_alpha)); DETR_PUT(DETR_OFF(detr_gemm_desc, b_dtype));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, a_dtype)); DETR_PUT(DETR_OFF(detr_gemm_desc, c_dtype)); DETR_PUT(DETR_OFF(detr_gemm_desc, r_dtype));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, m_dtype)); DETR_PUT(DETR_OFF(detr_gemm_desc, dropout_step)); DETR_PUT(DETR_OFF(detr_gemm_desc, defer_out));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, maskbits_out)); DETR_PUT(DETR_OFF(detr_gemm_desc, ld_maskbits_out));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, ln_gamma)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_beta)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_y));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, ln_mean)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_rstd)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_add));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, ln_add_rows)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_y2)); DETR_PUT(DETR_OFF(detr_gemm_desc, ln_y16));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, ln_eps));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_h)); DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_w)); DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_ho));
-        DETR_PUT(DETR_OFF(detr_gemm_desc, res_sub_wo));
-        break;
-    case 2:   // detr_conv3x3_desc
-        DETR_PUT((int32_t)sizeof(detr_conv3x3_desc));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, N)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, Hi)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, Wi));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, Ci)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, Ho)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, Wo));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, Co)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, stride)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, pad));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, x)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, w)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, y));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, alpha)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, scale)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, bias));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, residual)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, mask)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, act));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, split)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, workspace)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, workspace_bytes));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, compute)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, w_dtype)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, x_dtype));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, y_dtype)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, r_dtype)); DETR_PUT(DETR_OFF(detr_conv3x3_desc, m_dtype));
-        DETR_PUT(DETR_OFF(detr_conv3x3_desc, maskbits_out));
-        break;
-    case 3:   // detr_stem_desc
-        DETR_PUT((int32_t)sizeof(detr_stem_desc));
-        DETR_PUT(DETR_OFF(detr_stem_desc, N)); DETR_PUT(DETR_OFF(detr_stem_desc, H)); DETR_PUT(DETR_OFF(detr_stem_desc, W));
-        DETR_PUT(DETR_OFF(detr_stem_desc, Ho)); DETR_PUT(DETR_OFF(detr_stem_desc, Wo)); DETR_PUT(DETR_OFF(detr_stem_desc, img));
-        DETR_PUT(DETR_OFF(detr_stem_desc, w)); DETR_PUT(DETR_OFF(detr_stem_desc, y)); DETR_PUT(DETR_OFF(detr_stem_desc, alpha));
-        DETR_PUT(DETR_OFF(detr_stem_desc, scale)); DETR_PUT(DETR_OFF(detr_stem_desc, bias)); DETR_PUT(DETR_OFF(detr_stem_desc, act));
-        DETR_PUT(DETR_OFF(detr_stem_desc, split)); DETR_PUT(DETR_OFF(detr_stem_desc, workspace)); DETR_PUT(DETR_OFF(detr_stem_desc, workspace_bytes));
-        DETR_PUT(DETR_OFF(detr_stem_desc, compute)); DETR_PUT(DETR_OFF(detr_stem_desc, w_dtype)); DETR_PUT(DETR_OFF(detr_stem_desc, y_dtype));
-        break;
-    case 4:   // detr_layernorm_desc
-        DETR_PUT((int32_t)sizeof(detr_layernorm_desc));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, rows)); DETR_PUT(DETR_OFF(detr_layernorm_desc, C)); DETR_PUT(DETR_OFF(detr_layernorm_desc, eps));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, x)); DETR_PUT(DETR_OFF(detr_layernorm_desc, gamma)); DETR_PUT(DETR_OFF(detr_layernorm_desc, beta));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, y)); DETR_PUT(DETR_OFF(detr_layernorm_desc, mean)); DETR_PUT(DETR_OFF(detr_layernorm_desc, rstd));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, add)); DETR_PUT(DETR_OFF(detr_layernorm_desc, add_rows)); DETR_PUT(DETR_OFF(detr_layernorm_desc, y2));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, y16)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dy)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dx));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, dgamma)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dbeta)); DETR_PUT(DETR_OFF(detr_layernorm_desc, workspace));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, workspace_bytes)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dx_add));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, dx_drop)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dropout_p)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dropout_site));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, dropout_step)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dx_drop16));
-        DETR_PUT(DETR_OFF(detr_layernorm_desc, defer_blocks_out)); DETR_PUT(DETR_OFF(detr_layernorm_desc, dy_add));
-        break;
-    case 5:   // detr_attn_desc
-        DETR_PUT((int32_t)sizeof(detr_attn_desc));
-        DETR_PUT(DETR_OFF(detr_attn_desc, B)); DETR_PUT(DETR_OFF(detr_attn_desc, H)); DETR_PUT(DETR_OFF(detr_attn_desc, T));
-        DETR_PUT(DETR_OFF(detr_attn_desc, S)); DETR_PUT(DETR_OFF(detr_attn_desc, q)); DETR_PUT(DETR_OFF(detr_attn_desc, ldq));
-        DETR_PUT(DETR_OFF(detr_attn_desc, k)); DETR_PUT(DETR_OFF(detr_attn_desc, ldk)); DETR_PUT(DETR_OFF(detr_attn_desc, v));
-        DETR_PUT(DETR_OFF(detr_attn_desc, ldv)); DETR_PUT(DETR_OFF(detr_attn_desc, o)); DETR_PUT(DETR_OFF(detr_attn_desc, ldo));
-        DETR_PUT(DETR_OFF(detr_attn_desc, lse)); DETR_PUT(DETR_OFF(detr_attn_desc, d_o)); DETR_PUT(DETR_OFF(detr_attn_desc, ldd_o));
-        DETR_PUT(DETR_OFF(detr_attn_desc, dq)); DETR_PUT(DETR_OFF(detr_attn_desc, lddq)); DETR_PUT(DETR_OFF(detr_attn_desc, dk));
-        DETR_PUT(DETR_OFF(detr_attn_desc, lddk)); DETR_PUT(DETR_OFF(detr_attn_desc, dv)); DETR_PUT(DETR_OFF(detr_attn_desc, lddv));
-        DETR_PUT(DETR_OFF(detr_attn_desc, delta)); DETR_PUT(DETR_OFF(detr_attn_desc, scale)); DETR_PUT(DETR_OFF(detr_attn_desc, dropout_p));
-        DETR_PUT(DETR_OFF(detr_attn_desc, dropout_site)); DETR_PUT(DETR_OFF(detr_attn_desc, dropout_step)); DETR_PUT(DETR_OFF(detr_attn_desc, compute));
-        DETR_PUT(DETR_OFF(detr_attn_desc, io_dtype)); DETR_PUT(DETR_OFF(detr_attn_desc, dropmask));
-        break;
-    case 6:   // detr_setloss_desc
-        DETR_PUT((int32_t)sizeof(detr_setloss_desc));
-        DETR_PUT(DETR_OFF(detr_setloss_desc, levels)); DETR_PUT(DETR_OFF(detr_setloss_desc, B)); DETR_PUT(DETR_OFF(detr_setloss_desc, Q));
-        DETR_PUT(DETR_OFF(detr_setloss_desc, C)); DETR_PUT(DETR_OFF(detr_setloss_desc, R)); DETR_PUT(DETR_OFF(detr_setloss_desc, logits));
-        DETR_PUT(DETR_OFF(detr_setloss_desc, sL_l)); DETR_PUT(DETR_OFF(detr_setloss_desc, sL_b)); DETR_PUT(DETR_OFF(detr_setloss_desc, sL_q));
-        DETR_PUT(DETR_OFF(detr_setloss_desc, boxes)); DETR_PUT(DETR_OFF(detr_setloss_desc, sB_l)); DETR_PUT(DETR_OFF(detr_setloss_desc, sB_b));
-        DETR_PUT(DETR_OFF(detr_setloss_desc, sB_q)); DETR_PUT(DETR_OFF(detr_setloss_desc, t_bbox)); DETR_PUT(DETR_OFF(detr_setloss_desc, t_class));
-        DETR_PUT(DETR_OFF(detr_setloss_desc, background_class));
-        break;
-    case 7:   // detr_input_desc
-        DETR_PUT((int32_t)sizeof(detr_input_desc));
-        DETR_PUT(DETR_OFF(detr_input_desc, B)); DETR_PUT(DETR_OFF(detr_input_desc, Hs)); DETR_PUT(DETR_OFF(detr_input_desc, Ws));
-        DETR_PUT(DETR_OFF(detr_input_desc, Hd)); DETR_PUT(DETR_OFF(detr_input_desc, Wd)); DETR_PUT(DETR_OFF(detr_input_desc, src));
-        DETR_PUT(DETR_OFF(detr_input_desc, src_batch_stride)); DETR_PUT(DETR_OFF(detr_input_desc, dst)); DETR_PUT(DETR_OFF(detr_input_desc, lut));
-        DETR_PUT(DETR_OFF(detr_input_desc, perm)); DETR_PUT(DETR_OFF(detr_input_desc, interpolation));
-        break;
-    case 8:   // detr_postprocess_desc
-        DETR_PUT((int32_t)sizeof(detr_postprocess_desc));
-        DETR_PUT(DETR_OFF(detr_postprocess_desc, B)); DETR_PUT(DETR_OFF(detr_postprocess_desc, Q)); DETR_PUT(DETR_OFF(detr_postprocess_desc, C));
-        DETR_PUT(DETR_OFF(detr_postprocess_desc, logits)); DETR_PUT(DETR_OFF(detr_postprocess_desc, sL_b)); DETR_PUT(DETR_OFF(detr_postprocess_desc, sL_q));
-        DETR_PUT(DETR_OFF(detr_postprocess_desc, boxes)); DETR_PUT(DETR_OFF(detr_postprocess_desc, sB_b)); DETR_PUT(DETR_OFF(detr_postprocess_desc, sB_q));
-        DETR_PUT(DETR_OFF(detr_postprocess_desc, background_class)); DETR_PUT(DETR_OFF(detr_postprocess_desc, bbox_format));
-        DETR_PUT(DETR_OFF(detr_postprocess_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_postprocess_desc, out_labels));
-        DETR_PUT(DETR_OFF(detr_postprocess_desc, out_scores)); DETR_PUT(DETR_OFF(detr_postprocess_desc, counts));
-        break;
-    case 9:   // detr_map_match_desc
-        DETR_PUT((int32_t)sizeof(detr_map_match_desc));
-        DETR_PUT(DETR_OFF(detr_map_match_desc, B)); DETR_PUT(DETR_OFF(detr_map_match_desc, Q)); DETR_PUT(DETR_OFF(detr_map_match_desc, R));
-        DETR_PUT(DETR_OFF(detr_map_match_desc, nb_class)); DETR_PUT(DETR_OFF(detr_map_match_desc, n_thr)); DETR_PUT(DETR_OFF(detr_map_match_desc, boxes));
-        DETR_PUT(DETR_OFF(detr_map_match_desc, labels)); DETR_PUT(DETR_OFF(detr_map_match_desc, scores)); DETR_PUT(DETR_OFF(detr_map_match_desc, counts));
-        DETR_PUT(DETR_OFF(detr_map_match_desc, sD_b)); DETR_PUT(DETR_OFF(detr_map_match_desc, t_bbox)); DETR_PUT(DETR_OFF(detr_map_match_desc, sT_b));
-        DETR_PUT(DETR_OFF(detr_map_match_desc, t_class)); DETR_PUT(DETR_OFF(detr_map_match_desc, sC_b)); DETR_PUT(DETR_OFF(detr_map_match_desc, thresholds));
-        DETR_PUT(DETR_OFF(detr_map_match_desc, rec_score)); DETR_PUT(DETR_OFF(detr_map_match_desc, rec_class)); DETR_PUT(DETR_OFF(detr_map_match_desc, rec_flags));
-        DETR_PUT(DETR_OFF(detr_map_match_desc, num_gt)); DETR_PUT(DETR_OFF(detr_map_match_desc, status));
-        break;
-    case 100:   // detr_detect_desc (appended descriptors count from 100, include/detr_hip.h)
-        DETR_PUT((int32_t)sizeof(detr_detect_desc));
-        DETR_PUT(DETR_OFF(detr_detect_desc, B)); DETR_PUT(DETR_OFF(detr_detect_desc, Q)); DETR_PUT(DETR_OFF(detr_detect_desc, C));
-        DETR_PUT(DETR_OFF(detr_detect_desc, logits)); DETR_PUT(DETR_OFF(detr_detect_desc, sL_b)); DETR_PUT(DETR_OFF(detr_detect_desc, sL_q));
-        DETR_PUT(DETR_OFF(detr_detect_desc, boxes)); DETR_PUT(DETR_OFF(detr_detect_desc, sB_b)); DETR_PUT(DETR_OFF(detr_detect_desc, sB_q));
-        DETR_PUT(DETR_OFF(detr_detect_desc, sizes)); DETR_PUT(DETR_OFF(detr_detect_desc, background_class));
-        DETR_PUT(DETR_OFF(detr_detect_desc, score_threshold)); DETR_PUT(DETR_OFF(detr_detect_desc, max_detections));
-        DETR_PUT(DETR_OFF(detr_detect_desc, bbox_format)); DETR_PUT(DETR_OFF(detr_detect_desc, clip));
-        DETR_PUT(DETR_OFF(detr_detect_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_detect_desc, out_labels));
-        DETR_PUT(DETR_OFF(detr_detect_desc, out_scores)); DETR_PUT(DETR_OFF(detr_detect_desc, out_query)); DETR_PUT(DETR_OFF(detr_detect_desc, counts));
-        break;
-    case 200:   // detr_tile_merge_desc (the second appended list counts from 200, include/detr_hip.h)
-        DETR_PUT((int32_t)sizeof(detr_tile_merge_desc));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, B)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, N)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, Q));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, C)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, logits)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, sL_b));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, sL_q)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, boxes)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, sB_b));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, sB_q)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, tile_start)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, tile_start_host));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, windows)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, sizes)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, background_class));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, score_threshold)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, max_detections)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, bbox_format));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, clip)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, match)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, class_agnostic));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, edge_margin)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, nms_threshold)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_boxes));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_labels)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_scores)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_query));
-        DETR_PUT(DETR_OFF(detr_tile_merge_desc, out_tile)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, counts)); DETR_PUT(DETR_OFF(detr_tile_merge_desc, status));
-        break;
-    case 300:   // detr_overlay_desc (the third appended list counts from 300, include/detr_hip.h)
-        DETR_PUT((int32_t)sizeof(detr_overlay_desc));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, B)); DETR_PUT(DETR_OFF(detr_overlay_desc, D)); DETR_PUT(DETR_OFF(detr_overlay_desc, src));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, src_off)); DETR_PUT(DETR_OFF(detr_overlay_desc, dst)); DETR_PUT(DETR_OFF(detr_overlay_desc, dst_off));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, sizes)); DETR_PUT(DETR_OFF(detr_overlay_desc, sizes_host)); DETR_PUT(DETR_OFF(detr_overlay_desc, boxes));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, labels)); DETR_PUT(DETR_OFF(detr_overlay_desc, scores)); DETR_PUT(DETR_OFF(detr_overlay_desc, counts));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, thickness)); DETR_PUT(DETR_OFF(detr_overlay_desc, label_alpha)); DETR_PUT(DETR_OFF(detr_overlay_desc, fill_alpha));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, colors)); DETR_PUT(DETR_OFF(detr_overlay_desc, n_colors)); DETR_PUT(DETR_OFF(detr_overlay_desc, names));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, name_len)); DETR_PUT(DETR_OFF(detr_overlay_desc, n_names)); DETR_PUT(DETR_OFF(detr_overlay_desc, name_cap));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, atlas)); DETR_PUT(DETR_OFF(detr_overlay_desc, n_glyph)); DETR_PUT(DETR_OFF(detr_overlay_desc, gh));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, gw)); DETR_PUT(DETR_OFF(detr_overlay_desc, glyph_digit0)); DETR_PUT(DETR_OFF(detr_overlay_desc, glyph_colon));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, glyph_dot)); DETR_PUT(DETR_OFF(detr_overlay_desc, scale)); DETR_PUT(DETR_OFF(detr_overlay_desc, heat));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, sH_b)); DETR_PUT(DETR_OFF(detr_overlay_desc, sH_y)); DETR_PUT(DETR_OFF(detr_overlay_desc, sH_x));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, Hf)); DETR_PUT(DETR_OFF(detr_overlay_desc, Wf)); DETR_PUT(DETR_OFF(detr_overlay_desc, map_step));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, map_valid)); DETR_PUT(DETR_OFF(detr_overlay_desc, map_scale)); DETR_PUT(DETR_OFF(detr_overlay_desc, lut));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, heat_alpha)); DETR_PUT(DETR_OFF(detr_overlay_desc, workspace)); DETR_PUT(DETR_OFF(detr_overlay_desc, workspace_bytes));
-        DETR_PUT(DETR_OFF(detr_overlay_desc, status));
-        break;
-    case 400:   // detr_track_desc (the fourth appended list counts from 400, include/detr_hip.h)
-        DETR_PUT((int32_t)sizeof(detr_track_desc));
-        DETR_PUT(DETR_OFF(detr_track_desc, S)); DETR_PUT(DETR_OFF(detr_track_desc, D)); DETR_PUT(DETR_OFF(detr_track_desc, state));
-        DETR_PUT(DETR_OFF(detr_track_desc, state_bytes)); DETR_PUT(DETR_OFF(detr_track_desc, boxes)); DETR_PUT(DETR_OFF(detr_track_desc, labels));
-        DETR_PUT(DETR_OFF(detr_track_desc, scores)); DETR_PUT(DETR_OFF(detr_track_desc, query)); DETR_PUT(DETR_OFF(detr_track_desc, counts));
-        DETR_PUT(DETR_OFF(detr_track_desc, active)); DETR_PUT(DETR_OFF(detr_track_desc, track_threshold)); DETR_PUT(DETR_OFF(detr_track_desc, new_threshold));
-        DETR_PUT(DETR_OFF(detr_track_desc, match_threshold)); DETR_PUT(DETR_OFF(detr_track_desc, low_match_threshold)); DETR_PUT(DETR_OFF(detr_track_desc, max_age));
-        DETR_PUT(DETR_OFF(detr_track_desc, min_hits)); DETR_PUT(DETR_OFF(detr_track_desc, alpha)); DETR_PUT(DETR_OFF(detr_track_desc, beta));
-        DETR_PUT(DETR_OFF(detr_track_desc, class_agnostic)); DETR_PUT(DETR_OFF(detr_track_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_track_desc, out_labels));
-        DETR_PUT(DETR_OFF(detr_track_desc, out_scores)); DETR_PUT(DETR_OFF(detr_track_desc, out_query)); DETR_PUT(DETR_OFF(detr_track_desc, out_ids));
-        DETR_PUT(DETR_OFF(detr_track_desc, out_hits)); DETR_PUT(DETR_OFF(detr_track_desc, out_counts)); DETR_PUT(DETR_OFF(detr_track_desc, status));
-        break;
-    case 500:   // detr_track_embed_desc (the fifth appended list counts from 500, include/detr_hip.h)
-        DETR_PUT((int32_t)sizeof(detr_track_embed_desc));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, S)); DETR_PUT(DETR_OFF(detr_track_embed_desc, D)); DETR_PUT(DETR_OFF(detr_track_embed_desc, state));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, state_bytes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, boxes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, labels));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, scores)); DETR_PUT(DETR_OFF(detr_track_embed_desc, query)); DETR_PUT(DETR_OFF(detr_track_embed_desc, counts));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, active)); DETR_PUT(DETR_OFF(detr_track_embed_desc, track_threshold)); DETR_PUT(DETR_OFF(detr_track_embed_desc, new_threshold));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, match_threshold)); DETR_PUT(DETR_OFF(detr_track_embed_desc, low_match_threshold)); DETR_PUT(DETR_OFF(detr_track_embed_desc, max_age));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, min_hits)); DETR_PUT(DETR_OFF(detr_track_embed_desc, alpha)); DETR_PUT(DETR_OFF(detr_track_embed_desc, beta));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, class_agnostic)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_boxes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_labels));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, out_scores)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_query)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_ids));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, out_hits)); DETR_PUT(DETR_OFF(detr_track_embed_desc, out_counts)); DETR_PUT(DETR_OFF(detr_track_embed_desc, status));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, embed)); DETR_PUT(DETR_OFF(detr_track_embed_desc, sE_s)); DETR_PUT(DETR_OFF(detr_track_embed_desc, sE_r));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, R)); DETR_PUT(DETR_OFF(detr_track_embed_desc, E)); DETR_PUT(DETR_OFF(detr_track_embed_desc, embed_state));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, embed_state_bytes)); DETR_PUT(DETR_OFF(detr_track_embed_desc, workspace)); DETR_PUT(DETR_OFF(detr_track_embed_desc, workspace_bytes));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, appearance_weight)); DETR_PUT(DETR_OFF(detr_track_embed_desc, reid)); DETR_PUT(DETR_OFF(detr_track_embed_desc, reid_threshold));
-        DETR_PUT(DETR_OFF(detr_track_embed_desc, momentum));
-        break;
-    case 600:   // detr_track_motion_desc (the sixth appended list counts from 600, include/detr_hip.h)
-        DETR_PUT((int32_t)sizeof(detr_track_motion_desc));
-        DETR_PUT(DETR_OFF(detr_track_motion_desc, S)); DETR_PUT(DETR_OFF(detr_track_motion_desc, frames)); DETR_PUT(DETR_OFF(detr_track_motion_desc, frames_bytes));
-        DETR_PUT(DETR_OFF(detr_track_motion_desc, offsets)); DETR_PUT(DETR_OFF(detr_track_motion_desc, sizes)); DETR_PUT(DETR_OFF(detr_track_motion_desc, active));
-        DETR_PUT(DETR_OFF(detr_track_motion_desc, radius)); DETR_PUT(DETR_OFF(detr_track_motion_desc, motion_state)); DETR_PUT(DETR_OFF(detr_track_motion_desc, motion_state_bytes));
-        DETR_PUT(DETR_OFF(detr_track_motion_desc, state)); DETR_PUT(DETR_OFF(detr_track_motion_desc, state_bytes)); DETR_PUT(DETR_OFF(detr_track_motion_desc, workspace));
-        DETR_PUT(DETR_OFF(detr_track_motion_desc, workspace_bytes)); DETR_PUT(DETR_OFF(detr_track_motion_desc, out_motion)); DETR_PUT(DETR_OFF(detr_track_motion_desc, status));
-        break;
-    default:
-        detr::set_error("struct_layout: unknown struct %d", which);
-        return -1;
+#define DETR_REDUCE_FIELDS(F) F(ws) F(splits) F(part_stride) F(rows) F(cols) F(C) F(ldc) F(alpha) F(scale) F(rs_ws) F(rs_out) \
+    F(rs_alpha) F(ts_bm) F(ts_bn) F(ts_tiles_n)
+#define DETR_GEMM_FIELDS(F) F(M) F(N) F(K) F(A) F(lda) F(a_kcontig) F(B) F(ldb) F(b_kcontig) F(C) F(ldc) F(batch) F(batch_inner) \
+    F(sA0) F(sA1) F(sB0) F(sB1) F(sC0) F(sC1) F(alpha) F(scale) F(bias) F(residual) F(ldr) F(mask) F(ldmask) F(act) F(split_k) \
+    F(workspace) F(workspace_bytes) F(dropout_p) F(dropout_seed) F(compute) F(rowsum_a) F(rowsum_alpha) F(b_dtype) F(a_dtype) \
+    F(c_dtype) F(r_dtype) F(m_dtype) F(dropout_step) F(defer_out) F(maskbits_out) F(ld_maskbits_out) F(ln_gamma) F(ln_beta) \
+    F(ln_y) F(ln_mean) F(ln_rstd) F(ln_add) F(ln_add_rows) F(ln_y2) F(ln_y16) F(ln_eps) F(res_sub_h) F(res_sub_w) F(res_sub_ho) \
+    F(res_sub_wo)
+#define DETR_CONV3X3_FIELDS(F) F(N) F(Hi) F(Wi) F(Ci) F(Ho) F(Wo) F(Co) F(stride) F(pad) F(x) F(w) F(y) F(alpha) F(scale) F(bias) \
+    F(residual) F(mask) F(act) F(split) F(workspace) F(workspace_bytes) F(compute) F(w_dtype) F(x_dtype) F(y_dtype) F(r_dtype) \
+    F(m_dtype) F(maskbits_out)
+#define DETR_STEM_FIELDS(F) F(N) F(H) F(W) F(Ho) F(Wo) F(img) F(w) F(y) F(alpha) F(scale) F(bias) F(act) F(split) F(workspace) \
+    F(workspace_bytes) F(compute) F(w_dtype) F(y_dtype)
+#define DETR_LAYERNORM_FIELDS(F) F(rows) F(C) F(eps) F(x) F(gamma) F(beta) F(y) F(mean) F(rstd) F(add) F(add_rows) F(y2) F(y16) \
+    F(dy) F(dx) F(dgamma) F(dbeta) F(workspace) F(workspace_bytes) F(dx_add) F(dx_drop) F(dropout_p) F(dropout_site) \
+    F(dropout_step) F(dx_drop16) F(defer_blocks_out) F(dy_add)
+#define DETR_ATTN_FIELDS(F) F(B) F(H) F(T) F(S) F(q) F(ldq) F(k) F(ldk) F(v) F(ldv) F(o) F(ldo) F(lse) F(d_o) F(ldd_o) F(dq) \
+    F(lddq) F(dk) F(lddk) F(dv) F(lddv) F(delta) F(scale) F(dropout_p) F(dropout_site) F(dropout_step) F(compute) F(io_dtype) \
+    F(dropmask)
+#define DETR_SETLOSS_FIELDS(F) F(levels) F(B) F(Q) F(C) F(R) F(logits) F(sL_l) F(sL_b) F(sL_q) F(boxes) F(sB_l) F(sB_b) F(sB_q) \
+    F(t_bbox) F(t_class) F(background_class)
+#define DETR_INPUT_FIELDS(F) F(B) F(Hs) F(Ws) F(Hd) F(Wd) F(src) F(src_batch_stride) F(dst) F(lut) F(perm) F(interpolation)
+#define DETR_POSTPROCESS_FIELDS(F) F(B) F(Q) F(C) F(logits) F(sL_b) F(sL_q) F(boxes) F(sB_b) F(sB_q) F(background_class) \
+    F(bbox_format) F(out_boxes) F(out_labels) F(out_scores) F(counts)
+#define DETR_MAP_MATCH_FIELDS(F) F(B) F(Q) F(R) F(nb_class) F(n_thr) F(boxes) F(labels) F(scores) F(counts) F(sD_b) F(t_bbox) \
+    F(sT_b) F(t_class) F(sC_b) F(thresholds) F(rec_score) F(rec_class) F(rec_flags) F(num_gt) F(status)
+#define DETR_DETECT_FIELDS(F) F(B) F(Q) F(C) F(logits) F(sL_b) F(sL_q) F(boxes) F(sB_b) F(sB_q) F(sizes) F(background_class) \
+    F(score_threshold) F(max_detections) F(bbox_format) F(clip) F(out_boxes) F(out_labels) F(out_scores) F(out_query) F(counts)
+#define DETR_TILE_MERGE_FIELDS(F) F(B) F(N) F(Q) F(C) F(logits) F(sL_b) F(sL_q) F(boxes) F(sB_b) F(sB_q) F(tile_start) \
+    F(tile_start_host) F(windows) F(sizes) F(background_class) F(score_threshold) F(max_detections) F(bbox_format) F(clip) \
+    F(match) F(class_agnostic) F(edge_margin) F(nms_threshold) F(out_boxes) F(out_labels) F(out_scores) F(out_query) F(out_tile) \
+    F(counts) F(status)
+#define DETR_OVERLAY_FIELDS(F) F(B) F(D) F(src) F(src_off) F(dst) F(dst_off) F(sizes) F(sizes_host) F(boxes) F(labels) F(scores) \
+    F(counts) F(thickness) F(label_alpha) F(fill_alpha) F(colors) F(n_colors) F(names) F(name_len) F(n_names) F(name_cap) F(atlas) \
+    F(n_glyph) F(gh) F(gw) F(glyph_digit0) F(glyph_colon) F(glyph_dot) F(scale) F(heat) F(sH_b) F(sH_y) F(sH_x) F(Hf) F(Wf) \
+    F(map_step) F(map_valid) F(map_scale) F(lut) F(heat_alpha) F(workspace) F(workspace_bytes) F(status)
+#define DETR_TRACK_FIELDS(F) F(S) F(D) F(state) F(state_bytes) F(boxes) F(labels) F(scores) F(query) F(counts) F(active) \
+    F(track_threshold) F(new_threshold) F(match_threshold) F(low_match_threshold) F(max_age) F(min_hits) F(alpha) F(beta) \
+    F(class_agnostic) F(out_boxes) F(out_labels) F(out_scores) F(out_query) F(out_ids) F(out_hits) F(out_counts) F(status)
+#define DETR_TRACK_EMBED_FIELDS(F) DETR_TRACK_FIELDS(F) F(embed) F(sE_s) F(sE_r) F(R) F(E) F(embed_state) F(embed_state_bytes) \
+    F(workspace) F(workspace_bytes) F(appearance_weight) F(reid) F(reid_threshold) F(momentum)
+#define DETR_TRACK_MOTION_FIELDS(F) F(S) F(frames) F(frames_bytes) F(offsets) F(sizes) F(active) F(radius) F(motion_state) \
+    F(motion_state_bytes) F(state) F(state_bytes) F(workspace) F(workspace_bytes) F(out_motion) F(status)
+#define DETR_CONV3X3D_FIELDS(F) DETR_CONV3X3_FIELDS(F) F(dilation)
+#define DETR_COCO_MATCH_FIELDS(F) F(B) F(Q) F(R) F(nb_class) F(n_thr) F(n_area) F(boxes) F(labels) F(scores) F(counts) F(sD_b) \
+    F(t_bbox) F(sT_b) F(t_class) F(sC_b) F(t_crowd) F(t_area) F(sM_b) F(sizes) F(thresholds) F(area_ranges) F(rec_score) \
+    F(rec_class) F(rec_rank) F(rec_flags) F(npig) F(status)
+// id, struct, field list.  The ids are ABI (include/detr_hip.h); the id behind each one stays unknown.
+#define DETR_LAYOUTS(X) \
+    X(0, detr_reduce_desc, DETR_REDUCE_FIELDS) X(1, detr_gemm_desc, DETR_GEMM_FIELDS) X(2, detr_conv3x3_desc, DETR_CONV3X3_FIELDS) \
+    X(3, detr_stem_desc, DETR_STEM_FIELDS) X(4, detr_layernorm_desc, DETR_LAYERNORM_FIELDS) X(5, detr_attn_desc, DETR_ATTN_FIELDS) \
+    X(6, detr_setloss_desc, DETR_SETLOSS_FIELDS) X(7, detr_input_desc, DETR_INPUT_FIELDS) \
+    X(8, detr_postprocess_desc, DETR_POSTPROCESS_FIELDS) X(9, detr_map_match_desc, DETR_MAP_MATCH_FIELDS) \
+    X(100, detr_detect_desc, DETR_DETECT_FIELDS) X(200, detr_tile_merge_desc, DETR_TILE_MERGE_FIELDS) \
+    X(300, detr_overlay_desc, DETR_OVERLAY_FIELDS) X(400, detr_track_desc, DETR_TRACK_FIELDS) \
+    X(500, detr_track_embed_desc, DETR_TRACK_EMBED_FIELDS) X(600, detr_track_motion_desc, DETR_TRACK_MOTION_FIELDS) \
+    X(700, detr_conv3x3d_desc, DETR_CONV3X3D_FIELDS) X(800, detr_coco_match_desc, DETR_COCO_MATCH_FIELDS)
+// per struct: values[] = {sizeof, offsetof ...} as the entry point reports them, and ends[] = where each field ends -- the last
+// listed field, rounded up to the struct's alignment, must close the struct
+#define DETR_OFF(f) (int32_t)offsetof(ST, f),
+#define DETR_END(f) offsetof(ST, f) + sizeof(ST::f),
+#define DETR_DEFINE(id, S, FIELDS)                                                                                          \
+    namespace layout_##S {                                                                                                  \
+    using ST = S;                                                                                                           \
+    constexpr int32_t values[] = {(int32_t)sizeof(ST), FIELDS(DETR_OFF)};                                                   \
+    constexpr size_t ends[] = {FIELDS(DETR_END)};                                                                           \
+    constexpr size_t last = ends[sizeof(ends) / sizeof(ends[0]) - 1];                                                       \
+    static_assert((last + alignof(ST) - 1) / alignof(ST) * alignof(ST) == sizeof(ST), #S ": its field list stops before the struct ends"); \
     }
-#undef DETR_PUT
-    return n;        // number of values (may exceed cap: call again with a larger buffer)
+DETR_LAYOUTS(DETR_DEFINE)
+#define DETR_ENTRY(id, S, FIELDS) {id, layout_##S::values, (int32_t)(sizeof(layout_##S::values) / sizeof(int32_t))},
+static const struct { int32_t id; const int32_t *values; int32_t count; } g_layouts[] = {DETR_LAYOUTS(DETR_ENTRY)};
+
+extern "C" int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap) {
+    for (const auto &e : g_layouts) {
+        if (e.id != which) continue;
+        for (int32_t i = 0; i < e.count && i < cap; ++i) out[i] = e.values[i];
+        return e.count;        // number of values (may exceed cap: call again with a larger buffer)
+    }
+    detr::set_error("struct_layout: unknown struct %d", which);
+    return -1;
 }

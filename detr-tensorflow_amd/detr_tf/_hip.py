@@ -336,16 +336,10 @@ _SIGNATURES_I64 = {
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
-# detr_hip_struct_layout's `which` -> mirror: 0..9 are the descriptors of ABI 9, the ones appended since are numbered 100, 200, 300
-# (include/detr_hip.h), so the id behind each of them stays unknown to the library
+# detr_hip_struct_layout's `which` -> mirror, every descriptor struct of include/detr_hip.h (the table above the entry point there)
 LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: LayerNormDesc, 5: AttnDesc, 6: SetLossDesc, 7: InputDesc,
-                  8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc}
-# the descriptors appended after detr_overlay_desc, by the same numbering; check_struct_layouts walks both tables
-LAYOUT_STRUCTS_APPENDED = {400: TrackDesc}
-# and the one behind detr_track_desc (a fifth list, 500), in a table of its own for the same reason
-LAYOUT_STRUCTS_APPENDED_500 = {500: TrackEmbedDesc}
-# and detr_track_motion_desc (a sixth list, 600)
-LAYOUT_STRUCTS_APPENDED_600 = {600: TrackMotionDesc}
+                  8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc, 400: TrackDesc,
+                  500: TrackEmbedDesc, 600: TrackMotionDesc, 700: Conv3x3DDesc, 800: CocoMatchDesc}
 
 _lib = None
 
@@ -580,12 +574,13 @@ def struct_layout_mirror(S):
 def check_struct_layouts(lib):
     """The descriptor structs are mirrored by hand above: compare every size / field offset with what the library was
     compiled with (detr_hip_struct_layout) -- a drifted mirror would silently scramble arguments."""
-    for which, S in sorted({**LAYOUT_STRUCTS, **LAYOUT_STRUCTS_APPENDED, **LAYOUT_STRUCTS_APPENDED_500, **LAYOUT_STRUCTS_APPENDED_600}.items()):
+    for which, S in sorted(LAYOUT_STRUCTS.items()):
         want = struct_layout_mirror(S)
-        buf = (c_int32 * 96)()
-        n = lib.detr_hip_struct_layout(which, buf, 96)
-        got = list(buf[:max(n, 0)])
-        if n != len(want) or got != want:
+        n = max(lib.detr_hip_struct_layout(which, None, 0), 0)                      # the count first, then a buffer of that size
+        buf = (c_int32 * n)()
+        lib.detr_hip_struct_layout(which, buf, n)
+        got = list(buf)
+        if got != want:
             raise RuntimeError(f"ctypes mirror of struct {which} ({S.__name__}) does not match {LIB_PATH}: library {got}, mirror {want}")
 
 

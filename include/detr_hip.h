@@ -36,12 +36,16 @@ int detr_hip_abi_version(void);
  * read from the environment ONCE, when the library is loaded -- never on the launch path.  A process that changes one afterwards
  * (tests, tuning scripts) calls this to have it re-read. */
 int detr_hip_reload_tuning(void);
-/* ABI self-check for hand-written mirrors of the descriptor structs below (ctypes / cgo / JNI): for struct `which`
- * (0 detr_reduce_desc, 1 detr_gemm_desc, 2 detr_conv3x3_desc, 3 detr_stem_desc, 4 detr_layernorm_desc, 5 detr_attn_desc,
- * 6 detr_setloss_desc, 7 detr_input_desc, 8 detr_postprocess_desc, 9 detr_map_match_desc) writes out[0] = sizeof, out[1..] = offsetof of every field in
- * declaration order, and returns the number of values (negative: unknown struct).  Descriptors appended after ABI 9 are numbered
- * from 100 (100 detr_detect_desc): binders probe the id behind the last one they know to find the end of the first list.  A second
- * appended list counts from 200 (200 detr_tile_merge_desc), so that 101 stays the unknown id behind the first one. */
+/* ABI self-check for hand-written mirrors of the descriptor structs below (ctypes / cgo / JNI): for struct `which` writes
+ * out[0] = sizeof, out[1..] = offsetof of every field in declaration order, and returns the number of values even when that
+ * exceeds `cap` (never more than `cap` values are written; call again with a larger buffer).  An unknown id returns a negative
+ * code and leaves a message.  The ids are opaque numbers, and the id behind each known one stays unknown (10..99, 101, 201, ...,
+ * 801): a binder may probe it.
+ *     0 detr_reduce_desc      1 detr_gemm_desc        2 detr_conv3x3_desc       3 detr_stem_desc       4 detr_layernorm_desc
+ *     5 detr_attn_desc        6 detr_setloss_desc     7 detr_input_desc         8 detr_postprocess_desc
+ *     9 detr_map_match_desc 100 detr_detect_desc    200 detr_tile_merge_desc  300 detr_overlay_desc  400 detr_track_desc
+ *   500 detr_track_embed_desc                       600 detr_track_motion_desc
+ *   700 detr_conv3x3d_desc  800 detr_coco_match_desc */
 int detr_hip_struct_layout(int32_t which, int32_t *out, int32_t cap);
 /* zero fill of accumulators (an ordinary kernel: a captured hipMemsetAsync node did not replay reliably) */
 int detr_hip_memset_zero(void *ptr, size_t bytes, void *stream);
@@ -955,7 +959,7 @@ int64_t detr_hip_workspace_bytes_overlay(const detr_overlay_desc *d);
  *   float x[DETR_TRACK_MAX][4]; float v[DETR_TRACK_MAX][4]; int64_t label[DETR_TRACK_MAX]; float score[DETR_TRACK_MAX];
  *   int32_t id[DETR_TRACK_MAX], hits[DETR_TRACK_MAX], miss[DETR_TRACK_MAX], confirmed[DETR_TRACK_MAX]; int32_t frame, next_id, pad[2].
  * Limits: S 1..65535, D 1..1024; thresholds, alpha, beta finite; max_age >= 0; min_hits >= 1; boxes, out_boxes, state 16-byte aligned.
- * detr_hip_struct_layout knows detr_track_desc as 400 (a fourth appended list; 300 is detr_overlay_desc).
+ * detr_hip_struct_layout knows detr_track_desc as 400.
  * ------------------------------------------------------------------------------------------- */
 #define DETR_TRACK_MAX 256
 #define DETR_TRACK_FULL 1
@@ -1022,7 +1026,7 @@ int64_t detr_hip_track_state_bytes(int32_t streams);
  *   similarities [S][DETR_TRACK_MAX][D] of the pairs that pass a walk's gate, filled by whole waves before the walk.
  * Limits: those of detr_hip_track; R >= 1; E a multiple of 4 in 4..512; sE_r >= E, sE_s >= 0; embed, embed_state and workspace
  *   16-byte aligned; appearance_weight in [0, 1]; reid 0 or 1; reid_threshold finite; momentum in [0, 1].
- * detr_hip_struct_layout knows detr_track_embed_desc as 500 (a fifth appended list).
+ * detr_hip_struct_layout knows detr_track_embed_desc as 500.
  * ------------------------------------------------------------------------------------------- */
 #define DETR_TRACK_BAD_EMBED 4
 typedef struct {
@@ -1103,7 +1107,7 @@ int64_t detr_hip_workspace_bytes_track_embed(const detr_track_embed_desc *d);
  *   malformed), 16-byte aligned: the votes.
  * Limits: S 1..65535; radius 1..16; frames_bytes >= 1; motion_state, state and workspace 16-byte aligned, offsets 8-byte aligned.
  * No float atomics; integer atomics on *status and inside a workgroup's LDS only.  Nothing is read or written out of bounds for any
- * size or offset.  detr_hip_struct_layout knows detr_track_motion_desc as 600 (a sixth appended list).
+ * size or offset.  detr_hip_struct_layout knows detr_track_motion_desc as 600.
  * ------------------------------------------------------------------------------------------- */
 #define DETR_MOTION_SIDE 384
 #define DETR_MOTION_BLOCK 16

@@ -20,15 +20,21 @@ int main(void) {
 
     /* layout self-check: sizeof must agree with this translation unit's view of the header */
     int32_t buf[96];
-    const size_t sizes[9] = {sizeof(detr_reduce_desc), sizeof(detr_gemm_desc), sizeof(detr_conv3x3_desc), sizeof(detr_stem_desc),
-                             sizeof(detr_layernorm_desc), sizeof(detr_attn_desc), sizeof(detr_setloss_desc), sizeof(detr_input_desc),
-                             sizeof(detr_postprocess_desc)};
-    for (int w = 0; w < 9; ++w) {
+    const struct { int32_t id; size_t size; } structs[18] = {
+        {0, sizeof(detr_reduce_desc)}, {1, sizeof(detr_gemm_desc)}, {2, sizeof(detr_conv3x3_desc)}, {3, sizeof(detr_stem_desc)},
+        {4, sizeof(detr_layernorm_desc)}, {5, sizeof(detr_attn_desc)}, {6, sizeof(detr_setloss_desc)}, {7, sizeof(detr_input_desc)},
+        {8, sizeof(detr_postprocess_desc)}, {9, sizeof(detr_map_match_desc)}, {100, sizeof(detr_detect_desc)},
+        {200, sizeof(detr_tile_merge_desc)}, {300, sizeof(detr_overlay_desc)}, {400, sizeof(detr_track_desc)},
+        {500, sizeof(detr_track_embed_desc)}, {600, sizeof(detr_track_motion_desc)}, {700, sizeof(detr_conv3x3d_desc)},
+        {800, sizeof(detr_coco_match_desc)}};
+    for (int i = 0; i < 18; ++i) {
+        const int32_t w = structs[i].id;
         const int n = detr_hip_struct_layout(w, buf, 96);
         EXPECT(n > 1 && n <= 96);
-        EXPECT((size_t)buf[0] == sizes[w]);
-        int32_t tiny[2] = {-1, -1};                     /* a short buffer is never overrun; the count is still reported */
-        EXPECT(detr_hip_struct_layout(w, tiny, 2) == n && tiny[0] == buf[0] && tiny[1] == buf[1]);
+        EXPECT((size_t)buf[0] == structs[i].size);
+        int32_t tiny[3] = {-1, -1, -1};                 /* a short buffer is never overrun; the count is still reported */
+        EXPECT(detr_hip_struct_layout(w, tiny, 2) == n && tiny[0] == buf[0] && tiny[1] == buf[1] && tiny[2] == -1);
+        if (w >= 9) EXPECT(detr_hip_struct_layout(w + 1, buf, 96) < 0 && strlen(detr_hip_last_error()) > 0);   /* 10, 101, ... 801 stay unknown */
     }
     EXPECT(detr_hip_struct_layout(-1, buf, 96) < 0 && strlen(detr_hip_last_error()) > 0);
 

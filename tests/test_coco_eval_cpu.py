@@ -1,11 +1,10 @@
-"""COCO-protocol evaluation, host side (no GPU): the C entry point detr_hip_coco_match (symbol, descriptor layout against a C
-program compiled with the header, every argument check), COCOAccumulator against the loop oracle tests/coco_eval_ref.py, the
+"""COCO-protocol evaluation, host side (no GPU): the C entry point detr_hip_coco_match (symbol, the descriptor's array sizes against the
+header, every argument check), COCOAccumulator against the loop oracle tests/coco_eval_ref.py, the
 hand-computed answers that pin the COCO semantics, and the loader's keep_crowd / with_meta / shuffle / drop_remainder."""
 import ctypes
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,16 +13,12 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import abi_header  # noqa: E402
 import coco_eval_ref as CR  # noqa: E402
 from map_match_ref import targets_to_yxyx  # noqa: E402
 
 
-def _lib():
-    from detr_tf import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as ge
-        ge.build()
-    return _hip, _hip.load()
+_lib = abi_header.hip_lib
 
 
 # ---- the C entry point -----------------------------------------------------------------------------------------------------------
@@ -42,20 +37,11 @@ def test_coco_match_symbol_declared_exported_appended():
     assert set(_hip.COCO_BAD) == {1, 2, 4, 8, 16} and "#define DETR_COCO_BAD_SIZE 16" in hdr
 
 
-def test_coco_match_desc_layout_matches_the_header(tmp_path):
+def test_coco_match_desc_layout_matches_the_header():
     _hip, _ = _lib()
-    names = [f[0] for f in _hip.CocoMatchDesc._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "detr_hip.h"\nint main(void) {\n'
-                   '  printf("%zu\\n", sizeof(detr_coco_match_desc));\n'
-                   + "".join(f'  printf("%zu\\n", offsetof(detr_coco_match_desc, {n}));\n' for n in names)
-                   + '  printf("%zu %zu\\n", sizeof(((detr_coco_match_desc *)0)->thresholds), sizeof(((detr_coco_match_desc *)0)->area_ranges));\n'
-                   "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).split()
-    got, (thr_bytes, area_bytes) = [int(v) for v in out[:-2]], [int(v) for v in out[-2:]]
-    assert got == _hip.struct_layout_mirror(_hip.CocoMatchDesc)
+    assert _hip.LAYOUT_STRUCTS[800] is _hip.CocoMatchDesc                      # sizeof / offsetof through gcc, for every struct: test_abi_layout_cpu.py
+    fields = dict(abi_header.header_structs()["detr_coco_match_desc"])        # the header's arrays, DETR_COCO_MAX_* resolved
+    thr_bytes, area_bytes = ctypes.sizeof(fields["thresholds"]), ctypes.sizeof(fields["area_ranges"])
     assert thr_bytes == 80 == ctypes.sizeof(_hip.CocoMatchDesc().thresholds) and area_bytes == 64 == ctypes.sizeof(_hip.CocoMatchDesc().area_ranges)
 
 

@@ -9,15 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _lib():
-    from detr_tf import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as ge
-        ge.build()
-    return _hip, _hip.load()
+_lib = abi_header.hip_lib
 
 
 class _Cfg:
@@ -169,36 +166,9 @@ def test_detect_symbol_declared_exported_appended():
 
 def test_detect_desc_layout_matches_the_header():
     _hip, lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "detr_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} detr_detect_desc;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        base = re.match(r"(const\s+)?(\w+)\s+(.*)", decl)
-        for item in base.group(3).split(","):
-            item = item.strip()
-            fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
-    assert fields == list(_hip.DetectDesc._fields_)                            # names, order and types of the C declaration
+    assert abi_header.header_structs()["detr_detect_desc"] == list(_hip.DetectDesc._fields_)    # names, order and types of the C declaration
     assert {w: S for w, S in _hip.LAYOUT_STRUCTS.items() if 100 <= w < 200} == {100: _hip.DetectDesc}
-    buf = (ctypes.c_int32 * 96)()
-    n = lib.detr_hip_struct_layout(100, buf, 96)
-    want = _hip.struct_layout_mirror(_hip.DetectDesc)
-    assert n == len(want) == 1 + len(_hip.DetectDesc._fields_) and list(buf[:n]) == want
-    assert lib.detr_hip_struct_layout(101, buf, 96) < 0
-    _hip.check_struct_layouts(lib)                                             # the load-time check covers it
-
-    class Drifted(ctypes.Structure):                                           # score_threshold widened: every later offset moves
-        _fields_ = [(f, (ctypes.c_double if f == "score_threshold" else t)) for f, t in _hip.DetectDesc._fields_]
-    try:
-        _hip.LAYOUT_STRUCTS[100] = Drifted
-        with pytest.raises(RuntimeError, match="Drifted"):
-            _hip.check_struct_layouts(lib)
-    finally:
-        _hip.LAYOUT_STRUCTS[100] = _hip.DetectDesc
+    _hip.check_struct_layouts(lib)                     # the load-time check covers it; library, unknown ids, drift: test_abi_layout_cpu.py
 
 
 def test_detect_rejects_bad_arguments_without_a_gpu():

@@ -192,23 +192,10 @@ def _hip_lib():
 
 
 def test_ctypes_mirrors_match_the_library_struct_layouts():
-    """Boundary hygiene: every descriptor struct mirrored by hand in detr_tf/_hip.py has the size and the
-    field offsets the library was compiled with (detr_hip_struct_layout); a deliberately drifted mirror is caught."""
-    import ctypes
+    """Boundary hygiene: the load-time check of every mirror in detr_tf/_hip.py; id by id: test_abi_layout_cpu.py."""
     _hip, lib = _hip_lib()
     assert sorted(_hip.LAYOUT_STRUCTS)[:10] == list(range(10))
-    for which, S in sorted(_hip.LAYOUT_STRUCTS.items()):
-        buf = (ctypes.c_int32 * 96)()
-        n = lib.detr_hip_struct_layout(which, buf, 96)
-        assert n == 1 + len(S._fields_), (S.__name__, n)
-        assert list(buf[:n]) == _hip.struct_layout_mirror(S), S.__name__
-    assert lib.detr_hip_struct_layout(99, (ctypes.c_int32 * 4)(), 4) < 0
-
-    class Drifted(ctypes.Structure):          # detr_reduce_desc with `rows` widened: every later offset moves
-        _fields_ = [(n, (ctypes.c_int64 if n == "rows" else t)) for n, t in _hip.ReduceDesc._fields_]
-    buf = (ctypes.c_int32 * 96)()
-    n = lib.detr_hip_struct_layout(0, buf, 96)
-    assert list(buf[:n]) != _hip.struct_layout_mirror(Drifted)
+    _hip.check_struct_layouts(lib)
 
 
 def test_workspace_bytes_queries_and_tuning_reload():

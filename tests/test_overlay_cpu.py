@@ -8,15 +8,14 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import overlay_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
-def _lib():
-    from detr_tf import _hip
-    return _hip, _hip.load()
+_lib = abi_header.hip_lib
 
 
 # ---- the C entry point ---------------------------------------------------------------------------------------------------------
@@ -38,38 +37,10 @@ def test_overlay_symbol_declared_exported_appended():
 
 def test_overlay_desc_layout_matches_the_header():
     _hip, lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "detr_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} detr_overlay_desc;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        base = re.match(r"(const\s+)?(\w+)\s+(.*)", decl)
-        for item in base.group(3).split(","):
-            item = item.strip()
-            fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
-    assert fields == list(_hip.OverlayDesc._fields_)                            # names, order and types of the C declaration
-    assert {w: S for w, S in _hip.LAYOUT_STRUCTS.items() if w >= 100} == {100: _hip.DetectDesc, 200: _hip.TileMergeDesc, 300: _hip.OverlayDesc}
+    assert abi_header.header_structs()["detr_overlay_desc"] == list(_hip.OverlayDesc._fields_)     # names, order and types of the C declaration
+    assert {w: S for w, S in _hip.LAYOUT_STRUCTS.items() if 100 <= w <= 300} == {100: _hip.DetectDesc, 200: _hip.TileMergeDesc, 300: _hip.OverlayDesc}
     assert sorted(w for w in _hip.LAYOUT_STRUCTS if w < 100) == list(range(10))
-    buf = (ctypes.c_int32 * 96)()
-    n = lib.detr_hip_struct_layout(300, buf, 96)
-    want = _hip.struct_layout_mirror(_hip.OverlayDesc)
-    assert n == len(want) == 1 + len(_hip.OverlayDesc._fields_) and list(buf[:n]) == want
-    for unknown in (99, 101, 201, 301):
-        assert lib.detr_hip_struct_layout(unknown, buf, 96) < 0
-    _hip.check_struct_layouts(lib)                                              # the load-time check covers it
-
-    class Drifted(ctypes.Structure):                                            # thickness widened: every later offset moves
-        _fields_ = [(f, (ctypes.c_int64 if f == "thickness" else t)) for f, t in _hip.OverlayDesc._fields_]
-    try:
-        _hip.LAYOUT_STRUCTS[300] = Drifted
-        with pytest.raises(RuntimeError, match="Drifted"):
-            _hip.check_struct_layouts(lib)
-    finally:
-        _hip.LAYOUT_STRUCTS[300] = _hip.OverlayDesc
+    _hip.check_struct_layouts(lib)                     # the load-time check covers it; library, unknown ids, drift: test_abi_layout_cpu.py
 
 
 def test_overlay_rejects_bad_arguments_without_a_gpu():

@@ -10,15 +10,14 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import abi_header
 import tile_merge_ref as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
-def _lib():
-    from detr_tf import _hip
-    return _hip, _hip.load()
+_lib = abi_header.hip_lib
 
 
 # ---- tile_records --------------------------------------------------------------------------------------------------------------
@@ -192,36 +191,9 @@ def test_tile_merge_symbol_declared_exported_appended():
 
 def test_tile_merge_desc_layout_matches_the_header():
     _hip, lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "detr_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} detr_tile_merge_desc;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        base = re.match(r"(const\s+)?(\w+)\s+(.*)", decl)
-        for item in base.group(3).split(","):
-            item = item.strip()
-            fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
-    assert fields == list(_hip.TileMergeDesc._fields_)                          # names, order and types of the C declaration
+    assert abi_header.header_structs()["detr_tile_merge_desc"] == list(_hip.TileMergeDesc._fields_)   # names, order and types of the C declaration
     assert {w: S for w, S in _hip.LAYOUT_STRUCTS.items() if 200 <= w < 300} == {200: _hip.TileMergeDesc}
-    buf = (ctypes.c_int32 * 96)()
-    n = lib.detr_hip_struct_layout(200, buf, 96)
-    want = _hip.struct_layout_mirror(_hip.TileMergeDesc)
-    assert n == len(want) == 1 + len(_hip.TileMergeDesc._fields_) and list(buf[:n]) == want
-    assert lib.detr_hip_struct_layout(201, buf, 96) < 0
-    _hip.check_struct_layouts(lib)                                              # the load-time check covers it
-
-    class Drifted(ctypes.Structure):                                            # edge_margin widened: every later offset moves
-        _fields_ = [(f, (ctypes.c_double if f == "edge_margin" else t)) for f, t in _hip.TileMergeDesc._fields_]
-    try:
-        _hip.LAYOUT_STRUCTS[200] = Drifted
-        with pytest.raises(RuntimeError, match="Drifted"):
-            _hip.check_struct_layouts(lib)
-    finally:
-        _hip.LAYOUT_STRUCTS[200] = _hip.TileMergeDesc
+    _hip.check_struct_layouts(lib)                     # the load-time check covers it; library, unknown ids, drift: test_abi_layout_cpu.py
 
 
 def test_tile_merge_rejects_bad_arguments_without_a_gpu():

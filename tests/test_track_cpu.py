@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import track_cases as C
 import track_ref as R
 
@@ -16,9 +17,7 @@ F = np.float32
 SCENARIOS = C.scenarios()
 
 
-def _lib():
-    from detr_tf import _hip
-    return _hip, _hip.load()
+_lib = abi_header.hip_lib
 
 
 def _run(name):
@@ -166,36 +165,9 @@ def test_track_symbols_declared_exported_appended():
 def test_track_desc_layout_and_state_size_match_the_header():
     _hip, lib = _lib()
     from detr_tf import inference
-    hdr = open(os.path.join(ROOT, "include", "detr_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} detr_track_desc;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        base = re.match(r"(const\s+)?(\w+)\s+(.*)", decl)
-        for item in base.group(3).split(","):
-            item = item.strip()
-            fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
-    assert fields == list(_hip.TrackDesc._fields_)                             # names, order and types of the C declaration
-    assert _hip.LAYOUT_STRUCTS_APPENDED == {400: _hip.TrackDesc}
-    buf = (ctypes.c_int32 * 96)()
-    n = lib.detr_hip_struct_layout(400, buf, 96)
-    want = _hip.struct_layout_mirror(_hip.TrackDesc)
-    assert n == len(want) == 1 + len(_hip.TrackDesc._fields_) and list(buf[:n]) == want
-    assert lib.detr_hip_struct_layout(401, buf, 96) < 0
-    _hip.check_struct_layouts(lib)                                             # the load-time check covers it
-
-    class Drifted(ctypes.Structure):                                           # alpha widened: every later offset moves
-        _fields_ = [(f, (ctypes.c_double if f == "alpha" else t)) for f, t in _hip.TrackDesc._fields_]
-    try:
-        _hip.LAYOUT_STRUCTS_APPENDED[400] = Drifted
-        with pytest.raises(RuntimeError, match="Drifted"):
-            _hip.check_struct_layouts(lib)
-    finally:
-        _hip.LAYOUT_STRUCTS_APPENDED[400] = _hip.TrackDesc
+    assert abi_header.header_structs()["detr_track_desc"] == list(_hip.TrackDesc._fields_)       # names, order and types of the C declaration
+    assert _hip.LAYOUT_STRUCTS[400] is _hip.TrackDesc
+    _hip.check_struct_layouts(lib)                     # the load-time check covers it; library, unknown ids, drift: test_abi_layout_cpu.py
     # the state: the header's layout, field by field, is the binding's record, and the library sizes it
     T = _hip.TRACK_MAX
     per_stream = 2 * T * 4 * 4 + T * 8 + T * 4 + 4 * T * 4 + 4 * 4

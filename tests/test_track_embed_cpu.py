@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import track_cases as C
 import track_embed_cases as EC
 import track_embed_ref as ER
@@ -19,9 +20,7 @@ F = np.float32
 SCENARIOS = EC.scenarios()
 
 
-def _lib():
-    from detr_tf import _hip
-    return _hip, _hip.load()
+_lib = abi_header.hip_lib
 
 
 def _ids(results):
@@ -172,44 +171,15 @@ def test_track_embed_symbols_declared_exported_appended():
 
 def check_track_embed_desc_layout():
     _hip, lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "detr_hip.h")).read()
-
-    def fields_of(name):
-        body = re.search(r"typedef struct \{([^}]*)\} %s;" % name, hdr).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
-        fields = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            base = re.match(r"(const\s+)?(\w+)\s+(.*)", decl)
-            for item in base.group(3).split(","):
-                item = item.strip()
-                fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
-        return fields
-
-    fields = fields_of("detr_track_embed_desc")
+    fields_of = abi_header.header_structs()
+    fields = fields_of["detr_track_embed_desc"]
     assert fields == list(_hip.TrackEmbedDesc._fields_)                        # names, order and types of the C declaration
-    assert fields[:len(_hip.TrackDesc._fields_)] == fields_of("detr_track_desc") == list(_hip.TrackDesc._fields_)     # every field of detr_track_desc first
+    assert fields[:len(_hip.TrackDesc._fields_)] == fields_of["detr_track_desc"] == list(_hip.TrackDesc._fields_)     # every field of detr_track_desc first
     assert [f for f, _ in fields[len(_hip.TrackDesc._fields_):]] == ["embed", "sE_s", "sE_r", "R", "E", "embed_state", "embed_state_bytes", "workspace",
                                                                    "workspace_bytes", "appearance_weight", "reid", "reid_threshold", "momentum"]
-    assert _hip.LAYOUT_STRUCTS_APPENDED_500 == {500: _hip.TrackEmbedDesc}
-    buf = (ctypes.c_int32 * 96)()
-    n = lib.detr_hip_struct_layout(500, buf, 96)
-    want = _hip.struct_layout_mirror(_hip.TrackEmbedDesc)
-    assert n == len(want) == 1 + len(_hip.TrackEmbedDesc._fields_) and list(buf[:n]) == want
-    assert lib.detr_hip_struct_layout(501, buf, 96) < 0
-    _hip.check_struct_layouts(lib)                                             # the load-time check covers it
-
-    class Drifted(ctypes.Structure):                                           # R widened: every later offset moves
-        _fields_ = [(f, (ctypes.c_int64 if f == "R" else t)) for f, t in _hip.TrackEmbedDesc._fields_]
-    try:
-        _hip.LAYOUT_STRUCTS_APPENDED_500[500] = Drifted
-        with pytest.raises(RuntimeError, match="Drifted"):
-            _hip.check_struct_layouts(lib)
-    finally:
-        _hip.LAYOUT_STRUCTS_APPENDED_500[500] = _hip.TrackEmbedDesc
+    assert _hip.LAYOUT_STRUCTS[500] is _hip.TrackEmbedDesc
+    assert abi_header.library_layout(lib, 500) == _hip.struct_layout_mirror(_hip.TrackEmbedDesc) and abi_header.library_layout(lib, 501) is None
+    _hip.check_struct_layouts(lib)                     # the load-time check covers it; every id, drift: test_abi_layout_cpu.py
 
 
 def test_track_embed_desc_layout_and_sizes_match_the_header():

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 import track_cases as C
 import track_motion_cases as MC
 import track_motion_ref as M
@@ -37,9 +38,7 @@ def run_ref(name, motion=True):
     return steps
 
 
-def _lib():
-    from detr_tf import _hip
-    return _hip, _hip.load()
+_lib = abi_header.hip_lib
 
 
 # ---- the reference on synthetic videos -------------------------------------------------------------------------------------------
@@ -182,36 +181,18 @@ def test_track_motion_symbols_declared_exported_appended():
 def test_track_motion_desc_layout_and_state_size_match_the_header():
     _hip, lib = _lib()
     from detr_tf import inference
-    hdr = open(os.path.join(ROOT, "include", "detr_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} detr_track_motion_desc;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        base = re.match(r"(const\s+)?(\w+)\s+(.*)", decl)
-        for item in base.group(3).split(","):
-            item = item.strip()
-            fields.append((item.lstrip("*").strip(), ctypes.c_void_p if item.startswith("*") else ctype[base.group(2)]))
-    assert fields == list(_hip.TrackMotionDesc._fields_)                        # names, order and types of the C declaration
-    assert _hip.LAYOUT_STRUCTS_APPENDED_600 == {600: _hip.TrackMotionDesc}
-    buf = (ctypes.c_int32 * 96)()
-    n = lib.detr_hip_struct_layout(600, buf, 96)
-    want = _hip.struct_layout_mirror(_hip.TrackMotionDesc)
-    assert n == len(want) == 1 + len(_hip.TrackMotionDesc._fields_) and list(buf[:n]) == want
-    assert lib.detr_hip_struct_layout(601, buf, 96) < 0
-    _hip.check_struct_layouts(lib)                                             # the load-time check covers it
+    assert abi_header.header_structs()["detr_track_motion_desc"] == list(_hip.TrackMotionDesc._fields_)   # names, order and types of the C declaration
+    assert _hip.LAYOUT_STRUCTS[600] is _hip.TrackMotionDesc
 
-    class Drifted(ctypes.Structure):                                           # a field inserted behind S: every later offset moves
+    class Drifted(ctypes.Structure):                   # a field INSERTED behind S (test_abi_layout_cpu.py widens one): every later offset moves
         _fields_ = list(_hip.TrackMotionDesc._fields_[:1]) + [("D", ctypes.c_int64)] + list(_hip.TrackMotionDesc._fields_[1:])
     try:
-        _hip.LAYOUT_STRUCTS_APPENDED_600[600] = Drifted
+        _hip.LAYOUT_STRUCTS[600] = Drifted
         with pytest.raises(RuntimeError, match="Drifted"):
             _hip.check_struct_layouts(lib)
     finally:
-        _hip.LAYOUT_STRUCTS_APPENDED_600[600] = _hip.TrackMotionDesc
+        _hip.LAYOUT_STRUCTS[600] = _hip.TrackMotionDesc
+    _hip.check_struct_layouts(lib)                                             # the load-time check covers it
     per_stream = 16 * 4 + 2 * 384 * 384
     assert inference.MOTION_STATE.itemsize == per_stream and per_stream % 16 == 0
     assert [inference.MOTION_STATE.fields[k][1] for k in ("head", "thumb")] == [0, 64] and inference.MOTION_HEAD == M.HEAD
