@@ -7,8 +7,9 @@
 // through VGPRs with a bf16 packing pass in every workgroup that streamed them, and ran one workgroup barrier per 32 keys.  Here:
 //   * operands are bf16 in memory (the projection GEMMs store them; Q carries scale * log2(e)), outputs bf16: no conversion pass,
 //     half the bytes of every K / V re-stream;
-//   * the dropout keep flags are BITS, produced once per step by attn2_dropmask_kernel (one launch per attention site, off the
-//     critical path) in ONE layout that all three kernels read -- one word per (query, 32-key tile), bit = key -- so that an
+//   * the dropout keep flags are BITS, produced once per step by attn2_dropmask_kernel (one launch for all attention sites, off
+//     the critical path) in the ONE layout that all three kernels read -- one word per (query, 32-key tile), bit = key (the dK / dV
+//     kernel, whose lanes own keys, takes the words of its queries with its key as the bit index; there is no second layout) -- so that an
 //     element's flag is v_bfe_i32 + v_and_b32 on a word that arrived with the tile.  Same function as common.h::drop_keep, bit for bit;
 //   * a WAVE is the unit of work: 64 queries (two independent 32-query chains that share every K / V fragment) x a contiguous run
 //     of key tiles.  Its K / V / flag tiles arrive by LDS-DMA (buffer_load ... lds) in a wave-PRIVATE ring of three stages,

@@ -739,14 +739,16 @@ SPLIT_TARGET_64 = int(os.environ.get("DETR_HIP_SPLIT_TARGET64", "1024"))
 X3_SPLIT_TARGET = int(os.environ.get("DETR_HIP_X3_SPLIT_TARGET", "512"))      # workgroups a split-K f32x3 GEMM on 128 x 128 tiles aims at
 
 
-def pick_split_k(M, N, K, max_split=1024):
-    """Reduction-heavy GEMMs (weight gradients): split K so that enough workgroups exist to fill 256 CUs."""
-    if COMPUTE_BF16 == 1 and ((N >= 128 and K >= 16384) or (M >= 512 and N >= 512 and K >= 4096) or
+def pick_split_k(M, N, K, max_split=1024, compute=None):
+    """Reduction-heavy GEMMs (weight gradients): split K so that enough workgroups exist to fill 256 CUs.
+    compute: the launch's detr_gemm_desc.compute (None: the module default COMPUTE_BF16)."""
+    compute = COMPUTE_BF16 if compute is None else int(compute)
+    if compute == 1 and ((N >= 128 and K >= 16384) or (M >= 512 and N >= 512 and K >= 4096) or
                          (K >= 4096 and ((M >= 256 and N >= 2048) or (M >= 2048 and N >= 256)))):   # 128x128 tiles (gemm_f32.hip: gemm_pick_tile)
         tiles = -(-M // 128) * -(-N // 128)
         ktiles = -(-K // 32)
         return int(max(1, min(max(1, SPLIT_TARGET_128 // tiles), max_split, ktiles // 8 if ktiles >= 16 else 1)))
-    if COMPUTE_BF16 == 2 and X3_SPLIT_TARGET > 0 and N >= 128 and K >= 256 and M >= 128:
+    if compute == 2 and X3_SPLIT_TARGET > 0 and N >= 128 and K >= 256 and M >= 128:
         # f32x3 (gemm_x3.h): 128 x 128 tiles, two workgroups per CU = 512 slots; the 64 x 64 plan below left e.g. the 256 x 1024 weight gradient of layer3
         # with 16 tiles x 16 splits = 256 workgroups, half a round of single workgroups per CU (round 6; DETR_HIP_X3_SPLIT_TARGET=0: the old plan)
         t128 = -(-M // 128) * -(-N // 128)
@@ -758,41 +760,43 @@ def pick_split_k(M, N, K, max_split=1024):
     # 64x64 tiles (fp32 always; bf16 for small outputs, see gemm_f32.hip): ~1024 workgroups measured best
     tiles = -(-M // 64) * -(-N // 64)
     want = max(1, SPLIT_TARGET_64 // max(tiles, 1))
-    ktiles = -(-K // (32 if COMPUTE_BF16 == 1 else 16))
+    ktiles = -(-K // (32 if compute == 1 else 16))
     cap = ktiles // 8 if ktiles >= 64 else ktiles // 4      # short reductions: 4 k-tiles per split are enough
     return int(max(1, min(want, max_split, cap)))
 
 
 def linear_fwd_call(x2d, w_out_in, bias, out2d, *, alpha=1.0, residual=None, act=0, dropout_p=0.0, dropout_seed=0,
-                    dropout_step=None, ln=None):
+                    dropout_step=None, ln=None, compute=None):
     """(args, kwargs) of the gemm() that computes out = act((x @ W^T + b) * alpha + residual); W is (out, in) like
-    custom_layers.Linear.  The *_call forms exist so that independent Linear products can be issued with gemm_group()."""
+    custom_layers.Linear.  The *_call forms exist so that independent Linear products can be issued with gemm_group().
+    compute (here and in the two gradient forms): detr_gemm_desc.compute of the launch, None = the module default."""
     M, K = x2d.shape
     N = w_out_in.shape[0]
     return ((M, N, K, x2d, x2d.stride(0), 1, w_out_in, w_out_in.stride(0), 1, out2d, out2d.stride(0)),
             dict(alpha=alpha, bias=bias, residual=residual, ldr=(residual.stride(0) if residual is not None else 0), act=act,
-                 dropout_p=dropout_p, dropout_seed=dropout_seed, dropout_step=dropout_step, **({"ln": ln} if ln is not None else {})))
+                 dropout_p=dropout_p, dropout_seed=dropout_seed, dropout_step=dropout_step, compute=compute,
+                 **({"ln": ln} if ln is not None else {})))
 
 
-def linear_dgrad_call(dy2d, w_out_in, dx2d, *, alpha=1.0, residual=None, mask=None):
+def linear_dgrad_call(dy2d, w_out_in, dx2d, *, alpha=1.0, residual=None, mask=None, compute=None):
     """dx = (dy @ W) * alpha (+ residual) (masked by mask > 0)."""
     M, N = dy2d.shape
     K = w_out_in.shape[1]
     return ((M, K, N, dy2d, dy2d.stride(0), 1, w_out_in, w_out_in.stride(0), 0, dx2d, dx2d.stride(0)),
             dict(alpha=alpha, residual=residual, ldr=(residual.stride(0) if residual is not None else 0),
-                 mask=mask, ldmask=(mask.stride(0) if mask is not None else 0)))
+                 mask=mask, ldmask=(mask.stride(0) if mask is not None else 0), compute=compute))
 
 
-def linear_wgrad_call(dy2d, x2d, dw_out_in, *, alpha=1.0, bias_grad=None):
+def linear_wgrad_call(dy2d, x2d, dw_out_in, *, alpha=1.0, bias_grad=None, compute=None):
     """dW(out,in) += alpha * dy^T @ x (deterministic split-K through the workspace; dW holds zeros / the running sum);
     bias_grad (out,) += alpha * column sums of dy, fused into the same launch (row sums of the A operand)."""
     M, N = dy2d.shape
     K = x2d.shape[1]
-    sk = pick_split_k(N, K, M)
+    sk = pick_split_k(N, K, M, compute=compute)
     args = (N, K, M, dy2d, dy2d.stride(0), 0, x2d, x2d.stride(0), 0, dw_out_in, dw_out_in.stride(0))
     if sk == 1:
-        return args, dict(alpha=alpha, residual=dw_out_in, ldr=dw_out_in.stride(0), rowsum_a=bias_grad, rowsum_alpha=alpha)
-    return args, dict(alpha=alpha, split_k=sk, rowsum_a=bias_grad, rowsum_alpha=alpha)
+        return args, dict(alpha=alpha, residual=dw_out_in, ldr=dw_out_in.stride(0), rowsum_a=bias_grad, rowsum_alpha=alpha, compute=compute)
+    return args, dict(alpha=alpha, split_k=sk, rowsum_a=bias_grad, rowsum_alpha=alpha, compute=compute)
 
 
 def linear_fwd(*a, **kw):

@@ -17,12 +17,14 @@ Reference lines implemented (paths relative to the reference root):
 import math
 import os
 from ctypes import byref, c_float
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _hip as hip
 from .params import ParamStore, RESNET50_BLOCKS, block_names, bn_conv_pairs, stem_names
+from .streams import DropMasks, SideStream
 
 D = 256
 HEADS = 8
@@ -125,6 +127,33 @@ def backbone_stride(replace_stride_with_dilation=None):
     return 4 * 2 ** sum(1 for f in dilation_flags(replace_stride_with_dilation) if not f)
 
 
+class Block(NamedTuple):
+    """What one bottleneck block's forward (_block_fwd) leaves for its backward (_block_bwd)."""
+    p: str                                  # buffer tag of the block
+    n: dict                                 # its parameter names (params.block_names)
+    x: torch.Tensor                         # block input [B, h, w, cin]
+    xs: torch.Tensor                        # ... at the pixels a stride-2 1x1 conv reads (= x otherwise)
+    x1: torch.Tensor                        # input of conv1 (x, or xs when the stride sits on conv1: tf_backbone)
+    y1: torch.Tensor                        # conv1 output [B, h1, w1, d1]
+    y2: torch.Tensor                        # conv2 output [B, ho, wo, d1]
+    out: torch.Tensor                       # block output [B, ho, wo, d2]
+    h: int
+    w: int
+    ho: int
+    wo: int
+    h1: int
+    w1: int
+    M1: int                                 # rows of conv1: B * h1 * w1
+    s2: int                                 # stride of the 3x3 conv
+    cin: int
+    d1: int
+    d2: int
+    stride: int                             # stride of the block
+    first: bool                             # first block of its stage: projection shortcut
+    out_bits: Optional[torch.Tensor]        # sign bits of `out` (the next block's ReLU mask), training + bf16 storage only
+    dil: int                                # dilation (= padding) of the 3x3 conv
+
+
 class DetrEngine:
     def __init__(self, device="cuda:0", blocks=RESNET50_BLOCKS, num_enc=6, num_dec=6, num_queries=100,
                  num_classes=92, nb_class=None, seed=0, tf_backbone=False, replace_stride_with_dilation=(False, False, False)):
@@ -158,6 +187,10 @@ class DetrEngine:
         self._attn_sites = ()        # attention sites whose head-averaged map this pass writes (forward(attn_sites=...))
         self.attn_maps = {}          # site name -> engine buffer [B, T, S] fp32 of the last pass that requested it
         self._shape = None
+        self._adt = torch.float32        # storage type of the backbone activations (and their gradients) of the last forward
+        self._block_recs = []            # one Block per bottleneck block of the last forward
+        self._feat_meta = None           # (feat, Hf, Wf, L) of the last forward
+        self._fold_table = self._shift_table = None
         self.bn_scale, self.bn_shift = {}, {}
         self._weights_version, self._built = 0, {}
         self.P.on_change = self._params_changed   # ParamStore.load / load_dict: refold the frozen BN, bump the weights version
@@ -176,6 +209,8 @@ class DetrEngine:
         self._cross = {}
         self._graph_replay = False       # True while a captured step is being recorded / replayed (training.GraphedTrainStep)
         self.phase_events = None         # list of (name, torch.cuda.Event) while a caller times the phases of a step (bench.py --phase-events)
+        self.side = SideStream(self.device)          # second launch stream (streams.SideStream)
+        self.masks = DropMasks(self, HEADS)          # dropout keep bits and their stream (streams.DropMasks)
 
     # Derived weight copies (BN-folded kernels, the bf16 shadow, the gathered cross-attention weights) are stamped with the
     # weights version they were built from.  EVERY mutation of the parameters bumps the version -- the optimiser after an
@@ -196,14 +231,19 @@ class DetrEngine:
         self._built[key] = self._weights_version
         return True
 
+    def seed_of_step(self, step_no):
+        return step_seed(self.dropout_seed, step_no, self.dp_rank)
+
     def advance_dropout_step(self):
         """Next training step: a new uint32 step seed (base seed, step counter, DP rank) is written to DEVICE memory; every
         dropout site derives its key from it inside the kernels, so a captured hipGraph sees the new masks on replay."""
         self._step_no += 1
-        self._step_seed = step_seed(self.dropout_seed, self._step_no, self.dp_rank)
+        self._step_seed = self.seed_of_step(self._step_no)
         # slot 1: the seed of the step after this one (the keep bits of the next step's attention sites are generated while this
-        # step's decoder / matcher leave most of the chip idle, _pregen_dropmasks)
-        hip.call("detr_hip_set_u32x8", self._seed_dev.data_ptr(), self._step_seed, step_seed(self.dropout_seed, self._step_no + 1, self.dp_rank),
+        # step's decoder / matcher leave most of the chip idle, DropMasks.pregen) -- a generation ahead that is still queued
+        # reads the slot this write replaces: behind it (never inside a capture: GraphedTrainStep calls this before the replay)
+        self.masks.settle()
+        hip.call("detr_hip_set_u32x8", self._seed_dev.data_ptr(), self._step_seed, self.seed_of_step(self._step_no + 1),
                  0, 0, 0, 0, 0, 0)
         self._drop = (float(self.dropout_p), self._step_seed)
         return self._step_seed
@@ -276,7 +316,7 @@ class DetrEngine:
     def _w(self, name):
         """Weight OPERAND of a GEMM: the fp32 tensor, or -- while the bf16-compute kernels are active -- its bf16 shadow
         (half the bytes, no conversion in the kernel).  Biases, LayerNorm vectors and gradients stay fp32."""
-        if hip.COMPUTE_BF16 == 1 and self.P.views16 is not None:
+        if self.compute == 1 and self.P.views16 is not None:
             return self.P.views16[name]
         return self.P.views[name]
 
@@ -289,7 +329,7 @@ class DetrEngine:
     def _refold_group(self):
         """Frozen-BN fold of every bf16 conv kernel (all but the stem) in one launch: a device table of
         (kernel, bn scale, bf16 out, n/4, cols/4) entries, built once -- the tensors it points at never move."""
-        if getattr(self, "_fold_table", None) is None:
+        if self._fold_table is None:
             rows = []
             for bn_name, conv in self._pairs[1:]:               # (the stem kernel takes the fp32 copy)
                 conv_name = f"{conv}/kernel"
@@ -325,13 +365,17 @@ class DetrEngine:
 
     # ---- small helpers ----------------------------------------------------------------------------
     @staticmethod
-    def _wgrad(M_out, N_out, K_red, A, lda, Bm, ldb, C, ldc, scale=None, alpha=1.0):
+    def _wgrad(M_out, N_out, K_red, A, lda, Bm, ldb, C, ldc, scale=None, alpha=1.0, compute=None):
         """C[M_out,N_out] += alpha * scale[n] * A'^T-style reduction (both operands reduction-major)."""
-        sk = hip.pick_split_k(M_out, N_out, K_red)
+        sk = hip.pick_split_k(M_out, N_out, K_red, compute=compute)
         if sk > 1:
-            hip.gemm(M_out, N_out, K_red, A, lda, 0, Bm, ldb, 0, C, ldc, alpha=alpha, scale=scale, split_k=sk)
+            hip.gemm(M_out, N_out, K_red, A, lda, 0, Bm, ldb, 0, C, ldc, alpha=alpha, scale=scale, split_k=sk, compute=compute)
         else:
-            hip.gemm(M_out, N_out, K_red, A, lda, 0, Bm, ldb, 0, C, ldc, alpha=alpha, scale=scale, residual=C, ldr=ldc)
+            hip.gemm(M_out, N_out, K_red, A, lda, 0, Bm, ldb, 0, C, ldc, alpha=alpha, scale=scale, residual=C, ldr=ldc, compute=compute)
+
+    def _a16(self, base):
+        """(buffer name, dtype) of an attention operand: bf16 compute mode stores them in bf16 under the name `base`16."""
+        return (f"{base}16", torch.bfloat16) if self.compute == 1 else (base, torch.float32)
 
     def _colsum(self, x2d, out, alpha=1.0):
         """out += alpha * column sums of x2d, in a FIXED order (round 5: the atomic form made input_proj/bias the one gradient of
@@ -362,49 +406,6 @@ class DetrEngine:
         return dict(gamma=self.P.views[f"{pfx}/gamma"], beta=self.P.views[f"{pfx}/beta"], y=y, mean=self.buf(f"{tag}:mean", (rows,)),
                     rstd=self.buf(f"{tag}:rstd", (rows,)), eps=LN_EPS, add=add, y2=y2, y16=y16)
 
-    # ---- second launch stream ----------------------------------------------------------------------------------------------
-    # Work that does not feed the critical chain is issued on a second HIP stream behind an event of the main stream that
-    # follows its producer (a graph edge when the pass is captured) and is joined where its result is read:
-    #   backward: every weight gradient (it feeds nothing but the bucket exchange / the optimiser) and the data gradient of a
-    #             stage's projection shortcut; forward: the projection shortcut and the decoder's shared K / V projection.
-    # They share the chip with the chain: the decoder's 800-row kernels fill a fifth of the CUs, the backbone's HBM-bound 1x1
-    # GEMMs leave the MFMA pipes idle.  The tensors a side launch reads are never rewritten within the same pass (_sx: one
-    # scratch tensor per site instead of one per shape; the backbone loop guards its recycled tensors with per-block events),
-    # so the only joins are in front of a reduction flush, a bucket hand-over, the consumer of a shortcut / of K, V, and the
-    # end of the pass.  Off (one stream): DETR_HIP_WGRAD_STREAM=0, and any backward with immediate split-K reductions.
-    def _side_begin(self, on):
-        self._side_on = bool(on)
-        hip.AFTER_FLUSH = self._side_sync if self._side_on else None
-        if self._side_on:
-            self._side_main = torch.cuda.current_stream()
-            if getattr(self, "_wg_stream", None) is None:
-                self._wg_stream = torch.cuda.Stream(device=self._side_main.device)
-
-    def _side_sync(self):
-        """After a reduction flush the slab pool is recycled: whichever stream ran the flush, the other one must not write a
-        recycled slab before the flush has read it."""
-        if getattr(self, "_side_on", False):
-            self._side_main.wait_stream(self._wg_stream)
-            self._wg_stream.wait_stream(self._side_main)
-
-    def _side(self, fn):
-        if not getattr(self, "_side_on", False):
-            fn()
-            return
-        ev = torch.cuda.Event()
-        ev.record(self._side_main)
-        self._wg_stream.wait_event(ev)
-        with torch.cuda.stream(self._wg_stream):
-            fn()
-
-    def _side_join(self):
-        if getattr(self, "_side_on", False):
-            self._side_main.wait_stream(self._wg_stream)
-
-    def _sx(self, site):
-        """Suffix that makes a scratch tensor private to one site while the second stream is in use."""
-        return f":{site}" if getattr(self, "_side_on", False) else ""
-
     def _ln_bwd(self, dy, x, pfx, dx, tag, dx_add=None, drop_site=None, want16=False, dy_add=None):
         """Backward of _ln_fwd w.r.t. x (+ dx_add); the incoming gradient is dy (+ dy_add).  drop_site: also return dropout_bwd(dx)
         -- the gradient through the Dropout in front of the residual add that feeds this LayerNorm -- as a second output of the
@@ -413,9 +414,9 @@ class DetrEngine:
         dx_drop = dx_drop16 = None
         if drop_site is not None:
             if want16:
-                dx_drop16 = self.buf(f"scratch:drop16:{dx.shape[0]}{self._sx(tag)}", dx.shape, torch.bfloat16)
+                dx_drop16 = self.buf(f"scratch:drop16:{dx.shape[0]}{self.side.suffix(tag)}", dx.shape, torch.bfloat16)
             elif dp > 0.0:
-                dx_drop = self.buf(f"scratch:drop:{dx.shape[0]}{self._sx(tag)}", dx.shape)
+                dx_drop = self.buf(f"scratch:drop:{dx.shape[0]}{self.side.suffix(tag)}", dx.shape)
         hip.layernorm_bwd(dy, x, self.P.views[f"{pfx}/gamma"], self._bufs[f"{tag}:mean"], self._bufs[f"{tag}:rstd"], dx,
                           self.P.gviews[f"{pfx}/gamma"], self.P.gviews[f"{pfx}/beta"], dx_add=dx_add, dx_drop=dx_drop,
                           dropout_p=dp, dropout_site=(drop_site or 0), dropout_step=self._seed_dev, dx_drop16=dx_drop16,
@@ -440,71 +441,10 @@ class DetrEngine:
     def attn16(self):
         return self.compute == 1
 
-    def _dropmask(self, site, B, T, S, which=None):
-        """Keep bits of the attention-probability dropout of `site` (hip.attention_dropmask): one buffer per site and step parity,
-        filled once per step by _gen_dropmasks() / one step ahead by _pregen_dropmasks()."""
-        which = getattr(self, "_mask_set", 0) if which is None else which
-        return self.buf(f"dropmask:{which}:{site}", (hip.attention_dropmask_words(B, HEADS, T, S),), torch.int32)
-
-    def _mask_sites(self, L):
-        Q = self.Q
-        sites = [(16 * i, L, L) for i in range(self.num_enc)]
-        for i in range(self.num_dec):
-            ds = 16 * (32 + i)
-            sites += [(ds, Q, Q), (ds + 2, Q, L)]
-        return sites
-
-    def _launch_dropmasks(self, B, L, which, seed_slot):
-        dp, _ = self._drop
-        main = torch.cuda.current_stream()
-        if getattr(self, "_mask_stream", None) is None:
-            self._mask_stream = torch.cuda.Stream(device=main.device)
-        bufs = [(self._dropmask(site, B, T, S, which), T, S, site) for site, T, S in self._mask_sites(L)]      # (allocated on the main stream)
-        self._mask_stream.wait_stream(main)
-        with torch.cuda.stream(self._mask_stream):
-            hip.attention_dropmask_many(bufs, B, HEADS, dropout_p=dp, dropout_step=self._seed_dev[seed_slot:])
-
-    def _gen_dropmasks(self, B, L):
-        """The keep-bit buffers of this step's attention sites: already there when the previous step generated them one step ahead
-        (_pregen_dropmasks; eager launches only), otherwise generated now on a stream of their own behind the seed write (they depend
-        on nothing else) and joined in front of the first encoder attention."""
-        dp, _ = self._drop
-        if not (self.attn16 and dp > 0.0):
-            return
-        self._mask_set = self._step_no & 1
-        tags = self.__dict__.setdefault("_mask_tags", {})
-        key = (self._step_seed, B, L, self.Q, dp)
-        if not (tags.get(self._mask_set) == key and not self._graph_replay):
-            self._launch_dropmasks(B, L, self._mask_set, 0)
-            tags[self._mask_set] = None if self._graph_replay else key
-        self._mask_pending = True
-
-    def _pregen_dropmasks(self, B, L, now=False):
-        """Called when the decoder forward begins (800-row kernels, then the matcher: most CUs idle for ~1.5 ms): the NEXT step's keep
-        bits, from its seed in slot 1 of the device seed block, into the other buffer set.  Eager launches only (a recorded graph keeps
-        the generation at the head of its own step).  On by default at the matcher (DETR_HIP_DROPMASK_AHEAD=2, pregen_dropmasks_at_matcher); from the
-        start of the decoder forward (=1) it measured +0.07 ms per step (profiles/r06_ab_results.txt #3); 0 turns it off."""
-        dp, _ = self._drop
-        if not (self.attn16 and dp > 0.0) or self._graph_replay or not DROPMASK_AHEAD:
-            return
-        if DROPMASK_AHEAD == 2 and not now:
-            self._pregen_args = (B, L)          # launched by the set loss between its cost and assignment kernels
-            return
-        nxt = (self._step_no + 1) & 1
-        self._launch_dropmasks(B, L, nxt, 1)
-        self._mask_tags[nxt] = (step_seed(self.dropout_seed, self._step_no + 1, self.dp_rank), B, L, self.Q, dp)
-
     def pregen_dropmasks_at_matcher(self):
-        """DETR_HIP_DROPMASK_AHEAD=2: the next step's keep bits next to the assignment kernel alone (one wave per problem, ~50 CUs for
-        ~0.7 ms), not next to the decoder's chain of short launches (which the co-running generator slowed: profiles/r06_ab_results.txt #3)."""
-        args, self._pregen_args = getattr(self, "_pregen_args", None), None
-        if args is not None:
-            self._pregen_dropmasks(*args, now=True)
-
-    def _join_dropmasks(self):
-        if getattr(self, "_mask_pending", False):
-            torch.cuda.current_stream().wait_stream(self._mask_stream)
-            self._mask_pending = False
+        """The set loss calls this between its cost and assignment kernels (training.run_train_step installs it): the next step's
+        keep bits, when DROPMASK_AHEAD = 2 deferred them to here (DropMasks.pregen)."""
+        self.masks.at_matcher()
 
     def _self_attn_fwd(self, tag, pfx, qk_in, v_in, B, T, out, site, ln=None, key_valid=None):
         W, bias = self._w(f"{pfx}/in_proj_kernel"), self.P.views[f"{pfx}/in_proj_bias"]
@@ -517,9 +457,9 @@ class DetrEngine:
                             hip.linear_fwd_call(qk_in, W[D:2 * D], bias[D:2 * D], QKV[:, D:2 * D]),
                             hip.linear_fwd_call(v_in, W[2 * D:], bias[2 * D:], QKV[:, 2 * D:])])                  # :302-304
             O = self.buf(f"{tag}:O16", (B * T, D), torch.bfloat16)
-            self._join_dropmasks()
+            self.masks.join()
             hip.attention(QKV[:, 0:D], QKV[:, D:2 * D], QKV[:, 2 * D:], O, lse, B, HEADS, T, T, scale=float(HD) ** -0.5, dropout_p=dp,
-                          dropout_site=site, dropout_step=self._seed_dev, dropmask=self._dropmask(site, B, T, T) if dp > 0.0 else None,
+                          dropout_site=site, dropout_step=self._seed_dev, dropmask=self.masks.mask(site, B, T, T) if dp > 0.0 else None,
                           key_valid=key_valid)
         else:
             QKV = self.buf(f"{tag}:QKV", (B * T, 3 * D))
@@ -569,26 +509,26 @@ class DetrEngine:
         G = self.P.gviews
         W, gW, gb = self._w(f"{pfx}/in_proj_kernel"), G[f"{pfx}/in_proj_kernel"], G[f"{pfx}/in_proj_bias"]
         a16 = self.attn16
-        adt = torch.bfloat16 if a16 else torch.float32
-        QKV, O = self._bufs[f"{tag}:QKV16" if a16 else f"{tag}:QKV"], self._bufs[f"{tag}:O16" if a16 else f"{tag}:O"]
+        (qkv, adt), (o, _) = self._a16(f"{tag}:QKV"), self._a16(f"{tag}:O")
+        QKV, O = self._bufs[qkv], self._bufs[o]
         dO = self.buf(f"scratch:dO:{B * T}:{int(a16)}", (B * T, D), adt)
         hip.linear_dgrad(d_out, self._w(f"{pfx}/out_proj_kernel"), dO)
-        dQKV = self.buf(f"scratch:dQKV:{B * T}:{int(a16)}{self._sx(tag)}", (B * T, 3 * D), adt)
+        dQKV = self.buf(f"scratch:dQKV:{B * T}:{int(a16)}{self.side.suffix(tag)}", (B * T, 3 * D), adt)
         delta = self.buf(f"scratch:delta:{B * T}", (2 * B * HEADS, T))       # (bf16 operands: delta / scale | lse * log2 e - log2 scale)
         dp, _ = self._drop
         hip.attention(QKV[:, 0:D], QKV[:, D:2 * D], QKV[:, 2 * D:], O, self._bufs[f"{tag}:lse"], B, HEADS, T, T,
                       scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=site, dropout_step=self._seed_dev,
                       d_o=dO, dq=dQKV[:, 0:D], dk=dQKV[:, D:2 * D], dv=dQKV[:, 2 * D:], delta=delta,
-                      dropmask=self._dropmask(site, B, T, T) if (a16 and dp > 0.0) else None, key_valid=key_valid)
+                      dropmask=self.masks.mask(site, B, T, T) if (a16 and dp > 0.0) else None, key_valid=key_valid)
         # weight gradients (bias gradients fused: row sums of dy^T), one grouped launch (bf16 operands: the out-projection's pair has
         # other storage types than the in-projections' and is a launch of its own)
         wg_out = hip.linear_wgrad_call(d_out, O, G[f"{pfx}/out_proj_kernel"], bias_grad=G[f"{pfx}/out_proj_bias"])
         wg_in = [hip.linear_wgrad_call(dQKV[:, 0:2 * D], qk_in, gW[0:2 * D], bias_grad=gb[0:2 * D]),
                  hip.linear_wgrad_call(dQKV[:, 2 * D:], v_in, gW[2 * D:], bias_grad=gb[2 * D:])]
         if a16:
-            self._side(lambda: (hip.gemm(*wg_out[0], **wg_out[1]), hip.gemm_group(wg_in)))
+            self.side.run(lambda: (hip.gemm(*wg_out[0], **wg_out[1]), hip.gemm_group(wg_in)))
         else:
-            self._side(lambda: hip.gemm_group([wg_out] + wg_in))
+            self.side.run(lambda: hip.gemm_group([wg_out] + wg_in))
         calls = []
         if acc_qk is not None:
             calls.append(hip.linear_dgrad_call(dQKV[:, 0:2 * D], W[0:2 * D], acc_qk, residual=acc_qk))
@@ -622,11 +562,11 @@ class DetrEngine:
         G = self.P.gviews
         h = self._bufs[f"{tag}:h"]                 # post-ReLU, post-dropout hidden activation
         dp, _ = self._drop
-        dh = self.buf(f"scratch:dh:{h.shape[0]}:{int(self.ffn16)}{self._sx(tag)}", h.shape,
+        dh = self.buf(f"scratch:dh:{h.shape[0]}:{int(self.ffn16)}{self.side.suffix(tag)}", h.shape,
                       torch.bfloat16 if self.ffn16 else torch.float32)
         # (h > 0) is both the ReLU and the keep mask of the hidden dropout; its 1/(1-p) scale goes in alpha
         hip.linear_dgrad(d_y, self._w(f"{pfx}/linear2/kernel"), dh, mask=h, alpha=(1.0 / (1.0 - dp)) if dp > 0.0 else 1.0)
-        self._side(lambda: hip.gemm_group([
+        self.side.run(lambda: hip.gemm_group([
             hip.linear_wgrad_call(d_y, h, G[f"{pfx}/linear2/kernel"], bias_grad=G[f"{pfx}/linear2/bias"]),
             hip.linear_wgrad_call(dh, x16 if x16 is not None else x, G[f"{pfx}/linear1/kernel"],
                                   bias_grad=G[f"{pfx}/linear1/bias"])]))
@@ -680,14 +620,13 @@ class DetrEngine:
             self._refresh_bias_shift()
         if masks is not None and not (torch.is_tensor(masks) and masks.is_cuda):
             masks = self._host_masks(masks, tuple(images.shape[:3]))        # validated before any launch
-        self._side_begin(WGRAD_STREAM and images.is_cuda)
+        self.side.begin(WGRAD_STREAM and images.is_cuda)
         try:
             return self._forward_impl(images, training, masks)
         finally:
             try:
-                self._side_join()
+                self.side.end()
             finally:
-                self._side_on = False
                 hip.COMPUTE_BF16 = 0
 
     def backward(self, d_logits, d_boxes, backbone=True, on_bucket=None):
@@ -699,21 +638,20 @@ class DetrEngine:
             hip.begin_deferred_reduces(self.device)
             if on_bucket:
                 def cb(i):
-                    self._side_join()
+                    self.side.join()
                     hip.flush_reduces()
                     on_bucket(i)
         elif on_bucket:
             def cb(i):
-                self._side_join()
+                self.side.join()
                 on_bucket(i)
         # (immediate split-K reductions share ONE slab workspace between all launches: single stream then)
-        self._side_begin(WGRAD_STREAM and DEFER_REDUCE and d_logits.is_cuda)
+        self.side.begin(WGRAD_STREAM and DEFER_REDUCE and d_logits.is_cuda)
         try:
             return self._backward_impl(d_logits, d_boxes, backbone, cb)
         finally:
             try:
-                self._side_join()
-                self._side_on = False
+                self.side.end()
                 hip.flush_reduces(end=True)
             finally:
                 hip.COMPUTE_BF16 = 0
@@ -757,6 +695,7 @@ class DetrEngine:
         if bad:
             raise ValueError(f"masks: image(s) {bad} have no valid (unpadded) position on the feature map")
 
+    # ---- the two passes: a sequence of stages ---------------------------------------------------------
     def _forward_impl(self, images, training=False, masks=None):
         """images: CUDA fp32 NHWC [B,H,W,3] (already normalised, processing.py:12-16).
         Returns (logits [Lv,B,Q,C], boxes [Lv,B,Q,4]) views of engine buffers."""
@@ -768,215 +707,51 @@ class DetrEngine:
             self._drop = (float(self.dropout_p), self._step_seed)
         else:
             self._drop = (0.0, 0)
-        dp, dseed = self._drop
         B, H, W, _ = images.shape
         self._shape = (B, H, W)
-        if dp > 0.0:
+        if self._drop[0] > 0.0:
             hf, wf = feature_size(H, W, self.dilate)        # stem conv, max-pool, layer2..4: each ceil(n / 2) unless dilated
-            self._gen_dropmasks(B, hf * wf)
+            self.masks.gen(B, hf * wf)
         self.images = images
-        V = self.P.views
         self.phase("fwd backbone")
-        # ---------------- stem (resnet_backbone.py:11-26) ----------------
-        H1, W1 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-        M1 = B * H1 * W1
-        ws = self._scaled_kernel(f"{self._stem['conv']}/kernel", self._stem["bn"])
-        adt = torch.bfloat16 if self.compute == 1 else torch.float32      # storage type of backbone activations (and their gradients)
-        self._adt = adt
-        stem = self.buf("stem:out", (B, H1, W1, 64), adt)
-        # implicit GEMM: the 7x7x3 patches are gathered from the image by the A loader (stem_conv.hip), no im2col buffer
-        hip.stem_conv(0, images, ws, stem, B, H, W, H1, W1, bias=self.bn_shift[self._stem["bn"]], act=1)
-        H2, W2 = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
-        pool = self.buf("stem:pool", (B, H2, W2, 64), adt)
-        amax = self.buf("stem:amax", (B, H2, W2, 64), torch.uint8)
-        hip.call("detr_hip_maxpool3x3s2_fwd_bf16" if adt == torch.bfloat16 else "detr_hip_maxpool3x3s2_fwd_f32", stem.data_ptr(),
-                 pool.data_ptr(), amax.data_ptr(), B, H1, W1, 64, H2, W2)
-        # ---------------- residual stages (resnet_backbone.py:116-137) ----------------
-        x, h, w, cin = pool, H2, W2, 64
-        self._block_meta = []
-        for li, nb in enumerate(self.blocks):
-            d1, d2 = 64 * 2 ** li, 256 * 2 ** li
+        x, h, w = self._stem_fwd(images, B, H, W)
+        cin = 64
+        self._block_recs = []
+        for li, nb in enumerate(self.blocks):               # residual stages (resnet_backbone.py:116-137)
             for b in range(nb):
-                n = block_names(li, b, self.tf_backbone)
-                p = n["tag"]
-                dilated = li > 0 and self.dilate[li - 1]         # the stage trades its stride for dilation (resnet_backbone.py:74-85)
-                stride = 2 if (b == 0 and li > 0 and not dilated) else 1
-                dil = 2 if (dilated and b > 0) else 1            # the stage's first block keeps dilation 1
-                ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-                M_in, M_out = B * h * w, B * ho * wo
-                xs = x
-                if stride == 2 and (b == 0):
-                    # stride-2 1x1 convs read every second pixel: gather them once (a plain 16-byte-chunk copy: bf16 tensors
-                    # pass as cin/2 "float" channels)
-                    xs = self.buf(f"{p}:xs", (B, ho, wo, cin), adt)
-                    hip.call("detr_hip_subsample2_fwd_f32", x.data_ptr(), xs.data_ptr(), B, h, w,
-                             cin // 2 if adt == torch.bfloat16 else cin, ho, wo)
-                if self.tf_backbone:            # ResNet v1 (keras.applications): the stride sits on the FIRST 1x1 conv
-                    x1, M1, h1, w1, s2 = xs, M_out, ho, wo, 1
-                else:                           # reference backbone (resnet_backbone.py:104-105): on the 3x3 conv
-                    x1, M1, h1, w1, s2 = x, M_in, h, w, stride
-                if b == 0:
-                    # the projection shortcut only meets the main branch at conv3's residual operand: second stream
-                    # (an HBM-bound 1x1 GEMM next to the MFMA-bound 3x3 conv)
-                    idn = self.buf(f"{p}:idn", (B, ho, wo, d2), adt)
-                    self._side(lambda: self._conv1x1_fwd(xs, M_out, cin, d2, f"{n['down']}/kernel", n["bnd"], idn, act=0))
-                else:
-                    idn = x
-                y1 = self.buf(f"{p}:y1", (B, h1, w1, d1), adt)
-                self._conv1x1_fwd(x1, M1, cin, d1, f"{n['conv1']}/kernel", n["bn1"], y1)
-                y2 = self.buf(f"{p}:y2", (B, ho, wo, d1), adt)
-                hip.conv3x3(0, y1, self._scaled_kernel(f"{n['conv2']}/kernel", n["bn2"]), y2, B, h1, w1, d1, ho, wo, d1,
-                            s2, bias=self.bn_shift[n["bn2"]], act=1, pad=dil, dilation=dil)
-                if b == 0:
-                    self._side_join()
-                out = self.buf(f"{p}:out", (B, ho, wo, d2), adt)
-                # training, bf16 activation storage: the block output's ReLU mask as BITS (1 byte per 8 channels) next to the tensor --
-                # the backward only needs the sign, and the GEMMs that apply it are HBM streams (1/16 of the mask bytes)
-                # (only where the consumer is the STREAMING kernel -- the conv1 input gradient of a following block of layer1-3: there the
-                #  mask stream is a third of the bytes; in the tile engine's / the 3x3 kernels' epilogues the byte loads measured 2-9 %
-                #  SLOWER than the 16-byte mask loads, so y1 / y2 and the layer4 blocks keep their bf16 masks)
-                nxt_d1 = 64 * 2 ** (li if b + 1 < nb else li + 1)        # d1 of the next block
-                last = (li + 1 == len(self.blocks)) and (b + 1 == nb)
-                obits = self.buf(f"{p}:out_bits", (M_out, d2 // 8), torch.uint8) \
-                    if (training and adt == torch.bfloat16 and not last and nxt_d1 <= 256) else None
-                self._conv1x1_fwd(y2, M_out, d1, d2, f"{n['conv3']}/kernel", n["bn3"], out, residual=idn, maskbits_out=obits)
-                self._block_meta.append(dict(p=p, n=n, x=x, xs=xs, x1=x1, y1=y1, y2=y2, out=out, h=h, w=w, ho=ho, wo=wo, h1=h1, w1=w1,
-                                             M1=M1, s2=s2, cin=cin, d1=d1, d2=d2, stride=stride, first=(b == 0), out_bits=obits, dil=dil))
-                x, h, w, cin = out, ho, wo, d2
-        feat, Hf, Wf = x, h, w
-        L = Hf * Wf
-        self._feat_meta = (feat, Hf, Wf, L)
+                m = self._block_fwd(li, b, x, h, w, cin, B, training)
+                self._block_recs.append(m)
+                x, h, w, cin = m.out, m.ho, m.wo, m.d2
+        L = h * w
+        self._feat_meta = (x, h, w, L)
         self.phase("fwd encoder")
-        # ---------------- input_proj + positional encoding (detr.py:172-175) ----------------
-        src = self.buf("enc:src0", (B * L, D))
-        hip.gemm(B * L, D, 2048, feat, 2048, 1, self._w("input_proj/kernel"), D, 0, src, D, bias=V["input_proj/bias"])
-        key = (Hf, Wf)
-        if masks is None:
-            self.key_valid = None
-            if key not in self._pos_cache:
-                self._pos_cache[key] = torch.from_numpy(position_embedding_sine_host(Hf, Wf)).to(self.device)
-            pos = self._pos_cache[key]
-        else:
-            # padded batch: per-image encoding [B*L, 256] (add_bcast / the LayerNorm's add[r % rows] take it as they take the
-            # [L, 256] constant) and the key padding mask of the encoder self-attention and every decoder cross-attention
-            pos = self._prepare_masks(masks, B, H, W, Hf, Wf)
-        self.pos = pos
-        # ---------------- encoder (transformer.py:157-179) ----------------
-        x = src
+        x, pos = self._input_proj_fwd(x, masks, B, L)
         qk = self.buf("enc0:qk", (B * L, D))
         self._add_bcast(x, pos, qk)                              # src + pos (:161-163); later layers get it from LayerNorm 2
         for i in range(self.num_enc):
-            pfx, tag = f"transformer/encoder/layer_{i}", f"enc{i}"
-            a = self.buf(f"{tag}:a", (B * L, D))
-            x1 = self.buf(f"{tag}:x1", (B * L, D))
-            x1h = self.buf(f"{tag}:x1h", (B * L, D), torch.bfloat16) if self.ffn16 else None
-            ln1 = self._ln_spec(B * L, f"{pfx}/norm1", x1, f"{tag}:ln1", y16=x1h)
-            self._self_attn_fwd(f"{tag}:sa", f"{pfx}/self_attn", qk, x, B, L, a, site=16 * i, ln=ln1, key_valid=self.key_valid)
-            if ln1 is None:
-                self._ln_fwd(a, f"{pfx}/norm1", x1, f"{tag}:ln1", y16=x1h)
-            f = self.buf(f"{tag}:f", (B * L, D))
-            x2 = self.buf(f"{tag}:x2", (B * L, D))
-            # x2 + pos = the q / k input of the next layer, or `memory + pos` of the decoder (:219), in the same launch
-            qk = self.buf(f"enc{i + 1}:qk" if i + 1 < self.num_enc else "dec:mem_pos", (B * L, D))
-            ln2 = self._ln_spec(B * L, f"{pfx}/norm2", x2, f"{tag}:ln2", add=pos, y2=qk, ffn=True)
-            self._ffn_fwd(tag, pfx, x1, f, seed=16 * i + 2, x16=x1h, ln=ln2)
-            if ln2 is None:
-                self._ln_fwd(f, f"{pfx}/norm2", x2, f"{tag}:ln2", add=pos, y2=qk)
-            x = x2
-        memory, mem_pos = x, qk
-        if self.num_enc == 0:
-            mem_pos = qk                                          # = src + pos
+            x, qk = self._encoder_layer_fwd(i, x, qk, pos, B, L)
         self.phase("fwd decoder")
         if training:
-            self._pregen_dropmasks(B, L)
+            self.masks.pregen(B, L, DROPMASK_AHEAD)
         # ---------------- decoder (transformer.py:207-234, :104-133) ----------------
         Q, nd = self.Q, self.num_dec
-        qpos = V["query_embed/kernel"]
+        qpos = self.P.views["query_embed/kernel"]
         tgt = self.buf("dec:tgt0", (B * Q, D))
         hip.zero_(tgt)                                           # transformer.py:45
         hs = self.buf("dec:hs", (nd, B * Q, D))
         t3all = self.buf("dec:t3all", (nd, B * Q, D))           # the layer outputs, contiguous: ONE final-norm launch over all levels
-        dp, _ = self._drop
-        # K / V projections of `memory` for ALL decoder layers at once: memory is layer-invariant (:221-223)
-        ct = self._cross_tables()
-        if self._stale(f"cross:{self.compute}"):
-            hip.multi_copy(ct["gather"])
-        a16 = self.attn16
-        KV = self.buf("dec:KV16" if a16 else "dec:KV", (B * L, 2 * nd * D), torch.bfloat16 if a16 else torch.float32)
-        # (second stream: the first decoder self-attention block -- 800-row kernels -- does not need it)
-        self._side(lambda: hip.gemm_group([hip.linear_fwd_call(mem_pos, ct["Wkv"][0:nd * D], ct["bkv"][0:nd * D], KV[:, 0:nd * D]),
-                                           hip.linear_fwd_call(memory, ct["Wkv"][nd * D:], ct["bkv"][nd * D:], KV[:, nd * D:])]))
+        KV = self._cross_kv_fwd(x, qk, B, L)                     # memory = x, memory + pos = qk (src + pos without an encoder)
         qin = self.buf("dec0:qin", (B * Q, D))
         self._add_bcast(tgt, qpos, qin)                          # tgt + query_pos (:209); later layers: from LayerNorm 3
         for i in range(nd):
-            pfx, tag = f"transformer/decoder/layer_{i}", f"dec{i}"
-            ds = 16 * (32 + i)
-            a1 = self.buf(f"{tag}:a1", (B * Q, D))
-            t1 = self.buf(f"{tag}:t1", (B * Q, D))
-            q2 = self.buf(f"{tag}:q2", (B * Q, D))
-            ln1 = self._ln_spec(B * Q, f"{pfx}/norm1", t1, f"{tag}:ln1", add=qpos, y2=q2)
-            self._self_attn_fwd(f"{tag}:sa", f"{pfx}/self_attn", qin, tgt, B, Q, a1, site=ds, ln=ln1)
-            if ln1 is None:
-                self._ln_fwd(a1, f"{pfx}/norm1", t1, f"{tag}:ln1", add=qpos, y2=q2)      # q2 = t1 + query_pos (:219)
-            # cross attention: Q from this layer, K / V column blocks of the shared projection buffer
-            cp = f"{pfx}/multihead_attn"
-            Wc, bc = self._w(f"{cp}/in_proj_kernel"), V[f"{cp}/in_proj_bias"]
-            Qc = self.buf(f"{tag}:ca:Q16" if a16 else f"{tag}:ca:Q", (B * Q, D), torch.bfloat16 if a16 else torch.float32)
-            hip.linear_fwd(q2, Wc[0:D], bc[0:D], Qc, alpha=QK_ALPHA if a16 else 1.0)
-            if i == 0:
-                self._side_join()                                # K / V of all layers
-            Oc = self.buf(f"{tag}:ca:O16" if a16 else f"{tag}:ca:O", (B * Q, D), torch.bfloat16 if a16 else torch.float32)
-            lse = self.buf(f"{tag}:ca:lse", (B * HEADS, Q))
-            hip.attention(Qc, KV[:, i * D:(i + 1) * D], KV[:, (nd + i) * D:(nd + i + 1) * D], Oc, lse, B, HEADS, Q, L,
-                          scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=ds + 2, dropout_step=self._seed_dev,
-                          dropmask=self._dropmask(ds + 2, B, Q, L) if (a16 and dp > 0.0) else None, key_valid=self.key_valid)
-            if cp in self._attn_sites:
-                self._attn_map(cp, Qc, KV[:, i * D:(i + 1) * D], lse, B, Q, L, self.key_valid)
-            a2 = self.buf(f"{tag}:a2", (B * Q, D))
-            t2 = self.buf(f"{tag}:t2", (B * Q, D))
-            t2h = self.buf(f"{tag}:t2h", (B * Q, D), torch.bfloat16) if self.ffn16 else None
-            ln2 = self._ln_spec(B * Q, f"{pfx}/norm2", t2, f"{tag}:ln2", y16=t2h)
-            hip.linear_fwd(Oc, self._w(f"{cp}/out_proj_kernel"), V[f"{cp}/out_proj_bias"], a2, residual=t1, dropout_p=dp,
-                           dropout_seed=ds + 3, dropout_step=self._seed_dev, ln=ln2)      # :226 (+ norm2)
-            if ln2 is None:
-                self._ln_fwd(a2, f"{pfx}/norm2", t2, f"{tag}:ln2", y16=t2h)
-            f = self.buf(f"{tag}:f", (B * Q, D))
-            t3 = self._bufs[f"{tag}:t3"] = t3all[i]
-            qin = self.buf(f"dec{i + 1}:qin", (B * Q, D)) if i + 1 < nd else None        # next layer's tgt + query_pos
-            ln3 = self._ln_spec(B * Q, f"{pfx}/norm3", t3, f"{tag}:ln3", add=qpos if qin is not None else None, y2=qin, ffn=True)
-            self._ffn_fwd(tag, pfx, t2, f, seed=ds + 4, x16=t2h, ln=ln3)
-            if ln3 is None:
-                self._ln_fwd(f, f"{pfx}/norm3", t3, f"{tag}:ln3", add=qpos if qin is not None else None, y2=qin)
-            tgt = t3
+            tgt, qin = self._decoder_layer_fwd(i, tgt, qin, qpos, KV, t3all[i], B, L)
         # the shared decoder norm of every level (:121-125) in one launch (round 4: it was one 800-row launch per layer, forward and backward)
         self._ln_fwd(t3all.view(nd * B * Q, D), "transformer/decoder/norm", hs.view(nd * B * Q, D), "dec:lnf")
         self.phase("fwd heads")
-        # ---------------- heads (detr.py:181-204 / :94-114) ----------------
-        hip.COMPUTE_BF16 = 0          # the heads, like LayerNorm / softmax / the set loss, always run in exact fp32
-        Lv = self.num_dec
-        R = Lv * B * Q
-        hs2 = hs.view(R, D)
-        logits = self.buf("head:logits", (R, self.C))
-        boxes = self.buf("head:boxes", (R, 4))
-        t_a, t_b = self.buf("head:t1", (R, D)), self.buf("head:t2", (R, D))
-        if self.nb_class is None:
-            hip.linear_fwd(hs2, V["class_embed/kernel"], V["class_embed/bias"], logits)
-            hip.linear_fwd(hs2, V["bbox_embed_0/kernel"], V["bbox_embed_0/bias"], t_a, act=1)
-            hip.linear_fwd(t_a, V["bbox_embed_1/kernel"], V["bbox_embed_1/bias"], t_b, act=1)
-            hip.linear_fwd(t_b, V["bbox_embed_2/kernel"], V["bbox_embed_2/bias"], boxes, act=2)
-        else:   # Keras Dense kernels are (in, out)
-            def dense(x, name, out, act):
-                k = V[f"{name}/kernel"]
-                hip.gemm(x.shape[0], k.shape[1], k.shape[0], x, x.stride(0), 1, k, k.shape[1], 0, out, out.stride(0),
-                         bias=V[f"{name}/bias"], act=act)
-            dense(hs2, "cls_layer", logits, 0)
-            dense(hs2, "pos_layer/dense_0", t_a, 1)
-            dense(t_a, "pos_layer/dense_1", t_b, 1)
-            dense(t_b, "pos_layer/dense_2", boxes, 2)
+        logits, boxes = self._heads_fwd(hs.view(nd * B * Q, D))
         self.phase("set loss")
-        return logits.view(Lv, B, Q, self.C), boxes.view(Lv, B, Q, 4)
+        return logits.view(nd, B, Q, self.C), boxes.view(nd, B, Q, 4)
 
-    # ---- backward ---------------------------------------------------------------------------------
     def zero_grad(self):
         hip.zero_(self.P.grad)
 
@@ -984,302 +759,499 @@ class DetrEngine:
         """d_logits [Lv,B,Q,C], d_boxes [Lv,B,Q,4] (contiguous CUDA fp32): gradients of the scalar
         loss w.r.t. the head outputs.  Parameter gradients are ACCUMULATED into P.grad.
         on_bucket(i) is called when gradient bucket i (ParamStore.bucket_bounds) is final."""
-        B, H, W = self._shape
-        V, G = self.P.views, self.P.gviews
-        Q, Lv = self.Q, self.num_dec
-        R = Lv * B * Q
-        hs = self._bufs["dec:hs"]
-        hs2 = hs.view(R, D)
-        dl = d_logits.reshape(R, self.C)
-        db = d_boxes.reshape(R, 4)
-        boxes, t_a, t_b = self._bufs["head:boxes"], self._bufs["head:t1"], self._bufs["head:t2"]
+        B = self._shape[0]
+        feat, _, _, L = self._feat_meta
+        nd, BQ = self.num_dec, B * self.Q
+        R = nd * BQ
         self.phase("bwd heads")
-        # ---------------- heads ----------------
-        hip.COMPUTE_BF16 = 0
-        dz3 = self.buf("scratch:dz3", (R, 4))
-        hip.call("detr_hip_sigmoid_bwd_f32", db.data_ptr(), boxes.data_ptr(), dz3.data_ptr(), R * 4)
-        d_hs = self.buf("scratch:d_hs", (R, D))
-        dt_b, dt_a = self.buf("scratch:dt_b", (R, D)), self.buf("scratch:dt_a", (R, D))
-        if self.nb_class is None:
-            hip.linear_wgrad(dz3, t_b, G["bbox_embed_2/kernel"], bias_grad=G["bbox_embed_2/bias"])
-            hip.linear_dgrad(dz3, V["bbox_embed_2/kernel"], dt_b, mask=t_b)
-            hip.linear_wgrad(dt_b, t_a, G["bbox_embed_1/kernel"], bias_grad=G["bbox_embed_1/bias"])
-            hip.linear_dgrad(dt_b, V["bbox_embed_1/kernel"], dt_a, mask=t_a)
-            hip.linear_wgrad(dt_a, hs2, G["bbox_embed_0/kernel"], bias_grad=G["bbox_embed_0/bias"])
-            hip.linear_dgrad(dt_a, V["bbox_embed_0/kernel"], d_hs)
-            hip.linear_wgrad(dl, hs2, G["class_embed/kernel"], bias_grad=G["class_embed/bias"])
-            hip.linear_dgrad(dl, V["class_embed/kernel"], d_hs, residual=d_hs)
-        else:
-            def dense_bwd(dy, x, name, dx, mask=None, residual=None):
-                k, gk = V[f"{name}/kernel"], G[f"{name}/kernel"]      # (in, out)
-                n_in, n_out = k.shape
-                self._wgrad(n_in, n_out, x.shape[0], x, x.stride(0), dy, dy.stride(0), gk, n_out)
-                self._colsum(dy, G[f"{name}/bias"])
-                hip.gemm(dy.shape[0], n_in, n_out, dy, dy.stride(0), 1, k, n_out, 1, dx, dx.stride(0), residual=residual,
-                         ldr=(dx.stride(0) if residual is not None else 0), mask=mask,
-                         ldmask=(mask.stride(0) if mask is not None else 0))
-            dense_bwd(dz3, t_b, "pos_layer/dense_2", dt_b, mask=t_b)
-            dense_bwd(dt_b, t_a, "pos_layer/dense_1", dt_a, mask=t_a)
-            dense_bwd(dt_a, hs2, "pos_layer/dense_0", d_hs)
-            dense_bwd(dl, hs2, "cls_layer", d_hs, residual=d_hs)
-        d_hs3 = d_hs.view(Lv, B * Q, D)
-        hip.COMPUTE_BF16 = self.gemm_mode
+        d_hs = self._heads_bwd(d_logits.reshape(R, self.C), d_boxes.reshape(R, 4))
         self.phase("bwd decoder")
-        # ---------------- decoder ----------------
-        feat, Hf, Wf, L = self._feat_meta
-        nd = self.num_dec
         memory = self._bufs[f"enc{self.num_enc - 1}:x2"] if self.num_enc > 0 else self._bufs["enc:src0"]
         mem_pos = self._bufs["dec:mem_pos"] if self.num_enc > 0 else self._bufs["enc0:qk"]
-        a16 = self.attn16
-        adt16 = torch.bfloat16 if a16 else torch.float32
-        KV = self._bufs["dec:KV16" if a16 else "dec:KV"]
-        ct = self._cross_tables()
-        qpos, g_qpos = V["query_embed/kernel"], G["query_embed/kernel"]
-        BQ = B * Q
-        dp, _ = self._drop
-        dKV = self.buf(f"scratch:dKV:{int(a16)}", (B * L, 2 * nd * D), adt16)      # every column block is written by its layer's attention backward
+        KV = self._bufs[self._a16("dec:KV")[0]]
+        dKV = self.buf(f"scratch:dKV:{int(self.attn16)}", KV.shape, KV.dtype)      # every column block is written by its layer's attention backward
         acc_qpos = self.buf("scratch:acc_qpos", (BQ, D))             # sum over layers / sites of d(tgt + query_pos): query_pos gradient
         hip.zero_(acc_qpos)
-        d_next = None                       # gradient flowing into t3 of layer i from layer i+1
         # the shared decoder norm, all levels at once: d_t3n[i] = gradient of level i's head input w.r.t. t3 of layer i
         d_t3n = self.buf("scratch:d_t3n", (nd, BQ, D))
-        self._ln_bwd(d_hs3.view(nd * BQ, D), self._bufs["dec:t3all"].view(nd * BQ, D), "transformer/decoder/norm", d_t3n.view(nd * BQ, D), "dec:lnf")
+        self._ln_bwd(d_hs, self._bufs["dec:t3all"].view(R, D), "transformer/decoder/norm", d_t3n.view(R, D), "dec:lnf")
+        d_next = None                       # gradient flowing into t3 of layer i from layer i+1
         for i in reversed(range(nd)):
-            pfx, tag = f"transformer/decoder/layer_{i}", f"dec{i}"
-            cp = f"{pfx}/multihead_attn"
-            t1, t2, t3 = self._bufs[f"{tag}:t1"], self._bufs[f"{tag}:t2"], self._bufs[f"{tag}:t3"]
-            a1, a2, f = self._bufs[f"{tag}:a1"], self._bufs[f"{tag}:a2"], self._bufs[f"{tag}:f"]
-            qin, q2 = self._bufs[f"{tag}:qin"], self._bufs[f"{tag}:q2"]
-            tgt = self._bufs[f"dec{i - 1}:t3"] if i > 0 else self._bufs["dec:tgt0"]
-            ds = 16 * (32 + i)
-            d_f = self.buf(f"scratch:d_f{self._sx(tag)}", (BQ, D))
-            # d_t3 = d_t3n[i] + d_next: the two branches are summed by the norm3 backward itself
-            d_y = self._ln_bwd(d_t3n[i], f, f"{pfx}/norm3", d_f, f"{tag}:ln3", drop_site=ds + 5, want16=self.ffn16, dy_add=d_next)
-            d_t2 = self.buf("scratch:d_t2", (BQ, D))
-            self._ffn_bwd(tag, pfx, d_y, d_f, t2, d_t2, x16=self._bufs.get(f"{tag}:t2h") if self.ffn16 else None)
-            d_a2 = self.buf(f"scratch:d_a2{self._sx(tag)}", (BQ, D))
-            d_out = self._ln_bwd(d_t2, a2, f"{pfx}/norm2", d_a2, f"{tag}:ln2", drop_site=ds + 3)
-            # ---- cross attention
-            Wc = self._w(f"{cp}/in_proj_kernel")
-            Qc, Oc = self._bufs[f"{tag}:ca:Q16" if a16 else f"{tag}:ca:Q"], self._bufs[f"{tag}:ca:O16" if a16 else f"{tag}:ca:O"]
-            dO = self.buf(f"scratch:dO:{BQ}:{int(a16)}", (BQ, D), adt16)
-            hip.linear_dgrad(d_out, self._w(f"{cp}/out_proj_kernel"), dO)
-            dQc = self.buf(f"scratch:dQc:{int(a16)}{self._sx(tag)}", (BQ, D), adt16)
-            delta = self.buf(f"scratch:delta:{BQ}", (2 * B * HEADS, Q))
-            hip.attention(Qc, KV[:, i * D:(i + 1) * D], KV[:, (nd + i) * D:(nd + i + 1) * D], Oc, self._bufs[f"{tag}:ca:lse"],
-                          B, HEADS, Q, L, scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=ds + 2, dropout_step=self._seed_dev,
-                          d_o=dO, dq=dQc, dk=dKV[:, i * D:(i + 1) * D], dv=dKV[:, (nd + i) * D:(nd + i + 1) * D], delta=delta,
-                          dropmask=self._dropmask(ds + 2, B, Q, L) if (a16 and dp > 0.0) else None, key_valid=self.key_valid)
-            self._side(lambda d_out=d_out, Oc=Oc, dQc=dQc, q2=q2, cp=cp: hip.gemm_group([
-                hip.linear_wgrad_call(d_out, Oc, G[f"{cp}/out_proj_kernel"], bias_grad=G[f"{cp}/out_proj_bias"]),
-                hip.linear_wgrad_call(dQc, q2, G[f"{cp}/in_proj_kernel"][0:D], bias_grad=G[f"{cp}/in_proj_bias"][0:D])]))
-            d_t1 = self.buf("scratch:d_t1", (BQ, D))
-            # q2 = t1 + query_pos ; a2 = attn + t1: the q gradient goes to t1 (with the residual path) and to the query_pos sum
-            hip.gemm_group([hip.linear_dgrad_call(dQc, Wc[0:D], acc_qpos, residual=acc_qpos),
-                            hip.linear_dgrad_call(dQc, Wc[0:D], d_t1, residual=d_a2)])
-            d_a1 = self.buf(f"scratch:d_a1{self._sx(tag)}", (BQ, D))
-            d_out = self._ln_bwd(d_t1, a1, f"{pfx}/norm1", d_a1, f"{tag}:ln1", drop_site=ds + 1)
-            # ---- self attention: qin = tgt + query_pos feeds q and k, tgt feeds v and the residual
-            d_tgt = self.buf(f"scratch:d_tgt{i & 1}", (BQ, D)) if i > 0 else None      # layer 0: tgt is the constant zero target
-            self._self_attn_bwd(f"{tag}:sa", f"{pfx}/self_attn", d_out, d_a1, qin, tgt, B, Q, d_tgt, site=ds, acc_qk=acc_qpos)
-            d_next = d_tgt
-        self._colsum(acc_qpos.view(B, Q * D), g_qpos.view(Q * D))      # d query_pos (sum over the batch)
-        # ---- K / V projections of all layers: weight gradient of the gathered copy (scattered back into the per-layer
-        #      in_proj gradients by one launch) and ONE data gradient GEMM with K = 2*nd*256
-        hip.zero_(ct["gW"])
-        hip.zero_(ct["gb"])
-        hip.gemm_group([hip.linear_wgrad_call(dKV[:, 0:nd * D], mem_pos, ct["gW"][0:nd * D], bias_grad=ct["gb"][0:nd * D]),
-                        hip.linear_wgrad_call(dKV[:, nd * D:], memory, ct["gW"][nd * D:], bias_grad=ct["gb"][nd * D:])])
-        self._side_join()
-        hip.flush_reduces()                            # the scatter reads the gathered gradient
-        hip.multi_copy(ct["scatter"])
-        d_mem = self.buf("scratch:d_mem", (B * L, D))
-        hip.linear_dgrad(dKV, ct["Wkv"], d_mem)        # d(memory + pos) through K and d(memory) through V land on the same tensor
+            d_next = self._decoder_layer_bwd(i, d_t3n[i], d_next, KV, dKV, acc_qpos, B, L)
+        self._colsum(acc_qpos.view(B, self.Q * D), self.P.gviews["query_embed/kernel"].view(self.Q * D))      # d query_pos (sum over the batch)
+        d_x = self._cross_kv_bwd(dKV, memory, mem_pos, B, L)
         self.phase("bwd encoder")
-        # ---------------- encoder ----------------
-        d_x = d_mem
         for i in reversed(range(self.num_enc)):
-            pfx, tag = f"transformer/encoder/layer_{i}", f"enc{i}"
-            x_in = self._bufs[f"enc{i - 1}:x2"] if i > 0 else self._bufs["enc:src0"]
-            qk, a, x1, f = (self._bufs[f"{tag}:{n}"] for n in ("qk", "a", "x1", "f"))
-            d_f = self.buf(f"scratch:e_d_f{self._sx(tag)}", (B * L, D))
-            d_y = self._ln_bwd(d_x, f, f"{pfx}/norm2", d_f, f"{tag}:ln2", drop_site=16 * i + 3, want16=self.ffn16)
-            d_x1 = self.buf("scratch:e_d_x1", (B * L, D))
-            self._ffn_bwd(tag, pfx, d_y, d_f, x1, d_x1, x16=self._bufs.get(f"{tag}:x1h") if self.ffn16 else None)
-            d_a = self.buf(f"scratch:e_d_a{self._sx(tag)}", (B * L, D))
-            d_out = self._ln_bwd(d_x1, a, f"{pfx}/norm1", d_a, f"{tag}:ln1", drop_site=16 * i + 1)
-            d_xn = self.buf(f"scratch:e_d_x{i & 1}", (B * L, D))
-            self._self_attn_bwd(f"{tag}:sa", f"{pfx}/self_attn", d_out, d_a, qk, x_in, B, L, d_xn, site=16 * i, key_valid=self.key_valid)
-            d_x = d_xn
+            d_x = self._encoder_layer_bwd(i, d_x, B, L)
         if on_bucket:
             on_bucket(0)
         self.phase("bwd backbone")
-        # ---------------- input_proj ----------------
-        self._wgrad(2048, D, B * L, feat, 2048, d_x, D, G["input_proj/kernel"], D)
-        self._colsum(d_x, G["input_proj/bias"])
+        g = self._input_proj_bwd(d_x, feat, B, L, want_dx=backbone)
         if not backbone:
             if on_bucket:
                 for i in (1, 2, 3):
                     on_bucket(i)
             return
-        adt = self._adt
-        g = self.buf("scratch:g_feat", feat.shape, adt)
-        hip.gemm(B * L, 2048, D, d_x, D, 1, self._w("input_proj/kernel"), D, 1, g, 2048, mask=feat, ldmask=2048)
-        # ---------------- residual stages ----------------
-        n_blocks = len(self._block_meta)
-        tfb = self.tf_backbone
-        f32c = 2 if adt == torch.bfloat16 else 1        # the subsample kernels copy 16-byte chunks: bf16 passes as C/2 "floats"
-
-        def bias_grad(conv, bn, dz, rows, cols):
-            """tf_backbone: db = scale * column sums of the gradient at the conv + BN output (the folded BN scales the bias)."""
-            if tfb:
-                hip.call("detr_hip_colsum_scaled", dz.data_ptr(), 1 if dz.dtype == torch.bfloat16 else 0, rows, cols, cols,
-                         self.bn_scale[bn].data_ptr(), G[f"{conv}/bias"].data_ptr())
-
-        # Weight gradients of a block do not feed the data-gradient chain (g -> dz2 -> dz1 -> gx): with WGRAD_STREAM they are
-        # issued on a second stream, each behind an event of the main stream that follows its producer, so a chip-filling
-        # but HBM-bound data-gradient GEMM and an MFMA/LDS-bound weight gradient share the CUs (inside the captured graph the
-        # fork / join events become plain graph edges).  The scratch tensors the side stream reads (dz2, dz1: double-buffered
-        # by block parity; gx) are only overwritten after the side work that read them has been waited for.
-        ws_on = self._side_on
-        main, wside = (self._side_main, self._wg_stream) if ws_on else (None, None)
-        side_done = {}
-        on_side = self._side
-
-        def side_mark(bi):
-            if ws_on:
-                ev = torch.cuda.Event()
-                ev.record(wside)
-                side_done[bi] = ev
-
-        def side_wait(bi):
-            ev = side_done.pop(bi, None)
-            if ev is not None:
-                main.wait_event(ev)
-
-        for bi in reversed(range(n_blocks)):
-            m = self._block_meta[bi]
-            side_wait(bi + 2)
-            par = f":{bi & 1}" if ws_on else ""
-            p, n, x, xs, x1, y1, y2 = m["p"], m["n"], m["x"], m["xs"], m["x1"], m["y1"], m["y2"]
-            h, w, ho, wo, cin, d1, d2, stride = m["h"], m["w"], m["ho"], m["wo"], m["cin"], m["d1"], m["d2"], m["stride"]
-            h1, w1, M1, s2 = m["h1"], m["w1"], m["M1"], m["s2"]
-            M_in, M_out = B * h * w, B * ho * wo
-            wk = "ws16" if self.compute == 1 else "ws"       # scaled kernels of the forward (bf16 shadow in bf16 mode)
-            ws1 = self._bufs[f"{wk}:{n['conv1']}/kernel"]
-            ws2 = self._bufs[f"{wk}:{n['conv2']}/kernel"]
-            ws3 = self._bufs[f"{wk}:{n['conv3']}/kernel"]
-            # conv3: g is the gradient w.r.t. (bn3(conv3(y2)) + identity), already ReLU-masked
-            strided = m["first"] and stride == 2
-            wsd = self._bufs[f"{wk}:{n['down']}/kernel"] if m["first"] else None
-            idg, idg_ready, idg_sub = g, None, None
-            # layer1's 64 -> 256 convolutions on bf16 tensors: g (274 MB at B = 8, 800 x 1333) is read once per convolution, not twice
-            fused_ok = BWD_FUSED and self.compute == 1 and adt == torch.bfloat16 and d2 == 256 and g.is_cuda
-            fuse3, fuse_down = fused_ok and d1 == 64, False
-            if m["first"] and not (tfb and strided):
-                # data gradient of the projection shortcut: only the block's last GEMM reads it (as its residual operand).
-                # Stride 2, bf16 tensors: it stays the compact [B, ho, wo, cin] tensor and the GEMM's residual row map
-                # (detr_gemm_desc.res_sub_*) adds it at the even pixels -- no zero-filled full-resolution copy is written or read
-                sub_res = strided and adt == torch.bfloat16
-                if sub_res:
-                    idg, idg_sub = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt), (h, w)
-                else:
-                    idg = self.buf(f"scratch:idg:{cin}:{h}", (B, h, w, cin), adt)
-
-                # (layer1, bf16: the shortcut's input gradient and weight gradient in ONE pass over g -- csrc/bwd_fused.hip)
-                fuse_down = fused_ok and not strided and cin == 64
-
-                def dg_down(g=g, idg=idg, sub_res=sub_res):
-                    if sub_res:
-                        hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, idg, cin)
-                    elif strided:
-                        dxs = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt)
-                        hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, dxs, cin)
-                        hip.call("detr_hip_subsample2_bwd_f32", dxs.data_ptr(), idg.data_ptr(), B, h, w, cin // f32c, ho, wo)
-                    elif fuse_down:
-                        hip.conv1x1_bwd_fused(g.view(M_out, d2), xs.view(M_out, cin), wsd.view(cin, d2), idg.view(M_out, cin), G[f"{n['down']}/kernel"].view(cin, d2),
-                                              self.buf(f"bwdfused:slabs:down:{M_out}", (hip.conv1x1_bwd_fused_scratch_floats(M_out),)),
-                                              scale=self.bn_scale[n["bnd"]], use_mask=False)
-                    else:
-                        hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, idg, cin)
-                on_side(dg_down)
-                if ws_on:
-                    idg_ready = torch.cuda.Event()
-                    idg_ready.record(wside)
-
-            def wg3(g=g, fuse3=fuse3, fuse_down=fuse_down):
-                if not fuse3:
-                    self._wgrad(d1, d2, M_out, y2, d1, g, d2, G[f"{n['conv3']}/kernel"], d2, scale=self.bn_scale[n["bn3"]])
-                bias_grad(n["conv3"], n["bn3"], g, M_out, d2)
-                if m["first"]:
-                    if not fuse_down:
-                        self._wgrad(cin, d2, M_out, xs, cin, g, d2, G[f"{n['down']}/kernel"], d2, scale=self.bn_scale[n["bnd"]])
-                    bias_grad(n["down"], n["bnd"], g, M_out, d2)
-            on_side(wg3)
-            dz2 = self.buf(f"scratch:dz2:{d1}:{ho}{par}", (B, ho, wo, d1), adt)
-            if fuse3:
-                hip.conv1x1_bwd_fused(g.view(M_out, d2), y2.view(M_out, d1), ws3.view(d1, d2), dz2.view(M_out, d1), G[f"{n['conv3']}/kernel"].view(d1, d2),
-                                      self.buf(f"bwdfused:slabs:{M_out}", (hip.conv1x1_bwd_fused_scratch_floats(M_out),)),
-                                      scale=self.bn_scale[n["bn3"]], use_mask=True)
-            else:
-                hip.gemm(M_out, d1, d2, g, d2, 1, ws3, d2, 1, dz2, d1, mask=y2, ldmask=d1)
-            # conv2 (3x3)
-
-            def wg2():
-                hip.conv3x3(2, y1, dz2, G[f"{n['conv2']}/kernel"], B, h1, w1, d1, ho, wo, d1, s2, scale=self.bn_scale[n["bn2"]],
-                            pad=m["dil"], dilation=m["dil"])
-                bias_grad(n["conv2"], n["bn2"], dz2, M_out, d1)
-            on_side(wg2)
-            dz1 = self.buf(f"scratch:dz1:{d1}:{h1}{par}", (B, h1, w1, d1), adt)
-            hip.conv3x3(1, dz2, ws2, dz1, B, h1, w1, d1, ho, wo, d1, s2, mask=y1, pad=m["dil"], dilation=m["dil"])
-            # conv1
-
-            def wg1():
-                self._wgrad(cin, d1, M1, x1, cin, dz1, d1, G[f"{n['conv1']}/kernel"], d1, scale=self.bn_scale[n["bn1"]])
-                bias_grad(n["conv1"], n["bn1"], dz1, M1, d1)
-            on_side(wg1)
-            side_mark(bi)
-            side_wait(bi + 1)               # gx of this parity was read (as g) by the side work of block bi + 1
-            is_first_block = bi == 0
-            gx = self.buf(f"scratch:gx:{cin}:{h}:{bi & 1}", (B, h, w, cin), adt)
-            mask = None if is_first_block else x           # x = ReLU output of the previous block
-            xbits = None if is_first_block else self._block_meta[bi - 1].get("out_bits")      # ... or its sign bits
-            if tfb and strided:
-                # both branches read the subsampled input: d_xs = g @ Wd^T + dz1 @ W1^T (ReLU-masked at the sampled pixels),
-                # scattered back into the zero-filled full-resolution gradient
-                dxs = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt)
-                hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, dxs, cin)
-                hip.gemm(M_out, cin, d1, dz1, d1, 1, ws1, d1, 1, dxs, cin, residual=dxs, ldr=cin,
-                         mask=(None if is_first_block else xs), ldmask=(0 if is_first_block else cin))
-                hip.call("detr_hip_subsample2_bwd_f32", dxs.data_ptr(), gx.data_ptr(), B, h, w, cin // f32c, ho, wo)
-            else:
-                if idg_ready is not None:
-                    main.wait_event(idg_ready)
-                if xbits is not None:
-                    hip.gemm(M_in, cin, d1, dz1, d1, 1, ws1, d1, 1, gx, cin, residual=idg, ldr=cin, mask=xbits, ldmask=xbits.stride(0),
-                             res_sub=idg_sub)
-                else:
-                    hip.gemm(M_in, cin, d1, dz1, d1, 1, ws1, d1, 1, gx, cin, residual=idg, ldr=cin, mask=mask,
-                             ldmask=(cin if mask is not None else 0), res_sub=idg_sub)
-            g = gx
-            if on_bucket:
-                if p == block_names(3, 0, tfb)["tag"]:
-                    on_bucket(1)
-                elif p == block_names(2, 0, tfb)["tag"]:
-                    on_bucket(2)
-        self._side_join()
-        # ---------------- stem ----------------
-        stem, pool, amax = (self._bufs[f"stem:{n}"] for n in ("out", "pool", "amax"))
-        H1, W1 = stem.shape[1], stem.shape[2]
-        H2, W2 = pool.shape[1], pool.shape[2]
-        d_stem = self.buf("scratch:d_stem", stem.shape, adt)
-        hip.call("detr_hip_maxpool3x3s2_bwd_bf16" if adt == torch.bfloat16 else "detr_hip_maxpool3x3s2_bwd_f32", g.data_ptr(),
-                 amax.data_ptr(), stem.data_ptr(), d_stem.data_ptr(), B, H1, W1, 64, H2, W2)
-        M1 = B * H1 * W1
-        hip.stem_conv(2, self.images, d_stem, G[f"{self._stem['conv']}/kernel"], B, self._shape[1], self._shape[2], H1, W1,
-                      scale=self.bn_scale[self._stem["bn"]], split=max(1, min(512, M1 // 4096)))
-        if self.tf_backbone:
-            hip.call("detr_hip_colsum_scaled", d_stem.data_ptr(), 1 if d_stem.dtype == torch.bfloat16 else 0, B * H1 * W1, 64, 64,
-                     self.bn_scale[self._stem["bn"]].data_ptr(), G[f"{self._stem['conv']}/bias"].data_ptr())
+        bucket_at = {block_names(3, 0, self.tf_backbone)["tag"]: 1, block_names(2, 0, self.tf_backbone)["tag"]: 2}
+        for bi in reversed(range(len(self._block_recs))):
+            g = self._block_bwd(bi, g, B)
+            if on_bucket and self._block_recs[bi].p in bucket_at:
+                on_bucket(bucket_at[self._block_recs[bi].p])
+        self.side.join()
+        self._stem_bwd(g, B)
         if on_bucket:
             on_bucket(3)
+
+    # ---- stem (resnet_backbone.py:11-26) --------------------------------------------------------------
+    def _pool_fn(self, which):
+        return f"detr_hip_maxpool3x3s2_{which}_{'bf16' if self._adt == torch.bfloat16 else 'f32'}"
+
+    def _chunks(self, c):
+        """The subsample kernels copy 16-byte chunks: a bf16 tensor passes as c / 2 "float" channels."""
+        return c // 2 if self._adt == torch.bfloat16 else c
+
+    def _bias_grad(self, conv, bn, dz, rows, cols):
+        """tf_backbone: db = scale * column sums of the gradient at the conv + BN output (the folded BN scales the bias)."""
+        if self.tf_backbone:
+            hip.call("detr_hip_colsum_scaled", dz.data_ptr(), 1 if dz.dtype == torch.bfloat16 else 0, rows, cols, cols,
+                     self.bn_scale[bn].data_ptr(), self.P.gviews[f"{conv}/bias"].data_ptr())
+
+    def _stem_fwd(self, images, B, H, W):
+        """7x7 / 2 conv + frozen BN + ReLU, 3x3 / 2 max pool.  Returns (pool, H2, W2)."""
+        H1, W1 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+        ws = self._scaled_kernel(f"{self._stem['conv']}/kernel", self._stem["bn"])
+        adt = self._adt = torch.bfloat16 if self.compute == 1 else torch.float32      # storage type of backbone activations (and their gradients)
+        stem = self.buf("stem:out", (B, H1, W1, 64), adt)
+        # implicit GEMM: the 7x7x3 patches are gathered from the image by the A loader (stem_conv.hip), no im2col buffer
+        hip.stem_conv(0, images, ws, stem, B, H, W, H1, W1, bias=self.bn_shift[self._stem["bn"]], act=1)
+        H2, W2 = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
+        pool = self.buf("stem:pool", (B, H2, W2, 64), adt)
+        amax = self.buf("stem:amax", (B, H2, W2, 64), torch.uint8)
+        hip.call(self._pool_fn("fwd"), stem.data_ptr(), pool.data_ptr(), amax.data_ptr(), B, H1, W1, 64, H2, W2)
+        return pool, H2, W2
+
+    def _stem_bwd(self, g, B):
+        stem, pool, amax = (self._bufs[f"stem:{n}"] for n in ("out", "pool", "amax"))
+        (H1, W1), (H2, W2) = stem.shape[1:3], pool.shape[1:3]
+        d_stem = self.buf("scratch:d_stem", stem.shape, self._adt)
+        hip.call(self._pool_fn("bwd"), g.data_ptr(), amax.data_ptr(), stem.data_ptr(), d_stem.data_ptr(), B, H1, W1, 64, H2, W2)
+        M1 = B * H1 * W1
+        hip.stem_conv(2, self.images, d_stem, self.P.gviews[f"{self._stem['conv']}/kernel"], B, self._shape[1], self._shape[2], H1, W1,
+                      scale=self.bn_scale[self._stem["bn"]], split=max(1, min(512, M1 // 4096)))
+        self._bias_grad(self._stem["conv"], self._stem["bn"], d_stem, M1, 64)
+
+    # ---- one bottleneck block (resnet_backbone.py:116-137) ----------------------------------------------
+    def _block_fwd(self, li, b, x, h, w, cin, B, training):
+        """Block b of stage li on x [B, h, w, cin].  Returns its Block record (.out: the output)."""
+        adt, nb = self._adt, self.blocks[li]
+        d1, d2 = 64 * 2 ** li, 256 * 2 ** li
+        n = block_names(li, b, self.tf_backbone)
+        p = n["tag"]
+        dilated = li > 0 and self.dilate[li - 1]         # the stage trades its stride for dilation (resnet_backbone.py:74-85)
+        stride = 2 if (b == 0 and li > 0 and not dilated) else 1
+        dil = 2 if (dilated and b > 0) else 1            # the stage's first block keeps dilation 1
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        M_in, M_out = B * h * w, B * ho * wo
+        xs = x
+        if stride == 2 and (b == 0):
+            # stride-2 1x1 convs read every second pixel: gather them once (a plain 16-byte-chunk copy)
+            xs = self.buf(f"{p}:xs", (B, ho, wo, cin), adt)
+            hip.call("detr_hip_subsample2_fwd_f32", x.data_ptr(), xs.data_ptr(), B, h, w, self._chunks(cin), ho, wo)
+        if self.tf_backbone:            # ResNet v1 (keras.applications): the stride sits on the FIRST 1x1 conv
+            x1, M1, h1, w1, s2 = xs, M_out, ho, wo, 1
+        else:                           # reference backbone (resnet_backbone.py:104-105): on the 3x3 conv
+            x1, M1, h1, w1, s2 = x, M_in, h, w, stride
+        if b == 0:
+            # the projection shortcut only meets the main branch at conv3's residual operand: second stream
+            # (an HBM-bound 1x1 GEMM next to the MFMA-bound 3x3 conv)
+            idn = self.buf(f"{p}:idn", (B, ho, wo, d2), adt)
+            self.side.run(lambda: self._conv1x1_fwd(xs, M_out, cin, d2, f"{n['down']}/kernel", n["bnd"], idn, act=0))
+        else:
+            idn = x
+        y1 = self.buf(f"{p}:y1", (B, h1, w1, d1), adt)
+        self._conv1x1_fwd(x1, M1, cin, d1, f"{n['conv1']}/kernel", n["bn1"], y1)
+        y2 = self.buf(f"{p}:y2", (B, ho, wo, d1), adt)
+        hip.conv3x3(0, y1, self._scaled_kernel(f"{n['conv2']}/kernel", n["bn2"]), y2, B, h1, w1, d1, ho, wo, d1,
+                    s2, bias=self.bn_shift[n["bn2"]], act=1, pad=dil, dilation=dil)
+        if b == 0:
+            self.side.join()
+        out = self.buf(f"{p}:out", (B, ho, wo, d2), adt)
+        # training, bf16 activation storage: the block output's ReLU mask as BITS (1 byte per 8 channels) next to the tensor --
+        # the backward only needs the sign, and the GEMMs that apply it are HBM streams (1/16 of the mask bytes)
+        # (only where the consumer is the STREAMING kernel -- the conv1 input gradient of a following block of layer1-3: there the
+        #  mask stream is a third of the bytes; in the tile engine's / the 3x3 kernels' epilogues the byte loads measured 2-9 %
+        #  SLOWER than the 16-byte mask loads, so y1 / y2 and the layer4 blocks keep their bf16 masks)
+        nxt_d1 = 64 * 2 ** (li if b + 1 < nb else li + 1)        # d1 of the next block
+        last = (li + 1 == len(self.blocks)) and (b + 1 == nb)
+        obits = self.buf(f"{p}:out_bits", (M_out, d2 // 8), torch.uint8) \
+            if (training and adt == torch.bfloat16 and not last and nxt_d1 <= 256) else None
+        self._conv1x1_fwd(y2, M_out, d1, d2, f"{n['conv3']}/kernel", n["bn3"], out, residual=idn, maskbits_out=obits)
+        return Block(p=p, n=n, x=x, xs=xs, x1=x1, y1=y1, y2=y2, out=out, h=h, w=w, ho=ho, wo=wo, h1=h1, w1=w1, M1=M1, s2=s2,
+                     cin=cin, d1=d1, d2=d2, stride=stride, first=(b == 0), out_bits=obits, dil=dil)
+
+    def _ws(self, conv):
+        """Scaled kernel of `conv` as the forward used it (the bf16 copy in bf16 mode)."""
+        return self._bufs[f"{'ws16' if self.compute == 1 else 'ws'}:{conv}/kernel"]
+
+    def _bwd_fused(self, m):
+        """(conv3, shortcut): which of layer1's 64 -> 256 convolutions on bf16 tensors take input AND weight gradient from one
+        pass over dY (csrc/bwd_fused.hip) -- dY (274 MB at B = 8, 800 x 1333) is read once per convolution, not twice."""
+        ok = BWD_FUSED and self.compute == 1 and self._adt == torch.bfloat16 and m.d2 == 256
+        return ok and m.d1 == 64, ok and m.first and m.stride == 1 and m.cin == 64
+
+    def _shortcut_dgrad(self, m, g, B):
+        """Data gradient of the block's shortcut: (idg, idg_sub, ready).  idg is the residual operand of the block's last GEMM
+        (g itself for an identity shortcut), idg_sub = (h, w) when idg is the COMPACT [B, ho, wo, cin] gradient of a stride-2
+        projection (bf16 tensors: the GEMM's residual row map, detr_gemm_desc.res_sub_*, adds it at the even pixels -- no
+        zero-filled full-resolution copy is written or read), ready = the side-stream event behind it (None: nothing to wait
+        for).  The tf backbone's strided blocks fold the shortcut into their own last GEMMs (_block_bwd)."""
+        strided = m.first and m.stride == 2
+        if not m.first or (self.tf_backbone and strided):
+            return g, None, None
+        adt, cin, d2, ho, wo, M_out = self._adt, m.cin, m.d2, m.ho, m.wo, B * m.ho * m.wo
+        wsd, n = self._ws(m.n["down"]), m.n
+        compact = strided and adt == torch.bfloat16
+        fuse_down = self._bwd_fused(m)[1]
+        idg = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt) if compact else self.buf(f"scratch:idg:{cin}:{m.h}", (B, m.h, m.w, cin), adt)
+
+        def dgrad():
+            if strided and not compact:         # fp32 tensors: scattered into the zero-filled full-resolution gradient
+                dxs = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt)
+                hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, dxs, cin)
+                hip.call("detr_hip_subsample2_bwd_f32", dxs.data_ptr(), idg.data_ptr(), B, m.h, m.w, self._chunks(cin), ho, wo)
+            elif fuse_down:                     # with the shortcut's weight gradient (_wg3 skips it)
+                hip.conv1x1_bwd_fused(g.view(M_out, d2), m.xs.view(M_out, cin), wsd.view(cin, d2), idg.view(M_out, cin),
+                                      self.P.gviews[f"{n['down']}/kernel"].view(cin, d2),
+                                      self.buf(f"bwdfused:slabs:down:{M_out}", (hip.conv1x1_bwd_fused_scratch_floats(M_out),)),
+                                      scale=self.bn_scale[n["bnd"]], use_mask=False)
+            else:
+                hip.gemm(M_out, cin, d2, g, d2, 1, wsd, d2, 1, idg, cin)
+        self.side.run(dgrad)
+        return idg, ((m.h, m.w) if compact else None), self.side.event()
+
+    # Weight gradients of a block do not feed the data-gradient chain (g -> dz2 -> dz1 -> gx): _block_bwd issues each group
+    # through side.run, behind an event of the main stream that follows its producer, so a chip-filling but HBM-bound
+    # data-gradient GEMM and an MFMA/LDS-bound weight gradient share the CUs.
+    def _wg3(self, m, g, M_out, fuse3, fuse_down):
+        """conv3 and the projection shortcut (both read g)."""
+        n, G = m.n, self.P.gviews
+        if not fuse3:
+            self._wgrad(m.d1, m.d2, M_out, m.y2, m.d1, g, m.d2, G[f"{n['conv3']}/kernel"], m.d2, scale=self.bn_scale[n["bn3"]])
+        self._bias_grad(n["conv3"], n["bn3"], g, M_out, m.d2)
+        if m.first:
+            if not fuse_down:
+                self._wgrad(m.cin, m.d2, M_out, m.xs, m.cin, g, m.d2, G[f"{n['down']}/kernel"], m.d2, scale=self.bn_scale[n["bnd"]])
+            self._bias_grad(n["down"], n["bnd"], g, M_out, m.d2)
+
+    def _wg2(self, m, dz2, B):
+        n, d1 = m.n, m.d1
+        hip.conv3x3(2, m.y1, dz2, self.P.gviews[f"{n['conv2']}/kernel"], B, m.h1, m.w1, d1, m.ho, m.wo, d1, m.s2,
+                    scale=self.bn_scale[n["bn2"]], pad=m.dil, dilation=m.dil)
+        self._bias_grad(n["conv2"], n["bn2"], dz2, B * m.ho * m.wo, d1)
+
+    def _wg1(self, m, dz1):
+        n = m.n
+        self._wgrad(m.cin, m.d1, m.M1, m.x1, m.cin, dz1, m.d1, self.P.gviews[f"{n['conv1']}/kernel"], m.d1, scale=self.bn_scale[n["bn1"]])
+        self._bias_grad(n["conv1"], n["bn1"], dz1, m.M1, m.d1)
+
+    def _block_bwd(self, bi, g, B):
+        """g: gradient w.r.t. the output of block bi (= bn3(conv3(y2)) + shortcut), already ReLU-masked.  Returns the gradient
+        w.r.t. its input, masked by the previous block's ReLU.  The scratch tensors the side stream reads (dz2, dz1: double-buffered
+        by block parity; gx) are only overwritten after the side work that read them has been waited for (side.mark / wait)."""
+        m, side, adt = self._block_recs[bi], self.side, self._adt
+        n, cin, d1, d2, ho, wo = m.n, m.cin, m.d1, m.d2, m.ho, m.wo
+        M_in, M_out = B * m.h * m.w, B * ho * wo
+        side.wait(bi + 2)
+        par = side.suffix(bi & 1)
+        fuse3, fuse_down = self._bwd_fused(m)
+        idg, idg_sub, idg_ready = self._shortcut_dgrad(m, g, B)
+        # conv3 (1x1)
+        side.run(lambda: self._wg3(m, g, M_out, fuse3, fuse_down))
+        dz2 = self.buf(f"scratch:dz2:{d1}:{ho}{par}", (B, ho, wo, d1), adt)
+        ws3 = self._ws(n["conv3"])
+        if fuse3:
+            hip.conv1x1_bwd_fused(g.view(M_out, d2), m.y2.view(M_out, d1), ws3.view(d1, d2), dz2.view(M_out, d1),
+                                  self.P.gviews[f"{n['conv3']}/kernel"].view(d1, d2),
+                                  self.buf(f"bwdfused:slabs:{M_out}", (hip.conv1x1_bwd_fused_scratch_floats(M_out),)),
+                                  scale=self.bn_scale[n["bn3"]], use_mask=True)
+        else:
+            hip.gemm(M_out, d1, d2, g, d2, 1, ws3, d2, 1, dz2, d1, mask=m.y2, ldmask=d1)
+        # conv2 (3x3)
+        side.run(lambda: self._wg2(m, dz2, B))
+        dz1 = self.buf(f"scratch:dz1:{d1}:{m.h1}{par}", (B, m.h1, m.w1, d1), adt)
+        hip.conv3x3(1, dz2, self._ws(n["conv2"]), dz1, B, m.h1, m.w1, d1, ho, wo, d1, m.s2, mask=m.y1, pad=m.dil, dilation=m.dil)
+        # conv1 (1x1)
+        side.run(lambda: self._wg1(m, dz1))
+        side.mark(bi)
+        side.wait(bi + 1)               # gx of this parity was read (as g) by the side work of block bi + 1
+        gx = self.buf(f"scratch:gx:{cin}:{m.h}:{bi & 1}", (B, m.h, m.w, cin), adt)
+        ws1 = self._ws(n["conv1"])
+        if self.tf_backbone and m.first and m.stride == 2:
+            # both branches read the subsampled input: d_xs = g @ Wd^T + dz1 @ W1^T (ReLU-masked at the sampled pixels),
+            # scattered back into the zero-filled full-resolution gradient
+            dxs = self.buf(f"scratch:dxs:{cin}:{ho}", (B, ho, wo, cin), adt)
+            hip.gemm(M_out, cin, d2, g, d2, 1, self._ws(n["down"]), d2, 1, dxs, cin)
+            hip.gemm(M_out, cin, d1, dz1, d1, 1, ws1, d1, 1, dxs, cin, residual=dxs, ldr=cin,
+                     mask=(m.xs if bi > 0 else None), ldmask=(cin if bi > 0 else 0))
+            hip.call("detr_hip_subsample2_bwd_f32", dxs.data_ptr(), gx.data_ptr(), B, m.h, m.w, self._chunks(cin), ho, wo)
+        else:
+            if idg_ready is not None:
+                side.main.wait_event(idg_ready)
+            mask, ldmask = None, 0
+            if bi > 0:                  # x = ReLU output of the previous block: masked by it, or by its sign bits where the forward kept them
+                bits = self._block_recs[bi - 1].out_bits
+                mask, ldmask = (m.x, cin) if bits is None else (bits, bits.stride(0))
+            hip.gemm(M_in, cin, d1, dz1, d1, 1, ws1, d1, 1, gx, cin, residual=idg, ldr=cin, mask=mask, ldmask=ldmask, res_sub=idg_sub)
+        return gx
+
+    # ---- input_proj + positional encoding (detr.py:172-175) ---------------------------------------------
+    def _input_proj_fwd(self, feat, masks, B, L):
+        """Returns (src [B*L, 256], pos)."""
+        _, H, W = self._shape
+        _, Hf, Wf, _ = self._feat_meta
+        src = self.buf("enc:src0", (B * L, D))
+        hip.gemm(B * L, D, 2048, feat, 2048, 1, self._w("input_proj/kernel"), D, 0, src, D, bias=self.P.views["input_proj/bias"])
+        if masks is None:
+            self.key_valid = None
+            if (Hf, Wf) not in self._pos_cache:
+                self._pos_cache[(Hf, Wf)] = torch.from_numpy(position_embedding_sine_host(Hf, Wf)).to(self.device)
+            pos = self._pos_cache[(Hf, Wf)]
+        else:
+            # padded batch: per-image encoding [B*L, 256] (add_bcast / the LayerNorm's add[r % rows] take it as they take the
+            # [L, 256] constant) and the key padding mask of the encoder self-attention and every decoder cross-attention
+            pos = self._prepare_masks(masks, B, H, W, Hf, Wf)
+        self.pos = pos
+        return src, pos
+
+    def _input_proj_bwd(self, d_x, feat, B, L, want_dx=True):
+        """Returns the gradient w.r.t. the backbone's feature map (ReLU-masked), None unless want_dx."""
+        G = self.P.gviews
+        self._wgrad(2048, D, B * L, feat, 2048, d_x, D, G["input_proj/kernel"], D)
+        self._colsum(d_x, G["input_proj/bias"])
+        if not want_dx:
+            return None
+        g = self.buf("scratch:g_feat", feat.shape, self._adt)
+        hip.gemm(B * L, 2048, D, d_x, D, 1, self._w("input_proj/kernel"), D, 1, g, 2048, mask=feat, ldmask=2048)
+        return g
+
+    # ---- encoder layer (transformer.py:157-179) -------------------------------------------------------------
+    def _encoder_layer_fwd(self, i, x, qk, pos, B, L):
+        """x: layer input, qk = x + pos.  Returns (output, output + pos)."""
+        pfx, tag = f"transformer/encoder/layer_{i}", f"enc{i}"
+        a = self.buf(f"{tag}:a", (B * L, D))
+        x1 = self.buf(f"{tag}:x1", (B * L, D))
+        x1h = self.buf(f"{tag}:x1h", (B * L, D), torch.bfloat16) if self.ffn16 else None
+        ln1 = self._ln_spec(B * L, f"{pfx}/norm1", x1, f"{tag}:ln1", y16=x1h)
+        self._self_attn_fwd(f"{tag}:sa", f"{pfx}/self_attn", qk, x, B, L, a, site=16 * i, ln=ln1, key_valid=self.key_valid)
+        if ln1 is None:
+            self._ln_fwd(a, f"{pfx}/norm1", x1, f"{tag}:ln1", y16=x1h)
+        f = self.buf(f"{tag}:f", (B * L, D))
+        x2 = self.buf(f"{tag}:x2", (B * L, D))
+        # x2 + pos = the q / k input of the next layer, or `memory + pos` of the decoder (:219), in the same launch
+        qk = self.buf(f"enc{i + 1}:qk" if i + 1 < self.num_enc else "dec:mem_pos", (B * L, D))
+        ln2 = self._ln_spec(B * L, f"{pfx}/norm2", x2, f"{tag}:ln2", add=pos, y2=qk, ffn=True)
+        self._ffn_fwd(tag, pfx, x1, f, seed=16 * i + 2, x16=x1h, ln=ln2)
+        if ln2 is None:
+            self._ln_fwd(f, f"{pfx}/norm2", x2, f"{tag}:ln2", add=pos, y2=qk)
+        return x2, qk
+
+    def _encoder_layer_bwd(self, i, d_x, B, L):
+        """d_x: gradient w.r.t. the layer's output.  Returns the gradient w.r.t. its input."""
+        pfx, tag = f"transformer/encoder/layer_{i}", f"enc{i}"
+        x_in = self._bufs[f"enc{i - 1}:x2"] if i > 0 else self._bufs["enc:src0"]
+        qk, a, x1, f = (self._bufs[f"{tag}:{n}"] for n in ("qk", "a", "x1", "f"))
+        d_f = self.buf(f"scratch:e_d_f{self.side.suffix(tag)}", (B * L, D))
+        d_y = self._ln_bwd(d_x, f, f"{pfx}/norm2", d_f, f"{tag}:ln2", drop_site=16 * i + 3, want16=self.ffn16)
+        d_x1 = self.buf("scratch:e_d_x1", (B * L, D))
+        self._ffn_bwd(tag, pfx, d_y, d_f, x1, d_x1, x16=self._bufs.get(f"{tag}:x1h") if self.ffn16 else None)
+        d_a = self.buf(f"scratch:e_d_a{self.side.suffix(tag)}", (B * L, D))
+        d_out = self._ln_bwd(d_x1, a, f"{pfx}/norm1", d_a, f"{tag}:ln1", drop_site=16 * i + 1)
+        d_xn = self.buf(f"scratch:e_d_x{i & 1}", (B * L, D))
+        self._self_attn_bwd(f"{tag}:sa", f"{pfx}/self_attn", d_out, d_a, qk, x_in, B, L, d_xn, site=16 * i, key_valid=self.key_valid)
+        return d_xn
+
+    # ---- decoder cross attention: Q from its layer, K / V column blocks of the shared projection buffer (_cross_kv_*) -----
+    def _cross_attn_fwd(self, tag, pfx, i, q_in, res, KV, B, L, out, site, ln=None):
+        """Cross attention of decoder layer i (tag = its buffer tag `dec{i}`); res: the residual operand of the out-projection."""
+        V, Q, nd = self.P.views, self.Q, self.num_dec
+        dp, _ = self._drop
+        a16 = self.attn16
+        W, bias = self._w(f"{pfx}/in_proj_kernel"), V[f"{pfx}/in_proj_bias"]
+        (q_name, adt), (o_name, _) = self._a16(f"{tag}:ca:Q"), self._a16(f"{tag}:ca:O")
+        Qc = self.buf(q_name, (B * Q, D), adt)
+        hip.linear_fwd(q_in, W[0:D], bias[0:D], Qc, alpha=QK_ALPHA if a16 else 1.0)
+        if i == 0:
+            self.side.join()                                 # K / V of all layers
+        Oc = self.buf(o_name, (B * Q, D), adt)
+        lse = self.buf(f"{tag}:ca:lse", (B * HEADS, Q))
+        K = KV[:, i * D:(i + 1) * D]
+        hip.attention(Qc, K, KV[:, (nd + i) * D:(nd + i + 1) * D], Oc, lse, B, HEADS, Q, L,
+                      scale=float(HD) ** -0.5, dropout_p=dp, dropout_site=site, dropout_step=self._seed_dev,
+                      dropmask=self.masks.mask(site, B, Q, L) if (a16 and dp > 0.0) else None, key_valid=self.key_valid)
+        if pfx in self._attn_sites:
+            self._attn_map(pfx, Qc, K, lse, B, Q, L, self.key_valid)
+        hip.linear_fwd(Oc, self._w(f"{pfx}/out_proj_kernel"), V[f"{pfx}/out_proj_bias"], out, residual=res, dropout_p=dp,
+                       dropout_seed=site + 1, dropout_step=self._seed_dev, ln=ln)      # :226 (+ the LayerNorm behind it)
+
+    def _cross_attn_bwd(self, tag, pfx, i, d_out, d_res, q_in, KV, dKV, B, L, d_x, site, acc_q):
+        """d_out: gradient of the out-projection output (dropout backward already applied), d_res: gradient of the block output
+        (residual path).  Writes d_x = gradient w.r.t. the residual input t1 (q_in = t1 + query_pos: the q gradient goes there too),
+        column blocks i of dKV, and ACCUMULATES the q gradient into acc_q (the query_pos sum)."""
+        G, Q, nd = self.P.gviews, self.Q, self.num_dec
+        dp, _ = self._drop
+        a16 = self.attn16
+        W = self._w(f"{pfx}/in_proj_kernel")
+        (q_name, adt), (o_name, _) = self._a16(f"{tag}:ca:Q"), self._a16(f"{tag}:ca:O")
+        Qc, Oc = self._bufs[q_name], self._bufs[o_name]
+        dO = self.buf(f"scratch:dO:{B * Q}:{int(a16)}", (B * Q, D), adt)
+        hip.linear_dgrad(d_out, self._w(f"{pfx}/out_proj_kernel"), dO)
+        dQc = self.buf(f"scratch:dQc:{int(a16)}{self.side.suffix(tag)}", (B * Q, D), adt)
+        delta = self.buf(f"scratch:delta:{B * Q}", (2 * B * HEADS, Q))
+        kc, vc = slice(i * D, (i + 1) * D), slice((nd + i) * D, (nd + i + 1) * D)
+        hip.attention(Qc, KV[:, kc], KV[:, vc], Oc, self._bufs[f"{tag}:ca:lse"], B, HEADS, Q, L, scale=float(HD) ** -0.5,
+                      dropout_p=dp, dropout_site=site, dropout_step=self._seed_dev, d_o=dO, dq=dQc, dk=dKV[:, kc], dv=dKV[:, vc],
+                      delta=delta, dropmask=self.masks.mask(site, B, Q, L) if (a16 and dp > 0.0) else None, key_valid=self.key_valid)
+        self.side.run(lambda: hip.gemm_group([
+            hip.linear_wgrad_call(d_out, Oc, G[f"{pfx}/out_proj_kernel"], bias_grad=G[f"{pfx}/out_proj_bias"]),
+            hip.linear_wgrad_call(dQc, q_in, G[f"{pfx}/in_proj_kernel"][0:D], bias_grad=G[f"{pfx}/in_proj_bias"][0:D])]))
+        hip.gemm_group([hip.linear_dgrad_call(dQc, W[0:D], acc_q, residual=acc_q),
+                        hip.linear_dgrad_call(dQc, W[0:D], d_x, residual=d_res)])
+
+    # ---- layer-invariant cross-attention K / V (transformer.py:221-223: memory is the same for every layer) --------------
+    def _cross_kv_fwd(self, memory, mem_pos, B, L):
+        """K / V projections of `memory` for ALL decoder layers at once, on the second stream: the first decoder self-attention
+        block -- 800-row kernels -- does not need them (_cross_attn_fwd of layer 0 joins)."""
+        nd = self.num_dec
+        ct = self._cross_tables()
+        if self._stale(f"cross:{self.compute}"):
+            hip.multi_copy(ct["gather"])
+        name, adt = self._a16("dec:KV")
+        KV = self.buf(name, (B * L, 2 * nd * D), adt)
+        self.side.run(lambda: hip.gemm_group([hip.linear_fwd_call(mem_pos, ct["Wkv"][0:nd * D], ct["bkv"][0:nd * D], KV[:, 0:nd * D]),
+                                              hip.linear_fwd_call(memory, ct["Wkv"][nd * D:], ct["bkv"][nd * D:], KV[:, nd * D:])]))
+        return KV
+
+    def _cross_kv_bwd(self, dKV, memory, mem_pos, B, L):
+        """Weight gradient of the gathered copy (scattered back into the per-layer in_proj gradients by one launch) and ONE data
+        gradient GEMM with K = 2*nd*256.  Returns d_mem."""
+        nd = self.num_dec
+        ct = self._cross_tables()
+        hip.zero_(ct["gW"])
+        hip.zero_(ct["gb"])
+        hip.gemm_group([hip.linear_wgrad_call(dKV[:, 0:nd * D], mem_pos, ct["gW"][0:nd * D], bias_grad=ct["gb"][0:nd * D]),
+                        hip.linear_wgrad_call(dKV[:, nd * D:], memory, ct["gW"][nd * D:], bias_grad=ct["gb"][nd * D:])])
+        self.side.join()
+        hip.flush_reduces()                            # the scatter reads the gathered gradient
+        hip.multi_copy(ct["scatter"])
+        d_mem = self.buf("scratch:d_mem", (B * L, D))
+        hip.linear_dgrad(dKV, ct["Wkv"], d_mem)        # d(memory + pos) through K and d(memory) through V land on the same tensor
+        return d_mem
+
+    # ---- decoder layer (transformer.py:207-234) -----------------------------------------------------------------
+    def _decoder_layer_fwd(self, i, tgt, qin, qpos, KV, t3, B, L):
+        """tgt: layer input, qin = tgt + query_pos; t3: where the output goes.  Returns (t3, t3 + query_pos; None behind the last layer)."""
+        pfx, tag = f"transformer/decoder/layer_{i}", f"dec{i}"
+        Q, ds = self.Q, 16 * (32 + i)
+        a1 = self.buf(f"{tag}:a1", (B * Q, D))
+        t1 = self.buf(f"{tag}:t1", (B * Q, D))
+        q2 = self.buf(f"{tag}:q2", (B * Q, D))
+        ln1 = self._ln_spec(B * Q, f"{pfx}/norm1", t1, f"{tag}:ln1", add=qpos, y2=q2)
+        self._self_attn_fwd(f"{tag}:sa", f"{pfx}/self_attn", qin, tgt, B, Q, a1, site=ds, ln=ln1)
+        if ln1 is None:
+            self._ln_fwd(a1, f"{pfx}/norm1", t1, f"{tag}:ln1", add=qpos, y2=q2)      # q2 = t1 + query_pos (:219)
+        a2 = self.buf(f"{tag}:a2", (B * Q, D))
+        t2 = self.buf(f"{tag}:t2", (B * Q, D))
+        t2h = self.buf(f"{tag}:t2h", (B * Q, D), torch.bfloat16) if self.ffn16 else None
+        ln2 = self._ln_spec(B * Q, f"{pfx}/norm2", t2, f"{tag}:ln2", y16=t2h)
+        self._cross_attn_fwd(tag, f"{pfx}/multihead_attn", i, q2, t1, KV, B, L, a2, site=ds + 2, ln=ln2)
+        if ln2 is None:
+            self._ln_fwd(a2, f"{pfx}/norm2", t2, f"{tag}:ln2", y16=t2h)
+        f = self.buf(f"{tag}:f", (B * Q, D))
+        self._bufs[f"{tag}:t3"] = t3
+        qin = self.buf(f"dec{i + 1}:qin", (B * Q, D)) if i + 1 < self.num_dec else None        # next layer's tgt + query_pos
+        ln3 = self._ln_spec(B * Q, f"{pfx}/norm3", t3, f"{tag}:ln3", add=qpos if qin is not None else None, y2=qin, ffn=True)
+        self._ffn_fwd(tag, pfx, t2, f, seed=ds + 4, x16=t2h, ln=ln3)
+        if ln3 is None:
+            self._ln_fwd(f, f"{pfx}/norm3", t3, f"{tag}:ln3", add=qpos if qin is not None else None, y2=qin)
+        return t3, qin
+
+    def _decoder_layer_bwd(self, i, d_t3n, d_next, KV, dKV, acc_qpos, B, L):
+        """d_t3n: gradient of this level's head input w.r.t. t3, d_next: the gradient the layer above sends into t3 (None above
+        the last layer).  Returns the gradient w.r.t. the layer's input (None for layer 0: the constant zero target)."""
+        pfx, tag = f"transformer/decoder/layer_{i}", f"dec{i}"
+        BQ, ds, sx = B * self.Q, 16 * (32 + i), self.side.suffix(tag)
+        t1, t2, a1, a2, f, qin, q2 = (self._bufs[f"{tag}:{n}"] for n in ("t1", "t2", "a1", "a2", "f", "qin", "q2"))
+        tgt = self._bufs[f"dec{i - 1}:t3"] if i > 0 else self._bufs["dec:tgt0"]
+        d_f = self.buf(f"scratch:d_f{sx}", (BQ, D))
+        # d_t3 = d_t3n + d_next: the two branches are summed by the norm3 backward itself
+        d_y = self._ln_bwd(d_t3n, f, f"{pfx}/norm3", d_f, f"{tag}:ln3", drop_site=ds + 5, want16=self.ffn16, dy_add=d_next)
+        d_t2 = self.buf("scratch:d_t2", (BQ, D))
+        self._ffn_bwd(tag, pfx, d_y, d_f, t2, d_t2, x16=self._bufs.get(f"{tag}:t2h") if self.ffn16 else None)
+        d_a2 = self.buf(f"scratch:d_a2{sx}", (BQ, D))
+        d_out = self._ln_bwd(d_t2, a2, f"{pfx}/norm2", d_a2, f"{tag}:ln2", drop_site=ds + 3)
+        d_t1 = self.buf("scratch:d_t1", (BQ, D))
+        # q2 = t1 + query_pos ; a2 = attn + t1: the q gradient goes to t1 (with the residual path) and to the query_pos sum
+        self._cross_attn_bwd(tag, f"{pfx}/multihead_attn", i, d_out, d_a2, q2, KV, dKV, B, L, d_t1, site=ds + 2, acc_q=acc_qpos)
+        d_a1 = self.buf(f"scratch:d_a1{sx}", (BQ, D))
+        d_out = self._ln_bwd(d_t1, a1, f"{pfx}/norm1", d_a1, f"{tag}:ln1", drop_site=ds + 1)
+        # self attention: qin = tgt + query_pos feeds q and k, tgt feeds v and the residual
+        d_tgt = self.buf(f"scratch:d_tgt{i & 1}", (BQ, D)) if i > 0 else None
+        self._self_attn_bwd(f"{tag}:sa", f"{pfx}/self_attn", d_out, d_a1, qin, tgt, B, self.Q, d_tgt, site=ds, acc_qk=acc_qpos)
+        return d_tgt
+
+    # ---- heads (detr.py:181-204 / :94-114): always exact fp32 (compute=0), like LayerNorm / softmax / the set loss -----------
+    def _head_layers(self):
+        """(parameter name, kernel stored as (in, out)) of the class Linear and the three of the box MLP: the reference's Linear
+        kernels are (out, in), the Keras Dense kernels of the nb_class heads (in, out)."""
+        if self.nb_class is None:
+            return [("class_embed", False)] + [(f"bbox_embed_{j}", False) for j in range(3)]
+        return [("cls_layer", True)] + [(f"pos_layer/dense_{j}", True) for j in range(3)]
+
+    def _dense(self, x, layer, out, act=0):
+        name, in_out = layer
+        k = self.P.views[f"{name}/kernel"]
+        hip.gemm(x.shape[0], k.shape[1 if in_out else 0], x.shape[1], x, x.stride(0), 1, k, k.stride(0), 0 if in_out else 1,
+                 out, out.stride(0), bias=self.P.views[f"{name}/bias"], act=act, compute=0)
+
+    def _dense_bwd(self, dy, x, layer, dx, mask=None, residual=None):
+        """Weight and bias gradient of one head Linear, then dx = dy @ W^T (+ residual) (masked by mask > 0)."""
+        name, in_out = layer
+        k, gk, gb = self.P.views[f"{name}/kernel"], self.P.gviews[f"{name}/kernel"], self.P.gviews[f"{name}/bias"]
+        if in_out:      # dW (in, out) = x^T dy: dy is the B operand, its column sums are a launch of their own
+            n_in, n_out = k.shape
+            self._wgrad(n_in, n_out, x.shape[0], x, x.stride(0), dy, dy.stride(0), gk, n_out, compute=0)
+            self._colsum(dy, gb)
+        else:           # dW (out, in) = dy^T x, the bias gradient as the row sums of its A operand
+            n_out, n_in = k.shape
+            hip.linear_wgrad(dy, x, gk, bias_grad=gb, compute=0)
+        hip.gemm(dy.shape[0], n_in, n_out, dy, dy.stride(0), 1, k, k.stride(0), 1 if in_out else 0, dx, dx.stride(0), residual=residual,
+                 ldr=(dx.stride(0) if residual is not None else 0), mask=mask, ldmask=(mask.stride(0) if mask is not None else 0), compute=0)
+
+    def _heads_fwd(self, hs2):
+        """hs2 [R, 256]: every decoder level's normalised output.  Returns (logits [R, C], boxes [R, 4])."""
+        R = hs2.shape[0]
+        cls, mlp0, mlp1, mlp2 = self._head_layers()
+        logits = self.buf("head:logits", (R, self.C))
+        boxes = self.buf("head:boxes", (R, 4))
+        t_a, t_b = self.buf("head:t1", (R, D)), self.buf("head:t2", (R, D))
+        self._dense(hs2, cls, logits)
+        self._dense(hs2, mlp0, t_a, act=1)
+        self._dense(t_a, mlp1, t_b, act=1)
+        self._dense(t_b, mlp2, boxes, act=2)
+        return logits, boxes
+
+    def _heads_bwd(self, dl, db):
+        """dl [R, C], db [R, 4]: gradients w.r.t. logits and (sigmoid) boxes.  Returns d_hs [R, 256]."""
+        R = dl.shape[0]
+        cls, mlp0, mlp1, mlp2 = self._head_layers()
+        hs2 = self._bufs["dec:hs"].view(R, D)
+        boxes, t_a, t_b = self._bufs["head:boxes"], self._bufs["head:t1"], self._bufs["head:t2"]
+        dz3 = self.buf("scratch:dz3", (R, 4))
+        hip.call("detr_hip_sigmoid_bwd_f32", db.data_ptr(), boxes.data_ptr(), dz3.data_ptr(), R * 4)
+        d_hs = self.buf("scratch:d_hs", (R, D))
+        dt_b, dt_a = self.buf("scratch:dt_b", (R, D)), self.buf("scratch:dt_a", (R, D))
+        self._dense_bwd(dz3, t_b, mlp2, dt_b, mask=t_b)
+        self._dense_bwd(dt_b, t_a, mlp1, dt_a, mask=t_a)
+        self._dense_bwd(dt_a, hs2, mlp0, d_hs)
+        self._dense_bwd(dl, hs2, cls, d_hs, residual=d_hs)
+        return d_hs

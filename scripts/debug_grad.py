@@ -29,12 +29,12 @@ def rel(a, b):
     a = a.detach().cpu().double(); b = b.detach().double()
     d = (a - b).abs()
     return float(d.max()) / (float(b.abs().max()) + 1e-30), int((d > 1e-3 * b.abs().max()).sum()), d
-for m in eng._block_meta:
-    p = m["p"]
+for m in eng._block_recs:          # engine.Block records of the last forward
+    p = m.p
     y1r, y2r = taps[f"{p}:y1"], taps[f"{p}:y2"]
-    r1 = rel(m["y1"], y1r); r2 = rel(m["y2"], y2r); rx = rel(m["x"], taps[f"{p}:x"])
+    r1 = rel(m.y1, y1r); r2 = rel(m.y2, y2r); rx = rel(m.x, taps[f"{p}:x"])
     line = f"{p:22s} fwd x {rx[0]:.1e} y1 {r1[0]:.1e} y2 {r2[0]:.1e}"
-    k1 = f"scratch:dz1:{m['d1']}:{m['h']}"; k2 = f"scratch:dz2:{m['d1']}:{m['ho']}"
+    k1 = f"scratch:dz1:{m.d1}:{m.h}"; k2 = f"scratch:dz2:{m.d1}:{m.ho}"
     # engine dz = dL/d(bn out, pre-relu) ; oracle: dL/dy * (y > 0)
     for nm, key, yr in (("dz1", k1, y1r), ("dz2", k2, y2r)):
         if key in eng._bufs and tuple(eng._bufs[key].shape) == tuple(yr.shape):
