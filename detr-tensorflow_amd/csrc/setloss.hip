@@ -7,9 +7,13 @@
 //                       prediction columns, wave-butterfly argmin
 //   K14 set_loss_*   : weighted CE, L1, GIoU (clipped xyxy), metrics, and the gradients w.r.t.
 //                      logits / boxes                              loss.py:37-96, bbox.py:29-124,171-183
+// The weights of the criterion (matcher cost, loss terms, no-object weight, per-class weights) are a policy parameter of
+// the cost / sums / finalize / gradient kernels: FixedCriterion holds the reference's literals as constexpr members (the
+// entry points without a criterion argument), RuntimeCriterion a by-value block filled by the *_crit_* entry points.
 // Compiled with -ffp-contract=off so that the box arithmetic rounds like the op-by-op reference.
 #include "common.h"
 #include <limits.h>
+#include <cmath>
 #include <type_traits>
 
 namespace detr {
@@ -20,6 +24,35 @@ struct SetLossArgs {
     const float *boxes;  long long sB_l, sB_b, sB_q;
     const float *t_bbox; const long long *t_class;
     int background_class;
+};
+
+// The reference's criterion, compiled in: 5 L1 + 1 class + 2 GIoU in the matcher, 1 label + 2 giou + 5 l1 in the total, weight
+// 0.1 on unmatched queries (loss.py:60-67), every class weight 1, box sums divided by the raw count of matched pairs.
+struct FixedCriterion {
+    static constexpr float cost_class = 1.0f, cost_bbox = 5.0f, cost_giou = 2.0f;
+    static constexpr float w_label = 1.0f, w_bbox = 5.0f, w_giou = 2.0f;
+    static constexpr float eos = 0.1f;
+    static constexpr bool weighted = false;
+    __device__ __forceinline__ float class_weight(int, int) const { return 1.0f; }
+    // the normaliser from the two COUNTS (see the note above set_loss_sums_kernel)
+    __device__ __forceinline__ float weight_sum(const float *s) const { return eos * s[3] + s[4]; }
+    __device__ __forceinline__ float box_count(float npos) const { return npos; }
+};
+
+// The same quantities read at run time.  class_weights: device float [C] or null (all 1); the host keeps them on multiples of
+// 1/64 in [0, 16], so that their float atomic sum (slot 1 of a level's eight) is exact in any order like the counts.
+struct RuntimeCriterion {
+    float cost_class, cost_bbox, cost_giou;
+    float w_label, w_bbox, w_giou;
+    float eos;
+    int min_one;                        // divide the box sums by max(matched pairs, 1)
+    const float *class_weights;
+    static constexpr bool weighted = true;
+    __device__ __forceinline__ float class_weight(int cls, int C) const {
+        return (class_weights != nullptr && cls >= 0 && cls < C) ? class_weights[cls] : 1.0f;
+    }
+    __device__ __forceinline__ float weight_sum(const float *s) const { return eos * s[3] + s[1]; }
+    __device__ __forceinline__ float box_count(float npos) const { return min_one ? fmaxf(npos, 1.0f) : npos; }
 };
 
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
@@ -66,7 +99,8 @@ constexpr int SL_MAXR = 128;
 
 constexpr int SL_QCHUNK = 8;      // queries per workgroup of the cost / sums / gradient kernels (two per wave)
 
-__global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, float *__restrict__ cost) {
+template <class Crit>
+__global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit crit, float *__restrict__ cost) {
     __shared__ float s_max[SL_QCHUNK], s_sum[SL_QCHUNK];
     __shared__ float s_t[SL_MAXR][4];
     __shared__ int s_cls[SL_MAXR];
@@ -110,7 +144,7 @@ __global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, float *_
         const float cost_class = -prob;
         const float cost_bbox = fabsf(pcx - tcx) + fabsf(pcy - tcy) + fabsf(pw - tw) + fabsf(ph - th);
         const float cost_giou = -giou_of(to_xyxy(pcx, pcy, pw, ph), to_xyxy(tcx, tcy, tw, th));
-        out[q * ldc + j] = 5.0f * cost_bbox + 1.0f * cost_class + 2.0f * cost_giou;
+        out[q * ldc + j] = crit.cost_bbox * cost_bbox + crit.cost_class * cost_class + crit.cost_giou * cost_giou;
     }
 }
 
@@ -387,7 +421,8 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
 
 // ------------------------------------------------------------------------------------------------
 // K14: loss sums, finalisation, gradients.
-//   sums[lv*8 + {0: sum w*CE, 1: sum w, 2: neg correct, 3: n_neg, 4: n_pos, 5: pos != bg, 6: pos correct}]
+//   sums[lv*8 + {0: sum w*CE, 1: sum of the matched targets' class weights (RuntimeCriterion only, else 0), 2: neg correct,
+//                3: n_neg, 4: n_pos, 5: pos != bg, 6: pos correct}]
 //   sums[levels*8 + lv*2 + {0: sum L1, 1: sum (1-GIoU)}]
 // ------------------------------------------------------------------------------------------------
 // The cross-entropy normaliser sum(w) (loss.py:60-67: weight 0.1 on the background class, 1 elsewhere) is derived from the
@@ -395,10 +430,12 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
 // number, so the order of 4 waves x B images of atomic adds moved it by an ulp from run to run -- and every gradient with
 // it (two runs of the same step then differed by up to 1e-2 in bf16-stored activation gradients of the near-degenerate
 // random-init model).  With this the gradients are a deterministic function of the matching; only the REPORTED loss values
-// (sums of w*CE, L1, 1-GIoU) keep the atomics' last-bit noise.
-__device__ __forceinline__ float ce_weight_sum(const float *s) { return 0.1f * s[3] + s[4]; }
+// (sums of w*CE, L1, 1-GIoU) keep the atomics' last-bit noise.  This is Crit::weight_sum.  With run-time class weights the
+// matched part of the normaliser is accumulated (slot 1) but stays exact all the same: the weights are multiples of 1/64 up
+// to 16 and at most 16384 of them are added, so every partial sum is a multiple of 1/64 below 2^24 / 64 -- a float.
 
-__global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, const int *__restrict__ tgt_for_pred,
+template <class Crit>
+__global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, Crit crit, const int *__restrict__ tgt_for_pred,
                                                             float *__restrict__ sums) {
     const int p = blockIdx.x;
     const int lv = p / a.B, b = p % a.B;
@@ -432,7 +469,7 @@ __global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, const
             const float lse = logf(s) + mx;
             if (t < 0) {
                 const float ce = lse - row[a.background_class];
-                acc[0] += 0.1f * ce;
+                acc[0] += crit.eos * ce;
                 acc[2] += (am == a.background_class) ? 1.f : 0.f;
                 acc[3] += 1.f;
             } else {
@@ -440,7 +477,9 @@ __global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, const
                 // a label outside [0, C) (e.g. the wrong nb_class when finetuning): no out-of-bounds read; the loss turns
                 // NaN like tf.nn.sparse_softmax_cross_entropy_with_logits on the GPU (the CPU op raises)
                 const float ce = (cls >= 0 && cls < a.C) ? lse - row[cls] : NAN;
-                acc[0] += ce;
+                const float w = crit.class_weight(cls, a.C);
+                acc[0] += w * ce;
+                if (Crit::weighted) acc[1] += w;      // slot 1 stays 0 under the fixed criterion
                 acc[4] += 1.f;
                 acc[5] += (am != a.background_class) ? 1.f : 0.f;
                 acc[6] += (am == cls) ? 1.f : 0.f;
@@ -466,7 +505,8 @@ __global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, const
     }
 }
 
-__global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int levels, float *__restrict__ losses,
+template <class Crit>
+__global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int levels, Crit crit, float *__restrict__ losses,
                                          float *__restrict__ total) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float tot = 0.f;
@@ -475,10 +515,11 @@ __global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int lev
         const int lv = (k == 0) ? levels - 1 : k - 1;
         const float *s = sums + lv * 8;
         const float *sb = sums + levels * 8 + lv * 2;
-        const float label = s[0] / ce_weight_sum(s);
-        const float npos = s[4];
-        const float giou = sb[1] / npos;
-        const float l1 = sb[0] / npos;
+        const float label = s[0] / crit.weight_sum(s);
+        const float npos = s[4];                   // the metrics divide by the raw count: 0 / 0 without a matched pair
+        const float nbox = crit.box_count(npos);
+        const float giou = sb[1] / nbox;
+        const float l1 = sb[0] / nbox;
         float *o = losses + lv * 6;
         o[0] = label;
         o[1] = s[2] / s[3];
@@ -486,14 +527,15 @@ __global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int lev
         o[3] = s[6] / npos;
         o[4] = giou;
         o[5] = l1;
-        tot += label * 1.0f;
-        tot += giou * 2.0f;
-        tot += l1 * 5.0f;
+        tot += label * crit.w_label;
+        tot += giou * crit.w_giou;
+        tot += l1 * crit.w_bbox;
     }
     total[0] = tot;
 }
 
-__global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, const int *__restrict__ tgt_for_pred,
+template <class Crit>
+__global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, Crit crit, const int *__restrict__ tgt_for_pred,
                                                             const float *__restrict__ sums, float loss_scale,
                                                             float *__restrict__ d_logits, float *__restrict__ d_boxes) {
     const int p = blockIdx.x;
@@ -503,8 +545,8 @@ __global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, const
     float *dlg = d_logits + lv * a.sL_l + b * a.sL_b;
     float *dbx = d_boxes + lv * a.sB_l + b * a.sB_b;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float sw = ce_weight_sum(sums + lv * 8);
-    const float npos = sums[lv * 8 + 4];
+    const float sw = crit.weight_sum(sums + lv * 8);
+    const float npos = crit.box_count(sums[lv * 8 + 4]);
     const int q0 = blockIdx.y * SL_QCHUNK, q1 = min(a.Q, q0 + SL_QCHUNK);
     for (int q = q0 + wave; q < q1; q += 4) {
         const float *row = lg + q * a.sL_q;
@@ -516,7 +558,7 @@ __global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, const
         for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
         s = wave_sum(s);
         const int cls = (t < 0) ? a.background_class : (int)a.t_class[(long long)b * a.R + 1 + t];
-        const float wq = ((t < 0) ? 0.1f : 1.0f) / sw * loss_scale;   // label weight 1 (loss.py:10-11)
+        const float wq = crit.w_label * ((t < 0) ? crit.eos : crit.class_weight(cls, a.C)) / sw * loss_scale;
         for (int c = lane; c < a.C; c += 64) {
             const float sm = expf(row[c] - mx) / s;
             dlg[q * a.sL_q + c] = wq * (sm - (c == cls ? 1.0f : 0.0f));
@@ -526,8 +568,8 @@ __global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, const
             if (t >= 0) {
                 const float *pb = bx + q * a.sB_q;
                 const float *tb = a.t_bbox + ((long long)b * a.R + 1 + t) * 4;
-                const float kl1 = 5.0f * loss_scale / npos;
-                const float kg = 2.0f * loss_scale / npos;
+                const float kl1 = crit.w_bbox * loss_scale / npos;
+                const float kg = crit.w_giou * loss_scale / npos;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const float d = pb[k] - tb[k];
@@ -593,17 +635,69 @@ static int fill_args(const detr_setloss_desc *d, SetLossArgs &a) {
     return 0;
 }
 
+// The host block of the *_crit_* entry points (DETR_CRITERION_FLOATS floats, include/detr_hip.h) -> the by-value kernel argument.
+static int fill_criterion(const float *c, const float *class_weights, RuntimeCriterion &r) {
+    DETR_REQUIRE(c != nullptr, "setloss: null criterion");
+    for (int i = 0; i < DETR_CRITERION_FLOATS; ++i)
+        DETR_REQUIRE(std::isfinite(c[i]) && c[i] >= 0.0f, "setloss: criterion[%d] = %g is not a finite value >= 0", i, (double)c[i]);
+    DETR_REQUIRE(c[7] == 0.0f || c[7] == 1.0f, "setloss: criterion[7] (num_boxes_min_one) = %g is neither 0 nor 1", (double)c[7]);
+    r.cost_class = c[0]; r.cost_bbox = c[1]; r.cost_giou = c[2];
+    r.w_label = c[3]; r.w_bbox = c[4]; r.w_giou = c[5];
+    r.eos = c[6];
+    r.min_one = c[7] != 0.0f;
+    r.class_weights = class_weights;
+    return 0;
+}
+
+// One launcher per kernel: the fixed and the run-time criterion differ in the policy object alone.
+template <class Crit>
+static int launch_match_cost(const detr_setloss_desc *d, const Crit &crit, float *cost, void *stream) {
+    SetLossArgs a;
+    if (fill_args(d, a)) return -1;
+    DETR_REQUIRE(cost, "match_cost: null cost");
+    hipLaunchKernelGGL(match_cost_kernel<Crit>, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
+                       cost);
+    DETR_LAUNCH_CHECK("match_cost");
+    return 0;
+}
+
+template <class Crit>
+static int launch_sums(const detr_setloss_desc *d, const Crit &crit, const int32_t *tgt_for_pred, float *sums, void *stream) {
+    SetLossArgs a;
+    if (fill_args(d, a)) return -1;
+    DETR_REQUIRE(tgt_for_pred && sums, "set_loss_sums: null operand");
+    hipLaunchKernelGGL(set_loss_sums_kernel<Crit>, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
+                       tgt_for_pred, sums);
+    DETR_LAUNCH_CHECK("set_loss_sums");
+    return 0;
+}
+
+template <class Crit>
+static int launch_finalize(const float *sums, int32_t levels, const Crit &crit, float *losses, float *total, void *stream) {
+    DETR_REQUIRE(sums && losses && total && levels > 0, "set_loss_finalize: bad args");
+    hipLaunchKernelGGL(set_loss_finalize_kernel<Crit>, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, levels, crit, losses, total);
+    DETR_LAUNCH_CHECK("set_loss_finalize");
+    return 0;
+}
+
+template <class Crit>
+static int launch_grad(const detr_setloss_desc *d, const Crit &crit, const int32_t *tgt_for_pred, const float *sums, float loss_scale,
+                       float *d_logits, float *d_boxes, void *stream) {
+    SetLossArgs a;
+    if (fill_args(d, a)) return -1;
+    DETR_REQUIRE(tgt_for_pred && sums && d_logits && d_boxes, "set_loss_grad: null operand");
+    hipLaunchKernelGGL(set_loss_grad_kernel<Crit>, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
+                       tgt_for_pred, sums, loss_scale, d_logits, d_boxes);
+    DETR_LAUNCH_CHECK("set_loss_grad");
+    return 0;
+}
+
 }  // namespace detr
 
 using namespace detr;
 
 extern "C" int detr_hip_match_cost_f32(const detr_setloss_desc *d, float *cost, void *stream) {
-    SetLossArgs a;
-    if (fill_args(d, a)) return -1;
-    DETR_REQUIRE(cost, "match_cost: null cost");
-    hipLaunchKernelGGL(match_cost_kernel, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, cost);
-    DETR_LAUNCH_CHECK("match_cost");
-    return 0;
+    return launch_match_cost(d, FixedCriterion(), cost, stream);
 }
 
 extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int32_t ldc, const float *t_bbox, int32_t B,
@@ -652,30 +746,44 @@ extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int3
 
 extern "C" int detr_hip_set_loss_sums_f32(const detr_setloss_desc *d, const int32_t *tgt_for_pred, float *sums,
                                           void *stream) {
-    SetLossArgs a;
-    if (fill_args(d, a)) return -1;
-    DETR_REQUIRE(tgt_for_pred && sums, "set_loss_sums: null operand");
-    hipLaunchKernelGGL(set_loss_sums_kernel, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, tgt_for_pred,
-                       sums);
-    DETR_LAUNCH_CHECK("set_loss_sums");
-    return 0;
+    return launch_sums(d, FixedCriterion(), tgt_for_pred, sums, stream);
 }
 
 extern "C" int detr_hip_set_loss_finalize_f32(const float *sums, int32_t levels, float *losses, float *total,
                                               void *stream) {
-    DETR_REQUIRE(sums && losses && total && levels > 0, "set_loss_finalize: bad args");
-    hipLaunchKernelGGL(set_loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, levels, losses, total);
-    DETR_LAUNCH_CHECK("set_loss_finalize");
-    return 0;
+    return launch_finalize(sums, levels, FixedCriterion(), losses, total, stream);
 }
 
 extern "C" int detr_hip_set_loss_grad_f32(const detr_setloss_desc *d, const int32_t *tgt_for_pred, const float *sums,
                                           float loss_scale, float *d_logits, float *d_boxes, void *stream) {
-    SetLossArgs a;
-    if (fill_args(d, a)) return -1;
-    DETR_REQUIRE(tgt_for_pred && sums && d_logits && d_boxes, "set_loss_grad: null operand");
-    hipLaunchKernelGGL(set_loss_grad_kernel, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, tgt_for_pred,
-                       sums, loss_scale, d_logits, d_boxes);
-    DETR_LAUNCH_CHECK("set_loss_grad");
-    return 0;
+    return launch_grad(d, FixedCriterion(), tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
+}
+
+// ---- the same four launches with the criterion as an argument (checked on the host before anything is launched) ----
+extern "C" int detr_hip_match_cost_crit_f32(const detr_setloss_desc *d, const float *criterion, float *cost, void *stream) {
+    RuntimeCriterion c;
+    if (fill_criterion(criterion, nullptr, c)) return -1;
+    return launch_match_cost(d, c, cost, stream);
+}
+
+extern "C" int detr_hip_set_loss_sums_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
+                                               const int32_t *tgt_for_pred, float *sums, void *stream) {
+    RuntimeCriterion c;
+    if (fill_criterion(criterion, class_weights, c)) return -1;
+    return launch_sums(d, c, tgt_for_pred, sums, stream);
+}
+
+extern "C" int detr_hip_set_loss_finalize_crit_f32(const float *sums, int32_t levels, const float *criterion, float *losses,
+                                                   float *total, void *stream) {
+    RuntimeCriterion c;
+    if (fill_criterion(criterion, nullptr, c)) return -1;
+    return launch_finalize(sums, levels, c, losses, total, stream);
+}
+
+extern "C" int detr_hip_set_loss_grad_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
+                                               const int32_t *tgt_for_pred, const float *sums, float loss_scale, float *d_logits,
+                                               float *d_boxes, void *stream) {
+    RuntimeCriterion c;
+    if (fill_criterion(criterion, class_weights, c)) return -1;
+    return launch_grad(d, c, tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
 }

@@ -300,6 +300,11 @@ _SIGNATURES = {
     "detr_hip_set_loss_sums_f32": [POINTER(SetLossDesc), c_void_p, f32p, c_void_p],
     "detr_hip_set_loss_finalize_f32": [f32p, c_int32, f32p, f32p, c_void_p],
     "detr_hip_set_loss_grad_f32": [POINTER(SetLossDesc), c_void_p, f32p, c_float, f32p, f32p, c_void_p],
+    # the same four launches with the criterion as an argument: CRITERION_FLOATS host floats (+ device class weights or None)
+    "detr_hip_match_cost_crit_f32": [POINTER(SetLossDesc), POINTER(c_float), f32p, c_void_p],
+    "detr_hip_set_loss_sums_crit_f32": [POINTER(SetLossDesc), POINTER(c_float), f32p, c_void_p, f32p, c_void_p],
+    "detr_hip_set_loss_finalize_crit_f32": [f32p, c_int32, POINTER(c_float), f32p, f32p, c_void_p],
+    "detr_hip_set_loss_grad_crit_f32": [POINTER(SetLossDesc), POINTER(c_float), f32p, c_void_p, f32p, c_float, f32p, f32p, c_void_p],
     "detr_hip_sumsq_segments_f32": [f32p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, f32p, c_void_p],
     "detr_hip_clip_adam_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, c_int32, c_int32, c_void_p],
     "detr_hip_axpy_f32": [f32p, f32p, c_float, c_int64, c_void_p],
@@ -336,6 +341,7 @@ _SIGNATURES_I64 = {
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
+CRITERION_FLOATS = 8                                                           # DETR_CRITERION_FLOATS
 # detr_hip_struct_layout's `which` -> mirror, every descriptor struct of include/detr_hip.h (the table above the entry point there)
 LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: LayerNormDesc, 5: AttnDesc, 6: SetLossDesc, 7: InputDesc,
                   8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc, 400: TrackDesc,

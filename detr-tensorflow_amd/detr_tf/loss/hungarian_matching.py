@@ -40,8 +40,12 @@ class Matcher:
         self.pred_for_tgt = torch.empty(self.P, R - 1, dtype=torch.int32, device=device)
         self.status = torch.empty(self.P, dtype=torch.int32, device=device)
 
-    def run(self, desc, t_bbox):
-        hip.call("detr_hip_match_cost_f32", byref(desc), self.cost.data_ptr())
+    def run(self, desc, t_bbox, criterion=None):
+        """criterion: a loss.Criterion; None or the default one runs the cost kernel with the reference's weights compiled in."""
+        if criterion is None or criterion.is_default:
+            hip.call("detr_hip_match_cost_f32", byref(desc), self.cost.data_ptr())
+        else:
+            hip.call("detr_hip_match_cost_crit_f32", byref(desc), criterion.floats(), self.cost.data_ptr())
         if before_assign is not None:       # work of another stream queued behind the cost matrix: the assignment keeps ~50 CUs busy
             before_assign()
         hip.call("detr_hip_assign_f32", self.cost.data_ptr(), self.P, self.Q, self.R - 1, t_bbox.data_ptr(), self.B,
@@ -54,8 +58,10 @@ def hungarian_matching(t_bbox, t_class, p_bbox, p_class, fcost_class=1, fcost_bb
     (pred_indices, target_indices, pred_selector, target_selector, t_bbox, t_class) --
     after the reference's double name swap position 0 holds the TARGET indices,
     position 1 the PREDICTION indices, position 2 the bool[n] selector over targets and position 3
-    the bool[Q] selector over predictions.  Runs the same two HIP kernels on a batch of one."""
-    assert (fcost_class, fcost_bbox, fcost_giou) == (1, 5, 2), "cost weights are compiled into K12"
+    the bool[Q] selector over predictions.  Runs the same two HIP kernels on a batch of one; cost weights other than 1 / 5 / 2
+    take the cost kernel's run-time criterion."""
+    from .loss import DEFAULT_CRITERION, criterion_of
+    crit = criterion_of(DEFAULT_CRITERION._replace(set_cost_class=fcost_class, set_cost_bbox=fcost_bbox, set_cost_giou=fcost_giou))
     assert slice_preds, "targets must carry the header row"
     dev = p_bbox.device
     Q, C = p_class.shape
@@ -64,7 +70,7 @@ def hungarian_matching(t_bbox, t_class, p_bbox, p_class, fcost_class=1, fcost_bb
     lg = p_class.reshape(1, 1, Q, C).contiguous().float()
     bx = p_bbox.reshape(1, 1, Q, 4).contiguous().float()
     m = Matcher(1, 1, Q, tb.shape[1], dev)
-    m.run(make_desc(lg, bx, tb, tc, 0), tb)
+    m.run(make_desc(lg, bx, tb, tc, 0), tb, crit)
     n = int(tb[0, 0, 0])
     pred_for_tgt = m.pred_for_tgt[0, :n].long()
     if int(m.status[0]) != 0:

@@ -3,11 +3,16 @@
 `get_losses(m_outputs, t_bbox, t_class, config)` keeps the reference signature and returns
 `(total_loss, log_dict)` with the same 36 keys (label_cost, true_neg, true_pos, pos_accuracy,
 giou_loss, l1_loss, + suffixes _0.._4) and the 1/2/5 weighting of `get_total_losss`.
+The criterion -- matcher cost weights, loss coefficients, the weight of unmatched queries, per-class weights, the clamp of
+the box count -- is read from the config at every call (`criterion_of`); at the reference's values the loss runs the four
+entry points that have them compiled in, otherwise the `_crit_` ones (the same kernel bodies on run-time values).
 All arithmetic runs in csrc/setloss.hip: cost matrix (K12), exact assignment (K13), loss sums /
 finalisation / gradients (K14).  Under data parallelism the per-level normalisers (sum of CE
 weights, number of matched boxes) are all-reduced between the "sums" and "finalize" kernels, so
 a B x world step has the reference's single-device whole-batch semantics (loss.py:66-67,82,94).
 """
+import math
+from collections import namedtuple
 from ctypes import byref, c_float
 
 import torch
@@ -18,9 +23,63 @@ from .hungarian_matching import Matcher, make_desc
 LOSS_NAMES = ("label_cost", "true_neg", "true_pos", "pos_accuracy", "giou_loss", "l1_loss")
 
 
-def get_total_losss(losses):
-    """loss.py:6-19: sum of 1*label_cost + 2*giou_loss + 5*l1_loss over every (suffixed) key."""
+CRITERION_FIELDS = ("set_cost_class", "set_cost_bbox", "set_cost_giou", "class_loss_coef", "bbox_loss_coef", "giou_loss_coef",
+                    "eos_coef", "num_boxes_min_one")                  # the order of DETR_CRITERION_FLOATS (include/detr_hip.h)
+CRITERION_DEFAULTS = (1.0, 5.0, 2.0, 1.0, 5.0, 2.0, 0.1, False)       # the reference's literals (loss.py:6-19,60-67, hungarian_matching.py:163)
+WEIGHT_QUANTUM, WEIGHT_MAX = 1.0 / 64.0, 16.0                         # class weights: multiples of 1/64 in [0, 16] ...
+WEIGHT_MAX_TERMS = 16384                                              # ... and at most this many added: every partial sum < 2^24 quanta
+
+
+class Criterion(namedtuple("Criterion", CRITERION_FIELDS + ("class_weights",))):
+    """The set criterion as an immutable, hashable record: seven floats, a bool, and the class weights as a tuple of multiples
+    of 1/64 (or None)."""
+    __slots__ = ()
+
+    @property
+    def is_default(self):
+        return tuple(self[:8]) == CRITERION_DEFAULTS and self.class_weights is None
+
+    def floats(self):
+        """The host block of the _crit_ entry points."""
+        return (c_float * hip.CRITERION_FLOATS)(*[float(v) for v in self[:8]])
+
+
+def round_class_weights(weights, nb_class=None):
+    """A sequence of class weights -> tuple of the nearest multiples of 1/64; ValueError outside [0, 16], on a non-finite
+    entry or a length other than nb_class."""
+    w = [float(v) for v in (weights.tolist() if hasattr(weights, "tolist") else weights)]
+    if nb_class is not None and len(w) != int(nb_class):
+        raise ValueError(f"class_weights has {len(w)} entries, the class head has {int(nb_class)}")
+    for c, v in enumerate(w):
+        if not math.isfinite(v) or v < 0.0 or v > WEIGHT_MAX:
+            raise ValueError(f"class_weights[{c}] = {v}: expected a finite value in [0, {WEIGHT_MAX:g}]")
+    return tuple(round(v / WEIGHT_QUANTUM) * WEIGHT_QUANTUM for v in w)
+
+
+def criterion_of(config, nb_class=None):
+    """The criterion a config asks for (attributes it lacks read as the defaults).  nb_class: the length class_weights must have,
+    where the caller knows it."""
+    vals = []
+    for name, default in zip(CRITERION_FIELDS[:7], CRITERION_DEFAULTS[:7]):
+        v = float(getattr(config, name, default))
+        if not math.isfinite(v) or v < 0.0:
+            raise ValueError(f"{name} = {v}: expected a finite value >= 0")
+        vals.append(v)
+    vals.append(bool(getattr(config, "num_boxes_min_one", False)))
+    cw = getattr(config, "class_weights", None)
+    return Criterion(*vals, None if cw is None else round_class_weights(cw, nb_class))
+
+
+DEFAULT_CRITERION = Criterion(*CRITERION_DEFAULTS, None)
+
+
+def get_total_losss(losses, config=None):
+    """loss.py:6-19: sum of 1*label_cost + 2*giou_loss + 5*l1_loss over every (suffixed) key; with a config, its
+    class_loss_coef / giou_loss_coef / bbox_loss_coef instead."""
     weights = {"label_cost": 1, "giou_loss": 2, "l1_loss": 5}
+    if config is not None:
+        crit = criterion_of(config)
+        weights = {"label_cost": crit.class_loss_coef, "giou_loss": crit.giou_loss_coef, "l1_loss": crit.bbox_loss_coef}
     total = 0
     for key, value in losses.items():
         hit = [w for n, w in weights.items() if n in key]
@@ -51,18 +110,48 @@ class SetLoss:
         self.d_boxes = torch.zeros(levels, B, Q, 4, dtype=torch.float32, device=device)
         self.desc = None
         self.reduce_sums = None          # hook: callable(tensor) doing the data-parallel all-reduce
+        self.criterion = DEFAULT_CRITERION
+        self._weights = (None, None)     # (tuple, device tensor) of the class weights last used
 
-    def forward(self, logits, boxes, t_bbox, t_class, background_class):
+    def _class_weights(self, crit, world):
+        """Device pointer of the criterion's class weights (None without): one tensor, rebuilt when the vector changes."""
+        if crit.class_weights is None:
+            return None
+        if len(crit.class_weights) != self.C:
+            raise ValueError(f"class_weights has {len(crit.class_weights)} entries, the class head has {self.C}")
+        if world * self.B * (self.R - 1) > WEIGHT_MAX_TERMS:
+            raise ValueError(f"class_weights: world * B * (R - 1) = {world * self.B * (self.R - 1)} matched targets could exceed "
+                             f"{WEIGHT_MAX_TERMS}, past which the sum of their weights is no longer exact in float32")
+        if self._weights[0] != crit.class_weights:
+            self._weights = (crit.class_weights, torch.tensor(crit.class_weights, dtype=torch.float32, device=self.sums.device))
+        return self._weights[1].data_ptr()
+
+    def forward(self, logits, boxes, t_bbox, t_class, background_class, criterion=DEFAULT_CRITERION, world=1):
+        """criterion: a `Criterion` (criterion_of).  world: data-parallel ranks whose sums the reduce_sums hook adds up."""
+        wptr = self._class_weights(criterion, max(1, int(world)))
+        self.criterion = criterion
         self.desc = make_desc(logits, boxes, t_bbox, t_class, background_class)
         self._keep = (logits, boxes, t_bbox, t_class)
-        tfp = self.matcher.run(self.desc, t_bbox)
+        tfp = self.matcher.run(self.desc, t_bbox, criterion)
         hip.zero_(self.sums)
-        hip.call("detr_hip_set_loss_sums_f32", byref(self.desc), tfp.data_ptr(), self.sums.data_ptr())
+        if criterion.is_default:
+            hip.call("detr_hip_set_loss_sums_f32", byref(self.desc), tfp.data_ptr(), self.sums.data_ptr())
+        else:
+            hip.call("detr_hip_set_loss_sums_crit_f32", byref(self.desc), criterion.floats(), wptr, tfp.data_ptr(),
+                     self.sums.data_ptr())
         if self.reduce_sums is not None:
             self.reduce_sums(self.sums)
-        hip.call("detr_hip_set_loss_finalize_f32", self.sums.data_ptr(), self.levels, self.losses.data_ptr(),
-                 self.total.data_ptr())
+        self.finalize()
         return self.total, self.losses
+
+    def finalize(self):
+        """losses / total of self.sums under the criterion of the last forward."""
+        if self.criterion.is_default:
+            hip.call("detr_hip_set_loss_finalize_f32", self.sums.data_ptr(), self.levels, self.losses.data_ptr(),
+                     self.total.data_ptr())
+        else:
+            hip.call("detr_hip_set_loss_finalize_crit_f32", self.sums.data_ptr(), self.levels, self.criterion.floats(),
+                     self.losses.data_ptr(), self.total.data_ptr())
 
     def grad(self, loss_scale=1.0):
         """Gradients of loss_scale * total w.r.t. logits / boxes, laid out [Lv,B,Q,*] contiguous."""
@@ -70,8 +159,14 @@ class SetLoss:
         d = make_desc(lg, self._keep[1], self._keep[2], self._keep[3], self.desc.background_class)
         # the gradient tensors use the same (level, image, query) strides as contiguous [Lv,B,Q,*]
         assert lg.is_contiguous() and self._keep[1].is_contiguous(), "set-loss gradients need contiguous head outputs"
-        hip.call("detr_hip_set_loss_grad_f32", byref(d), self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(),
-                 c_float(loss_scale), self.d_logits.data_ptr(), self.d_boxes.data_ptr())
+        if self.criterion.is_default:
+            hip.call("detr_hip_set_loss_grad_f32", byref(d), self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(),
+                     c_float(loss_scale), self.d_logits.data_ptr(), self.d_boxes.data_ptr())
+        else:
+            wptr = None if self.criterion.class_weights is None else self._weights[1].data_ptr()
+            hip.call("detr_hip_set_loss_grad_crit_f32", byref(d), self.criterion.floats(), wptr,
+                     self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(), c_float(loss_scale), self.d_logits.data_ptr(),
+                     self.d_boxes.data_ptr())
         return self.d_logits, self.d_boxes
 
 
@@ -112,7 +207,9 @@ def get_losses(m_outputs, t_bbox, t_class, config):
     sl = SetLoss.get(Lv, B, Q, C, tb.shape[1], lg.device)
     hook = getattr(m_outputs, "reduce_sums", None)
     sl.reduce_sums = hook
-    total, losses = sl.forward(lg, bx, tb, tc, config.background_class)
+    dp = getattr(getattr(m_outputs, "model", None), "dp", None)
+    world = getattr(dp, "world", 1) if hook is not None else 1
+    total, losses = sl.forward(lg, bx, tb, tc, config.background_class, criterion_of(config, C), world)
     if getattr(config, "check_matching", False):
         # opt-in (it synchronises): the reference's SciPy call raises ValueError on NaN / inf / infeasible cost matrices
         # (hungarian_matching.py:29); the device matcher records a status per problem instead of stopping the step

@@ -16,7 +16,7 @@ import torch
 from . import _hip as hip
 from .engine import downsample_mask_nearest, feature_size
 from .loss import hungarian_matching as _matching
-from .loss.loss import get_losses, log_from_losses
+from .loss.loss import criterion_of, get_losses, log_from_losses
 from .optimizers import GROUPS, aggregate_grad_and_apply, clip_mode, decay_active, gather_gradient, joint_optimizer
 
 PRINT_EVERY_TRAIN = 100         # training.py:57
@@ -127,7 +127,7 @@ class GraphedTrainStep:
     when training on several GPUs), clip + Adam of the three groups (or the joint AdamW sequence of config.global_clipnorm) into
     another -- and from then on a replayed step is:
     copy the batch into the static input buffers, write the new dropout seed / Adam step sizes to device memory, replay.
-    A new batch shape (or set of trained groups), and any re-allocation of an engine buffer since the recording (a forward
+    A new batch shape (or set of trained groups, or set criterion: its values are baked into the recorded launches), and any re-allocation of an engine buffer since the recording (a forward
     of another shape in between: engine.buf_generation), drop the recording: one eager step, then a new one.  Gradient
     accumulation and `config.check_matching` (a host synchronisation inside the loss) run eagerly.
     Every call returns FRESH loss / log tensors (clones of the static ones), like the eager path and the reference."""
@@ -157,7 +157,8 @@ class GraphedTrainStep:
         images, masks = split_images(images)
         return (tuple(images.shape), masks is not None, tuple(t_bbox.shape), bool(c.train_backbone), bool(c.train_transformers),
                 bool(c.train_nlayers), int(c.background_class), self.model.engine.compute, float(self.model.engine.dropout_p),
-                bool(getattr(c, "check_matching", False)), clip_mode(c), decay_active(c), tuple(self.model.engine.dilate))      # (other optimiser launches: re-record)
+                bool(getattr(c, "check_matching", False)), clip_mode(c), decay_active(c), tuple(self.model.engine.dilate),      # (other optimiser launches: re-record)
+                criterion_of(c))         # the criterion's values are launch ARGUMENTS of the set-loss kernels: a change re-records
 
     def _capture(self, images, t_bbox, t_class):
         model, opts, cfg = self.model, self.optimizers, self.config

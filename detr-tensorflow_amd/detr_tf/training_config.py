@@ -42,6 +42,10 @@ _FLAGS = (
     ("log", None, False, True),
     # not in the reference: AdamW decay, one model-wide gradient norm, Adam's epsilon (optimizers.py)
     ("weight_decay", float, 0.0, False), ("global_clipnorm", float, None, False), ("adam_epsilon", float, 1e-7, False),
+    # not in the reference (it compiles these in): the set criterion, named after the original DETR's flags (loss/loss.py criterion_of)
+    ("set_cost_class", float, 1.0, False), ("set_cost_bbox", float, 5.0, False), ("set_cost_giou", float, 2.0, False),
+    ("class_loss_coef", float, 1.0, False), ("bbox_loss_coef", float, 5.0, False), ("giou_loss_coef", float, 2.0, False),
+    ("eos_coef", float, 0.1, False), ("num_boxes_min_one", None, False, True),
 )
 
 
@@ -65,6 +69,13 @@ _DEFAULTS = dict(
     # global_clipnorm: clip by ONE L2 norm over all tensors of the trained groups; when it is not None it REPLACES the
     # per-tensor gradient_norm_clipping ("global wins": Keras refuses both, but gradient_norm_clipping defaults to 0.1 here).
     weight_decay=0.0, global_clipnorm=None, adam_epsilon=1e-7,
+    # The set criterion, read at EVERY step (loss/loss.py criterion_of): the matcher's cost = set_cost_bbox * L1 - set_cost_class * prob
+    # - set_cost_giou * GIoU, the total = class_loss_coef * label_cost + giou_loss_coef * giou_loss + bbox_loss_coef * l1_loss per
+    # level, eos_coef = the cross-entropy weight of an unmatched query, num_boxes_min_one = divide the box sums by max(matched, 1)
+    # (a batch without targets then has a finite total).  class_weights (no flag): a sequence of nb_class weights of the MATCHED
+    # targets' classes, rounded to multiples of 1/64 in [0, 16].  At these defaults the loss runs the reference's compiled-in criterion.
+    set_cost_class=1.0, set_cost_bbox=5.0, set_cost_giou=2.0, class_loss_coef=1.0, bbox_loss_coef=5.0, giou_loss_coef=2.0,
+    eos_coef=0.1, num_boxes_min_one=False, class_weights=None,
 )
 
 

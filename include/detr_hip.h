@@ -470,7 +470,8 @@ int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int32_t ldc, co
                         int32_t *status, void *stream);
 /* K14: loss.py:37-96.  Three steps so that data-parallel ranks can all-reduce `sums` in between:
  *   sums [levels][8] = {sum w*CE, -, n_neg_correct, n_neg, n_pos, n_pos_not_bg, n_pos_correct, -}
- *                      {.. [1], [7] unused: the normaliser sum w is derived as 0.1*n_neg + n_pos from the counts, which
+ *                      {.. [1], [7] unused ([1] stays 0 here; the *_crit_* entry points below keep the matched targets' class
+ *                      weights in it): the normaliser sum w is derived as 0.1*n_neg + n_pos from the counts, which
  *                      float atomics accumulate exactly in any order -- the gradients are then a deterministic function
  *                      of the matching};  box sums [levels][2] are stored at sums + levels*8:
  *                      {sum L1, sum (1-GIoU)} ; all ACCUMULATED atomically (zero them first). */
@@ -483,6 +484,34 @@ int detr_hip_set_loss_finalize_f32(const float *sums, int32_t levels, float *los
 /* gradients of loss_scale*total w.r.t. logits and boxes (same strides as the inputs) */
 int detr_hip_set_loss_grad_f32(const detr_setloss_desc *d, const int32_t *tgt_for_pred, const float *sums,
                                float loss_scale, float *d_logits, float *d_boxes, void *stream);
+
+/* The same four launches with a configurable criterion (appended; the ABI version is unchanged).  The four entry points above
+ * run the reference's criterion, compiled in; these run the same kernel bodies on run-time values.  Per level, with N the
+ * unmatched queries, M the matched pairs (q, j), w[c] = class_weights[c] (1 without class weights, and 1 for a label
+ * outside [0, C)):
+ *   cost[q][j]  = set_cost_bbox*L1 + set_cost_class*(-softmax[class_j]) + set_cost_giou*(-GIoU)
+ *   W           = eos_coef*|N| + sum_M w[class_j]          (a matched target gets w[class_j] even when that is the background class)
+ *   label_cost  = (eos_coef*sum_N CE(q, bg) + sum_M w[class_j]*CE(q, class_j)) / W
+ *   npos'       = num_boxes_min_one ? max(|M|, 1) : |M| ;   l1_loss = sum_M |p - t|_1 / npos' ;   giou_loss = sum_M (1 - GIoU) / npos'
+ *   total       = sum_lv class_loss_coef*label_cost + giou_loss_coef*giou_loss + bbox_loss_coef*l1_loss   (main level first)
+ * losses[] stay unweighted; true_pos / pos_accuracy divide by |M| itself.  sums_crit accumulates sum_M w[class_j] into slot
+ * [1] of a level's eight, and finalize_crit / grad_crit use W = eos_coef*sums[3] + sums[1]: callers keep class weights on
+ * multiples of 1/64 in [0, 16] and world*B*(R-1) <= 16384, so that this float atomic sum is exact in any order and the
+ * gradients stay a deterministic function of the matching.  At the reference's values the cost, the matching and the
+ * gradients are bit-identical to the four entry points above.
+ * criterion: DETR_CRITERION_FLOATS floats in HOST memory, read during the call:
+ *   [0] set_cost_class [1] set_cost_bbox [2] set_cost_giou [3] class_loss_coef [4] bbox_loss_coef [5] giou_loss_coef
+ *   [6] eos_coef [7] num_boxes_min_one (0 or 1).  class_weights: DEVICE float [C] or NULL (all 1).
+ * Rejected on the host, before anything is launched: a null criterion, a value that is not finite or is negative, [7] other
+ * than 0 or 1, and everything the entry points above reject. */
+#define DETR_CRITERION_FLOATS 8
+int detr_hip_match_cost_crit_f32(const detr_setloss_desc *d, const float *criterion, float *cost, void *stream);
+int detr_hip_set_loss_sums_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
+                                    const int32_t *tgt_for_pred, float *sums, void *stream);
+int detr_hip_set_loss_finalize_crit_f32(const float *sums, int32_t levels, const float *criterion, float *losses, float *total, void *stream);
+int detr_hip_set_loss_grad_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
+                                    const int32_t *tgt_for_pred, const float *sums, float loss_scale,
+                                    float *d_logits, float *d_boxes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Device-side input stage (the step's producer side; detr_tf/data/processing.py:6-21,35-55, data/transformation.py:82-91).
