@@ -216,9 +216,99 @@ __global__ __launch_bounds__(256) void adamw_kernel(float *__restrict__ param, c
     }
 }
 
+// ---- exponential moving average of the weights (tf.train.ExponentialMovingAverage) ----------------------------------
+// TensorFlow's form, shadow -= (1 - decay) * (shadow - param), as three operations that are each rounded on their own: the
+// 16-byte body, the scalar tail and a NumPy float32 restatement then give the same bits.
+__device__ __forceinline__ float ema_elem(float s, float p, float omd) {
+#pragma clang fp contract(off)
+    float t = s - p;
+    t = omd * t;
+    return s - t;
+}
+
+// One chunk per workgroup, the tables of adamw_kernel (the chunk list of the trained groups).  omd = 1 - decay is read from
+// device memory, so a replayed launch sees this step's value.  A pure stream: reads param and shadow, writes shadow; what
+// no chunk lists (alignment gaps, tensors of untrained groups) is not touched.
+__global__ __launch_bounds__(256) void ema_kernel(float *__restrict__ shadow, const float *__restrict__ param,
+                                                  const int *__restrict__ chunk_tensor,
+                                                  const long long *__restrict__ chunk_start,
+                                                  const long long *__restrict__ seg_end,
+                                                  const float *__restrict__ hyper, int chunk, int aligned16) {
+    const int c = blockIdx.x;
+    const int t = chunk_tensor[c];
+    const long long s0 = chunk_start[c];
+    long long s1 = s0 + chunk;
+    if (s1 > seg_end[t]) s1 = seg_end[t];
+    const float omd = hyper[0];
+    long long i0 = s0;
+    if (aligned16 && (s0 & 3) == 0) {
+        const long long nvec = (s1 - s0) >> 2;
+        float4 *__restrict__ s4 = reinterpret_cast<float4 *>(shadow + s0);
+        const float4 *__restrict__ p4 = reinterpret_cast<const float4 *>(param + s0);
+        for (long long j = threadIdx.x; j < nvec; j += blockDim.x) {
+            const float4 pp = p4[j];
+            float4 ss = s4[j];
+            ss.x = ema_elem(ss.x, pp.x, omd);
+            ss.y = ema_elem(ss.y, pp.y, omd);
+            ss.z = ema_elem(ss.z, pp.z, omd);
+            ss.w = ema_elem(ss.w, pp.w, omd);
+            s4[j] = ss;
+        }
+        i0 = s0 + (nvec << 2);
+    }
+    for (long long i = i0 + threadIdx.x; i < s1; i += blockDim.x) shadow[i] = ema_elem(shadow[i], param[i], omd);
+}
+
+// a[i] <-> b[i] over two disjoint ranges: nvec 16-byte pairs (only when both pointers are 16-byte aligned), then the scalar
+// tail [4 * nvec, n).  Grid-stride with 64-bit indices: n may exceed 2^31 bytes.
+__global__ __launch_bounds__(256) void exchange_kernel(float *__restrict__ a, float *__restrict__ b, long long n,
+                                                       long long nvec) {
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    float4 *__restrict__ a4 = reinterpret_cast<float4 *>(a);
+    float4 *__restrict__ b4 = reinterpret_cast<float4 *>(b);
+    for (long long j = tid; j < nvec; j += stride) {
+        const float4 x = a4[j], y = b4[j];
+        a4[j] = y;
+        b4[j] = x;
+    }
+    for (long long i = (nvec << 2) + tid; i < n; i += stride) {
+        const float x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
 }  // namespace detr
 
 using namespace detr;
+
+extern "C" int detr_hip_ema_f32(float *shadow, const float *param, const int32_t *chunk_tensor, const int64_t *chunk_start,
+                                const int64_t *seg_end, const float *hyper, int32_t n_chunks, int32_t chunk, void *stream) {
+    DETR_REQUIRE(shadow && param && chunk_tensor && chunk_start && seg_end && hyper, "ema: null operand");
+    DETR_REQUIRE(shadow != param, "ema: shadow and param are the same buffer");
+    DETR_REQUIRE(n_chunks > 0 && chunk > 0, "ema: bad chunking");
+    const int aligned16 = (((uintptr_t)shadow | (uintptr_t)param) & 15) == 0;       // the rule of detr_hip_adamw_f32
+    hipLaunchKernelGGL(ema_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, shadow, param, chunk_tensor,
+                       reinterpret_cast<const long long *>(chunk_start), reinterpret_cast<const long long *>(seg_end), hyper,
+                       chunk, aligned16);
+    DETR_LAUNCH_CHECK("ema");
+    return 0;
+}
+
+extern "C" int detr_hip_exchange_f32(float *a, float *b, int64_t n, void *stream) {
+    DETR_REQUIRE(a && b, "exchange: null operand");
+    DETR_REQUIRE(n > 0, "exchange: bad length");
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * 4;
+    DETR_REQUIRE(ua + bytes <= ub || ub + bytes <= ua, "exchange: the two ranges overlap");
+    const long long nvec = ((ua | ub) & 15) == 0 ? (long long)(n >> 2) : 0;
+    const long long work = nvec > 0 ? nvec + (n & 3) : (long long)n;
+    long long blocks = (work + 255) / 256;
+    if (blocks > 2048) blocks = 2048;                    // 256 CUs x 8 workgroups; the rest of the range by grid stride
+    hipLaunchKernelGGL(exchange_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, (long long)n, nvec);
+    DETR_LAUNCH_CHECK("exchange");
+    return 0;
+}
 
 extern "C" int detr_hip_set_floats16_f32(float *dst, const float *values, void *stream) {
     DETR_REQUIRE(dst && values, "set_floats16: null operand");

@@ -312,6 +312,8 @@ _SIGNATURES = {
     "detr_hip_set_floats16_f32": [f32p, POINTER(c_float * 16), c_void_p],
     "detr_hip_global_clip_scale_f32": [f32p, c_void_p, c_void_p, f32p, c_int32, f32p, c_void_p],
     "detr_hip_adamw_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, f32p, c_int32, c_int32, c_void_p],
+    "detr_hip_ema_f32": [f32p, f32p, c_void_p, c_void_p, c_void_p, f32p, c_int32, c_int32, c_void_p],
+    "detr_hip_exchange_f32": [f32p, f32p, c_int64, c_void_p],
     "detr_hip_conv3x3_dilated": [POINTER(Conv3x3DDesc), c_int32, c_void_p],
     "detr_hip_detect": [POINTER(DetectDesc), c_void_p],
     "detr_hip_tile_merge": [POINTER(TileMergeDesc), c_void_p],

@@ -69,11 +69,24 @@ def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_re
     return acc.result(class_names, print_result=print_result)
 
 
-def eval_model(model, config, class_names, valid_dt, max_batches=None, print_result=True, accumulate="host", *, protocol="reference"):
+def eval_model(model, config, class_names, valid_dt, max_batches=None, print_result=True, accumulate="host", *, protocol="reference",
+               **options):
+    """options: weights="model" (default) | "ema", keyword-only.  "ema" evaluates the averaged weights kept by config.ema_decay:
+    the whole evaluation runs inside optimizers.ema_weights(model), and the trained weights are back, bit for bit, when it
+    returns."""
+    weights = options.pop("weights", "model")
+    if options:
+        raise TypeError(f"eval_model() got an unexpected keyword argument {sorted(options)[0]!r}")
     if accumulate not in ("host", "device"):
         raise ValueError(f"eval_model: accumulate must be 'host' or 'device', got {accumulate!r}")
     if protocol not in ("reference", "coco"):
         raise ValueError(f"eval_model: protocol must be 'reference' or 'coco', got {protocol!r}")
+    if weights not in ("model", "ema"):
+        raise ValueError(f"eval_model: weights must be 'model' or 'ema', got {weights!r}")
+    if weights == "ema":
+        from .optimizers import ema_weights
+        with ema_weights(model):
+            return eval_model(model, config, class_names, valid_dt, max_batches, print_result, accumulate, protocol=protocol)
     if protocol == "coco":
         return _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate)
     acc = APAccumulator(len(class_names))

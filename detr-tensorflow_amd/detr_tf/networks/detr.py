@@ -148,8 +148,10 @@ class DetrModel:
             return missing
         return self.engine.P.load(self._npz(path_or_dict)) if isinstance(path_or_dict, str) else self.engine.load_params(path_or_dict)
 
-    def save_weights(self, path):
-        self.engine.P.save(self._npz(path))
+    def save_weights(self, path, weights="model"):
+        """weights="ema": the averaged weights kept by config.ema_decay (optimizers.WeightEMA) under the normal parameter
+        names, with the frozen-BN vectors: `load_weights(path)` into a fresh model gives the deployable averaged model."""
+        self.engine.P.save(self._npz(path), weights=weights)
 
     # ---- forward ----------------------------------------------------------------------------
     def _eval_forward(self, images, masks=None, attn_sites=()):

@@ -12,7 +12,10 @@ Opt-in extensions (training_config.py: weight_decay, global_clipnorm, adam_epsil
     the update of all trained groups -- three launches: partial sums, finalize, update (JointAdam) -- runs in the call
     of the LAST trained group of GROUPS at an apply step;
   * optimizer_state / load_optimizer_state (+ the .npz file forms) save and restore moments, step counts, pending
-    gradient accumulators and the engine's dropout step counter.
+    gradient accumulators and the engine's dropout step counter;
+  * config.ema_decay = d: an exponential moving average of the weights (tf.train.ExponentialMovingAverage) in a second flat
+    fp32 buffer, `store.ema`: ONE launch per apply step, after the update of the last trained group, over the chunk list of
+    all trained groups (WeightEMA); `ema_weights(model)` swaps the averaged weights in for evaluation / saving and back.
 With the defaults nothing below differs from the three Adam(clipnorm) optimisers: same launches, same bits.
 """
 import math
@@ -86,7 +89,8 @@ class GroupAdam:
 
     def apply_gradients(self, grad_flat, hyper_ready=False):
         """One Keras Adam step (AdamW with config.weight_decay > 0) on this group's tensors using the flat gradient buffer;
-        the clip is per tensor here whatever config.global_clipnorm says (the joint norm needs all groups: JointAdam)."""
+        the clip is per tensor here whatever config.global_clipnorm says (the joint norm needs all groups: JointAdam).
+        Called directly (outside aggregate_grad_and_apply) it does NOT update the weight average of config.ema_decay."""
         if not hyper_ready:
             self.set_step_hyper()
         if self.engine is not None:
@@ -123,6 +127,18 @@ def trained_groups(config):
     return [n for n in GROUPS if getattr(config, f"train_{n}")]
 
 
+def trained_chunk_table(tables, group_host, trained, device, cache):
+    """(chunk_tensor, chunk_start, n) of the chunks of the `trained` groups, in tensor order: the table of every launch that
+    covers all trained groups at once (JointAdam, WeightEMA).  Built once per set of trained groups (`cache`)."""
+    key = tuple(trained)
+    if key not in cache:
+        gids = {GROUPS.index(n) for n in trained}
+        keep = [i for i, t in enumerate(tables["chunk_tensor"].tolist()) if group_host[t] in gids]
+        idx = torch.tensor(keep, dtype=torch.int64, device=device)
+        cache[key] = (tables["chunk_tensor"][idx].contiguous(), tables["chunk_start"][idx].contiguous(), len(keep))
+    return cache[key]
+
+
 class JointAdam:
     """All trained groups in three launches: per-chunk sums of squares, a fixed-order finalize that leaves the clip factor
     c / max(G, c) in device memory, and one clip + decay + Adam launch.  The per-group step counts stay on the GroupAdam
@@ -153,13 +169,7 @@ class JointAdam:
 
     def _table(self, trained):
         """Chunk list of the trained groups, in tensor order (built once per set of trained groups)."""
-        key = tuple(trained)
-        if key not in self._chunks:
-            gids = {GROUPS.index(n) for n in trained}
-            keep = [i for i, t in enumerate(self.tables["chunk_tensor"].tolist()) if self.group_host[t] in gids]
-            idx = torch.tensor(keep, dtype=torch.int64, device=self.store.device)
-            self._chunks[key] = (self.tables["chunk_tensor"][idx].contiguous(), self.tables["chunk_start"][idx].contiguous(), len(keep))
-        return self._chunks[key]
+        return trained_chunk_table(self.tables, self.group_host, trained, self.store.device, self._chunks)
 
     def prepare(self):
         """Builds what the next apply needs on the device (nothing is allocated inside a recorded step)."""
@@ -224,6 +234,128 @@ def joint_optimizer(optimizers, config):
     return joint
 
 
+# ---- exponential moving average of the weights ---------------------------------------------------------------------------
+def ema_active(config):
+    return getattr(config, "ema_decay", None) is not None
+
+
+def ema_step_decay(decay, warmup, num_updates):
+    """This update's decay, in double: `decay`, or with warmup min(decay, (1 + n) / (10 + n)) for n = the updates done before
+    this one (tf.train.ExponentialMovingAverage(decay, num_updates=n))."""
+    d = float(decay)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must satisfy 0 <= ema_decay < 1, got {decay!r}")
+    if warmup:
+        d = min(d, (1.0 + num_updates) / (10.0 + num_updates))
+    return d
+
+
+def _in_ema_scope(store, what):
+    if getattr(store, "ema_swapped", False):
+        raise RuntimeError(f"{what}: not inside ema_weights(model) -- the parameter buffer holds the averaged weights there")
+
+
+class WeightEMA:
+    """tf.train.ExponentialMovingAverage over every trained tensor, on the device.  The shadow is `store.ema`, a flat fp32
+    buffer laid out like `store.flat` and created as a copy of it; per apply step ONE launch (detr_hip_ema_f32) over the chunk
+    list of all trained groups applies  t = shadow - w; t = (1 - d) * t; shadow -= t  with each operation rounded on its own.
+    1 - d travels through a device block written by set_step_hyper(), which also advances `num_updates`: a captured step is
+    replayed with fresh values.  Tensors of untrained groups are not visited (their shadow stays the copy it started as).
+    config.ema_decay and config.ema_warmup are read at every update; ema_decay = None pauses the updates and keeps the shadow.
+    The update belongs to `aggregate_grad_and_apply` (and training.GraphedTrainStep): a direct GroupAdam.apply_gradients or
+    JointAdam.apply does NOT average.
+    Data parallelism needs no communication: every rank applies the same update to identical parameters."""
+
+    def __init__(self, store, config, nlayers):
+        self.store, self.config, self.nlayers = store, config, list(nlayers)
+        self.tables = self.group_host = self.seg_end = self.hyper = None
+        self._chunks = {}
+        self.last_decay = None                 # the decay of the last update (after the warmup rule)
+
+    @property
+    def num_updates(self):
+        return self.store.ema_num_updates
+
+    @num_updates.setter
+    def num_updates(self, n):
+        self.store.ema_num_updates = int(n)
+
+    def prepare(self):
+        """Everything the next update needs on the device: the shadow (a copy of the current weights, if there is none yet),
+        the hyper block and the chunk table of the trained groups.  Called before a step is recorded; never inside one."""
+        st = self.store
+        if st.ema is None:
+            st.ema = st.flat.clone()
+            st.ema_num_updates = 0
+        if self.tables is None:
+            self.tables = st.build_tables(self.nlayers, CHUNK)
+            self.group_host = list(self.tables["group_host"])
+            self.seg_end = self.tables["seg_end"]
+            self.hyper = torch.zeros(8, dtype=torch.float32, device=st.device)
+        return trained_chunk_table(self.tables, self.group_host, trained_groups(self.config), st.device, self._chunks)
+
+    def set_step_hyper(self):
+        """Advances num_updates and writes this update's 1 - decay (float32 of the double difference) to device memory."""
+        d = ema_step_decay(self.config.ema_decay, bool(getattr(self.config, "ema_warmup", False)), self.num_updates)
+        if self.hyper is None:
+            self.prepare()
+        self.last_decay = d
+        self.num_updates += 1
+        hip.call("detr_hip_set_floats8_f32", self.hyper.data_ptr(), float(np.float32(1.0 - d)), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+    def apply(self, hyper_ready=False):
+        """One update of the shadow from the current weights (one launch; none when no trained group has a tensor)."""
+        if not hyper_ready:
+            self.set_step_hyper()
+        ct, cs, n = self.prepare()
+        if n == 0:
+            return
+        st = self.store
+        hip.call("detr_hip_ema_f32", st.ema.data_ptr(), st.flat.data_ptr(), ct.data_ptr(), cs.data_ptr(), self.seg_end.data_ptr(),
+                 self.hyper.data_ptr(), n, CHUNK)
+
+
+def weight_ema(optimizers, config):
+    """The WeightEMA of this optimiser dict (built when config.ema_decay is first found set, or by a state that carries one)."""
+    ema = optimizers.get("_ema")
+    if ema is None or ema.config is not config:
+        ema = optimizers["_ema"] = WeightEMA(optimizers["_store"], config, optimizers.get("_nlayers", getattr(config, "nlayers", [])))
+    return ema
+
+
+class ema_weights:
+    """`with ema_weights(model):` -- the model computes with the AVERAGED weights inside the scope (evaluation, save_weights).
+    Entry is one detr_hip_exchange_f32 launch over [0, total) of store.flat and store.ema followed by store.on_change() (the
+    frozen BN is refolded, the bf16 shadow and the evaluation graph go stale); exit does the same again.  The exchange is
+    exact, so training after the scope continues bit-identically.  The evaluation graph is keyed on the weights version:
+    every scope re-records it once (and the first evaluation after the scope once more).
+    Inside the scope aggregate_grad_and_apply, GraphedTrainStep.__call__, optimizer_state / load_optimizer_state, load_weights
+    and a nested scope raise RuntimeError.  Without a shadow: ValueError."""
+
+    def __init__(self, model):
+        self.store = model.engine.P if hasattr(model, "engine") else model
+
+    def _swap(self):
+        st = self.store
+        hip.call("detr_hip_exchange_f32", st.flat.data_ptr(), st.ema.data_ptr(), st.total)
+        if st.on_change is not None:
+            st.on_change()
+
+    def __enter__(self):
+        st = self.store
+        if getattr(st, "ema", None) is None:
+            raise ValueError("ema_weights: this model has no averaged weights (config.ema_decay was never set)")
+        _in_ema_scope(st, "ema_weights (nested)")
+        self._swap()
+        st.ema_swapped = True
+        return self
+
+    def __exit__(self, *exc):
+        self.store.ema_swapped = False
+        self._swap()
+        return False
+
+
 def setup_optimizers(model, config):
     """optimizers.py:67-107: returns the dict the training loop threads through."""
     store = model.engine.P
@@ -237,6 +369,8 @@ def setup_optimizers(model, config):
     out["_store"] = store
     out["_engine"] = model.engine
     out["_nlayers"] = list(config.nlayers)
+    if ema_active(config):              # the shadow starts as a copy of the weights the optimisers were set up on
+        weight_ema(out, config).prepare()
     return out
 
 
@@ -273,15 +407,20 @@ def aggregate_grad_and_apply(name, optimizers, gradients, step, config):
     """optimizers.py:137-163: zero the accumulator at step % agg == 0, add this step's gradient,
     apply at (step+1) % agg == 0; skipped when config.train_<name> is falsy.
     With config.global_clipnorm set, a call only accumulates; the call of the LAST trained group of GROUPS at an apply
-    step updates all trained groups at once (JointAdam), clipped by the norm of their whole (accumulated) gradient."""
+    step updates all trained groups at once (JointAdam), clipped by the norm of their whole (accumulated) gradient.
+    With config.ema_decay set, the call of the last trained group at an apply step ends with the ONE launch that averages
+    the weights of all trained groups into store.ema (WeightEMA): in both clip modes, never at a step that only accumulates."""
     gradient_aggregate = None
     if config.target_batch is not None:
         gradient_aggregate = int(config.target_batch // config.batch_size)
     if not getattr(config, f"train_{name}"):
         return
     store = optimizers["_store"]
+    _in_ema_scope(store, "aggregate_grad_and_apply")
     opt = optimizers[f"{name}_optimizer"]
     gname = f"{name}_gradients"
+    if ema_active(config):              # (the shadow starts as a copy of the weights BEFORE the first averaged update)
+        weight_ema(optimizers, config).prepare()
     if clip_mode(config) == "joint":
         joint = joint_optimizer(optimizers, config)
         last = name == trained_groups(config)[-1]
@@ -289,7 +428,7 @@ def aggregate_grad_and_apply(name, optimizers, gradients, step, config):
             optimizers[gname] = store.grad
             if last:
                 joint.apply(store.grad)
-                model_dirty(optimizers)
+                applied(name, optimizers, config)
             return
         acc = optimizers[gname] = joint.accumulator(optimizers)
         for a, b in joint.runs[opt.group_id]:           # only this group's slices of the shared accumulator
@@ -298,12 +437,12 @@ def aggregate_grad_and_apply(name, optimizers, gradients, step, config):
             hip.call("detr_hip_axpy_f32", acc.data_ptr() + 4 * a, store.grad.data_ptr() + 4 * a, c_float(1.0), b - a)
         if last and (step + 1) % gradient_aggregate == 0:
             joint.apply(acc)
-            model_dirty(optimizers)
+            applied(name, optimizers, config)
         return
     if gradient_aggregate is None or gradient_aggregate <= 1:
         optimizers[gname] = store.grad
         opt.apply_gradients(store.grad)
-        model_dirty(optimizers)
+        applied(name, optimizers, config)
         return
     acc = optimizers.get(gname)
     if not isinstance(acc, torch.Tensor) or acc is store.grad or acc is optimizers.get("_joint_gradients"):
@@ -316,7 +455,15 @@ def aggregate_grad_and_apply(name, optimizers, gradients, step, config):
         hip.call("detr_hip_axpy_f32", acc.data_ptr() + 4 * o, store.grad.data_ptr() + 4 * o, c_float(1.0), cnt)
     if (step + 1) % gradient_aggregate == 0:
         opt.apply_gradients(acc)
-        model_dirty(optimizers)
+        applied(name, optimizers, config)
+
+
+def applied(name, optimizers, config):
+    """After the update of group `name` at an apply step: the derived weight copies are stale, and behind the LAST trained
+    group the weight average takes its one update."""
+    model_dirty(optimizers)
+    if ema_active(config) and name == trained_groups(config)[-1]:
+        weight_ema(optimizers, config).apply()
 
 
 def model_dirty(optimizers):
@@ -329,8 +476,11 @@ def model_dirty(optimizers):
 def optimizer_state(optimizers):
     """Everything a stopped run needs besides the weights, as NumPy arrays: the Adam moments by parameter name
     (`m/<name>`, `v/<name>`), each group's step count (`iterations/<group>`), the gradient accumulators that exist
-    (`accum/<name>`, target_batch > batch_size) and the engine's dropout step counter (`engine/step_no`)."""
+    (`accum/<name>`, target_batch > batch_size) and the engine's dropout step counter (`engine/step_no`).  When the weight
+    average exists (config.ema_decay was set: store.ema), also `ema/<name>` per parameter and `ema/num_updates`; without it
+    the keys are exactly the ones above.  Under data parallelism every rank holds the same average: rank 0's state suffices."""
     store = optimizers["_store"]
+    _in_ema_scope(store, "optimizer_state")
     m, v = store.adam_m.cpu().numpy(), store.adam_v.cpu().numpy()
     out = {}
     for k, (o, n) in store.offsets.items():
@@ -348,6 +498,11 @@ def optimizer_state(optimizers):
     eng = optimizers.get("_engine")
     if eng is not None:
         out["engine/step_no"] = np.asarray(eng._step_no, dtype=np.int64)
+    if getattr(store, "ema", None) is not None:
+        e = store.ema.cpu().numpy()
+        for k, (o, n) in store.offsets.items():
+            out[f"ema/{k}"] = e[o:o + n].reshape(store.shapes[k]).copy()
+        out["ema/num_updates"] = np.asarray(store.ema_num_updates, dtype=np.int64)
     return out
 
 
@@ -355,16 +510,25 @@ def load_optimizer_state(optimizers, state):
     """Restores what optimizer_state returned.  Every name and shape is checked BEFORE the first copy: a state of another
     model raises ValueError and leaves the optimisers as they were.  The moments are overwritten in place and the step
     counts / the dropout counter reach the device with the next step's hyper-parameter writes, so a recorded training
-    graph stays valid."""
+    graph stays valid.
+    The weight average: `ema/*` keys restore store.ema in place (and create it when there is none) with `ema/num_updates`; a
+    state WITHOUT them loaded where a shadow exists resets the shadow to the current weights and num_updates to 0."""
     store = optimizers["_store"]
+    _in_ema_scope(store, "load_optimizer_state")
     problems = []
     known = set(store.shapes)
     for key in state:
         kind, _, k = key.partition("/")
         if kind in ("m", "v", "accum") and k not in known:
             problems.append(f"{key}: no such parameter")
-    staged = {"m": np.zeros(store.total, np.float32), "v": np.zeros(store.total, np.float32)}
-    for kind in ("m", "v"):
+        if kind == "ema" and k != "num_updates" and k not in known:
+            problems.append(f"{key}: no such parameter")
+    has_ema = any(key.startswith("ema/") for key in state)
+    kinds = ("m", "v", "ema") if has_ema else ("m", "v")
+    staged = {kind: np.zeros(store.total, np.float32) for kind in kinds}
+    if has_ema and "ema/num_updates" not in state:
+        problems.append("ema/num_updates: missing")
+    for kind in kinds:
         for k, (o, n) in store.offsets.items():
             if f"{kind}/{k}" not in state:
                 problems.append(f"{kind}/{k}: missing")
@@ -399,6 +563,13 @@ def load_optimizer_state(optimizers, state):
                          + (f"; ... ({len(problems)} in all)" if len(problems) > 8 else ""))
     store.adam_m.copy_(torch.from_numpy(staged["m"]))
     store.adam_v.copy_(torch.from_numpy(staged["v"]))
+    if has_ema:
+        if store.ema is None:
+            store.ema = torch.empty_like(store.flat)
+        store.ema.copy_(torch.from_numpy(staged["ema"]))
+        store.ema_num_updates = int(np.asarray(state["ema/num_updates"]))
+    elif getattr(store, "ema", None) is not None:
+        store.reset_ema()
     optimizers.pop("_joint_gradients", None)
     for name in GROUPS:
         optimizers[f"{name}_optimizer"].iterations = int(np.asarray(state[f"iterations/{name}"]))

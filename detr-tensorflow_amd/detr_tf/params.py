@@ -180,6 +180,9 @@ class ParamStore:
         self.gviews = {k: self.grad[o:o + n].view(self.shapes[k]) for k, (o, n) in self.offsets.items()}
         self.flat16, self.views16 = None, None      # bf16 shadow of `flat` (bf16 compute mode; refreshed by the engine)
         self.on_change = None            # called after every mutation of the parameters (the engine's weights-version bump)
+        # exponential moving average of `flat` (optimizers.WeightEMA; None until config.ema_decay is first set), the number of
+        # updates it has taken, and whether it is currently swapped into `flat` (optimizers.ema_weights)
+        self.ema, self.ema_num_updates, self.ema_swapped = None, 0, False
         # frozen BN raw vectors [4, C] per layer: weight, bias, running_mean, running_var
         self.bn_raw = {p: torch.zeros(4, c, dtype=torch.float32, device=device) for p, c in self.bn.items()}
         for p in self.bn_raw:
@@ -222,7 +225,11 @@ class ParamStore:
             self.bn_raw[p].copy_(torch.from_numpy(raw))
 
     def load_dict(self, params):
-        """params: name -> array, names per SURVEY.md A.6 (BN vectors as <prefix>/{weight,bias,running_mean,running_var})."""
+        """params: name -> array, names per SURVEY.md A.6 (BN vectors as <prefix>/{weight,bias,running_mean,running_var}).
+        A store that keeps a weight average (`ema`) restarts it from the loaded weights: shadow = weights, num_updates = 0
+        (an average across a reload would mix two unrelated models).  Refused inside optimizers.ema_weights(model)."""
+        if self.ema_swapped:
+            raise RuntimeError("load_weights: not inside ema_weights(model) -- the parameter buffer holds the averaged weights there")
         missing = []
         # every shape is checked BEFORE the first copy: a mismatch must not leave the store half overwritten (no BN refold, no
         # weights-version bump -> stale recorded graphs / bf16 shadow / folded kernels)
@@ -247,20 +254,38 @@ class ParamStore:
         try:
             for dst, v in staged:
                 dst.copy_(v)
+            self.reset_ema()
         finally:
             if self.on_change is not None:
                 self.on_change()
         return missing
 
-    def state_dict(self):
-        out = {k: v.detach().cpu().numpy().copy() for k, v in self.views.items()}
+    def reset_ema(self):
+        """The weight average (if there is one) restarts from the current weights."""
+        if self.ema is not None:
+            self.ema.copy_(self.flat)
+            self.ema_num_updates = 0
+
+    def state_dict(self, weights="model"):
+        """weights="ema": the averaged tensors under the normal parameter names (with the frozen-BN vectors, which have no
+        average: they are constants), i.e. a file a plain load() turns into the deployable averaged model."""
+        if weights not in ("model", "ema"):
+            raise ValueError(f"weights must be 'model' or 'ema', got {weights!r}")
+        if weights == "ema":
+            if self.ema is None:
+                raise ValueError("weights='ema': this model has no averaged weights (config.ema_decay was never set)")
+            # inside ema_weights(model) the two buffers are exchanged: the average is then the one in `flat`
+            host = (self.flat if self.ema_swapped else self.ema).cpu().numpy()
+            out = {k: host[o:o + n].reshape(self.shapes[k]).copy() for k, (o, n) in self.offsets.items()}
+        else:
+            out = {k: v.detach().cpu().numpy().copy() for k, v in self.views.items()}
         for p in self.bn:
             for i, leaf in enumerate(self.bn_leaves):
                 out[f"{p}/{leaf}"] = self.bn_raw[p][i].cpu().numpy().copy()
         return out
 
-    def save(self, path):
-        np.savez(path, **self.state_dict())
+    def save(self, path, weights="model"):
+        np.savez(path, **self.state_dict(weights))
 
     def load(self, path):
         with np.load(path) as z:

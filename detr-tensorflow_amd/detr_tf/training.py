@@ -6,6 +6,7 @@ synchronisation and no allocation, so `fit` can record it ONCE as a hipGraph (`G
 every further batch of the same shape: whatever changes between steps -- the batch, the dropout step seed, the Adam step
 sizes -- lives in device memory that is refreshed before each replay.
 """
+import contextlib
 import gc
 import os
 import time
@@ -17,7 +18,8 @@ from . import _hip as hip
 from .engine import downsample_mask_nearest, feature_size
 from .loss import hungarian_matching as _matching
 from .loss.loss import criterion_of, get_losses, log_from_losses
-from .optimizers import GROUPS, aggregate_grad_and_apply, clip_mode, decay_active, gather_gradient, joint_optimizer
+from .optimizers import (GROUPS, aggregate_grad_and_apply, clip_mode, decay_active, ema_active, ema_weights, gather_gradient,
+                         joint_optimizer, weight_ema)
 
 PRINT_EVERY_TRAIN = 100         # training.py:57
 PRINT_EVERY_VAL = 10            # training.py:80
@@ -125,7 +127,7 @@ class GraphedTrainStep:
     The first `eager_steps` calls run eagerly (they also allocate every buffer of the static memory plan); the next call
     records the launch sequence -- forward, set loss, backward into one graph (cut at the data-parallel exchange points
     when training on several GPUs), clip + Adam of the three groups (or the joint AdamW sequence of config.global_clipnorm) into
-    another -- and from then on a replayed step is:
+    another, followed by the weight average's one launch when config.ema_decay is set -- and from then on a replayed step is:
     copy the batch into the static input buffers, write the new dropout seed / Adam step sizes to device memory, replay.
     A new batch shape (or set of trained groups, or set criterion: its values are baked into the recorded launches), and any re-allocation of an engine buffer since the recording (a forward
     of another shape in between: engine.buf_generation), drop the recording: one eager step, then a new one.  Gradient
@@ -157,7 +159,7 @@ class GraphedTrainStep:
         images, masks = split_images(images)
         return (tuple(images.shape), masks is not None, tuple(t_bbox.shape), bool(c.train_backbone), bool(c.train_transformers),
                 bool(c.train_nlayers), int(c.background_class), self.model.engine.compute, float(self.model.engine.dropout_p),
-                bool(getattr(c, "check_matching", False)), clip_mode(c), decay_active(c), tuple(self.model.engine.dilate),      # (other optimiser launches: re-record)
+                bool(getattr(c, "check_matching", False)), clip_mode(c), decay_active(c), ema_active(c), tuple(self.model.engine.dilate),      # (other optimiser launches: re-record)
                 criterion_of(c))         # the criterion's values are launch ARGUMENTS of the set-loss kernels: a change re-records
 
     def _capture(self, images, t_bbox, t_class):
@@ -174,6 +176,8 @@ class GraphedTrainStep:
         dp = model.dp
         if clip_mode(cfg) == "joint":           # its tables are device tensors: built before the recording, not inside it
             joint_optimizer(opts, cfg).prepare()
+        if ema_active(cfg):                     # the shadow, its hyper block and chunk table: likewise
+            weight_ema(opts, cfg).prepare()
         seg = _Segments()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
@@ -212,6 +216,8 @@ class GraphedTrainStep:
                             opts[f"{name}_optimizer"].apply_gradients(store.grad, hyper_ready=True)
                 if joint:                   # config.global_clipnorm: all trained groups in one sequence (optimizers.JointAdam)
                     joint_optimizer(opts, cfg).apply(store.grad, hyper_ready=True)
+                if ema_active(cfg):         # config.ema_decay: one launch behind the last update (optimizers.WeightEMA)
+                    weight_ema(opts, cfg).apply(hyper_ready=True)
                 app.end()
         finally:
             if prev_hooks is not None:
@@ -263,6 +269,8 @@ class GraphedTrainStep:
                 for name in GROUPS:
                     if getattr(cfg, f"train_{name}"):
                         self.optimizers[f"{name}_optimizer"].set_step_hyper()
+            if ema_active(cfg):
+                weight_ema(self.optimizers, cfg).set_step_hyper()
             self.step_graph.replay()
             if model.dp is not None:
                 model.dp.finish()
@@ -305,6 +313,8 @@ class GraphedTrainStep:
     def __call__(self, images, t_bbox, t_class, epoch_step):
         cfg, model = self.config, self.model
         eng = model.engine
+        if getattr(eng.P, "ema_swapped", False):
+            raise RuntimeError("GraphedTrainStep: not inside ema_weights(model) -- the parameter buffer holds the averaged weights there")
         self.total_calls += 1
         key = self._signature(images, t_bbox, t_class)
         stale = self.step_graph is not None and self._gen != eng.buf_generation
@@ -422,13 +432,17 @@ def fit(model, train_dt, optimizers, config, epoch_nb, class_names):
         config.global_step += 1
 
 
-def eval(model, valid_dt, config, class_name, evaluation_step=200):
+def eval(model, valid_dt, config, class_name, evaluation_step=200, *, weights="model"):
     """Evaluate on the validation set (training.py:68-87): forward with training=False + set loss for at most
-    `evaluation_step` batches, console line every 10."""
+    `evaluation_step` batches, console line every 10.  weights="ema": with the averaged weights of config.ema_decay
+    (inside optimizers.ema_weights(model); the trained weights are back, bit for bit, when this returns)."""
+    if weights not in ("model", "ema"):
+        raise ValueError(f"eval: weights must be 'model' or 'ema', got {weights!r}")
     watch = _Stopwatch(reset=False)
-    for val_step, (images, t_bbox, t_class) in enumerate(valid_dt):
-        m_outputs, total_loss, log = run_val_step(model, images, t_bbox, t_class, config)
-        if val_step % PRINT_EVERY_VAL == 0:
-            print(_console(f"Validation step: [{val_step}]", log, watch.lap()))
-        if val_step + 1 >= evaluation_step:
-            break
+    with (ema_weights(model) if weights == "ema" else contextlib.nullcontext()):
+        for val_step, (images, t_bbox, t_class) in enumerate(valid_dt):
+            m_outputs, total_loss, log = run_val_step(model, images, t_bbox, t_class, config)
+            if val_step % PRINT_EVERY_VAL == 0:
+                print(_console(f"Validation step: [{val_step}]", log, watch.lap()))
+            if val_step + 1 >= evaluation_step:
+                break

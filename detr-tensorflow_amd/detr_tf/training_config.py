@@ -46,6 +46,8 @@ _FLAGS = (
     ("set_cost_class", float, 1.0, False), ("set_cost_bbox", float, 5.0, False), ("set_cost_giou", float, 2.0, False),
     ("class_loss_coef", float, 1.0, False), ("bbox_loss_coef", float, 5.0, False), ("giou_loss_coef", float, 2.0, False),
     ("eos_coef", float, 0.1, False), ("num_boxes_min_one", None, False, True),
+    # not in the reference: an exponential moving average of the weights kept on the device (optimizers.WeightEMA)
+    ("ema_decay", float, None, False), ("ema_warmup", None, False, True),
 )
 
 
@@ -76,6 +78,11 @@ _DEFAULTS = dict(
     # targets' classes, rounded to multiples of 1/64 in [0, 16].  At these defaults the loss runs the reference's compiled-in criterion.
     set_cost_class=1.0, set_cost_bbox=5.0, set_cost_giou=2.0, class_loss_coef=1.0, bbox_loss_coef=5.0, giou_loss_coef=2.0,
     eos_coef=0.1, num_boxes_min_one=False, class_weights=None,
+    # Weight average (tf.train.ExponentialMovingAverage), read at EVERY apply step.  ema_decay = d, 0 <= d < 1: after the update of
+    # the trained groups, shadow -= (1 - d) * (shadow - weights) on the device; None = no average (nothing allocated, nothing
+    # launched; setting it back to None pauses the updates and keeps the shadow).  ema_warmup: this step's decay is
+    # min(d, (1 + n) / (10 + n)), n = updates done so far (TensorFlow's num_updates rule).
+    ema_decay=None, ema_warmup=False,
 )
 
 

@@ -672,6 +672,22 @@ int detr_hip_adamw_f32(float *param, const float *g, float *m, float *v, const i
                        void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights (opt-in; tf.train.ExponentialMovingAverage).  `shadow` is a second flat fp32
+ * buffer laid out like `param`; the chunk tables are those of detr_hip_adamw_f32 (one table over all trained groups).
+ *   hyper (device, float[>= 1]): hyper[0] = omd = 1 - decay of this step, read by the kernel (stream ordered after a
+ *   detr_hip_set_floats8_f32 / detr_hip_set_floats16_f32 write, so a replayed launch sees the new value)
+ *   per element of the listed chunks, TensorFlow's form, every operation rounded on its own (no fused multiply-add):
+ *       t = shadow - param;  t = omd * t;  shadow = shadow - t
+ * Reads param and shadow, writes shadow; elements no chunk lists are not touched.  Null operands, shadow == param and
+ * n_chunks <= 0 or chunk <= 0 are rejected before any launch.
+ * detr_hip_exchange_f32 swaps a[0, n) and b[0, n) element for element (the averaged weights in, the trained ones out, and
+ * back: exact in both directions).  a == b and overlapping ranges are rejected; n may exceed 2^31 bytes.
+ * ------------------------------------------------------------------------------------------- */
+int detr_hip_ema_f32(float *shadow, const float *param, const int32_t *chunk_tensor, const int64_t *chunk_start,
+                     const int64_t *seg_end, const float *hyper, int32_t n_chunks, int32_t chunk, void *stream);
+int detr_hip_exchange_f32(float *a, float *b, int64_t n, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scratch sizing: the number of bytes `workspace` must hold for the call described by the descriptor to take its
  * DETERMINISTIC split-reduction path (0 = the call needs no scratch; negative = malformed descriptor).  Pointers inside the
  * descriptor are not dereferenced; only shapes, split counts, dtypes and (gemm) whether rowsum_a is set are read.  The same
