@@ -120,6 +120,12 @@ class DetectDesc(Structure):
 TILE_MAX_CAND = 2048                                                           # DETR_TILE_MAX_CAND
 TILE_BAD = {1: f"an image with more than {TILE_MAX_CAND} candidates (the cap of detr_hip_tile_merge: raise score_threshold or use fewer tiles)",
             2: "a tile_start entry that is not monotone inside [0, N]"}          # DETR_TILE_OVER_CAP, DETR_TILE_BAD_START
+FUSE_PARAMS, FUSE_MAX_CLUSTERS, FUSE_OVER_CLUSTERS = 6, 1024, 4                 # DETR_FUSE_PARAMS / _MAX_CLUSTERS / _OVER_CLUSTERS
+FUSE_METHODS = {"nms": 0, "soft_nms": 1, "soft_nms_gaussian": 2, "wbf": 3}      # fuse[0] of detr_hip_fuse_views
+# the status bits of detr_hip_fuse_views: detr_hip_tile_merge's (the cap is shared) plus the cluster cap of weighted box fusion
+FUSE_BAD = {**TILE_BAD,
+            FUSE_OVER_CLUSTERS: f"an image with more than {FUSE_MAX_CLUSTERS} clusters (the cluster cap of weighted box fusion: raise "
+                                "score_threshold or lower the threshold)"}
 
 
 class TileMergeDesc(Structure):
@@ -322,6 +328,7 @@ _SIGNATURES = {
     "detr_hip_track": [POINTER(TrackDesc), c_void_p],
     "detr_hip_track_embed": [POINTER(TrackEmbedDesc), c_void_p],
     "detr_hip_track_motion": [POINTER(TrackMotionDesc), c_void_p],
+    "detr_hip_fuse_views": [POINTER(TileMergeDesc), c_void_p, POINTER(ctypes.c_double * FUSE_PARAMS), c_void_p, c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {

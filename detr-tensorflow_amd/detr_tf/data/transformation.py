@@ -255,6 +255,35 @@ def tile_records(h0, w0, rows, cols, overlap=0.2, short=800, max_size=MULTISCALE
     return records
 
 
+def view_records(h0, w0, scales=(800,), max_size=MULTISCALE_MAX_SIZE, flip=False, interp=LINEAR, tiles=None, overlap=0.2, include_full=True):
+    """The records of test-time augmentation on an h0 x w0 image: for every shortest side s of `scales`, in order, the records of
+    that scale -- eval_record(h0, w0, s, ...), or with tiles=(rows, cols) tile_records(h0, w0, rows, cols, overlap, s, ...) --, and
+    with `flip` the same list once more with flip=True.  A flipped record's window is a window of the MIRRORED image (the kernel's
+    rule: flip, then window), so the windows of the second half equal those of the first.  Integer arithmetic only."""
+    h0, w0 = int(h0), int(w0)
+    if h0 < 1 or w0 < 1:
+        raise ValueError(f"view_records: bad image size {h0} x {w0}")
+    try:
+        scales = tuple(scales)
+    except TypeError:
+        raise ValueError(f"view_records: scales={scales!r} must be a non-empty sequence of positive integers") from None
+    if not scales or any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) or int(s) < 1 for s in scales):
+        raise ValueError(f"view_records: scales={scales!r} must be a non-empty sequence of positive integers")
+    if max_size is not None and int(max_size) < 1:
+        raise ValueError(f"view_records: max_size={max_size} must be positive or None")
+    if tiles is not None and len(tuple(tiles)) != 2:
+        raise ValueError(f"view_records: tiles={tiles!r} must be (rows, cols) or None")
+    records = []
+    for s in scales:
+        if tiles is None:
+            records.append(eval_record(h0, w0, int(s), max_size, interp))
+        else:
+            records += tile_records(h0, w0, tiles[0], tiles[1], overlap, int(s), max_size, interp, include_full)
+    if flip:
+        records += [r._replace(flip=True) for r in records]
+    return records
+
+
 def check_padded_record(t, canvas=None):
     """Host validation of one padded record (the kernel also clamps, but a wrong record is a caller's bug)."""
     if t.h0 < 1 or t.w0 < 1:

@@ -15,6 +15,10 @@ one launch of `detr_hip_tile_merge` (csrc/tile_merge.hip) maps every window's bo
 the overlaps create with a class-wise greedy NMS.  `Detector(tiles=(rows, cols))` runs that chain; `Detector(nms_threshold=...)`
 alone puts the same NMS behind the single-pass outputs.
 
+`fuse_views` is the last step of TEST-TIME AUGMENTATION (the model run on the mirrored image and / or at several shortest sides):
+one launch of `detr_hip_fuse_views` (csrc/fuse_views.hip) maps every view's boxes back -- a flipped view's through the mirror -- and
+combines them by hard NMS, soft-NMS (linear or Gaussian) or weighted box fusion.  `Detector(flip=, scales=, merge=)` runs that chain.
+
 `draw_detections` / `numpy_bbox_to_image` (detr_tf/overlay.py; reference inference.py:10-65) draw boxes, labels and an attention heat map
 onto the frames in one call of `detr_hip_overlay` (csrc/overlay.hip); `Detector.draw` feeds it the detector's own frames and maps.
 
@@ -24,7 +28,7 @@ onto the frames in one call of `detr_hip_overlay` (csrc/overlay.hip); `Detector.
 device from the frames themselves, moves the tracks with the camera before they are associated.
 """
 import math
-from ctypes import byref
+from ctypes import byref, c_double
 from typing import NamedTuple
 
 import numpy as np
@@ -243,6 +247,101 @@ def merge_tiles(m_outputs: dict, tile_start, windows, sizes, background_class, *
     if status:
         raise ValueError("merge_tiles: " + "; ".join(text for bit, text in hip.TILE_BAD.items() if status & bit))
     return [TiledDetections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k], out_t[b, :k]) for b, k in enumerate(counts)]
+
+
+class FusedDetections(NamedTuple):
+    """The fused detections of ONE image seen through several views, best first: TiledDetections' five fields -- tile is the VIEW
+    (its index within the image, in view_records' order) -- plus members [k] int32, the number of candidates the box was fused from
+    (1 except with method "wbf", where (tile, query) name the cluster's first, i.e. best-scoring, member)."""
+    boxes: torch.Tensor
+    labels: torch.Tensor
+    scores: torch.Tensor
+    query: torch.Tensor
+    tile: torch.Tensor
+    members: torch.Tensor
+
+
+FUSE_THRESHOLDS = {"nms": 0.5, "soft_nms": 0.5, "soft_nms_gaussian": 0.5, "wbf": 0.55}
+
+
+def _check_fuse_args(method, threshold, match, edge_margin, max_detections, sigma, score_min, expected_views, min_members):
+    """-> the fuse[] block of detr_hip_fuse_views and the threshold (the method's default for None)."""
+    if method not in hip.FUSE_METHODS:
+        raise ValueError(f"fuse_views: method must be one of {tuple(hip.FUSE_METHODS)}, got {method!r}")
+    if threshold is None:
+        threshold = FUSE_THRESHOLDS[method]
+    try:
+        _check_merge_args(threshold, match, edge_margin, max_detections)
+    except ValueError as e:
+        raise ValueError(str(e).replace("merge_tiles", "fuse_views").replace("nms_threshold", "threshold")) from None
+    if not (math.isfinite(float(sigma)) and float(sigma) > 0.0):
+        raise ValueError(f"fuse_views: sigma={sigma} must be finite and > 0")
+    if not (math.isfinite(float(score_min)) and float(score_min) >= 0.0):
+        raise ValueError(f"fuse_views: score_min={score_min} must be finite and >= 0")
+    if expected_views is not None and (float(expected_views) != int(expected_views) or int(expected_views) < 1):
+        raise ValueError(f"fuse_views: expected_views={expected_views} must be None or an integer >= 1")
+    if float(min_members) != int(min_members) or int(min_members) < 1:
+        raise ValueError(f"fuse_views: min_members={min_members} must be an integer >= 1")
+    block = (hip.FUSE_METHODS[method], float(sigma), float(score_min), 0 if expected_views is None else int(expected_views), int(min_members), 0)
+    return block, float(threshold)
+
+
+def fuse_views(m_outputs: dict, view_start, windows, flips, sizes, background_class, *, method="wbf", threshold=None, score_threshold=0.0,
+               max_detections=100, bbox_format="xyxy", clip=True, match="iou", class_agnostic=False, edge_margin=0.0, sigma=0.5,
+               score_min=0.001, expected_views=None, min_members=1):
+    """[FusedDetections] for every image of a batch seen through several VIEWS (test-time augmentation: mirrored, at several shortest
+    sides, whole or tiled -- transformation.view_records).  m_outputs, view_start, windows and sizes are merge_tiles' m_outputs,
+    tile_start, windows and sizes with a view for a tile; flips [N] says which views saw the MIRRORED image (a flipped record's window
+    is a window of the mirrored image).  Candidates, mapping to image pixels and the edge rule are merge_tiles'; a flipped view's box is
+    mapped in its own frame and then mirrored back, (x0, x1) <- (W - x1, W - x0).  Then, per image, `method`:
+      "nms": merge_tiles' greedy NMS (with no flipped view and a format other than "xy_center", merge_tiles' bits);
+      "soft_nms" / "soft_nms_gaussian" (Bodla et al. 2017): the best remaining box is emitted with its CURRENT score, then the scores of
+        the remaining boxes of its label (any label with class_agnostic) that match it are decayed -- by (1 - m) where m > threshold, or
+        by exp(-m * m / sigma) for every m -- and a box whose score is below score_min is removed;
+      "wbf" (weighted box fusion, Solovyev et al. 2021): the candidates are walked by descending score; each joins the cluster of its
+        label whose fused box matches it best if by more than `threshold`, else founds one; a cluster's box is the score-weighted mean of
+        its members' corners, its score their mean score, times min(members, expected_views) / expected_views when expected_views is
+        given (a box only some views found is marked down); clusters of fewer than min_members boxes are dropped.
+    `threshold` (strict; None: 0.5, or 0.55 for "wbf") is the match threshold of every method; match, class_agnostic, edge_margin,
+    clip and bbox_format as in merge_tiles, except that "xy_center" is derived from the final corners.  The first max_detections
+    results are returned, best first.  The defaults are the published methods' conventions (soft-NMS: sigma 0.5, minimum score 0.001;
+    WBF: 0.55) carried over, UNTUNED for DETR: there are no trained weights here to tune them on.  One launch of detr_hip_fuse_views
+    and ONE host synchronisation (counts + status).  An image with more than _hip.TILE_MAX_CAND candidates, or with "wbf" more than
+    _hip.FUSE_MAX_CLUSTERS clusters, raises ValueError.  CUDA inputs only."""
+    _check_model_outputs("fuse_views", "N", m_outputs["pred_logits"], m_outputs["pred_boxes"])
+    _check_detect_args(bbox_format, score_threshold, None)
+    block, threshold = _check_fuse_args(method, threshold, match, edge_margin, max_detections, sigma, score_min, expected_views, min_members)
+    logits, boxes = _model_outputs("fuse_views", "fusion", m_outputs["pred_logits"], m_outputs["pred_boxes"])
+    N, K = logits.shape[0], int(max_detections)
+    dev = logits.device
+    start_h = np.ascontiguousarray(np.asarray(view_start.cpu() if isinstance(view_start, torch.Tensor) else view_start), np.int32)
+    if start_h.ndim != 1 or start_h.shape[0] < 2:
+        raise RuntimeError(f"fuse_views: view_start must be [B + 1] offsets, got shape {tuple(start_h.shape)}")
+    B = start_h.shape[0] - 1
+    sizes = torch.as_tensor(sizes).to(device=dev, dtype=torch.int32).contiguous()
+    windows = torch.as_tensor(windows).to(device=dev, dtype=torch.int32).contiguous()
+    flips = torch.as_tensor(np.asarray(flips.cpu() if isinstance(flips, torch.Tensor) else flips).astype(bool).astype(np.int32)).to(dev)
+    if tuple(sizes.shape) != (B, 2) or tuple(windows.shape) != (N, 4) or tuple(flips.shape) != (N,):
+        raise RuntimeError(f"fuse_views: sizes must be [B, 2], windows [N, 4] and flips [N], got {tuple(sizes.shape)}, {tuple(windows.shape)} "
+                           f"and {tuple(flips.shape)} for B={B}, N={N}")
+    start_d = torch.from_numpy(start_h).to(dev)
+    out_b, out_l, out_s, out_q, out_t, out_m = _ranked_rows(B, K, dev, 3)
+    tail = torch.zeros(B + 1, dtype=torch.int32, device=dev)              # counts [B], then the status word
+    d = hip.TileMergeDesc()
+    _fill_model_outputs(d, logits, boxes, background_class)
+    d.B, d.N, d.score_threshold = B, N, float(score_threshold)
+    d.tile_start, d.tile_start_host, d.windows, d.sizes = start_d.data_ptr(), start_h.ctypes.data, windows.data_ptr(), sizes.data_ptr()
+    d.max_detections, d.bbox_format, d.clip = K, DETECT_FORMATS[bbox_format], int(bool(clip))
+    d.match, d.class_agnostic, d.edge_margin, d.nms_threshold = MATCH_MODES[match], int(bool(class_agnostic)), float(edge_margin), threshold
+    d.out_boxes, d.out_labels, d.out_scores, d.out_query, d.out_tile = (out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), out_q.data_ptr(),
+                                                                        out_t.data_ptr())
+    d.counts, d.status = tail.data_ptr(), tail.data_ptr() + 4 * B
+    params = (c_double * hip.FUSE_PARAMS)(*block)
+    hip._check(hip.load().detr_hip_fuse_views(byref(d), flips.data_ptr(), byref(params), out_m.data_ptr(), hip._stream()), "detr_hip_fuse_views")
+    *counts, status = tail.tolist()
+    if status:
+        raise ValueError("fuse_views: " + "; ".join(text for bit, text in hip.FUSE_BAD.items() if status & bit))
+    return [FusedDetections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k], out_t[b, :k], out_m[b, :k]) for b, k in enumerate(counts)]
 
 
 class TrackedDetections(NamedTuple):
@@ -560,7 +659,7 @@ class Tracker:
         They are packed into padded rows (as draw_detections packs them) and go through update_rows.  embeddings: update_rows'; the
         rows are the detections' query, and for a triple, which has none, its k detections take the rows 0..k-1 (and are emitted with
         those as query).  frames: update_rows'."""
-        if isinstance(detections, (Detections, TiledDetections)) or (isinstance(detections, tuple) and len(detections) == 3
+        if isinstance(detections, (Detections, TiledDetections, FusedDetections)) or (isinstance(detections, tuple) and len(detections) == 3
                                                                        and not isinstance(detections[0], (tuple, list))):
             detections = [detections]
         if len(detections) != self.streams:
@@ -600,14 +699,22 @@ class Detector:
     shortest-side rule, the model runs on all tiles of the call (in chunks of at most tile_batch; None: one batch) and ONE
     merge_tiles launch maps the boxes back and removes the duplicates (nms_threshold, default 0.5 here; match, class_agnostic,
     edge_margin: see merge_tiles).  The results are TiledDetections.  nms_threshold without tiles runs the same class-wise NMS behind
-    the single pass (one whole-image window per image).  With neither, the call is the plain path above."""
+    the single pass (one whole-image window per image).  With neither, the call is the plain path above.
+
+    flip=True, scales=(s0, s1, ...) and merge= turn on TEST-TIME AUGMENTATION (resize="shortest_side" only): every image is seen at
+    every shortest side of `scales` (None: shortest_side alone) and, with flip, mirrored as well (transformation.view_records; with
+    tiles, every view is the tiled one), the model runs on all views (in chunks of at most tile_batch) and ONE fuse_views launch
+    maps the boxes back -- mirrored views included -- and combines them by `merge`: "nms", "soft_nms", "soft_nms_gaussian" or "wbf"
+    (sigma, score_min, min_members: see fuse_views; nms_threshold, when given, is the fusion threshold; expected_views is the number of
+    views without tiles, None with them).  The results are FusedDetections.  The cost is one forward pass per view.  With
+    flip=False, scales=None and merge="nms" (the defaults) nothing of this runs."""
 
     RESIZE_MODES = ("shortest_side", "fixed")
 
     def __init__(self, model, config, *, background_class=None, score_threshold=0.7, max_detections=100, bbox_format="xyxy",
                  resize="shortest_side", shortest_side=800, max_size=1333, canvas=None, interpolation="cubic",
                  tiles=None, overlap=0.2, include_full=True, tile_batch=None, nms_threshold=None, match="iou", class_agnostic=False,
-                 edge_margin=0.0):
+                 edge_margin=0.0, flip=False, scales=None, merge="nms", sigma=0.5, score_min=0.001, min_members=1):
         from .data import processing, transformation
         if resize not in self.RESIZE_MODES:
             raise ValueError(f"Detector: resize must be one of {self.RESIZE_MODES}, got {resize!r}")
@@ -626,6 +733,20 @@ class Detector:
         self.bbox_format, self.resize, self.interpolation = bbox_format, resize, interpolation
         self.shortest_side, self.max_size = int(shortest_side), None if max_size is None else int(max_size)
         self.canvas = None if canvas is None else (int(canvas[0]), int(canvas[1]))
+        if merge not in hip.FUSE_METHODS:
+            raise ValueError(f"Detector: merge must be one of {tuple(hip.FUSE_METHODS)}, got {merge!r}")
+        self.flip, self.merge = bool(flip), merge
+        self.scales = None if scales is None else tuple(scales)
+        self.views = self.flip or self.scales is not None or merge != "nms"         # False: every path below is the one it was
+        if self.views:
+            if resize != "shortest_side":
+                raise ValueError(f"Detector: flip / scales / merge need resize='shortest_side', not {resize!r} (every view is resized by the "
+                                 "shortest-side rule)")
+            if tile_batch is not None and int(tile_batch) < 1:
+                raise ValueError(f"Detector: tile_batch={tile_batch} must be positive")
+            transformation.view_records(1, 1, (self.shortest_side,) if self.scales is None else self.scales, self.max_size)    # validates scales
+            _, self.fuse_threshold = _check_fuse_args(merge, nms_threshold, match, edge_margin, max_detections, sigma, score_min, None, min_members)
+        self.sigma, self.score_min, self.min_members = float(sigma), float(score_min), int(min_members)
         if tiles is not None:
             if resize != "shortest_side":
                 raise ValueError(f"Detector: tiles needs resize='shortest_side', not {resize!r} (every window is resized by the shortest-side rule)")
@@ -670,10 +791,36 @@ class Detector:
                            max_detections=self.max_detections, bbox_format=self.bbox_format, nms_threshold=self.nms_threshold,
                            match=self.match, class_agnostic=self.class_agnostic, edge_margin=self.edge_margin)
 
+    def view_records(self, images):
+        """Per image, the PaddedRecords of its views (flip / scales, with tiles the tiles of every view): transformation.view_records."""
+        from .data import transformation as T
+        interp = T.INTERP_NAMES.index(self.interpolation)
+        scales = (self.shortest_side,) if self.scales is None else self.scales
+        return [T.view_records(im.shape[0], im.shape[1], scales, self.max_size, self.flip, interp, self.tiles, self.overlap, self.include_full)
+                for im in images]
+
+    def _viewed(self, srcs, sizes):
+        """Test-time augmentation: one upload per image, the model on chunks of views, one fusion launch."""
+        recs = self.view_records(srcs)
+        images, masks, view_start = self.stage().augmented_tiles(srcs, recs, canvas=self.canvas)
+        windows = np.array([(t.y0, t.x0, t.hc, t.wc) for r in recs for t in r], np.int32)
+        flips = np.array([t.flip for r in recs for t in r], np.int32)
+        # a tile sees only part of the image: rescaling by the number of views would mark every object down
+        expected = None if self.tiles is not None else len(recs[0])
+        return fuse_views(self._run_chunks(images, masks), view_start, windows, flips, sizes, self.background_class, method=self.merge,
+                          threshold=self.fuse_threshold, score_threshold=self.score_threshold, max_detections=self.max_detections,
+                          bbox_format=self.bbox_format, match=self.match, class_agnostic=self.class_agnostic, edge_margin=self.edge_margin,
+                          sigma=self.sigma, score_min=self.score_min, expected_views=expected, min_members=self.min_members)
+
     def _tiled(self, srcs, sizes):
         """Sliced inference: one upload per image, the model on chunks of tiles, one merge launch."""
         recs = self.tile_records(srcs)
         images, masks, tile_start = self.stage().augmented_tiles(srcs, recs, canvas=self.canvas)
+        windows = np.array([(t.y0, t.x0, t.hc, t.wc) for r in recs for t in r], np.int32)
+        return self._merge(self._run_chunks(images, masks), tile_start, windows, sizes)
+
+    def _run_chunks(self, images, masks):
+        """The model on the N staged tiles / views in chunks of at most tile_batch -> pred_logits and pred_boxes of all N."""
         N = images.shape[0]
         step = N if self.tile_batch is None else self.tile_batch
         logits = boxes = None
@@ -684,8 +831,7 @@ class Detector:
                 boxes = torch.empty((N,) + tuple(out["pred_boxes"].shape[1:]), dtype=torch.float32, device=images.device)
             logits[at:at + step] = out["pred_logits"]                  # a replayed graph reuses its output buffers: copy out
             boxes[at:at + step] = out["pred_boxes"]
-        windows = np.array([(t.y0, t.x0, t.hc, t.wc) for r in recs for t in r], np.int32)
-        return self._merge({"pred_logits": logits, "pred_boxes": boxes}, tile_start, windows, sizes)
+        return {"pred_logits": logits, "pred_boxes": boxes}
 
     def _forward(self, srcs, sizes, need_weights=None, return_embeddings=False):
         """The single pass: input stage and model on the frames `srcs` -> (m_outputs, the input's shape)."""
@@ -712,6 +858,13 @@ class Detector:
         if not srcs or any(s.dtype != np.uint8 or s.ndim != 3 or s.shape[-1] != 3 for s in srcs):
             raise TypeError("Detector expects a uint8 image [h, w, 3] or a non-empty list of them")
         sizes = np.array([s.shape[:2] for s in srcs], np.int32)
+        if self.views:
+            if need_weights:
+                raise NotImplementedError("Detector: need_weights with flip / scales / merge: there is one attention map per view and no single "
+                                          "image to overlay it on; call the model on DeviceInputStage.augmented_tiles yourself")
+            detections = self._viewed(srcs, sizes)
+            self._last_frames = self.stage().last_upload
+            return detections[0] if single else detections
         if self.tiles is not None:
             if need_weights:
                 raise NotImplementedError("Detector: need_weights with tiles: there is one attention map per tile and no single image to "
@@ -756,10 +909,10 @@ class Detector:
         appearance = tracker.embed_dim is not None
         if appearance and tracker.embed_dim != 256:
             raise ValueError(f"Detector.track: the model's embeddings have 256 elements, the tracker was built with embed_dim={tracker.embed_dim}")
-        if self.tiles is not None or self.nms_threshold is not None:
+        if self.tiles is not None or self.nms_threshold is not None or self.views:
             if appearance:
-                raise NotImplementedError("Detector.track: tracking by appearance with tiles / nms_threshold: that path keeps no per-tile "
-                                          "embeddings; use a Tracker without embed_dim, or a Detector without tiles and nms_threshold")
+                raise NotImplementedError("Detector.track: tracking by appearance with tiles / nms_threshold / views: that path keeps no per-tile "
+                                          "embeddings; use a Tracker without embed_dim, or a Detector without tiles, nms_threshold and views")
             detections = self(srcs)
             tracked = tracker.update(detections, active, frames=self._last_frames if tracker.motion else None)
         else:
@@ -810,7 +963,7 @@ class Detector:
         results draw like plain ones; maps with tiles stays refused.  Further keywords are draw_detections'."""
         if self.bbox_format != "xyxy":
             raise ValueError(f"Detector.draw: boxes must be 'xyxy' pixels: build the Detector with bbox_format='xyxy', not {self.bbox_format!r}")
-        if maps is not None and self.tiles is not None:
+        if maps is not None and (self.tiles is not None or self.views):
             raise NotImplementedError("Detector.draw: maps with tiles: there is one attention map per tile and no single image to overlay it on")
         if images is None:
             images = self._last_frames
@@ -818,7 +971,7 @@ class Detector:
                 raise ValueError("Detector.draw: images=None draws on the frames of the last call, and there has been none")
         elif isinstance(images, np.ndarray) and images.ndim == 3:
             images = [images]
-        single = isinstance(detections, (Detections, TiledDetections))
+        single = isinstance(detections, (Detections, TiledDetections, FusedDetections))
         dets = [detections] if single else list(detections)
         if maps is not None:
             sizes = images.sizes if hasattr(images, "sizes") else [im.shape[:2] for im in images]
@@ -833,7 +986,7 @@ class Detector:
         sequence indexed by label; None: the label itself).  One copy to the host for the whole list."""
         if self.bbox_format != "xywh":
             raise ValueError(f"to_coco_results: COCO boxes are [x, y, w, h]: build the Detector with bbox_format='xywh', not {self.bbox_format!r}")
-        if isinstance(detections, (Detections, TiledDetections)):
+        if isinstance(detections, (Detections, TiledDetections, FusedDetections)):
             detections, image_ids = [detections], [image_ids]
         if len(detections) != len(image_ids):
             raise ValueError(f"to_coco_results: {len(detections)} images of detections, {len(image_ids)} image ids")

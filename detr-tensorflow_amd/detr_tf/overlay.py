@@ -156,8 +156,8 @@ def _upload_frames(images, on_device, device):
 def _check_detections(detections, B, want_scores):
     """Host-side checks: per image (boxes [k, 4] float32, labels [k] int64, scores [k] float32 or None) tensors, and whether scores
     are drawn."""
-    from .inference import Detections, TiledDetections
-    if isinstance(detections, (Detections, TiledDetections)) or (isinstance(detections, tuple) and len(detections) == 3 and B == 1
+    from .inference import Detections, FusedDetections, TiledDetections
+    if isinstance(detections, (Detections, TiledDetections, FusedDetections)) or (isinstance(detections, tuple) and len(detections) == 3 and B == 1
                                                                     and hasattr(detections[0], "shape")):
         detections = [detections]
     if not isinstance(detections, (list, tuple)) or len(detections) != B:
@@ -165,12 +165,12 @@ def _check_detections(detections, B, want_scores):
                          + (f" of {len(detections)}" if isinstance(detections, (list, tuple)) else ""))
     triples = []
     for d in detections:
-        if isinstance(d, (Detections, TiledDetections)):
+        if isinstance(d, (Detections, TiledDetections, FusedDetections)):
             triples.append((d.boxes, d.labels, d.scores))
         elif isinstance(d, (tuple, list)) and len(d) == 3:
             triples.append(tuple(d))
         else:
-            raise ValueError("draw_detections: detections must be Detections / TiledDetections in 'xyxy' or (boxes, labels, scores or None)")
+            raise ValueError("draw_detections: detections must be Detections / TiledDetections / FusedDetections in 'xyxy' or (boxes, labels, scores or None)")
     has_scores = [t[2] is not None for t in triples]
     if any(has_scores) != all(has_scores):
         raise ValueError("draw_detections: scores are given for some images and not for others")
@@ -229,7 +229,7 @@ def draw_detections(images, detections, class_names=None, *, scores=True, colors
     16-byte aligned in it).  One call of detr_hip_overlay: at most two launches, no host synchronisation.
 
     images: uint8 [h, w, 3] host arrays (uploaded once through one pinned staging buffer) or device tensors (used where they are), one
-      or a list of mixed sizes; or a RaggedFrames.  detections: per image a Detections / TiledDetections with boxes in "xyxy" pixels,
+      or a list of mixed sizes; or a RaggedFrames.  detections: per image a Detections / TiledDetections / FusedDetections with boxes in "xyxy" pixels,
       or a (boxes [k, 4], labels [k], scores [k] or None) triple, e.g. ground truth.  class_names: a sequence indexed by label (a label
       beyond it is drawn with its score alone, or without a label).  scores=False leaves the scores out of the labels.
     colors: uint8 [n, 3] indexed by label % n (None: class_palette(max(len(class_names), 100))).  thickness: outline width in pixels,

@@ -1181,6 +1181,59 @@ int detr_hip_track_motion(const detr_track_motion_desc *d, void *stream);
 int64_t detr_hip_track_motion_state_bytes(int32_t streams);
 int64_t detr_hip_workspace_bytes_track_motion(const detr_track_motion_desc *d);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fusion of the detections of several VIEWS of an image (test-time augmentation), appended (the ABI version is unchanged):
+ *   replaces: the host loop a user of get_model_inference writes to run a model on the mirrored image and / or at several shortest
+ *             sides and to combine the V x Q rows -- hard NMS, soft-NMS (Bodla et al. 2017) or weighted box fusion (Solovyev et al.
+ *             2021), each a sequential algorithm.
+ * One launch per batch, one workgroup per image (csrc/fuse_views.hip).  The descriptor is detr_tile_merge_desc, UNCHANGED, every
+ * field with its meaning there (a "tile" is a view; nms_threshold is the match threshold of every method, compared strictly); no
+ * struct, no layout id.  view_flip[n] != 0 says that view n saw the MIRRORED image: its window is a window of the mirrored image
+ * (flip, then window -- the rule of detr_hip_augment_padded).  fuse[] is read on the host during the call:
+ *   [0] method: 0 hard NMS, 1 soft-NMS linear, 2 soft-NMS Gaussian, 3 weighted box fusion
+ *   [1] sigma (method 2, > 0)          [2] score_min (methods 1, 2, >= 0)
+ *   [3] expected_views (method 3; 0 = no rescaling, otherwise an integer >= 1)      [4] min_members (method 3, integer >= 1)
+ *   [5] reserved, 0
+ * Per image:
+ *   1..4. candidates, mapping, edge rule and order are detr_hip_tile_merge's steps 1..4, the same code.  The one addition: for a
+ *      flipped view the mapping and the edge rule run in the view's own, mirrored frame; then the UNCLIPPED corners are mirrored,
+ *      (x0, x1) <- (W_b - x1, W_b - x0), one fp32 rounding each; the clip follows the mirror.
+ *   5. method 0: detr_hip_tile_merge's step 5.  With no flipped view and bbox_format 1..3 every output equals detr_hip_tile_merge's
+ *      bit for bit.
+ *      methods 1, 2 (soft-NMS): current scores in fp64, initialised from the fp32 scores; every candidate starts alive.  Repeat:
+ *      select the alive candidate with the largest current score (ties: lower position, i.e. lower view, then lower query; a NaN
+ *      score is never selected); stop when there is none or max_detections are emitted; emit it with score (float)current, it
+ *      dies; for every alive candidate j of its label (any label with class_agnostic) m = measure(selected, j) (step 5's fp64
+ *      measure): method 1: if m > nms_threshold, s_j <- s_j * (1.0 - m); method 2: s_j <- s_j * exp(-(m * m) / sigma) for every m;
+ *      then j dies if s_j < score_min (whether or not s_j changed).  fp64, one rounding per operation; exp is the device's
+ *      double-precision exp (method 2's scores are exact up to its last bit; exp(-0) = 1 leaves a score's bits alone).
+ *      method 3 (weighted box fusion): walk the candidates in the order of step 4.  Clusters are kept in creation order; a
+ *      cluster's label is its first member's.  For a candidate (score s, corners x_c) take the clusters of its label (all with
+ *      class_agnostic), m_k = measure(fused_k, box); the largest m_k wins, ties to the lower cluster (NaN never wins).  If that
+ *      m_k > nms_threshold the candidate joins cluster k: sw += s; sx[c] += s * x_c; cnt += 1; fused_c = (float)(sx[c] / sw) --
+ *      fp64, every product, sum and quotient one rounding.  Otherwise it founds a cluster: sw = s, sx[c] = s * x_c, cnt = 1,
+ *      fused = its own corners (copied), founder = its (view, query).  After the walk, which visits ALL candidates:
+ *      conf = sw / cnt; with expected_views = E > 0, conf = conf * min(cnt, E) / E, left to right; score = (float)conf; clusters
+ *      with cnt < min_members are dropped; the rest are ordered by descending score, ties by lower cluster.
+ *   6. the first max_detections rows are written as detr_hip_tile_merge writes them, with two differences: bbox_format 0 is
+ *      derived from the final corners for EVERY method, ((x0 + x1) * 0.5, (y0 + y1) * 0.5, x1 - x0, y1 - y0), single fp32
+ *      roundings; and out_members[row] = 1 (methods 0..2) or cnt, with out_query / out_tile the founder's (method 3).  counts[b]
+ *      rows, then zeros (out_members too).
+ * Status: DETR_TILE_OVER_CAP and DETR_TILE_BAD_START as detr_hip_tile_merge; method 3 holds at most DETR_FUSE_MAX_CLUSTERS clusters
+ * per image: one that would found more sets DETR_FUSE_OVER_CLUSTERS and gets counts[b] = 0 and zero rows.  Nothing is truncated
+ * silently; nothing is accessed out of bounds.  No float atomics: a rerun is bit-identical.
+ * Rejected before any launch: everything detr_hip_tile_merge rejects; null fuse or out_members; a non-finite fuse[] value; an
+ * unknown method; a non-integral or out-of-range [3] or [4]; sigma <= 0 with method 2; score_min < 0 with methods 1, 2; [5] != 0.
+ * ------------------------------------------------------------------------------------------- */
+#define DETR_FUSE_PARAMS 6
+#define DETR_FUSE_MAX_CLUSTERS 1024
+#define DETR_FUSE_OVER_CLUSTERS 4
+int detr_hip_fuse_views(const detr_tile_merge_desc *d,
+                        const int32_t *view_flip,   /* DEVICE [N], 0 | 1, or NULL = none flipped */
+                        const double  *fuse,        /* HOST [DETR_FUSE_PARAMS], read during the call */
+                        int32_t       *out_members, /* DEVICE [B, max_detections] */
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
