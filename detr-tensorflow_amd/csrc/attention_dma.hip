@@ -433,6 +433,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
 // ------------------------------------------------------------------------------------------------
 // backward 1/2: dQ per query block (streams the keys) + the row statistics for the dK / dV kernel
+// the 8 bf16 of a K column fragment with the elements of masked keys zeroed: element j belongs to the key of flag bit (j & 3) + 8 (j >> 2)
+__device__ __forceinline__ bf16x8 a2_zero_masked8(bf16x8 f, unsigned flags) {
+    uint4 u = __builtin_bit_cast(uint4, f);
+    auto pair = [&](int j) -> unsigned {           // the two bf16 of dword j / 2: elements j and j + 1
+        const unsigned lo = (flags >> ((j & 3) + 8 * (j >> 2))) & 1u, hi2 = (flags >> (((j + 1) & 3) + 8 * ((j + 1) >> 2))) & 1u;
+        return (lo ? 0x0000FFFFu : 0u) | (hi2 ? 0xFFFF0000u : 0u);
+    };
+    u.x &= pair(0);
+    u.y &= pair(2);
+    u.z &= pair(4);
+    u.w &= pair(6);
+    return __builtin_bit_cast(bf16x8, u);
+}
+
 // ------------------------------------------------------------------------------------------------
 template <bool DROP, bool MASK = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn2_bwd_dq_kernel(Attn2Args a) {
@@ -531,7 +545,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             s[c] = A2_MFMA(k1, qb[c][1], s[c]);
             dp[c] = A2_MFMA(vr1, dob[c][1], dp[c]);
         }
-        const bf16x8 kc0 = a2_frag_col(st, fr, 0), kc1 = a2_frag_col(st, fr, 1);
+        bf16x8 kc0 = a2_frag_col(st, fr, 0), kc1 = a2_frag_col(st, fr, 1);
+        if constexpr (MASK) {
+            // a masked key is absent: its K values are SELECTED away here, not multiplied by dS = 0 below (0 * NaN of a masked key's
+            // content would reach dQ).  Element j of kc0 / kc1 is the key of ds[j] / ds[8 + j]: bit (r & 3) + 8 (r >> 2) of kv >> 4 hi.
+            if (kv != ~0u) {
+                A2_NO_IFCVT();
+                const unsigned kvs = kv >> (4 * hi);
+                kc0 = a2_zero_masked8(kc0, kvs);
+                kc1 = a2_zero_masked8(kc1, kvs >> 16);
+            }
+        }
         unsigned w[2] = {0u, 0u};
         if constexpr (DROP) {
 #pragma unroll

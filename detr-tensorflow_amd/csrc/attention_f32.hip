@@ -263,9 +263,15 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(AttnArgs a) {
                     if (((kv >> krow(r, hi)) & 1u) == 0u) ds[r] = 0.0f;
             }
         }
+        // a masked key is absent: its K row is SELECTED away, not multiplied by dS = 0 (0 * NaN of a masked key's content would reach dQ)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-            dq = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[cur][krow(r, hi)][l31], ds[r], dq, 0, 0, 0);
+        for (int r = 0; r < 16; ++r) {
+            float kx = Ks[cur][krow(r, hi)][l31];
+            if constexpr (MASK) {
+                if (kv != ~0u) kx = ((kv >> krow(r, hi)) & 1u) ? kx : 0.0f;      // (wave-uniform: a fully valid tile pays nothing)
+            }
+            dq = __builtin_amdgcn_mfma_f32_32x32x2f32(kx, ds[r], dq, 0, 0, 0);
+        }
         }
         if (more) {
             rk.store(Ks[cur ^ 1], tid);

@@ -112,7 +112,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TH / 2][BN / 6
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 v[j] += bi[j];
-                if (e.act == 1) v[j] = fmaxf(v[j], 0.0f);
+                if (e.act == 1) v[j] = relu_keep_nan(v[j]);
                 const float m = bf16_bits_to_f32((j & 1) ? (mw[j >> 1] >> 16) : (mw[j >> 1] & 0xFFFFu));
                 v[j] = (m > 0.0f) ? v[j] : 0.0f;
             }

@@ -89,13 +89,12 @@ __device__ __forceinline__ float4 ld_bf16x4(const void *base, long long elem) {
 __device__ __forceinline__ float ld_bf16x1(const void *base, long long elem) {
     return bf16_bits_to_f32(reinterpret_cast<const unsigned short *>(base)[elem]);
 }
-// max(x, lo) as ONE v_max_f32: fmaxf() costs two under the IEEE mode of compute kernels (v_max x, x first, to quiet a signalling NaN
-// that these epilogues never see -- their inputs are sums of finite products)
-__device__ __forceinline__ float vmax_raw(float x, float lo) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(lo));
-    return r;
-}
+// ReLU of every epilogue (GEMM, 3x3 and stem convolutions): a compare and a select, no more than the two instructions fmaxf() costs
+// under the IEEE mode of compute kernels.  NOT a maximum: fmaxf() and v_max_f32 return the other operand for a NaN, which turned the
+// NaN of a diverged run into 0 (and, against a floor of -inf, into -inf) that the next layer could no longer see.  `x <= 0` is false
+// for a NaN, so it passes; +Inf passes, -Inf and -0.0 give +0.0: the bits of fmaxf(x, 0.0f) for every x that is not a NaN.
+// ("Non-finite values")
+__device__ __forceinline__ float relu_keep_nan(float x) { return x <= 0.0f ? 0.0f : x; }
 __device__ __forceinline__ unsigned f32_to_bf16_pair(float a, float b) {
     typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
     bf2 r;
@@ -464,7 +463,7 @@ __device__ __forceinline__ float epi_one(float v, float sc, float bi, const EpiA
     const bool drop = e.drop_scale != 0.0f;
     if (drop && e.residual) v = keep ? v * e.drop_scale : 0.0f;
     v += res;
-    if (e.act == 1) v = fmaxf(v, 0.0f);
+    if (e.act == 1) v = relu_keep_nan(v);
     else if (e.act == 2) v = 1.0f / (1.0f + expf(-v));
     if (drop && !e.residual) v = keep ? v * e.drop_scale : 0.0f;
     if (e.mask) v = (msk > 0.0f) ? v : 0.0f;

@@ -125,7 +125,6 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
     dstC.init_bytes(a.C, ((long long)(a.M - 1) * a.ldc + a.N) * 2);
     if (MBO) dstB.init_bytes(a.mbits_out, (long long)(a.M - 1) * a.ld_mbits + a.N / 8);
     const unsigned ldc2 = (unsigned)(a.ldc * 2), ldr2 = (unsigned)(a.ldr * 2), ldm2 = (unsigned)(a.ldm * 2), ldm1 = (unsigned)a.ldm, ldb1 = (unsigned)a.ld_mbits;
-    const float act_floor = a.act == 1 ? 0.0f : -__builtin_huge_valf();      // ReLU without a branch: max(v, 0) or max(v, -inf)
     float *stage = &sm.stage[wave][0][0];
     const unsigned a_lane = (unsigned)(h * 16);    // byte offset of this lane's 8 k values inside a 16-k step
     const uint32_t dkey = (EXT && a.drop_scale != 0.0f) ? drop_key(a.drop_seed, a.drop_step) : 0u;
@@ -273,8 +272,10 @@ __global__ __launch_bounds__(64 * (StreamSmem<K, SL, NW>::WAVES), (StreamOcc<K, 
 #pragma unroll
                     for (int i = 0; i < 8; ++i) v[i] += r[i];
                 }
+                if (a.act == 1) {                      // uniform over the launch; without an activation v is left alone (a NaN stays a NaN)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = vmax_raw(v[i], act_floor);
+                    for (int i = 0; i < 8; ++i) v[i] = relu_keep_nan(v[i]);
+                }
                 if constexpr (EXT) {
                     if (!RES && a.drop_scale != 0.0f) {
 #pragma unroll

@@ -32,6 +32,11 @@ __global__ __launch_bounds__(256) void sumsq_segments_kernel(const float *__rest
     if (threadIdx.x == 0) sumsq[c] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// tf.clip_by_norm / tf.clip_by_global_norm: clip / max(nrm, clip), exactly 1 when nrm <= clip.  Not fmaxf(), which ignores a NaN
+// operand: a NaN norm (one NaN gradient element) must give a NaN factor, so that the update poisons what the reference's does
+// instead of going through unclipped.  An Inf norm gives 0, as the formula does.
+__device__ __forceinline__ float clip_factor(float nrm, float clip) { return nrm > clip ? clip / nrm : (nrm == nrm ? 1.0f : nrm); }
+
 __global__ __launch_bounds__(256) void clip_adam_kernel(float *__restrict__ param, const float *__restrict__ g,
                                                         float *__restrict__ m, float *__restrict__ v,
                                                         const int *__restrict__ chunk_tensor,
@@ -70,7 +75,7 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float *__restrict__ para
         if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
         __syncthreads();
         const float nrm = sqrtf((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
-        cs = clip / fmaxf(nrm, clip);
+        cs = clip_factor(nrm, clip);
     }
     for (long long i = s0 + threadIdx.x; i < s1; i += blockDim.x) {
         const float gi = g[i] * cs;
@@ -120,7 +125,7 @@ __global__ __launch_bounds__(256) void global_clip_scale_kernel(const float *__r
     if (threadIdx.x == 0) {
         const float clip = hyper[3];
         const float nrm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-        scale[0] = clip > 0.f ? clip / fmaxf(nrm, clip) : 1.0f;      // exactly 1 when nrm <= clip
+        scale[0] = clip > 0.f ? clip_factor(nrm, clip) : 1.0f;
         scale[1] = nrm;
     }
 }
@@ -185,7 +190,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float *__restrict__ param, c
         if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
         __syncthreads();
         const float nrm = sqrtf((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
-        cs = clip / fmaxf(nrm, clip);
+        cs = clip_factor(nrm, clip);
     }
     long long i0 = s0;
     if (aligned16 && (s0 & 3) == 0) {

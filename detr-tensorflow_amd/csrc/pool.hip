@@ -63,7 +63,9 @@ __device__ __forceinline__ void pool_pixel(long long idx, int CV, int rows, int 
     n = (int)(t / (unsigned)rows);
 }
 
-// y[n,ho,wo,c] = max over the 3x3 / stride-2 window of the zero-padded map; the FIRST maximal tap wins (strict `>` in kh-major order)
+// y[n,ho,wo,c] = max over the 3x3 / stride-2 window of the zero-padded map; the FIRST maximal tap wins (strict `>` in kh-major order).
+// A NaN tap is taken too and then never replaced (nothing compares greater than it): a window that holds a NaN gives NaN, as
+// F.max_pool2d does, and its argmax byte names a NaN tap (the last one), where the backward then puts the window's gradient.
 template <class T, int V>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const typename PoolLane<T, V>::vec *__restrict__ x,
                                                           typename PoolLane<T, V>::vec *__restrict__ y,
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const typename PoolLan
                 L::to_f32(raw, v);
 #pragma unroll
                 for (int e = 0; e < V; ++e)
-                    if (v[e] > best[e]) { best[e] = v[e]; bi[e] = (uint32_t)(kh * 3 + kw); }
+                    if (v[e] > best[e] || v[e] != v[e]) { best[e] = v[e]; bi[e] = (uint32_t)(kh * 3 + kw); }
             }
         y[idx] = L::from_f32(best);                  // exact: inputs are bf16
         amax[idx] = pack_taps(bi);
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const typename PoolLan
         float xv[V];
         L::to_f32(xraw, xv);
 #pragma unroll
-        for (int e = 0; e < V; ++e) g[e] = xv[e] > 0.0f ? g[e] : 0.0f;
+        for (int e = 0; e < V; ++e) g[e] = xv[e] <= 0.0f ? 0.0f : g[e];      // (a NaN pixel keeps its gradient, like the oracle's ReLU)
         dx[idx] = L::from_f32(g);
     }
 }

@@ -116,8 +116,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void stem_fwd_rows_bf16_kernel(Ste
     for (int s = 0; s < 11; ++s) {
         const int kp = 16 * s + 8 * hi;
         const int kh = kp / 24, j = kp - 24 * kh;
-        aoff[s] = (kh < 7 ? kh : 6) * SR_PLD + 6 * (wm * 32 + l31) + (kh < 7 ? j : 0);      // (k' >= 168: zero weights, any finite data)
+        aoff[s] = (kh < 7 ? kh : 6) * SR_PLD + 6 * (wm * 32 + l31) + (kh < 7 ? j : 0);      // (k' >= 168: zero weights on taps of the pixel's own window)
     }
+    const uint32_t pad_lo[2] = {hi == 0 ? 0x0000FFFFu : 0xFFFFFFFFu, hi == 1 ? 0x0000FFFFu : 0xFFFFFFFFu};      // see the k loop
+    const uint32_t pad_hi[2] = {hi == 0 ? 0u : 0xFFFFFFFFu, hi == 1 ? 0u : 0xFFFFFFFFu};
     float rp[14];
     auto patch_load = [&](int t, float (&rp)[14]) {                  // tile t >= ntiles: out-of-range offsets, no traffic
         const int twi = t % tiles_w;
@@ -160,7 +162,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void stem_fwd_rows_bf16_kernel(Ste
 #pragma unroll
         for (int s = 0; s < 11; ++s) {
             const uint32_t *pa = reinterpret_cast<const uint32_t *>(P + aoff[s]);
-            const bf16x8 fa = __builtin_bit_cast(bf16x8, make_uint4(pa[0], pa[1], pa[2], pa[3]));
+            // entries 21 .. 23 of a kernel row are padding: their weights are zero, but the staged data behind them is the NEXT pixel,
+            // and 0 * NaN (or 0 * Inf) would poison an output pixel whose window does not hold it.  The fragment that starts at entry 16
+            // (k' % 24 == 16: hi == 0 where s % 3 == 1, hi == 1 where s % 3 == 2) gets zeros there.
+            uint32_t p2 = pa[2], p3 = pa[3];
+            if (s % 3 == 1) { p2 &= pad_lo[0]; p3 &= pad_hi[0]; }
+            if (s % 3 == 2) { p2 &= pad_lo[1]; p3 &= pad_hi[1]; }
+            const bf16x8 fa = __builtin_bit_cast(bf16x8, make_uint4(pa[0], pa[1], p2, p3));
             const bf16x8 fb = frag_tr<64>(reinterpret_cast<const unsigned short (*)[BF_LD]>(sm.B + (s >> 1) * 2048), wn * 32, (s & 1) * 16, lane);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc, 0, 0, 0);
         }
@@ -186,7 +194,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void stem_fwd_rows_bf16_kernel(Ste
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 v[j] += bi[j];
-                if (a.e.act == 1) v[j] = fmaxf(v[j], 0.0f);
+                if (a.e.act == 1) v[j] = relu_keep_nan(v[j]);
             }
             if (tw < wn_ok)
                 *reinterpret_cast<uint4 *>(reinterpret_cast<unsigned short *>(a.y) + (prow0 + tw) * 64 + col) =
