@@ -92,6 +92,9 @@ enum TuneKey {
     T_X3_WG_ROUNDS,      // f32x3 3x3 weight gradient: rounds of workgroups the split plan aims at (0 = 2)
     T_X3_CONV,           // f32x3 3x3 convolutions: 2 = the per-wave split of the first form (conv3x3_kernel<.., SPLIT3>) everywhere, 1 = split once into LDS (conv_x3.h) everywhere, 0 = rule
     T_SPLIT3_ALL,        // compute = 2: 1 = every 64x64 / 128x128 GEMM launch takes the split kernel (tests), 0 = where it is faster
+    T_SPLIT_TARGET,      // split-K plan (gemm_split_plan): workgroups a bf16 launch on 128 x 128 tiles aims at (0 = 256)
+    T_SPLIT_TARGET64,    // split-K plan: workgroups a launch on 64 x 64 tiles aims at (0 = 1024)
+    T_X3_SPLIT_TARGET,   // split-K plan: workgroups an f32x3 launch on 128 x 128 tiles aims at (0 = 512); negative: f32x3 takes the 64 x 64 plan
     T_COUNT
 };
 int tune(TuneKey k);

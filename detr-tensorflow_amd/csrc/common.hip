@@ -42,6 +42,9 @@ static const char *const g_tune_names[T_COUNT] = {
     "DETR_HIP_X3_WG_ROUNDS",
     "DETR_HIP_X3_CONV",
     "DETR_HIP_SPLIT3_ALL",
+    "DETR_HIP_SPLIT_TARGET",
+    "DETR_HIP_SPLIT_TARGET64",
+    "DETR_HIP_X3_SPLIT_TARGET",
 };
 static int g_tune[T_COUNT];
 static void load_tuning() {

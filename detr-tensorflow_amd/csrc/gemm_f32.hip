@@ -334,8 +334,18 @@ static bool gemm_ring_wgrad_operands(const detr_gemm_desc *d) {
 // per fragment, so the narrow (N <= 64: 0.77x) and the short-K (K <= 128: 0.92-0.96x) 1x1-convolution GEMMs and the 64-row weight gradients
 // (0.85x) keep the exact kernel (scripts/micro_split3.py, profiles/r06_micro_split3.txt) -- both are fp32-accurate, the mode only decides
 // which matrix instruction computes the products.  DETR_HIP_SPLIT3_ALL=1: every shape (tests).
+static bool gemm_x3_shape(int M, int N, int K) { return N >= 128 && K >= 256 && M >= 128; }
 static bool gemm_split3_shape(const detr_gemm_desc *d) {
-    return d->compute == 2 && d->N > 32 && (tune(T_SPLIT3_ALL) == 1 || (d->N >= 128 && d->K >= 256 && d->M >= 128));
+    return d->compute == 2 && d->N > 32 && (tune(T_SPLIT3_ALL) == 1 || gemm_x3_shape(d->M, d->N, d->K));
+}
+// compute = 1: the split-K shapes that run on 128 x 128 tiles (gemm_pick_tile) and are planned for them (gemm_split_plan).
+// round 3, cold-cache sweeps (scripts/micro_wgrad.py, micro_gemm.py --cold; profiles/r03_micro_*): the layer4 weight
+// gradients (M, N >= 512, K = 8400) gain 15-25 % on 128x128 tiles (512x2048: 64 -> 53 us, 1024x2048: 109 -> 80), and so do
+// the wide K = 512 GEMMs of layer3's first block (M33600 N1024: 100 -> 89 us, with residual + mask 163 -> 151)
+// round 4 (scripts/experiments/tile_force.sh): the encoder's FFN weight-gradient pair (256 x 2048 and 2048 x 256 outputs, K = 8400)
+// 54.7 us as one grouped launch of 64x64 tiles -> 45.3 us as two launches of 128x128 tiles
+static bool gemm_big_split(int M, int N, int K) {
+    return (N >= 128 && K >= 16384) || (M >= 512 && N >= 512 && K >= 4096) || (K >= 4096 && ((M >= 256 && N >= 2048) || (M >= 2048 && N >= 256)));
 }
 static GemmTile gemm_pick_tile(const detr_gemm_desc *d, int split, int batch) {
     const bool bf16c = d->compute == 1;
@@ -347,13 +357,7 @@ static GemmTile gemm_pick_tile(const detr_gemm_desc *d, int split, int batch) {
         // reuse) pays only for the long split-K weight gradients (K >= 16384, N >= 128) and for unsplit K >= 1024 GEMMs
         // that still fill the chip with 128x128 tiles (M33600 N256 K1024: 54 vs 60 us)
         const long long t128 = (long long)cdiv(d->M, 128) * cdiv(d->N, 128) * batch;
-        // round 3, cold-cache sweeps (scripts/micro_wgrad.py, micro_gemm.py --cold; profiles/r03_micro_*): the layer4 weight
-        // gradients (M, N >= 512, K = 8400) gain 15-25 % on 128x128 tiles (512x2048: 64 -> 53 us, 1024x2048: 109 -> 80), and so do
-        // the wide K = 512 GEMMs of layer3's first block (M33600 N1024: 100 -> 89 us, with residual + mask 163 -> 151)
-        // round 4 (scripts/experiments/tile_force.sh): the encoder's FFN weight-gradient pair (256 x 2048 and 2048 x 256 outputs, K = 8400)
-        // 54.7 us as one grouped launch of 64x64 tiles -> 45.3 us as two launches of 128x128 tiles
-        const bool big_split = (d->N >= 128 && d->K >= 16384) || (d->M >= 512 && d->N >= 512 && d->K >= 4096) ||
-                               (d->K >= 4096 && ((d->M >= 256 && d->N >= 2048) || (d->M >= 2048 && d->N >= 256)));
+        const bool big_split = gemm_big_split(d->M, d->N, d->K);
         // round 4 (scripts/experiments/tile_shapes.py, every unsplit shape of the step on every tile): the rules hold within +-5 % except
         // M133600 N256 K512 (layer2's projection shortcut and its input gradient): 81.9 us on 64x64 tiles, 71.1 on 128x128
         const bool big_plain = (d->K >= 1024 && t128 >= 512) || (d->K >= 512 && d->N >= 512 && t128 >= 1024) ||
@@ -403,6 +407,41 @@ static GemmTile gemm_pick_tile(const detr_gemm_desc *d, int split, int batch) {
     else if (d->N <= 32) tile = TILE_128x32;
     else tile = TILE_64x64;      // measured (profiles/tune_r1.txt): 64x64 (8 waves/SIMD) beats 128x64 by 2-10 % and 128x128 by 15-50 % in fp32
     return tile;
+}
+// The split a reduction-heavy GEMM (a weight gradient) should ask for (detr_gemm_desc.split_k), so that enough workgroups exist to fill
+// 256 CUs on the tile gemm_pick_tile gives that split: the same predicates decide both.  Workgroup targets (A/B hooks): 128x128 tiles
+// DETR_HIP_SPLIT_TARGET, 512 -> 256 measured -0.23 ms per step on the same box (half the partial slabs to write and reduce;
+// scripts/micro_wgrad.py shows the same 3-7 % per launch with cold caches); 64x64 tiles DETR_HIP_SPLIT_TARGET64; f32x3 on 128x128
+// tiles DETR_HIP_X3_SPLIT_TARGET (negative: the 64x64 plan).  DETR_HIP_SPLIT3_ALL does not enter the plan.
+static int gemm_split_plan(int M, int N, int K, int compute, int max_split) {
+    const long long target128 = tune(T_SPLIT_TARGET) ? tune(T_SPLIT_TARGET) : 256;
+    const long long target64 = tune(T_SPLIT_TARGET64) ? tune(T_SPLIT_TARGET64) : 1024;
+    const long long target_x3 = tune(T_X3_SPLIT_TARGET) ? tune(T_X3_SPLIT_TARGET) : 512;
+    const long long t128 = (long long)cdiv(M, 128) * cdiv(N, 128), most = max_split;
+    if (compute == 1 && gemm_big_split(M, N, K)) {                               // 128x128 tiles
+        const long long ktiles = cdiv(K, 32);
+        return (int)std::max(1LL, std::min({std::max(1LL, target128 / t128), most, ktiles >= 16 ? ktiles / 8 : 1LL}));
+    }
+    if (compute == 2 && target_x3 > 0 && gemm_x3_shape(M, N, K)) {
+        // f32x3 (gemm_x3.h): 128 x 128 tiles, two workgroups per CU = 512 slots; the 64 x 64 plan below left e.g. the 256 x 1024 weight gradient of layer3
+        // with 16 tiles x 16 splits = 256 workgroups, half a round of single workgroups per CU (round 6)
+        const long long ktiles = cdiv(K, 32);
+        const long long cap = ktiles >= 64 ? ktiles / 8 : std::max(1LL, ktiles / 4);
+        const long long s128 = std::max(1LL, std::min({target_x3 / t128, most, cap}));
+        if (t128 * s128 >= x3_t128_threshold()) return (int)s128;                // (gemm_pick_tile: 128 x 128 tiles from that many of them on)
+    }
+    // 64x64 tiles (fp32 always; bf16 for small outputs, see gemm_pick_tile): ~1024 workgroups measured best
+    const long long tiles = (long long)cdiv(M, 64) * cdiv(N, 64);
+    const long long want = std::max(1LL, target64 / tiles);
+    const long long ktiles = cdiv(K, compute == 1 ? 32 : 16);
+    const long long cap = ktiles >= 64 ? ktiles / 8 : ktiles / 4;                // short reductions: 4 k-tiles per split are enough
+    return (int)std::max(1LL, std::min({want, most, cap}));
+}
+extern "C" int32_t detr_hip_gemm_split_plan(int32_t M, int32_t N, int32_t K, int32_t compute, int32_t max_split) {
+    DETR_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_split_plan: bad shape M=%d N=%d K=%d", M, N, K);
+    DETR_REQUIRE(compute >= 0 && compute <= 2, "gemm_split_plan: compute %d (0 = fp32, 1 = bf16, 2 = f32x3)", compute);
+    DETR_REQUIRE(max_split >= 1, "gemm_split_plan: max_split %d < 1", max_split);
+    return gemm_split_plan(M, N, K, compute, max_split);
 }
 // split count a GEMM really runs with: no empty splits (recomputed from the K tiles each split gets)
 static int gemm_effective_split(const detr_gemm_desc *d) {

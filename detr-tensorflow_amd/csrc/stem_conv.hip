@@ -516,20 +516,37 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void stem_wgrad_rows_bf16_kernel(S
 
 using namespace detr;
 
+// Host plan of the weight gradient (mode 2), shared by the scratch-size query and the launch.  rows: the descriptor's half of the
+// row-staging kernel's predicate (bf16 dy, 32-bit offsets; DETR_HIP_STEM_ROWS=2: the gathering kernel) -- one partial per workgroup of its
+// persistent grid; the launch adds that the workspace holds them.  Otherwise the gathering kernel: `split` slices of `rps` rows, a whole
+// number of K tiles each, no empty slice (split = 0 means 1).
+struct StemWgradPlan {
+    bool rows;
+    int chunks, nunits, wgs;      // row-staging kernel: chunks per output row, work units, workgroups
+    int split, rps;               // gathering kernel
+    long long part;               // floats per partial
+    long long bytes(int partials) const { return (long long)partials * part * 4; }
+};
+static StemWgradPlan stem_wgrad_plan(const detr_stem_desc *d) {
+    StemWgradPlan p;
+    const long long M = (long long)d->N * d->Ho * d->Wo;
+    p.part = (long long)STEM_K * 64;
+    p.rows = d->compute == 1 && d->w_dtype == 1 && M * 64 * 2 <= BUF_MAX_BYTES && tune(T_STEM_ROWS) != 2;
+    p.chunks = cdiv(d->Wo, SW_TW);
+    p.nunits = d->N * d->Ho * p.chunks;
+    p.wgs = p.nunits < 768 ? p.nunits : 768;
+    const int bk = d->compute == 1 ? BF_BK : GEMM_BK;
+    p.rps = cdiv(cdiv(M, d->split > 0 ? d->split : 1), bk) * bk;
+    p.split = cdiv(M, p.rps);
+    return p;
+}
+
 extern "C" int64_t detr_hip_workspace_bytes_stem(const detr_stem_desc *d, int32_t mode) {
     if (!d || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0) return -1;
     if (mode != 2) return 0;
-    const long long part = (long long)STEM_K * 64;
-    const long long M = (long long)d->N * d->Ho * d->Wo;
-    if (d->compute == 1 && d->w_dtype == 1 && M * 64 * 2 <= BUF_MAX_BYTES && tune(T_STEM_ROWS) != 2) {
-        const int nunits = d->N * d->Ho * cdiv(d->Wo, SW_TW);        // the row-staging kernel: one partial per workgroup
-        return (int64_t)(nunits < 768 ? nunits : 768) * part * 4;
-    }
-    int split = d->split > 0 ? d->split : 1;
-    const int bk = d->compute == 1 ? BF_BK : GEMM_BK;
-    const int rps = cdiv(cdiv(M, split), bk) * bk;
-    split = cdiv(M, rps);
-    return split > 1 ? (int64_t)split * part * 4 : 0;
+    const StemWgradPlan p = stem_wgrad_plan(d);
+    if (p.rows) return p.bytes(p.wgs);
+    return p.split > 1 ? p.bytes(p.split) : 0;
 }
 
 extern "C" int detr_hip_stem_conv7x7_f32(const detr_stem_desc *d, int32_t mode, void *stream) {
@@ -573,31 +590,24 @@ extern "C" int detr_hip_stem_conv7x7_f32(const detr_stem_desc *d, int32_t mode, 
     // weight gradient: d->w = dy [M, 64], d->y = dw [147, 64] (accumulated: dw += alpha * scale[co] * sum)
     DETR_REQUIRE(!d->bias && d->act == 0, "stem conv wgrad: only scale/alpha epilogue");
     a.dy = d->w; a.dw = d->y;
-    {   // bf16 dy: the row-staging kernel with its own persistent grid (DETR_HIP_STEM_ROWS=2: the gathering kernel)
-        const int chunks = cdiv(a.Wo, SW_TW), nunits = a.N * a.Ho * chunks;
-        const int wgs = nunits < 768 ? nunits : 768;
-        const long long part = (long long)STEM_K * 64;
-        if (bf && d->w_dtype == 1 && d->workspace && aligned16(d->workspace) && d->workspace_bytes >= (long long)wgs * part * 4 &&
-            (long long)a.M * 64 * 2 <= BUF_MAX_BYTES && tune(T_STEM_ROWS) != 2) {
-            a.dw = d->workspace;
-            a.part_stride = part;
-            hipLaunchKernelGGL(stem_wgrad_rows_bf16_kernel, dim3((unsigned)wgs), dim3(GEMM_THREADS), 0, s, a, chunks, nunits);
-            DETR_LAUNCH_CHECK("stem conv wgrad (staged rows)");
-            detr_reduce_desc r = {};
-            r.ws = d->workspace; r.splits = wgs; r.part_stride = part; r.rows = STEM_K; r.cols = 64;
-            r.C = d->y; r.ldc = 64; r.alpha = e.alpha; r.scale = e.scale;
-            launch_splitk_reduce(r, s);
-            DETR_LAUNCH_CHECK("stem conv wgrad reduce");
-            return 0;
-        }
+    const StemWgradPlan p = stem_wgrad_plan(d);
+    const long long part = p.part;
+    // bf16 dy: the row-staging kernel with its own persistent grid
+    if (p.rows && d->workspace && aligned16(d->workspace) && d->workspace_bytes >= p.bytes(p.wgs)) {
+        a.dw = d->workspace;
+        a.part_stride = part;
+        hipLaunchKernelGGL(stem_wgrad_rows_bf16_kernel, dim3((unsigned)p.wgs), dim3(GEMM_THREADS), 0, s, a, p.chunks, p.nunits);
+        DETR_LAUNCH_CHECK("stem conv wgrad (staged rows)");
+        detr_reduce_desc r = {};
+        r.ws = d->workspace; r.splits = p.wgs; r.part_stride = part; r.rows = STEM_K; r.cols = 64;
+        r.C = d->y; r.ldc = 64; r.alpha = e.alpha; r.scale = e.scale;
+        launch_splitk_reduce(r, s);
+        DETR_LAUNCH_CHECK("stem conv wgrad reduce");
+        return 0;
     }
-    int split = d->split > 0 ? d->split : 1;
-    const int bk = bf ? BF_BK : GEMM_BK;
-    int rps = cdiv(cdiv(a.M, split), bk) * bk;
-    split = cdiv(a.M, rps);
-    a.rows_per_split = rps;
-    const long long part = (long long)STEM_K * 64;
-    const bool partial = split > 1 && d->workspace && aligned16(d->workspace) && d->workspace_bytes >= (long long)split * part * 4;
+    const int split = p.split;
+    a.rows_per_split = p.rps;
+    const bool partial = split > 1 && d->workspace && aligned16(d->workspace) && d->workspace_bytes >= p.bytes(split);
     DETR_REQUIRE(split == 1 || partial, "stem conv wgrad: split > 1 needs a workspace of split*147*64 floats");
     EpiArgs fin = e;
     if (partial) {

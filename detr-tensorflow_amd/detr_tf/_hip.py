@@ -254,6 +254,7 @@ _SIGNATURES = {
     "detr_hip_gemm_f32": [POINTER(GemmDesc), c_void_p],
     "detr_hip_gemm_group_f32": [POINTER(GemmDesc), c_int32, c_void_p],
     "detr_hip_gemm_family": [POINTER(GemmDesc)],
+    "detr_hip_gemm_split_plan": [c_int32, c_int32, c_int32, c_int32, c_int32],
     "detr_hip_gemm_ring_plan": [c_int32, c_int32, c_int32, POINTER(c_int32)],
     "detr_hip_splitk_reduce_many": [POINTER(ReduceDesc), c_int32, c_void_p],
     "detr_hip_conv3x3_f32": [POINTER(Conv3x3Desc), c_int32, c_void_p],
@@ -416,9 +417,8 @@ class KernelProfiler:
 
 PROFILER = None
 # Deferred split-K reductions: while DEFER is a list (the engine's backward pass), every split-K GEMM gets a private slab from
-# the bump allocator over DEFER_WS and only DESCRIBES its reduction; flush_reduces() then reduces up to 16 slab sets per launch.
+# the bump allocator over the slab pool (_defer_slab) and only DESCRIBES its reduction; flush_reduces() then reduces up to 16 slab sets per launch.
 DEFER = None
-DEFER_WS = None
 _defer_top = 0
 _defer_outs = set()
 COMPUTE_BF16 = 0      # default compute mode of gemm / conv3x3: 0 = exact fp32 MFMA, 1 = bf16 MFMA (fp32 storage), 2 = f32x3 (fp32 accuracy on the bf16 pipe)
@@ -608,6 +608,7 @@ def set_tuning(name, value):
         os.environ[name] = str(value)
     _check(load().detr_hip_reload_tuning(), "detr_hip_reload_tuning")
     _WS_NEED.clear()        # the cached scratch sizes depend on the tuning variables (tile / split plans, slab layout)
+    _SPLIT_PLAN.clear()     # and so do the cached split plans (workgroup targets, the f32x3 tile threshold)
 
 
 def _stream():
@@ -747,37 +748,24 @@ def gemm_group(calls):
         PROFILER.end(infos[0][0], sum(i[1] for i in infos), ev0, f"group{n}: " + infos[0][2], sum(i[3] for i in infos))
 
 
-# workgroups a split-K launch aims for (A/B hooks).  128x128 tiles: 512 -> 256 measured -0.23 ms per step on the same box (half
-# the partial slabs to write and reduce; scripts/micro_wgrad.py shows the same 3-7 % per launch with cold caches)
-SPLIT_TARGET_128 = int(os.environ.get("DETR_HIP_SPLIT_TARGET", "256"))
-SPLIT_TARGET_64 = int(os.environ.get("DETR_HIP_SPLIT_TARGET64", "1024"))
-X3_SPLIT_TARGET = int(os.environ.get("DETR_HIP_X3_SPLIT_TARGET", "512"))      # workgroups a split-K f32x3 GEMM on 128 x 128 tiles aims at
+_SPLIT_PLAN = {}
 
 
 def pick_split_k(M, N, K, max_split=1024, compute=None):
-    """Reduction-heavy GEMMs (weight gradients): split K so that enough workgroups exist to fill 256 CUs.
-    compute: the launch's detr_gemm_desc.compute (None: the module default COMPUTE_BF16)."""
-    compute = COMPUTE_BF16 if compute is None else int(compute)
-    if compute == 1 and ((N >= 128 and K >= 16384) or (M >= 512 and N >= 512 and K >= 4096) or
-                         (K >= 4096 and ((M >= 256 and N >= 2048) or (M >= 2048 and N >= 256)))):   # 128x128 tiles (gemm_f32.hip: gemm_pick_tile)
-        tiles = -(-M // 128) * -(-N // 128)
-        ktiles = -(-K // 32)
-        return int(max(1, min(max(1, SPLIT_TARGET_128 // tiles), max_split, ktiles // 8 if ktiles >= 16 else 1)))
-    if compute == 2 and X3_SPLIT_TARGET > 0 and N >= 128 and K >= 256 and M >= 128:
-        # f32x3 (gemm_x3.h): 128 x 128 tiles, two workgroups per CU = 512 slots; the 64 x 64 plan below left e.g. the 256 x 1024 weight gradient of layer3
-        # with 16 tiles x 16 splits = 256 workgroups, half a round of single workgroups per CU (round 6; DETR_HIP_X3_SPLIT_TARGET=0: the old plan)
-        t128 = -(-M // 128) * -(-N // 128)
-        ktiles = -(-K // 32)
-        cap = ktiles // 8 if ktiles >= 64 else max(1, ktiles // 4)
-        s128 = int(max(1, min(X3_SPLIT_TARGET // t128, max_split, cap)))
-        if t128 * s128 >= 192:                      # (gemm_pick_tile: 128 x 128 tiles from 192 of them on)
-            return s128
-    # 64x64 tiles (fp32 always; bf16 for small outputs, see gemm_f32.hip): ~1024 workgroups measured best
-    tiles = -(-M // 64) * -(-N // 64)
-    want = max(1, SPLIT_TARGET_64 // max(tiles, 1))
-    ktiles = -(-K // (32 if compute == 1 else 16))
-    cap = ktiles // 8 if ktiles >= 64 else ktiles // 4      # short reductions: 4 k-tiles per split are enough
-    return int(max(1, min(want, max_split, cap)))
+    """Reduction-heavy GEMMs (weight gradients): the split_k that gives enough workgroups to fill 256 CUs -- the library's plan
+    (detr_hip_gemm_split_plan, beside the tile rule it depends on) through a per-shape cache: one ctypes call per distinct shape,
+    none per launch.  compute: the launch's detr_gemm_desc.compute (None: the module default COMPUTE_BF16)."""
+    if compute is None:
+        compute = COMPUTE_BF16
+    key = (M, N, K, compute, max_split)
+    sk = _SPLIT_PLAN.get(key)
+    if sk is None:
+        sk = int(load().detr_hip_gemm_split_plan(M, N, K, int(compute), max_split))
+        if sk < 1:
+            raise RuntimeError(f"detr_hip_gemm_split_plan rejected M{M} N{N} K{K} compute {compute} max_split {max_split}: "
+                               f"{load().detr_hip_last_error().decode()}")
+        _SPLIT_PLAN[key] = sk
+    return sk
 
 
 def linear_fwd_call(x2d, w_out_in, bias, out2d, *, alpha=1.0, residual=None, act=0, dropout_p=0.0, dropout_seed=0,
@@ -802,16 +790,26 @@ def linear_dgrad_call(dy2d, w_out_in, dx2d, *, alpha=1.0, residual=None, mask=No
                  mask=mask, ldmask=(mask.stride(0) if mask is not None else 0), compute=compute))
 
 
+def wgrad_call(M, N, K, A, lda, B, ldb, C, ldc, *, alpha=1.0, scale=None, rowsum_a=None, rowsum_alpha=1.0, compute=None):
+    """(args, kwargs) of the gemm() of an accumulate-into-C reduction GEMM: C[M, N] += alpha * scale[n] * A^T B over K rows, both
+    operands reduction-major.  THE one place that chooses between the two forms: the planned split (pick_split_k), whose deterministic
+    reduction adds to C, or, unsplit, C as its own residual."""
+    sk = pick_split_k(M, N, K, 1024, compute)
+    kw = {"alpha": alpha, "scale": scale, "rowsum_a": rowsum_a, "rowsum_alpha": rowsum_alpha, "compute": compute}
+    if sk > 1:
+        kw["split_k"] = sk
+    else:
+        kw["residual"], kw["ldr"] = C, ldc
+    return (M, N, K, A, lda, 0, B, ldb, 0, C, ldc), kw
+
+
 def linear_wgrad_call(dy2d, x2d, dw_out_in, *, alpha=1.0, bias_grad=None, compute=None):
     """dW(out,in) += alpha * dy^T @ x (deterministic split-K through the workspace; dW holds zeros / the running sum);
     bias_grad (out,) += alpha * column sums of dy, fused into the same launch (row sums of the A operand)."""
     M, N = dy2d.shape
     K = x2d.shape[1]
-    sk = pick_split_k(N, K, M, compute=compute)
-    args = (N, K, M, dy2d, dy2d.stride(0), 0, x2d, x2d.stride(0), 0, dw_out_in, dw_out_in.stride(0))
-    if sk == 1:
-        return args, dict(alpha=alpha, residual=dw_out_in, ldr=dw_out_in.stride(0), rowsum_a=bias_grad, rowsum_alpha=alpha, compute=compute)
-    return args, dict(alpha=alpha, split_k=sk, rowsum_a=bias_grad, rowsum_alpha=alpha, compute=compute)
+    return wgrad_call(N, K, M, dy2d, dy2d.stride(0), x2d, x2d.stride(0), dw_out_in, dw_out_in.stride(0), alpha=alpha,
+                      rowsum_a=bias_grad, rowsum_alpha=alpha, compute=compute)
 
 
 def linear_fwd(*a, **kw):

@@ -367,11 +367,8 @@ class DetrEngine:
     @staticmethod
     def _wgrad(M_out, N_out, K_red, A, lda, Bm, ldb, C, ldc, scale=None, alpha=1.0, compute=None):
         """C[M_out,N_out] += alpha * scale[n] * A'^T-style reduction (both operands reduction-major)."""
-        sk = hip.pick_split_k(M_out, N_out, K_red, compute=compute)
-        if sk > 1:
-            hip.gemm(M_out, N_out, K_red, A, lda, 0, Bm, ldb, 0, C, ldc, alpha=alpha, scale=scale, split_k=sk, compute=compute)
-        else:
-            hip.gemm(M_out, N_out, K_red, A, lda, 0, Bm, ldb, 0, C, ldc, alpha=alpha, scale=scale, residual=C, ldr=ldc, compute=compute)
+        args, kwargs = hip.wgrad_call(M_out, N_out, K_red, A, lda, Bm, ldb, C, ldc, scale=scale, alpha=alpha, compute=compute)
+        hip.gemm(*args, **kwargs)
 
     def _a16(self, base):
         """(buffer name, dtype) of an attention operand: bf16 compute mode stores them in bf16 under the name `base`16."""

@@ -160,6 +160,12 @@ int detr_hip_gemm_f32(const detr_gemm_desc *d, void *stream);
 /* the kernel family detr_hip_gemm_f32 would launch for this descriptor (no launch): 0 tile engine, 1 streaming kernel, 2 ring kernel (bf16),
  * 3 ring kernel (fp32), 4 GEMM + LayerNorm, 5 ring weight gradient; negative = rejected.  For callers that bill launches to roofline families. */
 int detr_hip_gemm_family(const detr_gemm_desc *d);
+/* the split_k a reduction-heavy [M, N] = [M, K] x [K, N] GEMM (a weight gradient) should ask for (appended; no launch): as many splits, at most
+ * max_split, as fill the chip with the tiles detr_hip_gemm_f32 runs that split on -- the plan and the tile rule share their shape predicates.
+ * compute as in detr_gemm_desc.  Tuning: DETR_HIP_SPLIT_TARGET / _SPLIT_TARGET64 / _X3_SPLIT_TARGET (workgroups aimed at on bf16 128 x 128, on
+ * 64 x 64 and on f32x3 128 x 128 tiles; a negative _X3_SPLIT_TARGET plans f32x3 on 64 x 64 tiles) and DETR_HIP_SPLIT3_T128.
+ * Returns the split (>= 1); -1 (detr_hip_last_error) for a non-positive dimension, compute outside 0 .. 2 or max_split < 1. */
+int32_t detr_hip_gemm_split_plan(int32_t M, int32_t N, int32_t K, int32_t compute, int32_t max_split);
 int detr_hip_splitk_reduce_many(const detr_reduce_desc *descs, int32_t n, void *stream);
 /* n independent GEMMs in one call.  Consecutive members (up to 4) that share one kernel variant -- 64x64 tiles, same operand
  * layouts / storage types, no batch -- are issued as ONE launch (members on blockIdx.y) and their split-K reductions as one

@@ -72,6 +72,12 @@ int main(void) {
         EXPECT(detr_hip_gemm_ring_plan(33600, 256, 1000, rp) == 0);        /* K % 64 != 0: no plan */
         EXPECT(detr_hip_gemm_ring_plan(8400, 64, 512, NULL) == 0);         /* narrower than one column panel */
     }
+    /* split-K plan of a weight gradient: 128 x 128 tiles in bf16 and f32x3, 64 x 64 in fp32; its rejections */
+    EXPECT(detr_hip_gemm_split_plan(256, 1024, 33600, 1, 1024) == 16);
+    EXPECT(detr_hip_gemm_split_plan(256, 1024, 8400, 2, 1024) == 32);
+    EXPECT(detr_hip_gemm_split_plan(256, 256, 8400, 0, 1024) == 64 && detr_hip_gemm_split_plan(256, 256, 8400, 0, 8) == 8);
+    EXPECT(detr_hip_gemm_split_plan(0, 256, 8400, 0, 1024) == -1 && detr_hip_gemm_split_plan(256, 256, 8400, 3, 1024) == -1);
+    EXPECT(detr_hip_gemm_split_plan(256, 256, 8400, 0, 0) == -1 && strstr(detr_hip_last_error(), "max_split") != NULL);
 
     /* rejection paths: every descriptor entry point validates before it launches (no GPU is touched here) */
     EXPECT(detr_hip_gemm_f32(NULL, NULL) < 0);

@@ -215,6 +215,30 @@ def test_gemm_fused_rowsum_with_bf16_stored_operands(hip, M, N, K, sk):
     close(dbs[1], x16.double().sum(0), rtol=2e-5, what="grouped bf16-stored bias gradient 1")
 
 
+def test_weight_gradient_forms_follow_the_library_split_plan(hip):
+    """linear_wgrad and the engine's _wgrad build their launch through hip.wgrad_call: with the planned split (2048 rows of 64 x 64 in fp32:
+    16, the value of tests/golden/gemm_splits.json) they equal the explicit split_k GEMM, and where the plan is 1 (32 rows) the
+    residual = C form, bit for bit."""
+    from detr_tf.engine import DetrEngine
+    torch.manual_seed(5)
+    hip.ensure_workspace(DEV)
+    assert hip.pick_split_k(64, 64, 2048, compute=0) == 16 and hip.pick_split_k(64, 64, 32, compute=0) == 1
+    for rows in (2048, 32):
+        dy, x = g(torch.randn(rows, 64)), g(torch.randn(rows, 64))
+        dw0 = torch.zeros(64, 64, device=DEV) if rows == 2048 else g(torch.randn(64, 64))
+        want, lin, eng = dw0.clone(), dw0.clone(), dw0.clone()
+        if rows == 2048:
+            hip.gemm(64, 64, rows, dy, 64, 0, x, 64, 0, want, 64, split_k=16, compute=0)
+        else:
+            hip.gemm(64, 64, rows, dy, 64, 0, x, 64, 0, want, 64, residual=want, ldr=64, compute=0)
+        hip.linear_wgrad(dy, x, lin, compute=0)
+        DetrEngine._wgrad(64, 64, rows, dy, 64, x, 64, eng, 64, compute=0)
+        torch.cuda.synchronize()
+        close(want, dw0.double() + dy.double().t() @ x.double(), what=f"wgrad reference form, {rows} rows")
+        assert torch.equal(lin, want), f"linear_wgrad differs from the explicit form at {rows} rows"
+        assert torch.equal(eng, want), f"DetrEngine._wgrad differs from the explicit form at {rows} rows"
+
+
 def test_gemm_batched_attention_layout(hip):
     """scores[b,h] = Q_h K_h^T and O = P V_h on the [B, L, heads*32] layout used by the transformer."""
     torch.manual_seed(4)
@@ -1202,11 +1226,8 @@ def test_conv1x1_backward_fused_reads_dy_once(hip, M, use_mask, pad):
     da_ref = torch.empty(M, d1, device=DEV, dtype=torch.bfloat16)
     hip.gemm(M, d1, d2, dy, dy.stride(0), 1, w, w.stride(0), 1, da_ref, d1, mask=(a if use_mask else None), ldmask=(a.stride(0) if use_mask else 0), compute=1)
     dw_ref = dw0.clone()
-    sk = hip.pick_split_k(d1, d2, M)
-    if sk > 1:
-        hip.gemm(d1, d2, M, a, a.stride(0), 0, dy, dy.stride(0), 0, dw_ref, d2, alpha=0.5, scale=scale, split_k=sk, compute=1)
-    else:
-        hip.gemm(d1, d2, M, a, a.stride(0), 0, dy, dy.stride(0), 0, dw_ref, d2, alpha=0.5, scale=scale, residual=dw_ref, ldr=d2, compute=1)
+    args, kwargs = hip.wgrad_call(d1, d2, M, a, a.stride(0), dy, dy.stride(0), dw_ref, d2, alpha=0.5, scale=scale, compute=1)
+    hip.gemm(*args, **kwargs)
     torch.cuda.synchronize()
     assert torch.equal(outs[0][0].view(torch.int16), da_ref.view(torch.int16)), "input gradient differs from the GEMM's"
     a64, dy64 = a.double().cpu(), dy.double().cpu()
