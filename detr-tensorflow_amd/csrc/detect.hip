@@ -31,6 +31,9 @@ struct DetectArgs {
     int *counts;                                    // [B]
 };
 
+// SCORING: SCORE_SOFTMAX drops the queries whose label is the background class; under SCORE_SIGMOID every query is a candidate
+// and the threshold alone decides.
+template <int SCORING>
 __global__ __launch_bounds__(DET_THREADS) void detect_kernel(DetectArgs a) {
     __shared__ float s_score[PP_MAXQ];
     __shared__ int s_label[PP_MAXQ];
@@ -38,13 +41,13 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(DetectArgs a) {
     __shared__ int s_order[PP_MAXQ];             // s_order[rank] = position in s_kept
     __shared__ int s_wave_cnt[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    query_scores_labels(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label);
+    query_scores_labels<SCORING>(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label, a.background);
     __syncthreads();
 
     int n = 0;
     for (int q0 = 0; q0 < a.Q; q0 += DET_THREADS) {
         const int q = q0 + tid;
-        const bool keep = q < a.Q && s_label[q] != a.background && s_score[q] >= a.thr;
+        const bool keep = q < a.Q && (SCORING == SCORE_SIGMOID || s_label[q] != a.background) && s_score[q] >= a.thr;
         n = compact_pass(keep, n, s_wave_cnt, [&](int i, int) { s_kept[i] = q; });
     }
     rank_sort(n, [&](int i) { return s_score[s_kept[i]]; }, s_order);      // a kept score passed >= thr: never NaN, plain descending order
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(DetectArgs a) {
 
 using namespace detr;
 
-extern "C" int detr_hip_detect(const detr_detect_desc *d, void *stream) {
+static int launch_detect(const detr_detect_desc *d, int scoring, void *stream) {
     DETR_REQUIRE(d, "detect: null descriptor");
     DETR_REQUIRE(d->logits && d->boxes && d->sizes, "detect: null operand (logits, boxes, sizes)");
     DETR_REQUIRE(d->out_boxes && d->out_labels && d->out_scores && d->out_query && d->counts,
@@ -93,7 +96,21 @@ extern "C" int detr_hip_detect(const detr_detect_desc *d, void *stream) {
     a.thr = d->score_threshold;
     a.out_boxes = d->out_boxes; a.out_labels = reinterpret_cast<long long *>(d->out_labels); a.out_scores = d->out_scores;
     a.out_query = d->out_query; a.counts = d->counts;
-    hipLaunchKernelGGL(detect_kernel, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    if (scoring == SCORE_SIGMOID) {
+        DETR_REQUIRE(d->C >= 2, "detect: sigmoid scoring needs a class beside the background class, C=%d", d->C);
+        DETR_REQUIRE(d->background_class >= 0 && d->background_class < d->C, "detect: background_class=%d outside [0, C=%d)",
+                     d->background_class, d->C);
+        hipLaunchKernelGGL(detect_kernel<SCORE_SIGMOID>, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    } else {
+        hipLaunchKernelGGL(detect_kernel<SCORE_SOFTMAX>, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    }
     DETR_LAUNCH_CHECK("detect");
     return 0;
+}
+
+extern "C" int detr_hip_detect(const detr_detect_desc *d, void *stream) { return launch_detect(d, SCORE_SOFTMAX, stream); }
+
+extern "C" int detr_hip_detect_scored(const detr_detect_desc *d, int32_t scoring, void *stream) {
+    DETR_REQUIRE(scoring == SCORE_SOFTMAX || scoring == SCORE_SIGMOID, "detect: scoring=%d must be 0 (softmax) or 1 (sigmoid)", scoring);
+    return launch_detect(d, scoring, stream);
 }

@@ -11,12 +11,49 @@ constexpr int DET_THREADS = 256;  // 4 waves: the shape query_scores_labels and 
 constexpr int PP_MAXQ = 1024;     // queries / detections of one image held in LDS
 constexpr int DET_MAXR = 256;     // rows of the padded targets incl. the header (the loaders ship 100)
 
-// One wave per query, 4 waves: s_score[q] = max softmax probability, s_label[q] = first arg-max of the PROBABILITIES
-// (inference.py:73-75 takes argmax(softmax)) of the logit rows lg[q * sl_q + 0 .. C), q < Q.  The caller synchronises the workgroup.
-__device__ __forceinline__ void query_scores_labels(const float *lg, long long sl_q, int Q, int C, float *s_score, int *s_label) {
+// How a logit row becomes a (score, label): the scoring policy of query_scores_labels (the `scoring` argument of the *_scored
+// entry points, include/detr_hip.h).
+constexpr int SCORE_SOFTMAX = 0;  // max softmax probability over all C classes; the callers drop label == background
+constexpr int SCORE_SIGMOID = 1;  // sigmoid of the largest non-background logit: the class head of the focal criterion
+
+// The one sigmoid of the post-model kernels: every entry point that scores with SCORE_SIGMOID gives these bits.
+__device__ __forceinline__ float sigmoid_score(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// One wave per query, 4 waves; the logit rows are lg[q * sl_q + 0 .. C), q < Q.  The caller synchronises the workgroup.
+// SCORE_SOFTMAX: s_score[q] = max softmax probability, s_label[q] = first arg-max of the PROBABILITIES (inference.py:73-75 takes
+// argmax(softmax)); `background` is not read.
+// SCORE_SIGMOID: s_label[q] = first arg-max of the logits over c != background, s_score[q] = sigmoid of that logit (C >= 2).  A
+// NaN among those logits makes the score NaN (det_before ranks it last, no threshold accepts it); the label is the first arg-max of
+// the others, or the first non-background class when there is none.
+template <int SCORING = SCORE_SOFTMAX>
+__device__ __forceinline__ void query_scores_labels(const float *lg, long long sl_q, int Q, int C, float *s_score, int *s_label,
+                                                    int background = -1) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int q = wave; q < Q; q += 4) {
         const float *row = lg + q * sl_q;
+        if constexpr (SCORING == SCORE_SIGMOID) {
+            float best = -INFINITY;
+            int arg = INT_MAX;
+            bool nan = false;
+            for (int c = lane; c < C; c += 64) {
+                if (c == background) continue;
+                const float x = row[c];
+                nan |= x != x;
+                if (x > best) { best = x; arg = c; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ob = __shfl_xor(best, o, 64);
+                const int oa = __shfl_xor(arg, o, 64);
+                if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+            }
+            const bool any_nan = __ballot(nan) != 0ull;
+            if (lane == 0) {
+                s_score[q] = any_nan ? NAN : sigmoid_score(best);
+                s_label[q] = arg != INT_MAX ? arg : (background == 0 ? 1 : 0);
+            }
+            continue;
+        }
         float mx = -INFINITY;
         for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
         mx = wave_max(mx);

@@ -20,18 +20,21 @@ struct PostArgs {
     int *counts;                                    // [B]
 };
 
+// SCORING: SCORE_SOFTMAX drops the queries whose label is the background class; SCORE_SIGMOID keeps every query (its label is
+// never the background class), so image b gets its Q rows in query order.
+template <int SCORING>
 __global__ __launch_bounds__(DET_THREADS) void postprocess_kernel(PostArgs a) {
     __shared__ float s_score[PP_MAXQ];
     __shared__ int s_label[PP_MAXQ];
     __shared__ int s_wave_cnt[4];
     const int b = blockIdx.x;
-    query_scores_labels(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label);      // detections.h, shared with detect.hip
+    query_scores_labels<SCORING>(a.logits + b * a.sl_b, a.sl_q, a.Q, a.C, s_score, s_label, a.background);      // detections.h, shared with detect.hip
     __syncthreads();
     // order-preserving compaction: 256 queries per pass
     int base = 0;
     for (int q0 = 0; q0 < a.Q; q0 += DET_THREADS) {
         const int q = q0 + threadIdx.x;
-        const bool keep = q < a.Q && s_label[q] != a.background;
+        const bool keep = q < a.Q && (SCORING == SCORE_SIGMOID || s_label[q] != a.background);
         base = compact_pass(keep, base, s_wave_cnt, [&](int pos, int) {
             const float *bx = a.boxes + b * a.sb_b + q * a.sb_q;
             const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(DET_THREADS) void postprocess_kernel(PostArgs a) {
 
 using namespace detr;
 
-extern "C" int detr_hip_postprocess(const detr_postprocess_desc *d, void *stream) {
+static int launch_postprocess(const detr_postprocess_desc *d, int scoring, void *stream) {
     DETR_REQUIRE(d && d->logits && d->boxes && d->out_boxes && d->out_labels && d->out_scores && d->counts, "postprocess: null operand");
     DETR_REQUIRE(d->B > 0 && d->Q > 0 && d->Q <= PP_MAXQ && d->C > 0, "postprocess: bad shape B=%d Q=%d C=%d (Q <= %d)", d->B, d->Q, d->C, PP_MAXQ);
     DETR_REQUIRE(d->bbox_format >= 0 && d->bbox_format <= 2, "postprocess: bbox_format must be 0 (xy_center), 1 (xyxy) or 2 (yxyx)");
@@ -64,7 +67,21 @@ extern "C" int detr_hip_postprocess(const detr_postprocess_desc *d, void *stream
     a.boxes = d->boxes; a.sb_b = d->sB_b; a.sb_q = d->sB_q;
     a.B = d->B; a.Q = d->Q; a.C = d->C; a.background = d->background_class; a.fmt = d->bbox_format;
     a.out_boxes = d->out_boxes; a.out_labels = reinterpret_cast<long long *>(d->out_labels); a.out_scores = d->out_scores; a.counts = d->counts;
-    hipLaunchKernelGGL(postprocess_kernel, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    if (scoring == SCORE_SIGMOID) {
+        DETR_REQUIRE(d->C >= 2, "postprocess: sigmoid scoring needs a class beside the background class, C=%d", d->C);
+        DETR_REQUIRE(d->background_class >= 0 && d->background_class < d->C, "postprocess: background_class=%d outside [0, C=%d)",
+                     d->background_class, d->C);
+        hipLaunchKernelGGL(postprocess_kernel<SCORE_SIGMOID>, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    } else {
+        hipLaunchKernelGGL(postprocess_kernel<SCORE_SOFTMAX>, dim3(d->B), dim3(DET_THREADS), 0, (hipStream_t)stream, a);
+    }
     DETR_LAUNCH_CHECK("postprocess");
     return 0;
+}
+
+extern "C" int detr_hip_postprocess(const detr_postprocess_desc *d, void *stream) { return launch_postprocess(d, SCORE_SOFTMAX, stream); }
+
+extern "C" int detr_hip_postprocess_scored(const detr_postprocess_desc *d, int32_t scoring, void *stream) {
+    DETR_REQUIRE(scoring == SCORE_SOFTMAX || scoring == SCORE_SIGMOID, "postprocess: scoring=%d must be 0 (softmax) or 1 (sigmoid)", scoring);
+    return launch_postprocess(d, scoring, stream);
 }

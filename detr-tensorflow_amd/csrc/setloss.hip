@@ -9,7 +9,9 @@
 //                      logits / boxes                              loss.py:37-96, bbox.py:29-124,171-183
 // The weights of the criterion (matcher cost, loss terms, no-object weight, per-class weights) are a policy parameter of
 // the cost / sums / finalize / gradient kernels: FixedCriterion holds the reference's literals as constexpr members (the
-// entry points without a criterion argument), RuntimeCriterion a by-value block filled by the *_crit_* entry points.
+// entry points without a criterion argument), RuntimeCriterion a by-value block filled by the *_crit_* entry points.  The class
+// term is a second policy of the same four kernels: SoftmaxClass (the reference's cross-entropy) or FocalClass (sigmoid focal
+// loss, the *_focal_* entry points).
 // Compiled with -ffp-contract=off so that the box arithmetic rounds like the op-by-op reference.
 #include "common.h"
 #include <limits.h>
@@ -53,6 +55,58 @@ struct RuntimeCriterion {
     }
     __device__ __forceinline__ float weight_sum(const float *s) const { return eos * s[3] + s[1]; }
     __device__ __forceinline__ float box_count(float npos) const { return min_one ? fmaxf(npos, 1.0f) : npos; }
+};
+
+// ---- the class term, a second policy beside Crit: what a logit row costs in the matcher, adds to slot 0 of the sums, is
+// normalised by, and contributes to d_logits.  The box terms, the launch grid, the sums layout and the reduction through LDS
+// do not depend on it.
+// SoftmaxClass: the reference's weighted cross-entropy over the C classes, unmatched queries on the background class; the
+// kernels keep that arithmetic in their `else` branches, unchanged.
+struct SoftmaxClass {
+    static constexpr bool focal = false;
+    template <class Crit>
+    __device__ __forceinline__ float label_norm(const Crit &crit, const float *s) const { return crit.weight_sum(s); }
+};
+
+// FocalClass: sigmoid focal loss, every one of the C logits a binary problem (a matched query one-hot on its target's class, an
+// unmatched one all zero; no column is special).  With sp(z) = max(z, 0) + log1p(exp(-|z|)), p = sigmoid(x) = exp(-sp(-x)) and
+// 1 - p = exp(-sp(x)):
+//   t = 1:  alpha       * (1 - p)^gamma * -log(p)     = alpha       * exp(-gamma * sp(x))  * sp(-x)
+//   t = 0:  (1 - alpha) * p^gamma       * -log(1 - p) = (1 - alpha) * exp(-gamma * sp(-x)) * sp(x)
+// finite for every finite logit (no pow, no log of 0); a NaN logit gives NaN.  The level's sum is divided by max(matched, 1),
+// read from the count in slot 4, so the gradients stay a deterministic function of the matching.  eos and the class weights
+// of Crit are not read.
+struct FocalClass {
+    float alpha, gamma;
+    static constexpr bool focal = true;
+    template <class Crit>
+    __device__ __forceinline__ float label_norm(const Crit &, const float *s) const { return fmaxf(s[4], 1.0f); }
+    // sp(x) and sp(-x) from one exp and one log1p
+    static __device__ __forceinline__ void softplus_pair(float x, float &sx, float &snx) {
+        const float l = log1pf(expf(-fabsf(x)));
+        sx = fmaxf(x, 0.0f) + l;
+        snx = fmaxf(-x, 0.0f) + l;
+    }
+    __device__ __forceinline__ float elem(float x, bool positive) const {
+        float sx, snx;
+        softplus_pair(x, sx, snx);
+        const float w = positive ? alpha : 1.0f - alpha;
+        const float a = positive ? sx : snx, b = positive ? snx : sx;
+        return w * expf(-gamma * a) * b;
+    }
+    // d elem / dx: with sp'(x) = p and sp'(-x) = -(1 - p),
+    //   t = 1: -alpha       * exp(-gamma * sp(x))  * (gamma * p * sp(-x) + (1 - p))
+    //   t = 0:  (1 - alpha) * exp(-gamma * sp(-x)) * (gamma * (1 - p) * sp(x) + p)
+    __device__ __forceinline__ float d_elem(float x, bool positive) const {
+        float sx, snx;
+        softplus_pair(x, sx, snx);
+        const float w = positive ? -alpha : 1.0f - alpha;
+        const float a = positive ? sx : snx, b = positive ? snx : sx;
+        return w * expf(-gamma * a) * (gamma * expf(-b) * b + expf(-a));
+    }
+    // the matcher's class cost of giving a query to a target of this logit's class: what the element loses as a positive
+    // minus what it stops paying as a negative (no 1e-8 inside a log: the stable forms need none)
+    __device__ __forceinline__ float cost(float x) const { return elem(x, true) - elem(x, false); }
 };
 
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
@@ -99,8 +153,8 @@ constexpr int SL_MAXR = 128;
 
 constexpr int SL_QCHUNK = 8;      // queries per workgroup of the cost / sums / gradient kernels (two per wave)
 
-template <class Crit>
-__global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit crit, float *__restrict__ cost) {
+template <class Crit, class Cls>
+__global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit crit, Cls clsterm, float *__restrict__ cost) {
     __shared__ float s_max[SL_QCHUNK], s_sum[SL_QCHUNK];
     __shared__ float s_t[SL_MAXR][4];
     __shared__ int s_cls[SL_MAXR];
@@ -120,15 +174,17 @@ __global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit cri
     // blockIdx.y: a chunk of SL_QCHUNK queries of the problem (one workgroup per problem walked its 100 queries in 25 rounds of
     // wave reductions: 45-80 us of pure latency on the path between the forward and the backward pass)
     const int q0 = blockIdx.y * SL_QCHUNK, q1 = min(a.Q, q0 + SL_QCHUNK);
-    for (int q = q0 + wave; q < q1; q += 4) {
-        const float *row = lg + q * a.sL_q;
-        float mx = -INFINITY;
-        for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, row[c]);
-        mx = wave_max(mx);
-        float s = 0.f;
-        for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
-        s = wave_sum(s);
-        if (lane == 0) { s_max[q - q0] = mx; s_sum[q - q0] = s; }
+    if constexpr (!Cls::focal) {          // the softmax row statistics; the focal cost of an element needs its own logit alone
+        for (int q = q0 + wave; q < q1; q += 4) {
+            const float *row = lg + q * a.sL_q;
+            float mx = -INFINITY;
+            for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, row[c]);
+            mx = wave_max(mx);
+            float s = 0.f;
+            for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
+            s = wave_sum(s);
+            if (lane == 0) { s_max[q - q0] = mx; s_sum[q - q0] = s; }
+        }
     }
     __syncthreads();
     float *out = cost + (long long)p * a.Q * ldc;
@@ -139,9 +195,14 @@ __global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit cri
         const float pcx = pb[0], pcy = pb[1], pw = pb[2], ph = pb[3];
         const float tcx = s_t[j][0], tcy = s_t[j][1], tw = s_t[j][2], th = s_t[j][3];
         const int cls = s_cls[j];
-        float prob = 0.0f;
-        if (cls >= 0 && cls < a.C) prob = expf(lg[q * a.sL_q + cls] - s_max[ql]) / s_sum[ql];
-        const float cost_class = -prob;
+        float cost_class;
+        if constexpr (Cls::focal) {
+            cost_class = (cls >= 0 && cls < a.C) ? clsterm.cost(lg[q * a.sL_q + cls]) : 0.0f;      // a label outside [0, C) costs 0
+        } else {
+            float prob = 0.0f;
+            if (cls >= 0 && cls < a.C) prob = expf(lg[q * a.sL_q + cls] - s_max[ql]) / s_sum[ql];
+            cost_class = -prob;
+        }
         const float cost_bbox = fabsf(pcx - tcx) + fabsf(pcy - tcy) + fabsf(pw - tw) + fabsf(ph - th);
         const float cost_giou = -giou_of(to_xyxy(pcx, pcy, pw, ph), to_xyxy(tcx, tcy, tw, th));
         out[q * ldc + j] = crit.cost_bbox * cost_bbox + crit.cost_class * cost_class + crit.cost_giou * cost_giou;
@@ -434,8 +495,8 @@ __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ co
 // matched part of the normaliser is accumulated (slot 1) but stays exact all the same: the weights are multiples of 1/64 up
 // to 16 and at most 16384 of them are added, so every partial sum is a multiple of 1/64 below 2^24 / 64 -- a float.
 
-template <class Crit>
-__global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, Crit crit, const int *__restrict__ tgt_for_pred,
+template <class Crit, class Cls>
+__global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, Crit crit, Cls clsterm, const int *__restrict__ tgt_for_pred,
                                                             float *__restrict__ sums) {
     const int p = blockIdx.x;
     const int lv = p / a.B, b = p % a.B;
@@ -449,45 +510,83 @@ __global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, Crit 
     for (int q = q0 + wave; q < q1; q += 4) {
         const float *row = lg + q * a.sL_q;
         const int t = tgt_for_pred[(long long)p * a.Q + q];
-        // logsumexp + first-occurrence argmax over the classes
-        float mx = -INFINITY;
-        int am = INT_MAX;
-        for (int c = lane; c < a.C; c += 64) {
-            const float x = row[c];
-            if (x > mx) { mx = x; am = c; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float om = __shfl_xor(mx, o, 64);
-            const int oa = __shfl_xor(am, o, 64);
-            if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
-        }
-        float s = 0.f;
-        for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
-        s = wave_sum(s);
-        if (lane == 0) {
-            const float lse = logf(s) + mx;
-            if (t < 0) {
-                const float ce = lse - row[a.background_class];
-                acc[0] += crit.eos * ce;
-                acc[2] += (am == a.background_class) ? 1.f : 0.f;
-                acc[3] += 1.f;
-            } else {
-                const int cls = (int)a.t_class[(long long)b * a.R + 1 + t];
-                // a label outside [0, C) (e.g. the wrong nb_class when finetuning): no out-of-bounds read; the loss turns
-                // NaN like tf.nn.sparse_softmax_cross_entropy_with_logits on the GPU (the CPU op raises)
-                const float ce = (cls >= 0 && cls < a.C) ? lse - row[cls] : NAN;
-                const float w = crit.class_weight(cls, a.C);
-                acc[0] += w * ce;
-                if (Crit::weighted) acc[1] += w;      // slot 1 stays 0 under the fixed criterion
-                acc[4] += 1.f;
-                acc[5] += (am != a.background_class) ? 1.f : 0.f;
-                acc[6] += (am == cls) ? 1.f : 0.f;
-                const float *pb = bx + q * a.sB_q;
-                const float *tb = a.t_bbox + ((long long)b * a.R + 1 + t) * 4;
-                acc[7] += fabsf(pb[0] - tb[0]) + fabsf(pb[1] - tb[1]) + fabsf(pb[2] - tb[2]) + fabsf(pb[3] - tb[3]);
-                acc[8] += 1.0f - giou_of(to_xyxy(pb[0], pb[1], pb[2], pb[3]), to_xyxy(tb[0], tb[1], tb[2], tb[3]));
+        if constexpr (Cls::focal) {
+            // lanes stride over the classes: the elements of the row (one-hot on the target's class, all zero when unmatched) and
+            // the first arg-max over the non-background logits; one wave_sum per query
+            const int cls = (t < 0) ? -1 : (int)a.t_class[(long long)b * a.R + 1 + t];
+            float e = 0.f, mx = -INFINITY;
+            int am = INT_MAX;
+            for (int c = lane; c < a.C; c += 64) {
+                const float x = row[c];
+                e += clsterm.elem(x, c == cls);
+                if (c != a.background_class && x > mx) { mx = x; am = c; }
             }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float om = __shfl_xor(mx, o, 64);
+                const int oa = __shfl_xor(am, o, 64);
+                if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
+            }
+            e = wave_sum(e);
+            if (lane == 0) {
+                // the query predicts background when its largest non-background logit is <= 0 (every such sigmoid <= 1/2)
+                const int pred = (mx > 0.f) ? am : a.background_class;
+                if (t < 0) {
+                    acc[0] += e;
+                    acc[2] += (pred == a.background_class) ? 1.f : 0.f;
+                    acc[3] += 1.f;
+                } else {
+                    // a label outside [0, C): no element was read out of bounds (no column equals it); the loss turns NaN as
+                    // under the softmax criterion
+                    acc[0] += (cls >= 0 && cls < a.C) ? e : NAN;
+                    acc[4] += 1.f;
+                    acc[5] += (pred != a.background_class) ? 1.f : 0.f;
+                    acc[6] += (pred == cls) ? 1.f : 0.f;
+                }
+            }
+        } else {
+            // logsumexp + first-occurrence argmax over the classes
+            float mx = -INFINITY;
+            int am = INT_MAX;
+            for (int c = lane; c < a.C; c += 64) {
+                const float x = row[c];
+                if (x > mx) { mx = x; am = c; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float om = __shfl_xor(mx, o, 64);
+                const int oa = __shfl_xor(am, o, 64);
+                if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
+            }
+            float s = 0.f;
+            for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
+            s = wave_sum(s);
+            if (lane == 0) {
+                const float lse = logf(s) + mx;
+                if (t < 0) {
+                    const float ce = lse - row[a.background_class];
+                    acc[0] += crit.eos * ce;
+                    acc[2] += (am == a.background_class) ? 1.f : 0.f;
+                    acc[3] += 1.f;
+                } else {
+                    const int cls = (int)a.t_class[(long long)b * a.R + 1 + t];
+                    // a label outside [0, C) (e.g. the wrong nb_class when finetuning): no out-of-bounds read; the loss turns
+                    // NaN like tf.nn.sparse_softmax_cross_entropy_with_logits on the GPU (the CPU op raises)
+                    const float ce = (cls >= 0 && cls < a.C) ? lse - row[cls] : NAN;
+                    const float w = crit.class_weight(cls, a.C);
+                    acc[0] += w * ce;
+                    if (Crit::weighted) acc[1] += w;      // slot 1 stays 0 under the fixed criterion
+                    acc[4] += 1.f;
+                    acc[5] += (am != a.background_class) ? 1.f : 0.f;
+                    acc[6] += (am == cls) ? 1.f : 0.f;
+                }
+            }
+        }
+        if (lane == 0 && t >= 0) {            // the box sums of a matched pair, whatever the class term
+            const float *pb = bx + q * a.sB_q;
+            const float *tb = a.t_bbox + ((long long)b * a.R + 1 + t) * 4;
+            acc[7] += fabsf(pb[0] - tb[0]) + fabsf(pb[1] - tb[1]) + fabsf(pb[2] - tb[2]) + fabsf(pb[3] - tb[3]);
+            acc[8] += 1.0f - giou_of(to_xyxy(pb[0], pb[1], pb[2], pb[3]), to_xyxy(tb[0], tb[1], tb[2], tb[3]));
         }
     }
     // the four waves' partials are combined in LDS first: one set of atomics per workgroup (with a workgroup per query chunk
@@ -505,8 +604,8 @@ __global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, Crit 
     }
 }
 
-template <class Crit>
-__global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int levels, Crit crit, float *__restrict__ losses,
+template <class Crit, class Cls>
+__global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int levels, Crit crit, Cls clsterm, float *__restrict__ losses,
                                          float *__restrict__ total) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float tot = 0.f;
@@ -515,7 +614,7 @@ __global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int lev
         const int lv = (k == 0) ? levels - 1 : k - 1;
         const float *s = sums + lv * 8;
         const float *sb = sums + levels * 8 + lv * 2;
-        const float label = s[0] / crit.weight_sum(s);
+        const float label = s[0] / clsterm.label_norm(crit, s);
         const float npos = s[4];                   // the metrics divide by the raw count: 0 / 0 without a matched pair
         const float nbox = crit.box_count(npos);
         const float giou = sb[1] / nbox;
@@ -534,8 +633,8 @@ __global__ void set_loss_finalize_kernel(const float *__restrict__ sums, int lev
     total[0] = tot;
 }
 
-template <class Crit>
-__global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, Crit crit, const int *__restrict__ tgt_for_pred,
+template <class Crit, class Cls>
+__global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, Crit crit, Cls clsterm, const int *__restrict__ tgt_for_pred,
                                                             const float *__restrict__ sums, float loss_scale,
                                                             float *__restrict__ d_logits, float *__restrict__ d_boxes) {
     const int p = blockIdx.x;
@@ -545,23 +644,30 @@ __global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, Crit 
     float *dlg = d_logits + lv * a.sL_l + b * a.sL_b;
     float *dbx = d_boxes + lv * a.sB_l + b * a.sB_b;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float sw = crit.weight_sum(sums + lv * 8);
+    const float sw = clsterm.label_norm(crit, sums + lv * 8);
     const float npos = crit.box_count(sums[lv * 8 + 4]);
     const int q0 = blockIdx.y * SL_QCHUNK, q1 = min(a.Q, q0 + SL_QCHUNK);
     for (int q = q0 + wave; q < q1; q += 4) {
         const float *row = lg + q * a.sL_q;
         const int t = tgt_for_pred[(long long)p * a.Q + q];
-        float mx = -INFINITY;
-        for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, row[c]);
-        mx = wave_max(mx);
-        float s = 0.f;
-        for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
-        s = wave_sum(s);
-        const int cls = (t < 0) ? a.background_class : (int)a.t_class[(long long)b * a.R + 1 + t];
-        const float wq = crit.w_label * ((t < 0) ? crit.eos : crit.class_weight(cls, a.C)) / sw * loss_scale;
-        for (int c = lane; c < a.C; c += 64) {
-            const float sm = expf(row[c] - mx) / s;
-            dlg[q * a.sL_q + c] = wq * (sm - (c == cls ? 1.0f : 0.0f));
+        if constexpr (Cls::focal) {
+            // every lane writes its columns; an unmatched query and a label outside [0, C) have no positive column
+            const int cls = (t < 0) ? -1 : (int)a.t_class[(long long)b * a.R + 1 + t];
+            const float wq = crit.w_label / sw * loss_scale;
+            for (int c = lane; c < a.C; c += 64) dlg[q * a.sL_q + c] = wq * clsterm.d_elem(row[c], c == cls);
+        } else {
+            float mx = -INFINITY;
+            for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, row[c]);
+            mx = wave_max(mx);
+            float s = 0.f;
+            for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
+            s = wave_sum(s);
+            const int cls = (t < 0) ? a.background_class : (int)a.t_class[(long long)b * a.R + 1 + t];
+            const float wq = crit.w_label * ((t < 0) ? crit.eos : crit.class_weight(cls, a.C)) / sw * loss_scale;
+            for (int c = lane; c < a.C; c += 64) {
+                const float sm = expf(row[c] - mx) / s;
+                dlg[q * a.sL_q + c] = wq * (sm - (c == cls ? 1.0f : 0.0f));
+            }
         }
         if (lane == 0) {
             float g[4] = {0.f, 0.f, 0.f, 0.f};
@@ -649,45 +755,54 @@ static int fill_criterion(const float *c, const float *class_weights, RuntimeCri
     return 0;
 }
 
-// One launcher per kernel: the fixed and the run-time criterion differ in the policy object alone.
-template <class Crit>
-static int launch_match_cost(const detr_setloss_desc *d, const Crit &crit, float *cost, void *stream) {
+// The host block of the *_focal_* entry points (DETR_FOCAL_FLOATS floats) -> the class-term policy.
+static int fill_focal(const float *f, FocalClass &r) {
+    DETR_REQUIRE(f != nullptr, "setloss: null focal block");
+    DETR_REQUIRE(std::isfinite(f[0]) && f[0] > 0.0f && f[0] < 1.0f, "setloss: focal[0] (alpha) = %g is not inside (0, 1)", (double)f[0]);
+    DETR_REQUIRE(std::isfinite(f[1]) && f[1] >= 0.0f && f[1] <= 8.0f, "setloss: focal[1] (gamma) = %g is not inside [0, 8]", (double)f[1]);
+    r.alpha = f[0]; r.gamma = f[1];
+    return 0;
+}
+
+// One launcher per kernel: the entry points differ in the two policy objects alone.
+template <class Crit, class Cls>
+static int launch_match_cost(const detr_setloss_desc *d, const Crit &crit, const Cls &cls, float *cost, void *stream) {
     SetLossArgs a;
     if (fill_args(d, a)) return -1;
     DETR_REQUIRE(cost, "match_cost: null cost");
-    hipLaunchKernelGGL(match_cost_kernel<Crit>, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
-                       cost);
+    hipLaunchKernelGGL((match_cost_kernel<Crit, Cls>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
+                       cls, cost);
     DETR_LAUNCH_CHECK("match_cost");
     return 0;
 }
 
-template <class Crit>
-static int launch_sums(const detr_setloss_desc *d, const Crit &crit, const int32_t *tgt_for_pred, float *sums, void *stream) {
+template <class Crit, class Cls>
+static int launch_sums(const detr_setloss_desc *d, const Crit &crit, const Cls &cls, const int32_t *tgt_for_pred, float *sums, void *stream) {
     SetLossArgs a;
     if (fill_args(d, a)) return -1;
     DETR_REQUIRE(tgt_for_pred && sums, "set_loss_sums: null operand");
-    hipLaunchKernelGGL(set_loss_sums_kernel<Crit>, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
-                       tgt_for_pred, sums);
+    hipLaunchKernelGGL((set_loss_sums_kernel<Crit, Cls>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
+                       cls, tgt_for_pred, sums);
     DETR_LAUNCH_CHECK("set_loss_sums");
     return 0;
 }
 
-template <class Crit>
-static int launch_finalize(const float *sums, int32_t levels, const Crit &crit, float *losses, float *total, void *stream) {
+template <class Crit, class Cls>
+static int launch_finalize(const float *sums, int32_t levels, const Crit &crit, const Cls &cls, float *losses, float *total, void *stream) {
     DETR_REQUIRE(sums && losses && total && levels > 0, "set_loss_finalize: bad args");
-    hipLaunchKernelGGL(set_loss_finalize_kernel<Crit>, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, levels, crit, losses, total);
+    hipLaunchKernelGGL((set_loss_finalize_kernel<Crit, Cls>), dim3(1), dim3(64), 0, (hipStream_t)stream, sums, levels, crit, cls, losses, total);
     DETR_LAUNCH_CHECK("set_loss_finalize");
     return 0;
 }
 
-template <class Crit>
-static int launch_grad(const detr_setloss_desc *d, const Crit &crit, const int32_t *tgt_for_pred, const float *sums, float loss_scale,
+template <class Crit, class Cls>
+static int launch_grad(const detr_setloss_desc *d, const Crit &crit, const Cls &cls, const int32_t *tgt_for_pred, const float *sums, float loss_scale,
                        float *d_logits, float *d_boxes, void *stream) {
     SetLossArgs a;
     if (fill_args(d, a)) return -1;
     DETR_REQUIRE(tgt_for_pred && sums && d_logits && d_boxes, "set_loss_grad: null operand");
-    hipLaunchKernelGGL(set_loss_grad_kernel<Crit>, dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
-                       tgt_for_pred, sums, loss_scale, d_logits, d_boxes);
+    hipLaunchKernelGGL((set_loss_grad_kernel<Crit, Cls>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
+                       cls, tgt_for_pred, sums, loss_scale, d_logits, d_boxes);
     DETR_LAUNCH_CHECK("set_loss_grad");
     return 0;
 }
@@ -697,7 +812,7 @@ static int launch_grad(const detr_setloss_desc *d, const Crit &crit, const int32
 using namespace detr;
 
 extern "C" int detr_hip_match_cost_f32(const detr_setloss_desc *d, float *cost, void *stream) {
-    return launch_match_cost(d, FixedCriterion(), cost, stream);
+    return launch_match_cost(d, FixedCriterion(), SoftmaxClass(), cost, stream);
 }
 
 extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int32_t ldc, const float *t_bbox, int32_t B,
@@ -746,38 +861,38 @@ extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int3
 
 extern "C" int detr_hip_set_loss_sums_f32(const detr_setloss_desc *d, const int32_t *tgt_for_pred, float *sums,
                                           void *stream) {
-    return launch_sums(d, FixedCriterion(), tgt_for_pred, sums, stream);
+    return launch_sums(d, FixedCriterion(), SoftmaxClass(), tgt_for_pred, sums, stream);
 }
 
 extern "C" int detr_hip_set_loss_finalize_f32(const float *sums, int32_t levels, float *losses, float *total,
                                               void *stream) {
-    return launch_finalize(sums, levels, FixedCriterion(), losses, total, stream);
+    return launch_finalize(sums, levels, FixedCriterion(), SoftmaxClass(), losses, total, stream);
 }
 
 extern "C" int detr_hip_set_loss_grad_f32(const detr_setloss_desc *d, const int32_t *tgt_for_pred, const float *sums,
                                           float loss_scale, float *d_logits, float *d_boxes, void *stream) {
-    return launch_grad(d, FixedCriterion(), tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
+    return launch_grad(d, FixedCriterion(), SoftmaxClass(), tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
 }
 
 // ---- the same four launches with the criterion as an argument (checked on the host before anything is launched) ----
 extern "C" int detr_hip_match_cost_crit_f32(const detr_setloss_desc *d, const float *criterion, float *cost, void *stream) {
     RuntimeCriterion c;
     if (fill_criterion(criterion, nullptr, c)) return -1;
-    return launch_match_cost(d, c, cost, stream);
+    return launch_match_cost(d, c, SoftmaxClass(), cost, stream);
 }
 
 extern "C" int detr_hip_set_loss_sums_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
                                                const int32_t *tgt_for_pred, float *sums, void *stream) {
     RuntimeCriterion c;
     if (fill_criterion(criterion, class_weights, c)) return -1;
-    return launch_sums(d, c, tgt_for_pred, sums, stream);
+    return launch_sums(d, c, SoftmaxClass(), tgt_for_pred, sums, stream);
 }
 
 extern "C" int detr_hip_set_loss_finalize_crit_f32(const float *sums, int32_t levels, const float *criterion, float *losses,
                                                    float *total, void *stream) {
     RuntimeCriterion c;
     if (fill_criterion(criterion, nullptr, c)) return -1;
-    return launch_finalize(sums, levels, c, losses, total, stream);
+    return launch_finalize(sums, levels, c, SoftmaxClass(), losses, total, stream);
 }
 
 extern "C" int detr_hip_set_loss_grad_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
@@ -785,5 +900,40 @@ extern "C" int detr_hip_set_loss_grad_crit_f32(const detr_setloss_desc *d, const
                                                float *d_boxes, void *stream) {
     RuntimeCriterion c;
     if (fill_criterion(criterion, class_weights, c)) return -1;
-    return launch_grad(d, c, tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
+    return launch_grad(d, c, SoftmaxClass(), tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
+}
+
+// ---- the sigmoid focal class term on the run-time criterion (checked on the host before anything is launched): eos_coef is
+// not read and there are no class weights ----
+extern "C" int detr_hip_match_cost_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal, float *cost,
+                                             void *stream) {
+    RuntimeCriterion c;
+    FocalClass f;
+    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
+    return launch_match_cost(d, c, f, cost, stream);
+}
+
+extern "C" int detr_hip_set_loss_sums_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal,
+                                                const int32_t *tgt_for_pred, float *sums, void *stream) {
+    RuntimeCriterion c;
+    FocalClass f;
+    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
+    return launch_sums(d, c, f, tgt_for_pred, sums, stream);
+}
+
+extern "C" int detr_hip_set_loss_finalize_focal_f32(const float *sums, int32_t levels, const float *criterion, const float *focal,
+                                                    float *losses, float *total, void *stream) {
+    RuntimeCriterion c;
+    FocalClass f;
+    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
+    return launch_finalize(sums, levels, c, f, losses, total, stream);
+}
+
+extern "C" int detr_hip_set_loss_grad_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal,
+                                                const int32_t *tgt_for_pred, const float *sums, float loss_scale, float *d_logits,
+                                                float *d_boxes, void *stream) {
+    RuntimeCriterion c;
+    FocalClass f;
+    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
+    return launch_grad(d, c, f, tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
 }

@@ -312,6 +312,11 @@ _SIGNATURES = {
     "detr_hip_set_loss_sums_crit_f32": [POINTER(SetLossDesc), POINTER(c_float), f32p, c_void_p, f32p, c_void_p],
     "detr_hip_set_loss_finalize_crit_f32": [f32p, c_int32, POINTER(c_float), f32p, f32p, c_void_p],
     "detr_hip_set_loss_grad_crit_f32": [POINTER(SetLossDesc), POINTER(c_float), f32p, c_void_p, f32p, c_float, f32p, f32p, c_void_p],
+    # ... and with the sigmoid focal class term: CRITERION_FLOATS and FOCAL_FLOATS host floats, no class weights
+    "detr_hip_match_cost_focal_f32": [POINTER(SetLossDesc), POINTER(c_float), POINTER(c_float), f32p, c_void_p],
+    "detr_hip_set_loss_sums_focal_f32": [POINTER(SetLossDesc), POINTER(c_float), POINTER(c_float), c_void_p, f32p, c_void_p],
+    "detr_hip_set_loss_finalize_focal_f32": [f32p, c_int32, POINTER(c_float), POINTER(c_float), f32p, f32p, c_void_p],
+    "detr_hip_set_loss_grad_focal_f32": [POINTER(SetLossDesc), POINTER(c_float), POINTER(c_float), c_void_p, f32p, c_float, f32p, f32p, c_void_p],
     "detr_hip_sumsq_segments_f32": [f32p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, f32p, c_void_p],
     "detr_hip_clip_adam_f32": [f32p, f32p, f32p, f32p, c_void_p, c_void_p, c_void_p, c_void_p, f32p, f32p, c_int32, c_int32, c_void_p],
     "detr_hip_axpy_f32": [f32p, f32p, c_float, c_int64, c_void_p],
@@ -330,6 +335,8 @@ _SIGNATURES = {
     "detr_hip_track_embed": [POINTER(TrackEmbedDesc), c_void_p],
     "detr_hip_track_motion": [POINTER(TrackMotionDesc), c_void_p],
     "detr_hip_fuse_views": [POINTER(TileMergeDesc), c_void_p, POINTER(ctypes.c_double * FUSE_PARAMS), c_void_p, c_void_p],
+    "detr_hip_postprocess_scored": [POINTER(PostprocessDesc), c_int32, c_void_p],
+    "detr_hip_detect_scored": [POINTER(DetectDesc), c_int32, c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
@@ -352,6 +359,8 @@ _SIGNATURES_I64 = {
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIGNATURES_I64) + ["detr_hip_last_error"])
 ABI_VERSION = 9
 CRITERION_FLOATS = 8                                                           # DETR_CRITERION_FLOATS
+FOCAL_FLOATS = 2                                                               # DETR_FOCAL_FLOATS: alpha, gamma
+SCORINGS = {"softmax": 0, "sigmoid": 1}                                        # the `scoring` argument of the *_scored entry points
 # detr_hip_struct_layout's `which` -> mirror, every descriptor struct of include/detr_hip.h (the table above the entry point there)
 LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: LayerNormDesc, 5: AttnDesc, 6: SetLossDesc, 7: InputDesc,
                   8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc, 400: TrackDesc,

@@ -12,13 +12,13 @@ import numpy as np
 import torch
 
 from . import bbox
-from .inference import get_model_inference_batched
+from .inference import _scoring, get_model_inference_batched, scoring_of
 from .loss.coco_eval import COCOAccumulator, DeviceCOCOAccumulator, check_meta
 from .loss.compute_map import APAccumulator, DeviceAPAccumulator
 
 
-def _add_batch_host(acc, model, m_outputs, target_bbox, target_class, background_class):
-    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx")
+def _add_batch_host(acc, model, m_outputs, target_bbox, target_class, background_class, scoring="softmax"):
+    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx", scoring=scoring)
     if getattr(model, "engine", None) is not None:
         model.engine.check_mask_status()      # (padded batches with a device mask; the detections are read on the host anyway)
     tb = torch.as_tensor(np.asarray(target_bbox) if not torch.is_tensor(target_bbox) else target_bbox).float().cpu()
@@ -34,8 +34,8 @@ def _host(x):
     return (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).cpu()
 
 
-def _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, background_class):
-    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx")
+def _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, background_class, scoring="softmax"):
+    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx", scoring=scoring)
     if getattr(model, "engine", None) is not None:
         model.engine.check_mask_status()
     tb, tc = _host(target_bbox).float(), _host(target_class)
@@ -47,7 +47,7 @@ def _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta,
                       crowd[b, 1:1 + n], area[b, 1:1 + n], size[b])
 
 
-def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate):
+def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate, scoring="softmax"):
     acc = COCOAccumulator(len(class_names))
     for it, batch in enumerate(valid_dt):
         if not isinstance(batch, (tuple, list)) or len(batch) != 4:
@@ -59,11 +59,11 @@ def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_re
         if accumulate == "device":
             if it == 0:
                 acc = DeviceCOCOAccumulator(len(class_names), device=m_outputs["pred_logits"].device)
-            acc.add_batch(m_outputs, target_bbox, target_class, meta, config.background_class)
+            acc.add_batch(m_outputs, target_bbox, target_class, meta, config.background_class, scoring)
             if getattr(model, "engine", None) is not None:
                 model.engine.check_mask_status()
         else:
-            _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, config.background_class)
+            _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, config.background_class, scoring)
         if max_batches is not None and it + 1 >= max_batches:
             break
     return acc.result(class_names, print_result=print_result)
@@ -73,8 +73,12 @@ def eval_model(model, config, class_names, valid_dt, max_batches=None, print_res
                **options):
     """options: weights="model" (default) | "ema", keyword-only.  "ema" evaluates the averaged weights kept by config.ema_decay:
     the whole evaluation runs inside optimizers.ema_weights(model), and the trained weights are back, bit for bit, when it
-    returns."""
+    returns.  scoring="softmax" | "sigmoid" (get_model_inference_batched's), keyword-only; None (default) takes it from
+    config.class_criterion: "focal" -> "sigmoid"."""
     weights = options.pop("weights", "model")
+    scoring = options.pop("scoring", None)
+    scoring = scoring_of(config) if scoring is None else scoring
+    _scoring(scoring)
     if options:
         raise TypeError(f"eval_model() got an unexpected keyword argument {sorted(options)[0]!r}")
     if accumulate not in ("host", "device"):
@@ -86,20 +90,20 @@ def eval_model(model, config, class_names, valid_dt, max_batches=None, print_res
     if weights == "ema":
         from .optimizers import ema_weights
         with ema_weights(model):
-            return eval_model(model, config, class_names, valid_dt, max_batches, print_result, accumulate, protocol=protocol)
+            return eval_model(model, config, class_names, valid_dt, max_batches, print_result, accumulate, protocol=protocol, scoring=scoring)
     if protocol == "coco":
-        return _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate)
+        return _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate, scoring)
     acc = APAccumulator(len(class_names))
     for it, (images, target_bbox, target_class) in enumerate(valid_dt):
         m_outputs = model(images, training=False)
         if accumulate == "device":
             if it == 0:
                 acc = DeviceAPAccumulator(len(class_names), device=m_outputs["pred_logits"].device)
-            acc.add_batch(m_outputs, target_bbox, target_class, config.background_class)
+            acc.add_batch(m_outputs, target_bbox, target_class, config.background_class, scoring)
             if getattr(model, "engine", None) is not None:
                 model.engine.check_mask_status()  # (reads the mask status words of a padded batch; a no-op for an unpadded one)
         else:
-            _add_batch_host(acc, model, m_outputs, target_bbox, target_class, config.background_class)
+            _add_batch_host(acc, model, m_outputs, target_bbox, target_class, config.background_class, scoring)
         if max_batches is not None and it + 1 >= max_batches:
             break
     return acc.result(class_names, print_result=print_result)

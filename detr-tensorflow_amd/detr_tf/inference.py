@@ -62,9 +62,23 @@ def _fill_model_outputs(d, logits, boxes, background_class):
     d.background_class = int(background_class)
 
 
-def _post(logits, boxes, background_class, bbox_format):
+def _scoring(scoring):
+    """The `scoring` argument of the *_scored entry points: "softmax" (max softmax probability, background queries dropped) or
+    "sigmoid" (sigmoid of the best non-background logit, every query a candidate: the class head of the focal criterion)."""
+    if scoring not in hip.SCORINGS:
+        raise ValueError(f"scoring must be one of {tuple(hip.SCORINGS)}, got {scoring!r}")
+    return hip.SCORINGS[scoring]
+
+
+def scoring_of(config):
+    """The scoring that goes with a config's class criterion: "sigmoid" for class_criterion = "focal", else "softmax"."""
+    return "sigmoid" if getattr(config, "class_criterion", "softmax") == "focal" else "softmax"
+
+
+def _post(logits, boxes, background_class, bbox_format, scoring="softmax"):
     if bbox_format not in BBOX_FORMATS:
         raise NotImplementedError()                                     # inference.py:92-93
+    mode = _scoring(scoring)
     logits, boxes = _model_outputs("get_model_inference", "post-processing", logits, boxes)
     B, Q, _ = logits.shape
     dev = logits.device
@@ -76,21 +90,26 @@ def _post(logits, boxes, background_class, bbox_format):
     _fill_model_outputs(d, logits, boxes, background_class)
     d.B, d.bbox_format = B, BBOX_FORMATS[bbox_format]
     d.out_boxes, d.out_labels, d.out_scores, d.counts = out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), counts.data_ptr()
-    hip._check(hip.load().detr_hip_postprocess(byref(d), hip._stream()), "detr_hip_postprocess")
+    if mode == 0:
+        hip._check(hip.load().detr_hip_postprocess(byref(d), hip._stream()), "detr_hip_postprocess")
+    else:
+        hip._check(hip.load().detr_hip_postprocess_scored(byref(d), mode, hip._stream()), "detr_hip_postprocess_scored")
     return out_b, out_l, out_s, counts
 
 
-def get_model_inference_batched(m_outputs: dict, background_class, bbox_format="xy_center"):
+def get_model_inference_batched(m_outputs: dict, background_class, bbox_format="xy_center", scoring="softmax"):
     """[(boxes [k_b, 4], labels [k_b] int64, scores [k_b])] for every image b of the batch: one kernel launch and ONE
-    host synchronisation (the per-image detection counts)."""
-    out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"], m_outputs["pred_boxes"], background_class, bbox_format)
+    host synchronisation (the per-image detection counts).  scoring="sigmoid": all Q queries of every image, in query order,
+    scored by the sigmoid of their best non-background logit."""
+    out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"], m_outputs["pred_boxes"], background_class, bbox_format, scoring)
     n = counts.tolist()
     return [(out_b[b, :k], out_l[b, :k], out_s[b, :k]) for b, k in enumerate(n)]
 
 
-def get_model_inference(m_outputs: dict, background_class, bbox_format="xy_center"):
-    """inference.py:68-95: (predicted_bbox, predicted_labels, predicted_scores) of batch element 0."""
-    out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"][0:1], m_outputs["pred_boxes"][0:1], background_class, bbox_format)
+def get_model_inference(m_outputs: dict, background_class, bbox_format="xy_center", scoring="softmax"):
+    """inference.py:68-95: (predicted_bbox, predicted_labels, predicted_scores) of batch element 0; scoring as
+    get_model_inference_batched."""
+    out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"][0:1], m_outputs["pred_boxes"][0:1], background_class, bbox_format, scoring)
     k = int(counts[0])
     return out_b[0, :k], out_l[0, :k], out_s[0, :k]
 
@@ -142,7 +161,8 @@ def _ranked_rows(B, K, dev, n_index):
             torch.empty(B, K, dtype=torch.float32, device=dev), *(torch.empty(B, K, dtype=torch.int32, device=dev) for _ in range(n_index)))
 
 
-def _detect(logits, boxes, sizes, background_class, score_threshold, max_detections, bbox_format, clip):
+def _detect(logits, boxes, sizes, background_class, score_threshold, max_detections, bbox_format, clip, scoring="softmax"):
+    mode = _scoring(scoring)
     _check_model_outputs("detect", "B", logits, boxes)
     B, Q, _ = logits.shape
     _check_detect_args(bbox_format, score_threshold, max_detections, Q)
@@ -160,20 +180,26 @@ def _detect(logits, boxes, sizes, background_class, score_threshold, max_detecti
     d.max_detections, d.bbox_format, d.clip = K, DETECT_FORMATS[bbox_format], int(bool(clip))
     d.out_boxes, d.out_labels, d.out_scores, d.out_query, d.counts = (out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), out_q.data_ptr(),
                                                                       counts.data_ptr())
-    hip._check(hip.load().detr_hip_detect(byref(d), hip._stream()), "detr_hip_detect")
+    if mode == 0:
+        hip._check(hip.load().detr_hip_detect(byref(d), hip._stream()), "detr_hip_detect")
+    else:
+        hip._check(hip.load().detr_hip_detect_scored(byref(d), mode, hip._stream()), "detr_hip_detect_scored")
     return out_b, out_l, out_s, out_q, counts
 
 
-def detect_batched(m_outputs: dict, sizes, background_class, *, score_threshold=0.0, max_detections=None, bbox_format="xyxy", clip=True):
+def detect_batched(m_outputs: dict, sizes, background_class, *, score_threshold=0.0, max_detections=None, bbox_format="xyxy", clip=True,
+                   scoring="softmax"):
     """[Detections] for every image of the batch, in pixels.  `sizes` [B, 2] = (height, width) of every ORIGINAL image (host
     array or device tensor): the model's boxes are normalised to the image's own extent -- in a padded batch too, where the canvas
     is larger --, so that is what they are scaled by.  A query is kept when its label is not `background_class` and its score
     (max softmax probability, exactly get_model_inference's) is >= score_threshold; the kept ones are sorted by descending score
     (ties: lower query index first) and cut to max_detections (None: all Q).  bbox_format: "xy_center" (cx, cy, w, h), "xyxy",
     "yxyx" or "xywh" (top-left + width / height); clip clamps the corners of the last three to the image.  One launch of
-    detr_hip_detect and ONE host synchronisation (the per-image counts).  CUDA inputs only."""
+    detr_hip_detect and ONE host synchronisation (the per-image counts).  CUDA inputs only.
+    scoring="sigmoid" (a model trained with class_criterion = "focal"): the score is the sigmoid of the best non-background logit, the
+    label its first arg-max, and every query is a candidate: the threshold alone decides (detr_hip_detect_scored)."""
     out_b, out_l, out_s, out_q, counts = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, background_class,
-                                                 score_threshold, max_detections, bbox_format, clip)
+                                                 score_threshold, max_detections, bbox_format, clip, scoring)
     return [Detections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k]) for b, k in enumerate(counts.tolist())]
 
 
@@ -202,7 +228,7 @@ def _check_merge_args(nms_threshold, match, edge_margin, max_detections):
 
 
 def merge_tiles(m_outputs: dict, tile_start, windows, sizes, background_class, *, score_threshold=0.0, max_detections=100,
-                bbox_format="xyxy", clip=True, nms_threshold=0.5, match="iou", class_agnostic=False, edge_margin=0.0):
+                bbox_format="xyxy", clip=True, nms_threshold=0.5, match="iou", class_agnostic=False, edge_margin=0.0, scoring="softmax"):
     """[TiledDetections] for every image of a sliced batch.  m_outputs holds pred_logits [N, Q, C] / pred_boxes [N, Q, 4] of all N
     tiles, the tiles of image b at rows [tile_start[b], tile_start[b + 1]) (tile_start: host int array [B + 1], as
     DeviceInputStage.augmented_tiles returns it); windows [N, 4] = (y0, x0, hc, wc) of every tile in pixels of its image (the fields
@@ -214,7 +240,10 @@ def merge_tiles(m_outputs: dict, tile_start, windows, sizes, background_class, *
     class_agnostic) matches it by MORE than nms_threshold; match "iou", or "ios" = intersection over the smaller area, which also
     removes a part-box lying inside the box of the whole object.  The first max_detections survivors are returned.  One launch of
     detr_hip_tile_merge and ONE host synchronisation (counts + status).  An image with more than _hip.TILE_MAX_CAND candidates
-    raises ValueError.  CUDA inputs only."""
+    raises ValueError.  CUDA inputs only.
+    scoring: "softmax" only; "sigmoid" raises NotImplementedError (this kernel scores from the logits itself, by softmax)."""
+    if _scoring(scoring) != 0:
+        raise NotImplementedError(f"merge_tiles: scoring={scoring!r}: the kernel scores from the logits itself, by softmax only")
     _check_model_outputs("merge_tiles", "N", m_outputs["pred_logits"], m_outputs["pred_boxes"])
     _check_detect_args(bbox_format, score_threshold, None)
     _check_merge_args(nms_threshold, match, edge_margin, max_detections)
@@ -288,7 +317,7 @@ def _check_fuse_args(method, threshold, match, edge_margin, max_detections, sigm
 
 def fuse_views(m_outputs: dict, view_start, windows, flips, sizes, background_class, *, method="wbf", threshold=None, score_threshold=0.0,
                max_detections=100, bbox_format="xyxy", clip=True, match="iou", class_agnostic=False, edge_margin=0.0, sigma=0.5,
-               score_min=0.001, expected_views=None, min_members=1):
+               score_min=0.001, expected_views=None, min_members=1, scoring="softmax"):
     """[FusedDetections] for every image of a batch seen through several VIEWS (test-time augmentation: mirrored, at several shortest
     sides, whole or tiled -- transformation.view_records).  m_outputs, view_start, windows and sizes are merge_tiles' m_outputs,
     tile_start, windows and sizes with a view for a tile; flips [N] says which views saw the MIRRORED image (a flipped record's window
@@ -307,7 +336,10 @@ def fuse_views(m_outputs: dict, view_start, windows, flips, sizes, background_cl
     results are returned, best first.  The defaults are the published methods' conventions (soft-NMS: sigma 0.5, minimum score 0.001;
     WBF: 0.55) carried over, UNTUNED for DETR: there are no trained weights here to tune them on.  One launch of detr_hip_fuse_views
     and ONE host synchronisation (counts + status).  An image with more than _hip.TILE_MAX_CAND candidates, or with "wbf" more than
-    _hip.FUSE_MAX_CLUSTERS clusters, raises ValueError.  CUDA inputs only."""
+    _hip.FUSE_MAX_CLUSTERS clusters, raises ValueError.  CUDA inputs only.
+    scoring: "softmax" only; "sigmoid" raises NotImplementedError (this kernel scores from the logits itself, by softmax)."""
+    if _scoring(scoring) != 0:
+        raise NotImplementedError(f"fuse_views: scoring={scoring!r}: the kernel scores from the logits itself, by softmax only")
     _check_model_outputs("fuse_views", "N", m_outputs["pred_logits"], m_outputs["pred_boxes"])
     _check_detect_args(bbox_format, score_threshold, None)
     block, threshold = _check_fuse_args(method, threshold, match, edge_margin, max_detections, sigma, score_min, expected_views, min_members)
@@ -707,15 +739,23 @@ class Detector:
     maps the boxes back -- mirrored views included -- and combines them by `merge`: "nms", "soft_nms", "soft_nms_gaussian" or "wbf"
     (sigma, score_min, min_members: see fuse_views; nms_threshold, when given, is the fusion threshold; expected_views is the number of
     views without tiles, None with them).  The results are FusedDetections.  The cost is one forward pass per view.  With
-    flip=False, scales=None and merge="nms" (the defaults) nothing of this runs."""
+    flip=False, scales=None and merge="nms" (the defaults) nothing of this runs.
+
+    scoring: "softmax" or "sigmoid" (detect_batched's); None takes it from config.class_criterion ("focal" -> "sigmoid").  The
+    plain path and track() score that way; tiles, nms_threshold, flip, scales and merge with "sigmoid" raise NotImplementedError."""
 
     RESIZE_MODES = ("shortest_side", "fixed")
 
     def __init__(self, model, config, *, background_class=None, score_threshold=0.7, max_detections=100, bbox_format="xyxy",
                  resize="shortest_side", shortest_side=800, max_size=1333, canvas=None, interpolation="cubic",
                  tiles=None, overlap=0.2, include_full=True, tile_batch=None, nms_threshold=None, match="iou", class_agnostic=False,
-                 edge_margin=0.0, flip=False, scales=None, merge="nms", sigma=0.5, score_min=0.001, min_members=1):
+                 edge_margin=0.0, flip=False, scales=None, merge="nms", sigma=0.5, score_min=0.001, min_members=1, scoring=None):
         from .data import processing, transformation
+        self.scoring = scoring_of(config) if scoring is None else scoring
+        _scoring(self.scoring)
+        if self.scoring != "softmax" and (tiles is not None or nms_threshold is not None or flip or scales is not None or merge != "nms"):
+            raise NotImplementedError(f"Detector: scoring={self.scoring!r} with tiles / nms_threshold / flip / scales / merge: merge_tiles and "
+                                      "fuse_views score from the logits themselves, by softmax only; use the plain path")
         if resize not in self.RESIZE_MODES:
             raise ValueError(f"Detector: resize must be one of {self.RESIZE_MODES}, got {resize!r}")
         names = transformation.INTERP_NAMES if resize == "shortest_side" else tuple(processing.INTERPOLATIONS)
@@ -878,7 +918,7 @@ class Detector:
             detections = self._merge(m_outputs, np.arange(len(srcs) + 1, dtype=np.int32), windows, sizes)
         else:
             detections = detect_batched(m_outputs, sizes, self.background_class, score_threshold=self.score_threshold,
-                                        max_detections=self.max_detections, bbox_format=self.bbox_format)
+                                        max_detections=self.max_detections, bbox_format=self.bbox_format, scoring=self.scoring)
         detections = detections[0] if single else detections
         if "attn" in m_outputs:
             return detections, _feature_maps(self.model, shape, m_outputs["attn"])
@@ -919,7 +959,7 @@ class Detector:
             sizes = np.array([s.shape[:2] for s in srcs], np.int32)
             m_outputs, _ = self._forward(srcs, sizes, return_embeddings=appearance)
             rows = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, self.background_class, self.score_threshold,
-                           self.max_detections, self.bbox_format, True)
+                           self.max_detections, self.bbox_format, True, self.scoring)
             tracked = tracker.update_rows(*rows, active, m_outputs["embed"] if appearance else None,
                                           self._last_frames if tracker.motion else None)
         return tracked[0] if single else tracked

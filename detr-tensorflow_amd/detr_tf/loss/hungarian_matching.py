@@ -41,8 +41,11 @@ class Matcher:
         self.status = torch.empty(self.P, dtype=torch.int32, device=device)
 
     def run(self, desc, t_bbox, criterion=None):
-        """criterion: a loss.Criterion; None or the default one runs the cost kernel with the reference's weights compiled in."""
-        if criterion is None or criterion.is_default:
+        """criterion: a loss.Criterion; None or the default one runs the cost kernel with the reference's weights compiled in, a
+        focal one the cost kernel with the focal class cost."""
+        if criterion is not None and criterion.is_focal:
+            hip.call("detr_hip_match_cost_focal_f32", byref(desc), criterion.floats(), criterion.focal_floats(), self.cost.data_ptr())
+        elif criterion is None or criterion.is_default:
             hip.call("detr_hip_match_cost_f32", byref(desc), self.cost.data_ptr())
         else:
             hip.call("detr_hip_match_cost_crit_f32", byref(desc), criterion.floats(), self.cost.data_ptr())

@@ -4,8 +4,10 @@
 `(total_loss, log_dict)` with the same 36 keys (label_cost, true_neg, true_pos, pos_accuracy,
 giou_loss, l1_loss, + suffixes _0.._4) and the 1/2/5 weighting of `get_total_losss`.
 The criterion -- matcher cost weights, loss coefficients, the weight of unmatched queries, per-class weights, the clamp of
-the box count -- is read from the config at every call (`criterion_of`); at the reference's values the loss runs the four
-entry points that have them compiled in, otherwise the `_crit_` ones (the same kernel bodies on run-time values).
+the box count, and the class term itself (softmax cross-entropy or sigmoid focal loss) -- is read from the config at every call
+(`criterion_of`); at the reference's values the loss runs the four entry points that have them compiled in, otherwise the
+`_crit_` ones (the same kernel bodies on run-time values), and with class_criterion = "focal" the `_focal_` ones (the same kernel
+bodies with the focal class term; include/detr_hip.h states its semantics).
 All arithmetic runs in csrc/setloss.hip: cost matrix (K12), exact assignment (K13), loss sums /
 finalisation / gradients (K14).  Under data parallelism the per-level normalisers (sum of CE
 weights, number of matched boxes) are all-reduced between the "sums" and "finalize" kernels, so
@@ -30,18 +32,67 @@ WEIGHT_QUANTUM, WEIGHT_MAX = 1.0 / 64.0, 16.0                         # class we
 WEIGHT_MAX_TERMS = 16384                                              # ... and at most this many added: every partial sum < 2^24 quanta
 
 
+CLASS_CRITERIA = ("softmax", "focal")
+CLASS_TERM_FIELDS = ("class_criterion", "focal_alpha", "focal_gamma")
+CLASS_TERM_DEFAULTS = ("softmax", 0.25, 2.0)                          # alpha, gamma: the published values (Lin et al.; Deformable DETR)
+FOCAL_GAMMA_MAX = 8.0
+
+
 class Criterion(namedtuple("Criterion", CRITERION_FIELDS + ("class_weights",))):
-    """The set criterion as an immutable, hashable record: seven floats, a bool, and the class weights as a tuple of multiples
-    of 1/64 (or None)."""
-    __slots__ = ()
+    """The set criterion as an immutable, hashable record: seven floats, a bool and the class weights as a tuple of multiples of
+    1/64 (or None) -- the nine entries of the tuple, as ever --, and beside them the class term: class_criterion ("softmax" or
+    "focal"), focal_alpha and focal_gamma, keyword (or trailing positional) arguments with defaults that take part in ==, hash
+    and _replace."""
+
+    def __new__(cls, *args, **kw):
+        term = list(CLASS_TERM_DEFAULTS)
+        for k, v in enumerate(args[9:]):
+            term[k] = v
+        for k, name in enumerate(CLASS_TERM_FIELDS):
+            if name in kw:
+                term[k] = kw.pop(name)
+        self = super().__new__(cls, *args[:9], **kw)
+        object.__setattr__(self, "_class_term", (str(term[0]), float(term[1]), float(term[2])))
+        return self
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"Criterion is immutable: cannot set {name!r}")
+
+    class_criterion = property(lambda self: self._class_term[0])
+    focal_alpha = property(lambda self: self._class_term[1])
+    focal_gamma = property(lambda self: self._class_term[2])
+
+    def __eq__(self, other):
+        return tuple.__eq__(self, other) is True and self._class_term == getattr(other, "_class_term", CLASS_TERM_DEFAULTS)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self._class_term))
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + "".join(f", {n}={v!r}" for n, v in zip(CLASS_TERM_FIELDS, self._class_term)) + ")"
+
+    def _replace(self, **kw):
+        term = {n: kw.pop(n, v) for n, v in zip(CLASS_TERM_FIELDS, self._class_term)}
+        return Criterion(*super()._replace(**kw), **term)
 
     @property
     def is_default(self):
-        return tuple(self[:8]) == CRITERION_DEFAULTS and self.class_weights is None
+        return tuple(self[:8]) == CRITERION_DEFAULTS and self.class_weights is None and not self.is_focal
+
+    @property
+    def is_focal(self):
+        return self.class_criterion == "focal"
 
     def floats(self):
-        """The host block of the _crit_ entry points."""
+        """The host block of the _crit_ and _focal_ entry points."""
         return (c_float * hip.CRITERION_FLOATS)(*[float(v) for v in self[:8]])
+
+    def focal_floats(self):
+        """The second host block of the _focal_ entry points."""
+        return (c_float * hip.FOCAL_FLOATS)(self.focal_alpha, self.focal_gamma)
 
 
 def round_class_weights(weights, nb_class=None):
@@ -67,7 +118,17 @@ def criterion_of(config, nb_class=None):
         vals.append(v)
     vals.append(bool(getattr(config, "num_boxes_min_one", False)))
     cw = getattr(config, "class_weights", None)
-    return Criterion(*vals, None if cw is None else round_class_weights(cw, nb_class))
+    kind = getattr(config, "class_criterion", "softmax")
+    if kind not in CLASS_CRITERIA:
+        raise ValueError(f"class_criterion = {kind!r}: expected one of {CLASS_CRITERIA}")
+    alpha, gamma = float(getattr(config, "focal_alpha", CLASS_TERM_DEFAULTS[1])), float(getattr(config, "focal_gamma", CLASS_TERM_DEFAULTS[2]))
+    if not (math.isfinite(alpha) and 0.0 < alpha < 1.0):
+        raise ValueError(f"focal_alpha = {alpha}: expected a finite value inside (0, 1)")
+    if not (math.isfinite(gamma) and 0.0 <= gamma <= FOCAL_GAMMA_MAX):
+        raise ValueError(f"focal_gamma = {gamma}: expected a finite value in [0, {FOCAL_GAMMA_MAX:g}]")
+    if kind == "focal" and cw is not None:
+        raise ValueError("class_weights with class_criterion = 'focal': the focal class term has no per-class weights")
+    return Criterion(*vals, None if cw is None else round_class_weights(cw, nb_class), kind, alpha, gamma)
 
 
 DEFAULT_CRITERION = Criterion(*CRITERION_DEFAULTS, None)
@@ -134,7 +195,10 @@ class SetLoss:
         self._keep = (logits, boxes, t_bbox, t_class)
         tfp = self.matcher.run(self.desc, t_bbox, criterion)
         hip.zero_(self.sums)
-        if criterion.is_default:
+        if criterion.is_focal:
+            hip.call("detr_hip_set_loss_sums_focal_f32", byref(self.desc), criterion.floats(), criterion.focal_floats(), tfp.data_ptr(),
+                     self.sums.data_ptr())
+        elif criterion.is_default:
             hip.call("detr_hip_set_loss_sums_f32", byref(self.desc), tfp.data_ptr(), self.sums.data_ptr())
         else:
             hip.call("detr_hip_set_loss_sums_crit_f32", byref(self.desc), criterion.floats(), wptr, tfp.data_ptr(),
@@ -146,7 +210,10 @@ class SetLoss:
 
     def finalize(self):
         """losses / total of self.sums under the criterion of the last forward."""
-        if self.criterion.is_default:
+        if self.criterion.is_focal:
+            hip.call("detr_hip_set_loss_finalize_focal_f32", self.sums.data_ptr(), self.levels, self.criterion.floats(),
+                     self.criterion.focal_floats(), self.losses.data_ptr(), self.total.data_ptr())
+        elif self.criterion.is_default:
             hip.call("detr_hip_set_loss_finalize_f32", self.sums.data_ptr(), self.levels, self.losses.data_ptr(),
                      self.total.data_ptr())
         else:
@@ -159,7 +226,11 @@ class SetLoss:
         d = make_desc(lg, self._keep[1], self._keep[2], self._keep[3], self.desc.background_class)
         # the gradient tensors use the same (level, image, query) strides as contiguous [Lv,B,Q,*]
         assert lg.is_contiguous() and self._keep[1].is_contiguous(), "set-loss gradients need contiguous head outputs"
-        if self.criterion.is_default:
+        if self.criterion.is_focal:
+            hip.call("detr_hip_set_loss_grad_focal_f32", byref(d), self.criterion.floats(), self.criterion.focal_floats(),
+                     self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(), c_float(loss_scale), self.d_logits.data_ptr(),
+                     self.d_boxes.data_ptr())
+        elif self.criterion.is_default:
             hip.call("detr_hip_set_loss_grad_f32", byref(d), self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(),
                      c_float(loss_scale), self.d_logits.data_ptr(), self.d_boxes.data_ptr())
         else:

@@ -153,6 +153,22 @@ class DetrModel:
         names, with the frozen-BN vectors: `load_weights(path)` into a fresh model gives the deployable averaged model."""
         self.engine.P.save(self._npz(path), weights=weights)
 
+    def set_class_prior(self, prior=0.01):
+        """Focal-loss initialisation of the class head (Lin et al., section 4.1): every bias becomes -log((1 - prior) / prior), so a
+        fresh head scores every class at sigmoid = `prior` and the focal loss of the many unmatched queries starts small (without it
+        a fresh head starts with a label_cost in the hundreds).  Written through load_weights' path: the bf16 shadow, the recorded
+        graphs and a weight average follow.  Returns the bias value."""
+        import math
+        prior = float(prior)
+        if not (math.isfinite(prior) and 0.0 < prior < 1.0):
+            raise ValueError(f"set_class_prior: prior = {prior}: expected a value inside (0, 1)")
+        if self.headless:
+            raise ValueError("set_class_prior: this model has no class head (include_top=False without nb_class)")
+        name = self.engine._head_layers()[0][0] + "/bias"
+        value = -math.log((1.0 - prior) / prior)
+        self.engine.load_params({name: np.full(tuple(self.engine.P.shapes[name]), value, np.float32)})
+        return value
+
     # ---- forward ----------------------------------------------------------------------------
     def _eval_forward(self, images, masks=None, attn_sites=()):
         """Eval-mode forward.  The launch sequence of a fixed input shape is static, so the second call with the same shape

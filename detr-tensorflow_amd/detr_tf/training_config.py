@@ -46,6 +46,8 @@ _FLAGS = (
     ("set_cost_class", float, 1.0, False), ("set_cost_bbox", float, 5.0, False), ("set_cost_giou", float, 2.0, False),
     ("class_loss_coef", float, 1.0, False), ("bbox_loss_coef", float, 5.0, False), ("giou_loss_coef", float, 2.0, False),
     ("eos_coef", float, 0.1, False), ("num_boxes_min_one", None, False, True),
+    # not in the reference: the class term of the criterion, "softmax" (the reference's) or "focal" (sigmoid focal loss)
+    ("class_criterion", str, "softmax", False), ("focal_alpha", float, 0.25, False), ("focal_gamma", float, 2.0, False),
     # not in the reference: an exponential moving average of the weights kept on the device (optimizers.WeightEMA)
     ("ema_decay", float, None, False), ("ema_warmup", None, False, True),
 )
@@ -78,6 +80,14 @@ _DEFAULTS = dict(
     # targets' classes, rounded to multiples of 1/64 in [0, 16].  At these defaults the loss runs the reference's compiled-in criterion.
     set_cost_class=1.0, set_cost_bbox=5.0, set_cost_giou=2.0, class_loss_coef=1.0, bbox_loss_coef=5.0, giou_loss_coef=2.0,
     eos_coef=0.1, num_boxes_min_one=False, class_weights=None,
+    # class_criterion = "focal" swaps the class term for the sigmoid focal loss of Deformable DETR and its successors: every one of
+    # the nb_class logits a binary problem (matched queries one-hot on their class, unmatched ones all zero), focal_alpha in (0, 1)
+    # the weight of the positives, focal_gamma in [0, 8] the focusing exponent; the level's sum is divided by max(matched, 1),
+    # eos_coef is not read and class_weights must stay None.  The matcher's class cost becomes the focal cost (the published
+    # set_cost_class for it is 2; the default stays 1) and detections are scored by the sigmoid of the best non-background logit
+    # (inference.py scoring="sigmoid", what Detector and eval_model choose from this attribute).  Call model.set_class_prior() on a
+    # fresh head.  The defaults 0.25 / 2 are the published ones, untuned here.
+    class_criterion="softmax", focal_alpha=0.25, focal_gamma=2.0,
     # Weight average (tf.train.ExponentialMovingAverage), read at EVERY apply step.  ema_decay = d, 0 <= d < 1: after the update of
     # the trained groups, shadow -= (1 - d) * (shadow - weights) on the device; None = no average (nothing allocated, nothing
     # launched; setting it back to None pauses the updates and keeps the shadow).  ema_warmup: this step's decay is

@@ -519,6 +519,36 @@ int detr_hip_set_loss_grad_crit_f32(const detr_setloss_desc *d, const float *cri
                                     const int32_t *tgt_for_pred, const float *sums, float loss_scale,
                                     float *d_logits, float *d_boxes, void *stream);
 
+/* The same four launches with a sigmoid focal class term (appended; the ABI version is unchanged): the *_crit_* signatures
+ * with a `focal` block and without class weights.  The class head keeps its C logits, column background_class included, and no
+ * column is special in the loss: a matched query is one-hot on its target's class, an unmatched one all zero.  With x a logit,
+ * sp(z) = max(z, 0) + log1p(exp(-|z|)) and p = sigmoid(x), an element is
+ *   t = 1:  pos(x) = alpha * exp(-gamma * sp(x)) * sp(-x)            (= alpha * (1 - p)^gamma * -log p)
+ *   t = 0:  neg(x) = (1 - alpha) * exp(-gamma * sp(-x)) * sp(x)      (= (1 - alpha) * p^gamma * -log(1 - p))
+ * finite for every finite logit.  Per level, with M the matched pairs:
+ *   cost[q][j]  = set_cost_bbox*L1 + set_cost_class*(pos(x) - neg(x)) + set_cost_giou*(-GIoU),  x = logits[q][class_j]; a label
+ *                 outside [0, C) costs 0 in the class term.  No 1e-8 is added inside a logarithm: this differs from the published
+ *                 matcher only where p or 1 - p is below about 1e-6.
+ *   label_cost  = (sum of all B*Q*C elements) / max(|M|, 1)          (always clamped; eos_coef is not read)
+ *   l1_loss, giou_loss, total: as the *_crit_* entry points (the box sums follow num_boxes_min_one)
+ *   metrics: a query predicts the background class when its largest non-background logit is <= 0, otherwise the first arg-max over
+ *            c != background_class; true_neg, true_pos and pos_accuracy follow from that prediction as above.
+ * sums: slot 0 = the sum of the elements, slot 1 stays 0, slots 2..6 the counts; finalize_focal / grad_focal normalise by
+ * max(sums[4], 1), so the gradients are a deterministic function of the matching.  A matched label outside [0, C): the level's
+ * label_cost (and the total) is NaN, the gradient that of a row without a positive class, nothing is read out of bounds.
+ * focal: DETR_FOCAL_FLOATS floats in HOST memory, read during the call: [0] alpha in (0, 1), [1] gamma in [0, 8].
+ * Rejected on the host, before anything is launched: a null focal block, a value outside its range or not finite, and
+ * everything the *_crit_* entry points reject. */
+#define DETR_FOCAL_FLOATS 2
+int detr_hip_match_cost_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal, float *cost, void *stream);
+int detr_hip_set_loss_sums_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal,
+                                     const int32_t *tgt_for_pred, float *sums, void *stream);
+int detr_hip_set_loss_finalize_focal_f32(const float *sums, int32_t levels, const float *criterion, const float *focal, float *losses,
+                                         float *total, void *stream);
+int detr_hip_set_loss_grad_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal,
+                                     const int32_t *tgt_for_pred, const float *sums, float loss_scale,
+                                     float *d_logits, float *d_boxes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-side input stage (the step's producer side; detr_tf/data/processing.py:6-21,35-55, data/transformation.py:82-91).
  *   detr_hip_input_stage: uint8 NHWC batch -> fixed-size resize (cv2.resize semantics in fp32: half-pixel centres,
@@ -593,6 +623,12 @@ typedef struct {
     int32_t *counts;                             /* [B] */
 } detr_postprocess_desc;
 int detr_hip_postprocess(const detr_postprocess_desc *d, void *stream);
+/* The same launch with the scoring as an argument (appended; the ABI version is unchanged).  scoring 0 "softmax": exactly
+ * detr_hip_postprocess.  scoring 1 "sigmoid" (the class head of the focal criterion): label = first arg-max of the logits over
+ * c != background_class, score = sigmoid of that logit = 1 / (1 + exp(-x)); every query is kept, so image b gets Q rows in query
+ * order and counts[b] = Q.  A NaN among the non-background logits of a query makes its score NaN.  Rejected: C < 2 or a
+ * background_class outside [0, C) with scoring 1, a scoring other than 0 or 1, and everything detr_hip_postprocess rejects. */
+int detr_hip_postprocess_scored(const detr_postprocess_desc *d, int32_t scoring, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * mAP accumulation, per-image half (compute_map.py:183-272 cal_map, which eval.py:41-55 calls once per image on the host;
@@ -777,6 +813,10 @@ typedef struct {
     int32_t *counts;                             /* [B] */
 } detr_detect_desc;
 int detr_hip_detect(const detr_detect_desc *d, void *stream);
+/* The same launch with the scoring as an argument (appended; the ABI version is unchanged): scoring 0 is detr_hip_detect, scoring
+ * 1 scores as detr_hip_postprocess_scored does (bit-identical) and makes every query a candidate: score >= score_threshold alone
+ * decides (a NaN score fails it), then the ordering and the cut to max_detections as above.  Rejections as there. */
+int detr_hip_detect_scored(const detr_detect_desc *d, int32_t scoring, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * COCO-protocol evaluation, per-image half, appended (the ABI version is unchanged):
