@@ -37,6 +37,11 @@ extern "C" int detr_hip_conv3x3_dilated(const detr_conv3x3d_desc *d, int32_t mod
     DETR_REQUIRE(d->Ho == d->Hi && d->Wo == d->Wi, "conv3x3 dilated: output %dx%d must equal input %dx%d", d->Ho, d->Wo, d->Hi, d->Wi);
     DETR_REQUIRE(d->Ci > 0 && d->Co > 0 && d->Ci % 16 == 0 && d->Co % 16 == 0, "conv3x3 dilated: Ci=%d Co=%d must be multiples of 16", d->Ci, d->Co);
     DETR_REQUIRE(d->x && d->w && d->y, "conv3x3 dilated: null operand");
+    DETR_REQUIRE(d->compute >= 0 && d->compute <= 2, "conv3x3 dilated: compute %d (0 = fp32, 1 = bf16, 2 = f32x3)", d->compute);
+    DETR_REQUIRE((d->w_dtype == 0 || d->w_dtype == 1) && (d->x_dtype == 0 || d->x_dtype == 1) && (d->y_dtype == 0 || d->y_dtype == 1) &&
+                 (d->r_dtype == 0 || d->r_dtype == 1) && d->m_dtype >= 0 && d->m_dtype <= 2,
+                 "conv3x3 dilated: storage types w %d x %d y %d r %d (0 = fp32, 1 = bf16), m %d (2 = bit-packed as well)", d->w_dtype, d->x_dtype,
+                 d->y_dtype, d->r_dtype, d->m_dtype);
     DETR_REQUIRE(aligned16(d->x) && aligned16(d->w) && aligned16(d->y), "conv3x3 dilated: operands must be 16-byte aligned");
     // 32-bit buffer offsets: a tensor past the limit is rejected, never wrapped (DC5's layer4 tensors are four times the plain model's)
     DETR_REQUIRE((long long)d->N * d->Hi * d->Wi * d->Ci * 4 <= BUF_MAX_BYTES && (long long)d->N * d->Ho * d->Wo * d->Co * 4 <= BUF_MAX_BYTES,

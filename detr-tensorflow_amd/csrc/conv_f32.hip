@@ -1014,6 +1014,11 @@ extern "C" int detr_hip_conv3x3_f32(const detr_conv3x3_desc *d, int32_t mode, vo
                  "conv3x3: output %dx%d inconsistent with input %dx%d pad %d stride %d", d->Ho, d->Wo, d->Hi, d->Wi,
                  d->pad, d->stride);
     DETR_REQUIRE(d->x && d->w && d->y, "conv3x3: null operand");
+    DETR_REQUIRE(d->compute >= 0 && d->compute <= 2, "conv3x3: compute %d (0 = fp32, 1 = bf16, 2 = f32x3)", d->compute);
+    DETR_REQUIRE((d->w_dtype == 0 || d->w_dtype == 1) && (d->x_dtype == 0 || d->x_dtype == 1) && (d->y_dtype == 0 || d->y_dtype == 1) &&
+                 (d->r_dtype == 0 || d->r_dtype == 1) && d->m_dtype >= 0 && d->m_dtype <= 2,
+                 "conv3x3: storage types w %d x %d y %d r %d (0 = fp32, 1 = bf16), m %d (2 = bit-packed as well)", d->w_dtype, d->x_dtype, d->y_dtype,
+                 d->r_dtype, d->m_dtype);
     DETR_REQUIRE(aligned16(d->x) && aligned16(d->w) && aligned16(d->y), "conv3x3: operands must be 16-byte aligned");
     DETR_REQUIRE((long long)d->N * d->Hi * d->Wi * d->Ci * 4 <= BUF_MAX_BYTES &&
                      (long long)d->N * d->Ho * d->Wo * d->Co * 4 <= BUF_MAX_BYTES,

@@ -470,6 +470,16 @@ static int gemm_prepare(const detr_gemm_desc *d, GemmPlan &p) {
     DETR_REQUIRE(d != nullptr, "gemm: null descriptor");
     DETR_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
     DETR_REQUIRE(d->A && d->B && d->C, "gemm: null operand");
+    // the documented values only: any other one used to mean "exact fp32" / "fp32 storage" without a word
+    DETR_REQUIRE(d->compute >= 0 && d->compute <= 2, "gemm: compute %d (0 = fp32, 1 = bf16, 2 = f32x3)", d->compute);
+    DETR_REQUIRE((d->a_dtype == 0 || d->a_dtype == 1) && (d->b_dtype == 0 || d->b_dtype == 1) && (d->c_dtype == 0 || d->c_dtype == 1) &&
+                 (d->r_dtype == 0 || d->r_dtype == 1) && d->m_dtype >= 0 && d->m_dtype <= 2,
+                 "gemm: storage types a %d b %d c %d r %d (0 = fp32, 1 = bf16), m %d (2 = bit-packed as well)", d->a_dtype, d->b_dtype, d->c_dtype,
+                 d->r_dtype, d->m_dtype);
+    // bf16 storage is bf16 compute only (include/detr_hip.h): the exact and the f32x3 kernels are instantiated for fp32 tensors
+    DETR_REQUIRE(d->compute == 1 || (d->c_dtype == 0 && d->r_dtype == 0 && d->m_dtype == 0),
+                 "gemm: bf16 / bit-packed C, residual and mask need compute = bf16 (compute %d: c %d r %d m %d)", d->compute, d->c_dtype, d->r_dtype,
+                 d->m_dtype);
     const int batch = d->batch > 0 ? d->batch : 1;
     const int inner = d->batch_inner > 0 ? d->batch_inner : 1;
     const bool bf16c = d->compute == 1;

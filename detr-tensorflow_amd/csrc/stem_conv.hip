@@ -553,6 +553,10 @@ extern "C" int detr_hip_stem_conv7x7_f32(const detr_stem_desc *d, int32_t mode, 
     DETR_REQUIRE(d != nullptr, "stem conv: null descriptor");
     DETR_REQUIRE(mode == 0 || mode == 2, "stem conv: mode %d (0 = forward, 2 = weight gradient)", mode);
     DETR_REQUIRE(d->img && d->w && d->y, "stem conv: null operand");
+    DETR_REQUIRE(d->compute >= 0 && d->compute <= 2, "stem conv: compute %d (0 = fp32, 1 = bf16, 2 = f32x3)", d->compute);
+    DETR_REQUIRE((d->w_dtype == 0 || d->w_dtype == 1) && (d->y_dtype == 0 || d->y_dtype == 1),
+                 "stem conv: storage types w %d y %d (0 = fp32, 1 = bf16)", d->w_dtype, d->y_dtype);
+    DETR_REQUIRE(d->compute == 1 || (d->w_dtype == 0 && d->y_dtype == 0), "stem conv: a bf16 output / dy needs compute = bf16 (compute %d)", d->compute);
     DETR_REQUIRE(d->Ho == (d->H + 6 - 7) / 2 + 1 && d->Wo == (d->W + 6 - 7) / 2 + 1, "stem conv: bad output size");
     DETR_REQUIRE(aligned16(d->w) && aligned16(d->y) && ((uintptr_t)d->img % 4 == 0), "stem conv: alignment");
     DETR_REQUIRE((long long)d->N * d->H * d->W * 3 * 4 <= BUF_MAX_BYTES && (long long)d->N * d->Ho * d->Wo * 64 * 4 <= BUF_MAX_BYTES,

@@ -111,9 +111,14 @@ typedef struct {
      * matrix pipe: every fp32 operand value is split exactly into three bf16 values (x = h + m + l) and a product is the sum
      * of the six largest of the nine bf16 partial products, accumulated in fp32 (relative error of a product <= 2^-23, the
      * size of one fp32 rounding; csrc/gemm_core.h: mma_ktile_split3) -- 6 bf16 MFMAs instead of 8 fp32 MFMAs per 32x32x16
-     * block at 16x the instruction rate.  Operands, C, residual and mask must be fp32 (the *_dtype fields 0).  Both forms are
-     * fp32-accurate; the split kernel takes the shapes on which it is the faster one (csrc/gemm_f32.hip: gemm_split3_shape) --
-     * N > 32 and, unless DETR_HIP_SPLIT3_ALL=1, N >= 128, K >= 256 and M >= 128 -- and every other shape runs the exact kernel. */
+     * block at 16x the instruction rate.  Both forms are fp32-accurate; the split kernel takes the shapes on which it is the
+     * faster one (csrc/gemm_f32.hip: gemm_split3_shape) -- N > 32 and M >= 128, N >= 128, K >= 256; DETR_HIP_SPLIT3_ALL=1 leaves
+     * N > 32 alone -- and every other shape runs the exact kernel.  Any other value of `compute` is rejected.
+     * THE STORAGE RULE (here, detr_conv3x3_desc, detr_conv3x3d_desc, detr_stem_desc): every *_dtype field is 0 (fp32) or 1 (bf16;
+     * m_dtype also 2, bit-packed), anything else is rejected; a field other than 0 needs compute = 1 -- under compute 0 and 2
+     * operands, C, residual and mask are all fp32.  Under compute = 1 the fields are independent of each other: any mix of fp32 and
+     * bf16 A, B, C, residual and mask is accepted (subject to the alignment each bf16 operand states below) and computes the same
+     * fp32 epilogue values, rounded once where C is bf16; only the bit-packed masks need the all-bf16 form (maskbits_out). */
     int32_t compute;
     /* optional fused bias gradient of a weight-gradient GEMM (dW = dy^T x): rowsum_a[m] += rowsum_alpha * sum_k A[m][k]
      * (A must be MN-contiguous, a_kcontig = 0; batch == 1; with split_k > 1 the deterministic workspace path is
@@ -124,7 +129,7 @@ typedef struct {
      * engine keeps a per-step bf16 shadow of the weights so that the weight operand is read at half the bytes and
      * without conversion (K %% 8 == 0 for a k-contiguous B, N %% 4 == 0 otherwise). */
     int32_t b_dtype;
-    /* bf16 STORAGE of activation tensors (bf16 compute only; the engine's backbone tensors in bf16 mode): 1 = the
+    /* bf16 STORAGE of activation tensors (bf16 compute only, see `compute`; the engine's backbone tensors in bf16 mode): 1 = the
      * tensor is bf16 in memory (uint16, RNE; leading dimensions in elements), 0 = fp32.  The epilogue arithmetic stays
      * fp32 and the result is rounded once.  Not with split_k / batch (partial slabs and gradients of parameters stay fp32). */
     int32_t a_dtype, c_dtype, r_dtype, m_dtype;     /* A, C, residual, mask (m_dtype 2: bit-packed, see maskbits_out) */

@@ -1,6 +1,8 @@
 """Guard-band cases of the matrix kernels (GEMM families, 3x3 convolutions, stem, fused 1x1 backward): the case tables and the
 framing helpers shared by tests/test_gpu_guard_bands.py (device) and tests/test_guard_bands_cpu.py (routes, helpers, and why
-the zero-padded, tight-pitch method of the older tests cannot see the faults these cases look for).
+the zero-padded, tight-pitch method of the older tests cannot see the faults these cases look for).  The storage-matrix lists
+(storage_cases, conv_storage_cases, STEM_STORAGE: every accepted mix of fp32 and bf16 tensors) serve tests/test_gpu_storage_matrix.py
+and tests/test_storage_matrix_cpu.py through the same helpers.
 
 Rule of every case: each INPUT the kernel takes a pointer to lies inside a NaN-filled buffer (a lead in front, pad columns behind
 every row, a tail), each OUTPUT and scratch buffer inside a sentinel-filled one.  A read of padding that reaches the result shows
@@ -357,6 +359,117 @@ RING_WGRAD_SHAPES = [(264, 136, 2100, 3, {"DETR_HIP_GEMM_TILE": 1}), (120, 128, 
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# storage matrix: every accepted mix of fp32 and bf16 A / B / C / residual / mask (tests/test_gpu_storage_matrix.py,
+# tests/test_storage_matrix_cpu.py)
+# ------------------------------------------------------------------------------------------------------------------------
+STORE_ENV = {"DETR_HIP_GEMM_TILE": 3, "DETR_HIP_GEMM_RING": 2, "DETR_HIP_GEMM_STREAM": 2}
+STORE_MAIN, STORE_TAIL = (75, 136, 96), (77, 50, 40)
+RES_STORES, MASK_STORES = (None, "f32", "b16"), (None, "f32", "b16", "bits")
+PITCH_CLASSES = ("wide", "vec4", "odd", "Coff", "Roff")
+up8 = lambda n: (n + 7) // 8 * 8
+
+
+def storage_pitches(N, cls, mask=None):
+    """ldc / ldr / ldm / off of a pitch class: three pairwise different pitches.  wide: all % 8 == 0; vec4: % 4 == 0 but not % 8;
+    odd: odd; Coff / Roff: the wide pitches with the base of C / the residual one element off.  A bit-packed mask has its own
+    pitch in bytes."""
+    n8 = up8(N)
+    ldc, ldr, ldm = {"vec4": (n8 + 4, n8 + 12, n8 + 20), "odd": (n8 + 5, n8 + 7, n8 + 9)}.get(cls, (n8 + 8, n8 + 16, n8 + 24))
+    if mask == "bits":
+        ldm = (N + 7) // 8 + 3
+    return dict(ldc=ldc, ldr=ldr, ldm=ldm, off={"Coff": {"C": 1}, "Roff": {"residual": 1}}.get(cls, {}))
+
+
+def storage_key(c):
+    """The storage form of a GEMM case: what the completeness probe of tests/test_storage_matrix_cpu.py enumerates."""
+    return (c["compute"], c["a16"], c["b16"], c["c16"], c["res"], c["mask"])
+
+
+def storage_group(c):
+    """Cases with the same key compute the same fp32 epilogue values from the same A / B through the same kernel: their fp32 outputs
+    hold the same bits, their bf16 outputs those bits rounded once."""
+    return (c["group"], c["M"], c["N"], c["K"], c["ak"], c["bk"], c["compute"], c["a16"], c["b16"], c["res"] is not None, c["mask"] is not None,
+            c["act"], c["p"] > 0.0, tuple(sorted(c["env"].items())))
+
+
+def storage_group_id(key):
+    group, M, N, K, ak, bk, compute, a16, b16, res, mask, act, drop, env = key
+    return f"{group}-{M}x{N}x{K}-bk{bk}-c{compute}-a{a16}b{b16}-{'res' if res else 'nores'}-{'mask' if mask else 'nomask'}-act{act}{'-drop' if drop else ''}"
+
+
+def _content(name, res, mask):
+    if name == "rich":
+        return dict(scale=1, bias=1, alpha=0.75, act=1, res=res, mask=mask)
+    return dict(bias=1, res=res, p=0.1)
+
+
+def bits_accepted(c16, res, cls, N):
+    """Where the library takes a bit-packed mask: the all-bf16 8-column epilogue."""
+    return bool(c16) and res in (None, "b16") and cls == "wide" and N % 8 == 0
+
+
+def storage_cases():
+    out = []
+    # tile engine (family 0), bf16 compute on one pinned tile: the full product of storage forms on every pitch class
+    shapes = [(STORE_MAIN, 1), (STORE_MAIN, 0), (STORE_TAIL, 1)]
+    for (M, N, K), bk in shapes:
+        for a16 in (0, 1):
+            for b16 in (0, 1):
+                kw = dict(env=STORE_ENV, compute=1, a16=a16, b16=b16, lda=K + 8, ldb=(K if bk else N) + 8)
+                for c16 in (0, 1):
+                    for res in RES_STORES:
+                        for cls in PITCH_CLASSES:
+                            if cls == "Roff" and res is None:
+                                continue
+                            for mask in MASK_STORES:
+                                if mask == "bits" and not bits_accepted(c16, res, cls, N):
+                                    continue
+                                tag = f"a{a16}b{b16}c{c16}-r{res}-m{mask}-{cls}"
+                                out.append(gcase("store", M, N, K, 1, bk, c16=c16, tol="b16" if c16 else "f32", tag="rich-" + tag,
+                                                 **_content("rich", res, mask), **storage_pitches(N, cls, mask), **kw))
+                                if mask is None and res is not None:
+                                    out.append(gcase("store", M, N, K, 1, bk, c16=c16, tol="b16" if c16 else "f32", tag="drop-" + tag,
+                                                     **_content("drop", res, None), **storage_pitches(N, cls), **kw))
+    # the sigmoid in front of a bf16 C (and its fp32 twin)
+    M, N, K = STORE_MAIN
+    for c16 in (0, 1):
+        out.append(gcase("store", M, N, K, 1, 1, env=STORE_ENV, compute=1, a16=1, b16=1, c16=c16, bias=1, res="f32", act=2, lda=K + 8, ldb=K + 8,
+                         tol="b16" if c16 else "f32", tag=f"act2-c{c16}", **storage_pitches(N, "vec4")))
+    # fp32 storage under exact fp32 and f32x3: the forms those modes accept
+    for compute, env in ((0, STORE_ENV), (2, dict(STORE_ENV, DETR_HIP_SPLIT3_ALL=1))):
+        for res in (None, "f32"):
+            for mask in (None, "f32"):
+                for cls in ("vec4", "odd"):
+                    out.append(gcase("store32", M, N, K, 1, 1, env=env, compute=compute, lda=K + 4, ldb=K + 4, tag=f"r{res}-m{mask}-{cls}",
+                                     **_content("rich", res, mask), **storage_pitches(N, cls)))
+    # ring (family 2)
+    M, N, K = 33, 256, 192
+    env = {"DETR_HIP_GEMM_RING": 1, "DETR_HIP_GEMM_STREAM": 2}
+    for c16 in (0, 1):
+        for res in RES_STORES:
+            for cls in ("wide", "vec4"):
+                for mask in MASK_STORES:
+                    if mask == "bits" and not bits_accepted(c16, res, cls, N):
+                        continue
+                    out.append(gcase("storering", M, N, K, 1, 1, family=2, env=env, compute=1, a16=1, b16=1, c16=c16, lda=K + 8, ldb=K + 8,
+                                     tol="ring16" if c16 else "ring32", tag=f"c{c16}-r{res}-m{mask}-{cls}", **_content("rich", res, mask),
+                                     **storage_pitches(N, cls, mask)))
+    # streaming shapes the streaming kernel cannot serve because one tensor is fp32: the tile engine takes them
+    for M, N, K in ((16384 + 37, 64, 64), (16384 + 37, 256, 128)):
+        for name, c16, res, mask in (("res32", 1, "f32", "b16"), ("mask32", 1, "b16", "f32"), ("c32", 0, "b16", "b16")):
+            out.append(gcase("storefall", M, N, K, 1, 1, family=0, env={"DETR_HIP_GEMM_STREAM": 3}, compute=1, a16=1, b16=1, c16=c16, bias=1, res=res,
+                             mask=mask, act=1, lda=K + 8, ldb=K + 8, tol="b16" if c16 else "f32", tag=name, **storage_pitches(N, "wide")))
+    return out
+
+
+def storage_probe_case(compute, a16, b16, c16, res, mask):
+    """The main shape on all-aligned placements in one storage form, for the completeness probe."""
+    M, N, K = STORE_MAIN
+    return gcase("probe", M, N, K, 1, 1, env=STORE_ENV, compute=compute, a16=a16, b16=b16, c16=c16, lda=K + 8, ldb=K + 8,
+                 **_content("rich", res, mask), **storage_pitches(N, "wide", mask))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # 3x3 convolution and stem cases
 # ------------------------------------------------------------------------------------------------------------------------
 CONV_SHAPES = ((2, 9, 11), (2, 5, 33), (3, 2, 3))
@@ -421,6 +534,44 @@ def wgrad_cases():
 
 
 STEM_SHAPES = ((2, 37, 53), (1, 9, 8))
+# stem forward under bf16 compute: (id, y stored in bf16?, alpha); both carry scale, shift and the ReLU, so the bf16 output stays on the
+# gathering kernel's own c16 path without DETR_HIP_STEM_ROWS
+STEM_STORAGE = (("c1-y32", 0, 1.0), ("c1-y16-rich", 1, 0.75))
+
+
+def conv_storage_cases():
+    """Mixed fp32 / bf16 storage on the bf16 tile kernel, one dict per launch.  mode 0: y = relu((conv(x, w) * scale + shift) * 0.75 + residual),
+    mode 1: dx = 0.75 * mask(conv^T(dy, w)); s16 = (source, kernel, destination) stored in bf16?, aux = storage of the residual (mode 0) / the mask
+    (mode 1).  halo: the launch is one fp32 tensor away from the halo-staged kernels (bias + ReLU / plain input gradient)."""
+    out = []
+    env = {"DETR_HIP_CONV_TILE": 3, "DETR_HIP_DGRAD_S2_CLASSES": 3}
+
+    def product(name, env, ci, co, stride, dil, shape):
+        for mode in (0, 1):
+            for src in (0, 1):
+                for w in (0, 1):
+                    for dst in (0, 1):
+                        for aux in (None, "f32", "b16"):
+                            out.append(dict(id=f"{name}-{ci}x{co}-s{stride}-{'x'.join(map(str, shape))}", env=env, Ci=ci, Co=co, stride=stride, dil=dil,
+                                            shape=shape, mode=mode, s16=(src, w, dst), aux=aux, halo=0))
+
+    for shape in (CONV_SHAPES[0], CONV_SHAPES[2]):
+        for ci, co in ((64, 64), (128, 256)):
+            for stride in (1, 2):
+                product("tile", env, ci, co, stride, 1, shape)
+    product("dil2", env, 128, 256, 1, 2, CONV_SHAPES[0])
+    for mode in (0, 1):
+        for which in range(3):
+            s16 = tuple(int(i != which) for i in range(3))
+            out.append(dict(id="halo-128x128-s1-2x9x11", env={}, Ci=128, Co=128, stride=1, dil=1, shape=CONV_SHAPES[0], mode=mode, s16=s16,
+                            aux=None, halo=1))
+    out.append(dict(id="halo-128x128-s1-2x9x11", env={}, Ci=128, Co=128, stride=1, dil=1, shape=CONV_SHAPES[0], mode=1, s16=(1, 1, 1), aux="f32", halo=1))
+    return out
+
+
+def conv_storage_group(c):
+    """Launches that share source and kernel storage (and everything but the storage of destination, residual and mask)."""
+    return (c["id"], c["mode"], c["s16"][0], c["s16"][1], c["aux"] is not None)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
