@@ -10,8 +10,8 @@
 // The weights of the criterion (matcher cost, loss terms, no-object weight, per-class weights) are a policy parameter of
 // the cost / sums / finalize / gradient kernels: FixedCriterion holds the reference's literals as constexpr members (the
 // entry points without a criterion argument), RuntimeCriterion a by-value block filled by the *_crit_* entry points.  The class
-// term is a second policy of the same four kernels: SoftmaxClass (the reference's cross-entropy) or FocalClass (sigmoid focal
-// loss, the *_focal_* entry points).
+// term is a second policy of the same four kernels, each ONE body written against its interface: SoftmaxClass (the reference's
+// cross-entropy) or FocalClass (sigmoid focal loss, the *_focal_* entry points).  with_policies() builds the pair of a family.
 // Compiled with -ffp-contract=off so that the box arithmetic rounds like the op-by-op reference.
 #include "common.h"
 #include <limits.h>
@@ -59,13 +59,75 @@ struct RuntimeCriterion {
 
 // ---- the class term, a second policy beside Crit: what a logit row costs in the matcher, adds to slot 0 of the sums, is
 // normalised by, and contributes to d_logits.  The box terms, the launch grid, the sums layout and the reduction through LDS
-// do not depend on it.
-// SoftmaxClass: the reference's weighted cross-entropy over the C classes, unmatched queries on the background class; the
-// kernels keep that arithmetic in their `else` branches, unchanged.
+// do not depend on it.  Both terms implement one interface, and every kernel is one body written against it:
+//   Row, row_stats(row, C, lane)          what the cost and the gradient need of a whole row (wave-collective)
+//   cost(stats, x)                        the class cost of a target whose class logit is x
+//   unmatched_class(background)           the column an unmatched query is a positive of (-1: none)
+//   weight(crit, matched, cls, C)         the weight of a query's loss, in the sums and in the gradient
+//   row_loss(row, C, lane, cls, bg)       the row's unweighted loss and predicted class, valid on lane 0 (wave-collective)
+//   add_norm(crit, w, slot1)              what a matched query adds to slot 1, the part of label_norm that no count gives
+//   label_norm(crit, s)                   the normaliser of slot 0 from a level's sums
+//   grad_row(stats, row, d_row, C, lane, cls, wq)   d_row = wq * d loss / d row, every lane its columns
+struct RowLoss { float loss; int pred; };
+
+// first-occurrence arg-max across the wave: every lane ends with the largest mx and, among equals, the smallest am
+__device__ __forceinline__ void wave_argmax_first(float &mx, int &am) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(mx, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
+    }
+}
+
+// SoftmaxClass: the reference's weighted cross-entropy over the C classes, unmatched queries on the background class with
+// weight eos, matched ones with their class weight.
 struct SoftmaxClass {
-    static constexpr bool focal = false;
+    struct Row { float mx, sum; };
+    static __device__ __forceinline__ float sum_exp(const float *row, int C, int lane, float mx) {
+        float s = 0.f;
+        for (int c = lane; c < C; c += 64) s += expf(row[c] - mx);
+        return wave_sum(s);
+    }
+    __device__ __forceinline__ Row row_stats(const float *row, int C, int lane) const {
+        float mx = -INFINITY;
+        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
+        mx = wave_max(mx);
+        return {mx, sum_exp(row, C, lane, mx)};
+    }
+    __device__ __forceinline__ float cost(const Row &r, float x) const { return -(expf(x - r.mx) / r.sum); }
+    __device__ __forceinline__ int unmatched_class(int background) const { return background; }
+    template <class Crit>
+    __device__ __forceinline__ float weight(const Crit &crit, bool matched, int cls, int C) const {
+        return matched ? crit.class_weight(cls, C) : crit.eos;
+    }
+    // logsumexp - the class logit, and the first-occurrence arg-max over the classes; a cls outside [0, C) reads no logit (the
+    // caller turns that loss into NaN)
+    __device__ __forceinline__ RowLoss row_loss(const float *row, int C, int lane, int cls, int) const {
+        float mx = -INFINITY;
+        int am = INT_MAX;
+        for (int c = lane; c < C; c += 64) {
+            const float x = row[c];
+            if (x > mx) { mx = x; am = c; }
+        }
+        wave_argmax_first(mx, am);
+        const float s = sum_exp(row, C, lane, mx);
+        RowLoss r = {0.f, am};
+        if (lane == 0 && cls >= 0 && cls < C) r.loss = logf(s) + mx - row[cls];
+        return r;
+    }
+    template <class Crit>
+    __device__ __forceinline__ void add_norm(const Crit &, float w, float &slot1) const {
+        if (Crit::weighted) slot1 += w;       // slot 1 stays 0 under the fixed criterion
+    }
     template <class Crit>
     __device__ __forceinline__ float label_norm(const Crit &crit, const float *s) const { return crit.weight_sum(s); }
+    __device__ __forceinline__ void grad_row(const Row &r, const float *row, float *d_row, int C, int lane, int cls, float wq) const {
+        for (int c = lane; c < C; c += 64) {
+            const float sm = expf(row[c] - r.mx) / r.sum;
+            d_row[c] = wq * (sm - (c == cls ? 1.0f : 0.0f));
+        }
+    }
 };
 
 // FocalClass: sigmoid focal loss, every one of the C logits a binary problem (a matched query one-hot on its target's class, an
@@ -75,12 +137,11 @@ struct SoftmaxClass {
 //   t = 0:  (1 - alpha) * p^gamma       * -log(1 - p) = (1 - alpha) * exp(-gamma * sp(-x)) * sp(x)
 // finite for every finite logit (no pow, no log of 0); a NaN logit gives NaN.  The level's sum is divided by max(matched, 1),
 // read from the count in slot 4, so the gradients stay a deterministic function of the matching.  eos and the class weights
-// of Crit are not read.
+// of Crit are not read: every query weighs exactly 1.
 struct FocalClass {
     float alpha, gamma;
-    static constexpr bool focal = true;
-    template <class Crit>
-    __device__ __forceinline__ float label_norm(const Crit &, const float *s) const { return fmaxf(s[4], 1.0f); }
+    struct Row {};                       // the cost of an element needs its own logit alone
+    __device__ __forceinline__ Row row_stats(const float *, int, int) const { return {}; }
     // sp(x) and sp(-x) from one exp and one log1p
     static __device__ __forceinline__ void softplus_pair(float x, float &sx, float &snx) {
         const float l = log1pf(expf(-fabsf(x)));
@@ -104,9 +165,33 @@ struct FocalClass {
         const float a = positive ? sx : snx, b = positive ? snx : sx;
         return w * expf(-gamma * a) * (gamma * expf(-b) * b + expf(-a));
     }
-    // the matcher's class cost of giving a query to a target of this logit's class: what the element loses as a positive
-    // minus what it stops paying as a negative (no 1e-8 inside a log: the stable forms need none)
-    __device__ __forceinline__ float cost(float x) const { return elem(x, true) - elem(x, false); }
+    // what the element loses as a positive minus what it stops paying as a negative (no 1e-8 inside a log: the stable forms
+    // need none)
+    __device__ __forceinline__ float cost(const Row &, float x) const { return elem(x, true) - elem(x, false); }
+    __device__ __forceinline__ int unmatched_class(int) const { return -1; }
+    template <class Crit>
+    __device__ __forceinline__ float weight(const Crit &, bool, int, int) const { return 1.0f; }
+    // lanes stride over the classes: the elements of the row (one-hot on cls; none positive when cls is outside [0, C)) and
+    // the first arg-max over the non-background logits; the query predicts background when its largest non-background logit
+    // is <= 0 (every such sigmoid <= 1/2)
+    __device__ __forceinline__ RowLoss row_loss(const float *row, int C, int lane, int cls, int background) const {
+        float e = 0.f, mx = -INFINITY;
+        int am = INT_MAX;
+        for (int c = lane; c < C; c += 64) {
+            const float x = row[c];
+            e += elem(x, c == cls);
+            if (c != background && x > mx) { mx = x; am = c; }
+        }
+        wave_argmax_first(mx, am);
+        return {wave_sum(e), (mx > 0.f) ? am : background};
+    }
+    template <class Crit>
+    __device__ __forceinline__ void add_norm(const Crit &, float, float &) const {}
+    template <class Crit>
+    __device__ __forceinline__ float label_norm(const Crit &, const float *s) const { return fmaxf(s[4], 1.0f); }
+    __device__ __forceinline__ void grad_row(const Row &, const float *row, float *d_row, int C, int lane, int cls, float wq) const {
+        for (int c = lane; c < C; c += 64) d_row[c] = wq * d_elem(row[c], c == cls);
+    }
 };
 
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
@@ -155,7 +240,7 @@ constexpr int SL_QCHUNK = 8;      // queries per workgroup of the cost / sums / 
 
 template <class Crit, class Cls>
 __global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit crit, Cls clsterm, float *__restrict__ cost) {
-    __shared__ float s_max[SL_QCHUNK], s_sum[SL_QCHUNK];
+    __shared__ typename Cls::Row s_row[SL_QCHUNK];
     __shared__ float s_t[SL_MAXR][4];
     __shared__ int s_cls[SL_MAXR];
     const int p = blockIdx.x;
@@ -174,17 +259,9 @@ __global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit cri
     // blockIdx.y: a chunk of SL_QCHUNK queries of the problem (one workgroup per problem walked its 100 queries in 25 rounds of
     // wave reductions: 45-80 us of pure latency on the path between the forward and the backward pass)
     const int q0 = blockIdx.y * SL_QCHUNK, q1 = min(a.Q, q0 + SL_QCHUNK);
-    if constexpr (!Cls::focal) {          // the softmax row statistics; the focal cost of an element needs its own logit alone
-        for (int q = q0 + wave; q < q1; q += 4) {
-            const float *row = lg + q * a.sL_q;
-            float mx = -INFINITY;
-            for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, row[c]);
-            mx = wave_max(mx);
-            float s = 0.f;
-            for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
-            s = wave_sum(s);
-            if (lane == 0) { s_max[q - q0] = mx; s_sum[q - q0] = s; }
-        }
+    for (int q = q0 + wave; q < q1; q += 4) {
+        const typename Cls::Row r = clsterm.row_stats(lg + q * a.sL_q, a.C, lane);
+        if (lane == 0) s_row[q - q0] = r;
     }
     __syncthreads();
     float *out = cost + (long long)p * a.Q * ldc;
@@ -195,14 +272,7 @@ __global__ __launch_bounds__(256) void match_cost_kernel(SetLossArgs a, Crit cri
         const float pcx = pb[0], pcy = pb[1], pw = pb[2], ph = pb[3];
         const float tcx = s_t[j][0], tcy = s_t[j][1], tw = s_t[j][2], th = s_t[j][3];
         const int cls = s_cls[j];
-        float cost_class;
-        if constexpr (Cls::focal) {
-            cost_class = (cls >= 0 && cls < a.C) ? clsterm.cost(lg[q * a.sL_q + cls]) : 0.0f;      // a label outside [0, C) costs 0
-        } else {
-            float prob = 0.0f;
-            if (cls >= 0 && cls < a.C) prob = expf(lg[q * a.sL_q + cls] - s_max[ql]) / s_sum[ql];
-            cost_class = -prob;
-        }
+        const float cost_class = (cls >= 0 && cls < a.C) ? clsterm.cost(s_row[ql], lg[q * a.sL_q + cls]) : 0.0f;   // a label outside [0, C) costs 0
         const float cost_bbox = fabsf(pcx - tcx) + fabsf(pcy - tcy) + fabsf(pw - tw) + fabsf(ph - th);
         const float cost_giou = -giou_of(to_xyxy(pcx, pcy, pw, ph), to_xyxy(tcx, tcy, tw, th));
         out[q * ldc + j] = crit.cost_bbox * cost_bbox + crit.cost_class * cost_class + crit.cost_giou * cost_giou;
@@ -510,76 +580,22 @@ __global__ __launch_bounds__(256) void set_loss_sums_kernel(SetLossArgs a, Crit 
     for (int q = q0 + wave; q < q1; q += 4) {
         const float *row = lg + q * a.sL_q;
         const int t = tgt_for_pred[(long long)p * a.Q + q];
-        if constexpr (Cls::focal) {
-            // lanes stride over the classes: the elements of the row (one-hot on the target's class, all zero when unmatched) and
-            // the first arg-max over the non-background logits; one wave_sum per query
-            const int cls = (t < 0) ? -1 : (int)a.t_class[(long long)b * a.R + 1 + t];
-            float e = 0.f, mx = -INFINITY;
-            int am = INT_MAX;
-            for (int c = lane; c < a.C; c += 64) {
-                const float x = row[c];
-                e += clsterm.elem(x, c == cls);
-                if (c != a.background_class && x > mx) { mx = x; am = c; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float om = __shfl_xor(mx, o, 64);
-                const int oa = __shfl_xor(am, o, 64);
-                if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
-            }
-            e = wave_sum(e);
-            if (lane == 0) {
-                // the query predicts background when its largest non-background logit is <= 0 (every such sigmoid <= 1/2)
-                const int pred = (mx > 0.f) ? am : a.background_class;
-                if (t < 0) {
-                    acc[0] += e;
-                    acc[2] += (pred == a.background_class) ? 1.f : 0.f;
-                    acc[3] += 1.f;
-                } else {
-                    // a label outside [0, C): no element was read out of bounds (no column equals it); the loss turns NaN as
-                    // under the softmax criterion
-                    acc[0] += (cls >= 0 && cls < a.C) ? e : NAN;
-                    acc[4] += 1.f;
-                    acc[5] += (pred != a.background_class) ? 1.f : 0.f;
-                    acc[6] += (pred == cls) ? 1.f : 0.f;
-                }
-            }
-        } else {
-            // logsumexp + first-occurrence argmax over the classes
-            float mx = -INFINITY;
-            int am = INT_MAX;
-            for (int c = lane; c < a.C; c += 64) {
-                const float x = row[c];
-                if (x > mx) { mx = x; am = c; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float om = __shfl_xor(mx, o, 64);
-                const int oa = __shfl_xor(am, o, 64);
-                if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
-            }
-            float s = 0.f;
-            for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
-            s = wave_sum(s);
-            if (lane == 0) {
-                const float lse = logf(s) + mx;
-                if (t < 0) {
-                    const float ce = lse - row[a.background_class];
-                    acc[0] += crit.eos * ce;
-                    acc[2] += (am == a.background_class) ? 1.f : 0.f;
-                    acc[3] += 1.f;
-                } else {
-                    const int cls = (int)a.t_class[(long long)b * a.R + 1 + t];
-                    // a label outside [0, C) (e.g. the wrong nb_class when finetuning): no out-of-bounds read; the loss turns
-                    // NaN like tf.nn.sparse_softmax_cross_entropy_with_logits on the GPU (the CPU op raises)
-                    const float ce = (cls >= 0 && cls < a.C) ? lse - row[cls] : NAN;
-                    const float w = crit.class_weight(cls, a.C);
-                    acc[0] += w * ce;
-                    if (Crit::weighted) acc[1] += w;      // slot 1 stays 0 under the fixed criterion
-                    acc[4] += 1.f;
-                    acc[5] += (am != a.background_class) ? 1.f : 0.f;
-                    acc[6] += (am == cls) ? 1.f : 0.f;
-                }
+        const int cls = (t < 0) ? clsterm.unmatched_class(a.background_class) : (int)a.t_class[(long long)b * a.R + 1 + t];
+        const RowLoss r = clsterm.row_loss(row, a.C, lane, cls, a.background_class);
+        if (lane == 0) {
+            const float w = clsterm.weight(crit, t >= 0, cls, a.C);
+            if (t < 0) {
+                acc[0] += w * r.loss;
+                acc[2] += (r.pred == a.background_class) ? 1.f : 0.f;
+                acc[3] += 1.f;
+            } else {
+                // a label outside [0, C) (e.g. the wrong nb_class when finetuning): no out-of-bounds read; the loss turns NaN
+                // like tf.nn.sparse_softmax_cross_entropy_with_logits on the GPU (the CPU op raises)
+                acc[0] += w * ((cls >= 0 && cls < a.C) ? r.loss : NAN);
+                clsterm.add_norm(crit, w, acc[1]);
+                acc[4] += 1.f;
+                acc[5] += (r.pred != a.background_class) ? 1.f : 0.f;
+                acc[6] += (r.pred == cls) ? 1.f : 0.f;
             }
         }
         if (lane == 0 && t >= 0) {            // the box sums of a matched pair, whatever the class term
@@ -650,25 +666,10 @@ __global__ __launch_bounds__(256) void set_loss_grad_kernel(SetLossArgs a, Crit 
     for (int q = q0 + wave; q < q1; q += 4) {
         const float *row = lg + q * a.sL_q;
         const int t = tgt_for_pred[(long long)p * a.Q + q];
-        if constexpr (Cls::focal) {
-            // every lane writes its columns; an unmatched query and a label outside [0, C) have no positive column
-            const int cls = (t < 0) ? -1 : (int)a.t_class[(long long)b * a.R + 1 + t];
-            const float wq = crit.w_label / sw * loss_scale;
-            for (int c = lane; c < a.C; c += 64) dlg[q * a.sL_q + c] = wq * clsterm.d_elem(row[c], c == cls);
-        } else {
-            float mx = -INFINITY;
-            for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, row[c]);
-            mx = wave_max(mx);
-            float s = 0.f;
-            for (int c = lane; c < a.C; c += 64) s += expf(row[c] - mx);
-            s = wave_sum(s);
-            const int cls = (t < 0) ? a.background_class : (int)a.t_class[(long long)b * a.R + 1 + t];
-            const float wq = crit.w_label * ((t < 0) ? crit.eos : crit.class_weight(cls, a.C)) / sw * loss_scale;
-            for (int c = lane; c < a.C; c += 64) {
-                const float sm = expf(row[c] - mx) / s;
-                dlg[q * a.sL_q + c] = wq * (sm - (c == cls ? 1.0f : 0.0f));
-            }
-        }
+        const typename Cls::Row stats = clsterm.row_stats(row, a.C, lane);      // first: the target's class is not needed before the write
+        const int cls = (t < 0) ? clsterm.unmatched_class(a.background_class) : (int)a.t_class[(long long)b * a.R + 1 + t];
+        const float wq = crit.w_label * clsterm.weight(crit, t >= 0, cls, a.C) / sw * loss_scale;
+        clsterm.grad_row(stats, row, dlg + q * a.sL_q, a.C, lane, cls, wq);      // every lane writes its columns
         if (lane == 0) {
             float g[4] = {0.f, 0.f, 0.f, 0.f};
             if (t >= 0) {
@@ -764,47 +765,75 @@ static int fill_focal(const float *f, FocalClass &r) {
     return 0;
 }
 
-// One launcher per kernel: the entry points differ in the two policy objects alone.
-template <class Crit, class Cls>
-static int launch_match_cost(const detr_setloss_desc *d, const Crit &crit, const Cls &cls, float *cost, void *stream) {
-    SetLossArgs a;
-    if (fill_args(d, a)) return -1;
-    DETR_REQUIRE(cost, "match_cost: null cost");
-    hipLaunchKernelGGL((match_cost_kernel<Crit, Cls>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
-                       cls, cost);
-    DETR_LAUNCH_CHECK("match_cost");
-    return 0;
+// The family of an entry point and its host blocks, named so that no call site passes nulls by position: fixed (the reference's
+// literals, no block), crit (the criterion block; class weights or null) and focal (the criterion block, then the focal block;
+// eos_coef is not read and there are no class weights).
+struct Family {
+    enum Kind { fixed, crit, focal } kind;
+    const float *criterion, *class_weights, *focal_block;
+};
+static Family fixed_family() { return {Family::fixed, nullptr, nullptr, nullptr}; }
+static Family crit_family(const float *criterion, const float *class_weights = nullptr) { return {Family::crit, criterion, class_weights, nullptr}; }
+static Family focal_family(const float *criterion, const float *focal) { return {Family::focal, criterion, nullptr, focal}; }
+
+// The policy pair of a family, built and checked on the host before anything is launched, then handed to the generic `launch`.
+template <class F>
+static int with_policies(const Family &fam, F launch) {
+    if (fam.kind == Family::fixed) return launch(FixedCriterion(), SoftmaxClass());
+    RuntimeCriterion c;
+    if (fill_criterion(fam.criterion, fam.class_weights, c)) return -1;
+    if (fam.kind == Family::crit) return launch(c, SoftmaxClass());
+    FocalClass f;
+    if (fill_focal(fam.focal_block, f)) return -1;
+    return launch(c, f);
 }
 
-template <class Crit, class Cls>
-static int launch_sums(const detr_setloss_desc *d, const Crit &crit, const Cls &cls, const int32_t *tgt_for_pred, float *sums, void *stream) {
-    SetLossArgs a;
-    if (fill_args(d, a)) return -1;
-    DETR_REQUIRE(tgt_for_pred && sums, "set_loss_sums: null operand");
-    hipLaunchKernelGGL((set_loss_sums_kernel<Crit, Cls>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
-                       cls, tgt_for_pred, sums);
-    DETR_LAUNCH_CHECK("set_loss_sums");
-    return 0;
+// One launcher per kernel: the entry points of a kernel differ in the family and its blocks alone.
+static int launch_match_cost(const Family &fam, const detr_setloss_desc *d, float *cost, void *stream) {
+    return with_policies(fam, [=](auto crit, auto cls) {
+        SetLossArgs a;
+        if (fill_args(d, a)) return -1;
+        DETR_REQUIRE(cost, "match_cost: null cost");
+        hipLaunchKernelGGL((match_cost_kernel<decltype(crit), decltype(cls)>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0,
+                           (hipStream_t)stream, a, crit, cls, cost);
+        DETR_LAUNCH_CHECK("match_cost");
+        return 0;
+    });
 }
 
-template <class Crit, class Cls>
-static int launch_finalize(const float *sums, int32_t levels, const Crit &crit, const Cls &cls, float *losses, float *total, void *stream) {
-    DETR_REQUIRE(sums && losses && total && levels > 0, "set_loss_finalize: bad args");
-    hipLaunchKernelGGL((set_loss_finalize_kernel<Crit, Cls>), dim3(1), dim3(64), 0, (hipStream_t)stream, sums, levels, crit, cls, losses, total);
-    DETR_LAUNCH_CHECK("set_loss_finalize");
-    return 0;
+static int launch_sums(const Family &fam, const detr_setloss_desc *d, const int32_t *tgt_for_pred, float *sums, void *stream) {
+    return with_policies(fam, [=](auto crit, auto cls) {
+        SetLossArgs a;
+        if (fill_args(d, a)) return -1;
+        DETR_REQUIRE(tgt_for_pred && sums, "set_loss_sums: null operand");
+        hipLaunchKernelGGL((set_loss_sums_kernel<decltype(crit), decltype(cls)>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0,
+                           (hipStream_t)stream, a, crit, cls, tgt_for_pred, sums);
+        DETR_LAUNCH_CHECK("set_loss_sums");
+        return 0;
+    });
 }
 
-template <class Crit, class Cls>
-static int launch_grad(const detr_setloss_desc *d, const Crit &crit, const Cls &cls, const int32_t *tgt_for_pred, const float *sums, float loss_scale,
+static int launch_finalize(const Family &fam, const float *sums, int32_t levels, float *losses, float *total, void *stream) {
+    return with_policies(fam, [=](auto crit, auto cls) {
+        DETR_REQUIRE(sums && losses && total && levels > 0, "set_loss_finalize: bad args");
+        hipLaunchKernelGGL((set_loss_finalize_kernel<decltype(crit), decltype(cls)>), dim3(1), dim3(64), 0, (hipStream_t)stream, sums, levels,
+                           crit, cls, losses, total);
+        DETR_LAUNCH_CHECK("set_loss_finalize");
+        return 0;
+    });
+}
+
+static int launch_grad(const Family &fam, const detr_setloss_desc *d, const int32_t *tgt_for_pred, const float *sums, float loss_scale,
                        float *d_logits, float *d_boxes, void *stream) {
-    SetLossArgs a;
-    if (fill_args(d, a)) return -1;
-    DETR_REQUIRE(tgt_for_pred && sums && d_logits && d_boxes, "set_loss_grad: null operand");
-    hipLaunchKernelGGL((set_loss_grad_kernel<Crit, Cls>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0, (hipStream_t)stream, a, crit,
-                       cls, tgt_for_pred, sums, loss_scale, d_logits, d_boxes);
-    DETR_LAUNCH_CHECK("set_loss_grad");
-    return 0;
+    return with_policies(fam, [=](auto crit, auto cls) {
+        SetLossArgs a;
+        if (fill_args(d, a)) return -1;
+        DETR_REQUIRE(tgt_for_pred && sums && d_logits && d_boxes, "set_loss_grad: null operand");
+        hipLaunchKernelGGL((set_loss_grad_kernel<decltype(crit), decltype(cls)>), dim3(a.levels * a.B, cdiv(a.Q, SL_QCHUNK)), dim3(256), 0,
+                           (hipStream_t)stream, a, crit, cls, tgt_for_pred, sums, loss_scale, d_logits, d_boxes);
+        DETR_LAUNCH_CHECK("set_loss_grad");
+        return 0;
+    });
 }
 
 }  // namespace detr
@@ -812,7 +841,7 @@ static int launch_grad(const detr_setloss_desc *d, const Crit &crit, const Cls &
 using namespace detr;
 
 extern "C" int detr_hip_match_cost_f32(const detr_setloss_desc *d, float *cost, void *stream) {
-    return launch_match_cost(d, FixedCriterion(), SoftmaxClass(), cost, stream);
+    return launch_match_cost(fixed_family(), d, cost, stream);
 }
 
 extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int32_t ldc, const float *t_bbox, int32_t B,
@@ -861,79 +890,58 @@ extern "C" int detr_hip_assign_f32(const float *cost, int32_t P, int32_t Q, int3
 
 extern "C" int detr_hip_set_loss_sums_f32(const detr_setloss_desc *d, const int32_t *tgt_for_pred, float *sums,
                                           void *stream) {
-    return launch_sums(d, FixedCriterion(), SoftmaxClass(), tgt_for_pred, sums, stream);
+    return launch_sums(fixed_family(), d, tgt_for_pred, sums, stream);
 }
 
 extern "C" int detr_hip_set_loss_finalize_f32(const float *sums, int32_t levels, float *losses, float *total,
                                               void *stream) {
-    return launch_finalize(sums, levels, FixedCriterion(), SoftmaxClass(), losses, total, stream);
+    return launch_finalize(fixed_family(), sums, levels, losses, total, stream);
 }
 
 extern "C" int detr_hip_set_loss_grad_f32(const detr_setloss_desc *d, const int32_t *tgt_for_pred, const float *sums,
                                           float loss_scale, float *d_logits, float *d_boxes, void *stream) {
-    return launch_grad(d, FixedCriterion(), SoftmaxClass(), tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
+    return launch_grad(fixed_family(), d, tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
 }
 
-// ---- the same four launches with the criterion as an argument (checked on the host before anything is launched) ----
+// ---- the same four launches with the criterion as an argument ----
 extern "C" int detr_hip_match_cost_crit_f32(const detr_setloss_desc *d, const float *criterion, float *cost, void *stream) {
-    RuntimeCriterion c;
-    if (fill_criterion(criterion, nullptr, c)) return -1;
-    return launch_match_cost(d, c, SoftmaxClass(), cost, stream);
+    return launch_match_cost(crit_family(criterion), d, cost, stream);
 }
 
 extern "C" int detr_hip_set_loss_sums_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
                                                const int32_t *tgt_for_pred, float *sums, void *stream) {
-    RuntimeCriterion c;
-    if (fill_criterion(criterion, class_weights, c)) return -1;
-    return launch_sums(d, c, SoftmaxClass(), tgt_for_pred, sums, stream);
+    return launch_sums(crit_family(criterion, class_weights), d, tgt_for_pred, sums, stream);
 }
 
 extern "C" int detr_hip_set_loss_finalize_crit_f32(const float *sums, int32_t levels, const float *criterion, float *losses,
                                                    float *total, void *stream) {
-    RuntimeCriterion c;
-    if (fill_criterion(criterion, nullptr, c)) return -1;
-    return launch_finalize(sums, levels, c, SoftmaxClass(), losses, total, stream);
+    return launch_finalize(crit_family(criterion), sums, levels, losses, total, stream);
 }
 
 extern "C" int detr_hip_set_loss_grad_crit_f32(const detr_setloss_desc *d, const float *criterion, const float *class_weights,
                                                const int32_t *tgt_for_pred, const float *sums, float loss_scale, float *d_logits,
                                                float *d_boxes, void *stream) {
-    RuntimeCriterion c;
-    if (fill_criterion(criterion, class_weights, c)) return -1;
-    return launch_grad(d, c, SoftmaxClass(), tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
+    return launch_grad(crit_family(criterion, class_weights), d, tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
 }
 
-// ---- the sigmoid focal class term on the run-time criterion (checked on the host before anything is launched): eos_coef is
-// not read and there are no class weights ----
+// ---- ... and with the sigmoid focal class term on the run-time criterion ----
 extern "C" int detr_hip_match_cost_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal, float *cost,
                                              void *stream) {
-    RuntimeCriterion c;
-    FocalClass f;
-    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
-    return launch_match_cost(d, c, f, cost, stream);
+    return launch_match_cost(focal_family(criterion, focal), d, cost, stream);
 }
 
 extern "C" int detr_hip_set_loss_sums_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal,
                                                 const int32_t *tgt_for_pred, float *sums, void *stream) {
-    RuntimeCriterion c;
-    FocalClass f;
-    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
-    return launch_sums(d, c, f, tgt_for_pred, sums, stream);
+    return launch_sums(focal_family(criterion, focal), d, tgt_for_pred, sums, stream);
 }
 
 extern "C" int detr_hip_set_loss_finalize_focal_f32(const float *sums, int32_t levels, const float *criterion, const float *focal,
                                                     float *losses, float *total, void *stream) {
-    RuntimeCriterion c;
-    FocalClass f;
-    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
-    return launch_finalize(sums, levels, c, f, losses, total, stream);
+    return launch_finalize(focal_family(criterion, focal), sums, levels, losses, total, stream);
 }
 
 extern "C" int detr_hip_set_loss_grad_focal_f32(const detr_setloss_desc *d, const float *criterion, const float *focal,
                                                 const int32_t *tgt_for_pred, const float *sums, float loss_scale, float *d_logits,
                                                 float *d_boxes, void *stream) {
-    RuntimeCriterion c;
-    FocalClass f;
-    if (fill_criterion(criterion, nullptr, c) || fill_focal(focal, f)) return -1;
-    return launch_grad(d, c, f, tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
+    return launch_grad(focal_family(criterion, focal), d, tgt_for_pred, sums, loss_scale, d_logits, d_boxes, stream);
 }

@@ -439,7 +439,7 @@ class DetrEngine:
         return self.compute == 1
 
     def pregen_dropmasks_at_matcher(self):
-        """The set loss calls this between its cost and assignment kernels (training.run_train_step installs it): the next step's
+        """The set loss calls this between its cost and assignment kernels (training.run_train_step passes it to get_losses): the next step's
         keep bits, when DROPMASK_AHEAD = 2 deferred them to here (DropMasks.pregen)."""
         self.masks.at_matcher()
 

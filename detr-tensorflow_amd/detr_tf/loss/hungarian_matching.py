@@ -27,9 +27,6 @@ def make_desc(logits, boxes, t_bbox, t_class, background_class):
     return d
 
 
-before_assign = None     # hook of the training step (training.run_train_step): called between the cost and the assignment launches
-
-
 class Matcher:
     """Persistent device buffers of the matcher for one (levels, B, Q, R) shape."""
 
@@ -40,16 +37,12 @@ class Matcher:
         self.pred_for_tgt = torch.empty(self.P, R - 1, dtype=torch.int32, device=device)
         self.status = torch.empty(self.P, dtype=torch.int32, device=device)
 
-    def run(self, desc, t_bbox, criterion=None):
-        """criterion: a loss.Criterion; None or the default one runs the cost kernel with the reference's weights compiled in, a
-        focal one the cost kernel with the focal class cost."""
-        if criterion is not None and criterion.is_focal:
-            hip.call("detr_hip_match_cost_focal_f32", byref(desc), criterion.floats(), criterion.focal_floats(), self.cost.data_ptr())
-        elif criterion is None or criterion.is_default:
-            hip.call("detr_hip_match_cost_f32", byref(desc), self.cost.data_ptr())
-        else:
-            hip.call("detr_hip_match_cost_crit_f32", byref(desc), criterion.floats(), self.cost.data_ptr())
-        if before_assign is not None:       # work of another stream queued behind the cost matrix: the assignment keeps ~50 CUs busy
+    def run(self, desc, t_bbox, criterion=None, before_assign=None):
+        """criterion: a loss.Criterion (None: the default one); its family picks the cost kernel.  before_assign: a callable, called
+        once between the cost and the assignment launches -- work of another stream queued behind the cost matrix, while the
+        assignment keeps only ~50 CUs busy."""
+        (criterion or _loss.DEFAULT_CRITERION).call("match_cost", byref(desc), self.cost.data_ptr())
+        if before_assign is not None:
             before_assign()
         hip.call("detr_hip_assign_f32", self.cost.data_ptr(), self.P, self.Q, self.R - 1, t_bbox.data_ptr(), self.B,
                  self.R, self.tgt_for_pred.data_ptr(), self.pred_for_tgt.data_ptr(), self.status.data_ptr())
@@ -63,8 +56,7 @@ def hungarian_matching(t_bbox, t_class, p_bbox, p_class, fcost_class=1, fcost_bb
     position 1 the PREDICTION indices, position 2 the bool[n] selector over targets and position 3
     the bool[Q] selector over predictions.  Runs the same two HIP kernels on a batch of one; cost weights other than 1 / 5 / 2
     take the cost kernel's run-time criterion."""
-    from .loss import DEFAULT_CRITERION, criterion_of
-    crit = criterion_of(DEFAULT_CRITERION._replace(set_cost_class=fcost_class, set_cost_bbox=fcost_bbox, set_cost_giou=fcost_giou))
+    crit = _loss.criterion_of(_loss.DEFAULT_CRITERION._replace(set_cost_class=fcost_class, set_cost_bbox=fcost_bbox, set_cost_giou=fcost_giou))
     assert slice_preds, "targets must carry the header row"
     dev = p_bbox.device
     Q, C = p_class.shape
@@ -84,3 +76,6 @@ def hungarian_matching(t_bbox, t_class, p_bbox, p_class, fcost_class=1, fcost_bb
     p_sel = m.tgt_for_pred[0] >= 0
     t_sel = torch.ones(n, dtype=torch.bool, device=dev)
     return t_idx, p_idx, t_sel, p_sel, tb[0, 1:1 + n], tc[0, 1:1 + n]
+
+
+from . import loss as _loss      # noqa: E402  (last: loss.py imports Matcher and make_desc from this module)

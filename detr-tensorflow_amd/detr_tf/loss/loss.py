@@ -1,13 +1,15 @@
 """DETR set loss on the device (drop-in for detr_tf/loss/loss.py:6-179).
 
-`get_losses(m_outputs, t_bbox, t_class, config)` keeps the reference signature and returns
+`get_losses(m_outputs, t_bbox, t_class, config)` keeps the reference signature (plus one optional argument, `before_assign`: a
+callable run once between the matcher's cost and assignment launches) and returns
 `(total_loss, log_dict)` with the same 36 keys (label_cost, true_neg, true_pos, pos_accuracy,
 giou_loss, l1_loss, + suffixes _0.._4) and the 1/2/5 weighting of `get_total_losss`.
 The criterion -- matcher cost weights, loss coefficients, the weight of unmatched queries, per-class weights, the clamp of
 the box count, and the class term itself (softmax cross-entropy or sigmoid focal loss) -- is read from the config at every call
-(`criterion_of`); at the reference's values the loss runs the four entry points that have them compiled in, otherwise the
-`_crit_` ones (the same kernel bodies on run-time values), and with class_criterion = "focal" the `_focal_` ones (the same kernel
-bodies with the focal class term; include/detr_hip.h states its semantics).
+(`criterion_of`) into a `Criterion`, a plain twelve-field record; `Criterion.entry(kind)` is the one place that maps it to an entry
+point and its argument blocks: at the reference's values the four entry points that have them compiled in, otherwise the `_crit_`
+ones (the same kernel bodies on run-time values), and with class_criterion = "focal" the `_focal_` ones (the same kernel bodies
+with the focal class-term policy; include/detr_hip.h states its semantics).
 All arithmetic runs in csrc/setloss.hip: cost matrix (K12), exact assignment (K13), loss sums /
 finalisation / gradients (K14).  Under data parallelism the per-level normalisers (sum of CE
 weights, number of matched boxes) are all-reduced between the "sums" and "finalize" kernels, so
@@ -36,47 +38,15 @@ CLASS_CRITERIA = ("softmax", "focal")
 CLASS_TERM_FIELDS = ("class_criterion", "focal_alpha", "focal_gamma")
 CLASS_TERM_DEFAULTS = ("softmax", 0.25, 2.0)                          # alpha, gamma: the published values (Lin et al.; Deformable DETR)
 FOCAL_GAMMA_MAX = 8.0
+ENTRY_LEAD = {"match_cost": 1, "set_loss_sums": 1, "set_loss_finalize": 2, "set_loss_grad": 1}    # arguments in front of the criterion's blocks
+ENTRY_WEIGHTED = ("set_loss_sums", "set_loss_grad")                   # the kinds whose run-time entry point takes class weights
 
 
-class Criterion(namedtuple("Criterion", CRITERION_FIELDS + ("class_weights",))):
-    """The set criterion as an immutable, hashable record: seven floats, a bool and the class weights as a tuple of multiples of
-    1/64 (or None) -- the nine entries of the tuple, as ever --, and beside them the class term: class_criterion ("softmax" or
-    "focal"), focal_alpha and focal_gamma, keyword (or trailing positional) arguments with defaults that take part in ==, hash
-    and _replace."""
-
-    def __new__(cls, *args, **kw):
-        term = list(CLASS_TERM_DEFAULTS)
-        for k, v in enumerate(args[9:]):
-            term[k] = v
-        for k, name in enumerate(CLASS_TERM_FIELDS):
-            if name in kw:
-                term[k] = kw.pop(name)
-        self = super().__new__(cls, *args[:9], **kw)
-        object.__setattr__(self, "_class_term", (str(term[0]), float(term[1]), float(term[2])))
-        return self
-
-    def __setattr__(self, name, value):
-        raise AttributeError(f"Criterion is immutable: cannot set {name!r}")
-
-    class_criterion = property(lambda self: self._class_term[0])
-    focal_alpha = property(lambda self: self._class_term[1])
-    focal_gamma = property(lambda self: self._class_term[2])
-
-    def __eq__(self, other):
-        return tuple.__eq__(self, other) is True and self._class_term == getattr(other, "_class_term", CLASS_TERM_DEFAULTS)
-
-    def __ne__(self, other):
-        return not self == other
-
-    def __hash__(self):
-        return hash((tuple(self), self._class_term))
-
-    def __repr__(self):
-        return super().__repr__()[:-1] + "".join(f", {n}={v!r}" for n, v in zip(CLASS_TERM_FIELDS, self._class_term)) + ")"
-
-    def _replace(self, **kw):
-        term = {n: kw.pop(n, v) for n, v in zip(CLASS_TERM_FIELDS, self._class_term)}
-        return Criterion(*super()._replace(**kw), **term)
+class Criterion(namedtuple("Criterion", CRITERION_FIELDS + ("class_weights",) + CLASS_TERM_FIELDS, defaults=CLASS_TERM_DEFAULTS)):
+    """The set criterion as an immutable, hashable record of twelve fields: seven floats, a bool, the class weights as a tuple of
+    multiples of 1/64 (or None), and the class term -- class_criterion ("softmax" or "focal"), focal_alpha and focal_gamma, which
+    default to the reference's.  `criterion_of` builds one with normalised types."""
+    __slots__ = ()
 
     @property
     def is_default(self):
@@ -93,6 +63,23 @@ class Criterion(namedtuple("Criterion", CRITERION_FIELDS + ("class_weights",))):
     def focal_floats(self):
         """The second host block of the _focal_ entry points."""
         return (c_float * hip.FOCAL_FLOATS)(self.focal_alpha, self.focal_gamma)
+
+    def entry(self, kind, class_weights=None):
+        """The one place that maps a criterion to the entry point of a launch -- kind is "match_cost", "set_loss_sums",
+        "set_loss_finalize" or "set_loss_grad" -- and to the argument blocks of its own that the call takes behind the leading
+        ENTRY_LEAD[kind] arguments: none at the reference's values, floats() on the run-time criterion (then the device pointer
+        class_weights, or None, where the kind reads class weights), floats() and focal_floats() under the focal class term."""
+        if self.is_focal:
+            return f"detr_hip_{kind}_focal_f32", (self.floats(), self.focal_floats())
+        if self.is_default:
+            return f"detr_hip_{kind}_f32", ()
+        return f"detr_hip_{kind}_crit_f32", (self.floats(),) + ((class_weights,) if kind in ENTRY_WEIGHTED else ())
+
+    def call(self, kind, *args, class_weights=None):
+        """hip.call of the criterion's `kind` entry point on the kind's own arguments."""
+        name, blocks = self.entry(kind, class_weights)
+        lead = ENTRY_LEAD[kind]
+        hip.call(name, *args[:lead], *blocks, *args[lead:])
 
 
 def round_class_weights(weights, nb_class=None):
@@ -128,7 +115,7 @@ def criterion_of(config, nb_class=None):
         raise ValueError(f"focal_gamma = {gamma}: expected a finite value in [0, {FOCAL_GAMMA_MAX:g}]")
     if kind == "focal" and cw is not None:
         raise ValueError("class_weights with class_criterion = 'focal': the focal class term has no per-class weights")
-    return Criterion(*vals, None if cw is None else round_class_weights(cw, nb_class), kind, alpha, gamma)
+    return Criterion(*vals, None if cw is None else round_class_weights(cw, nb_class), str(kind), alpha, gamma)
 
 
 DEFAULT_CRITERION = Criterion(*CRITERION_DEFAULTS, None)
@@ -187,22 +174,16 @@ class SetLoss:
             self._weights = (crit.class_weights, torch.tensor(crit.class_weights, dtype=torch.float32, device=self.sums.device))
         return self._weights[1].data_ptr()
 
-    def forward(self, logits, boxes, t_bbox, t_class, background_class, criterion=DEFAULT_CRITERION, world=1):
-        """criterion: a `Criterion` (criterion_of).  world: data-parallel ranks whose sums the reduce_sums hook adds up."""
+    def forward(self, logits, boxes, t_bbox, t_class, background_class, criterion=DEFAULT_CRITERION, world=1, before_assign=None):
+        """criterion: a `Criterion` (criterion_of).  world: data-parallel ranks whose sums the reduce_sums hook adds up.
+        before_assign: see Matcher.run."""
         wptr = self._class_weights(criterion, max(1, int(world)))
         self.criterion = criterion
         self.desc = make_desc(logits, boxes, t_bbox, t_class, background_class)
         self._keep = (logits, boxes, t_bbox, t_class)
-        tfp = self.matcher.run(self.desc, t_bbox, criterion)
+        tfp = self.matcher.run(self.desc, t_bbox, criterion, before_assign)
         hip.zero_(self.sums)
-        if criterion.is_focal:
-            hip.call("detr_hip_set_loss_sums_focal_f32", byref(self.desc), criterion.floats(), criterion.focal_floats(), tfp.data_ptr(),
-                     self.sums.data_ptr())
-        elif criterion.is_default:
-            hip.call("detr_hip_set_loss_sums_f32", byref(self.desc), tfp.data_ptr(), self.sums.data_ptr())
-        else:
-            hip.call("detr_hip_set_loss_sums_crit_f32", byref(self.desc), criterion.floats(), wptr, tfp.data_ptr(),
-                     self.sums.data_ptr())
+        criterion.call("set_loss_sums", byref(self.desc), tfp.data_ptr(), self.sums.data_ptr(), class_weights=wptr)
         if self.reduce_sums is not None:
             self.reduce_sums(self.sums)
         self.finalize()
@@ -210,34 +191,15 @@ class SetLoss:
 
     def finalize(self):
         """losses / total of self.sums under the criterion of the last forward."""
-        if self.criterion.is_focal:
-            hip.call("detr_hip_set_loss_finalize_focal_f32", self.sums.data_ptr(), self.levels, self.criterion.floats(),
-                     self.criterion.focal_floats(), self.losses.data_ptr(), self.total.data_ptr())
-        elif self.criterion.is_default:
-            hip.call("detr_hip_set_loss_finalize_f32", self.sums.data_ptr(), self.levels, self.losses.data_ptr(),
-                     self.total.data_ptr())
-        else:
-            hip.call("detr_hip_set_loss_finalize_crit_f32", self.sums.data_ptr(), self.levels, self.criterion.floats(),
-                     self.losses.data_ptr(), self.total.data_ptr())
+        self.criterion.call("set_loss_finalize", self.sums.data_ptr(), self.levels, self.losses.data_ptr(), self.total.data_ptr())
 
     def grad(self, loss_scale=1.0):
         """Gradients of loss_scale * total w.r.t. logits / boxes, laid out [Lv,B,Q,*] contiguous."""
-        lg = self._keep[0]
-        d = make_desc(lg, self._keep[1], self._keep[2], self._keep[3], self.desc.background_class)
         # the gradient tensors use the same (level, image, query) strides as contiguous [Lv,B,Q,*]
-        assert lg.is_contiguous() and self._keep[1].is_contiguous(), "set-loss gradients need contiguous head outputs"
-        if self.criterion.is_focal:
-            hip.call("detr_hip_set_loss_grad_focal_f32", byref(d), self.criterion.floats(), self.criterion.focal_floats(),
-                     self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(), c_float(loss_scale), self.d_logits.data_ptr(),
-                     self.d_boxes.data_ptr())
-        elif self.criterion.is_default:
-            hip.call("detr_hip_set_loss_grad_f32", byref(d), self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(),
-                     c_float(loss_scale), self.d_logits.data_ptr(), self.d_boxes.data_ptr())
-        else:
-            wptr = None if self.criterion.class_weights is None else self._weights[1].data_ptr()
-            hip.call("detr_hip_set_loss_grad_crit_f32", byref(d), self.criterion.floats(), wptr,
-                     self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(), c_float(loss_scale), self.d_logits.data_ptr(),
-                     self.d_boxes.data_ptr())
+        assert self._keep[0].is_contiguous() and self._keep[1].is_contiguous(), "set-loss gradients need contiguous head outputs"
+        wptr = None if self.criterion.class_weights is None else self._weights[1].data_ptr()
+        self.criterion.call("set_loss_grad", byref(self.desc), self.matcher.tgt_for_pred.data_ptr(), self.sums.data_ptr(), c_float(loss_scale),
+                            self.d_logits.data_ptr(), self.d_boxes.data_ptr(), class_weights=wptr)
         return self.d_logits, self.d_boxes
 
 
@@ -270,8 +232,9 @@ def log_from_losses(vals):
     return log
 
 
-def get_losses(m_outputs, t_bbox, t_class, config):
-    """loss.py:22-34.  Returns (total_loss 0-d tensor, dict name -> 0-d tensor)."""
+def get_losses(m_outputs, t_bbox, t_class, config, before_assign=None):
+    """loss.py:22-34.  Returns (total_loss 0-d tensor, dict name -> 0-d tensor).  before_assign: an optional callable, called once
+    between the matcher's cost and assignment launches (Matcher.run)."""
     lg, bx = _stack_levels(m_outputs)
     tb, tc = _prep_targets(t_bbox, t_class, lg.device)
     Lv, B, Q, C = lg.shape
@@ -280,7 +243,7 @@ def get_losses(m_outputs, t_bbox, t_class, config):
     sl.reduce_sums = hook
     dp = getattr(getattr(m_outputs, "model", None), "dp", None)
     world = getattr(dp, "world", 1) if hook is not None else 1
-    total, losses = sl.forward(lg, bx, tb, tc, config.background_class, criterion_of(config, C), world)
+    total, losses = sl.forward(lg, bx, tb, tc, config.background_class, criterion_of(config, C), world, before_assign)
     if getattr(config, "check_matching", False):
         # opt-in (it synchronises): the reference's SciPy call raises ValueError on NaN / inf / infeasible cost matrices
         # (hungarian_matching.py:29); the device matcher records a status per problem instead of stopping the step

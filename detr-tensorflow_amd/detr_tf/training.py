@@ -16,7 +16,6 @@ import torch
 
 from . import _hip as hip
 from .engine import downsample_mask_nearest, feature_size
-from .loss import hungarian_matching as _matching
 from .loss.loss import criterion_of, get_losses, log_from_losses
 from .optimizers import (GROUPS, aggregate_grad_and_apply, clip_mode, decay_active, ema_active, ema_weights, gather_gradient,
                          joint_optimizer, weight_ema)
@@ -36,11 +35,7 @@ def run_train_step(model, images, t_bbox, t_class, optimizers, config):
     gradient_aggregate = _gradient_aggregate(config)
     optimizers["_engine"] = model.engine
     m_outputs = model(images, training=True)
-    _matching.before_assign = model.engine.pregen_dropmasks_at_matcher
-    try:
-        total_loss, log = get_losses(m_outputs, t_bbox, t_class, config)
-    finally:
-        _matching.before_assign = None
+    total_loss, log = get_losses(m_outputs, t_bbox, t_class, config, before_assign=model.engine.pregen_dropmasks_at_matcher)
     total_loss = total_loss / gradient_aggregate
     gradient_steps = gather_gradient(model, optimizers, total_loss, m_outputs, config, log,
                                      loss_scale=1.0 / gradient_aggregate)

@@ -154,7 +154,7 @@ def test_config_defaults_flags_and_empty_command_line():
         ["--set_cost_class", "2", "--set_cost_bbox", "3", "--set_cost_giou", "1.5", "--class_loss_coef", "1.5", "--bbox_loss_coef", "4",
          "--giou_loss_coef", "0.75", "--eos_coef", "0.25", "--num_boxes_min_one"]))
     crit = criterion_of(cfg)
-    assert tuple(crit) == (2.0, 3.0, 1.5, 1.5, 4.0, 0.75, 0.25, True, None) and not crit.is_default
+    assert tuple(crit) == (2.0, 3.0, 1.5, 1.5, 4.0, 0.75, 0.25, True, None, "softmax", 0.25, 2.0) and not crit.is_default
     assert tuple(crit)[:8] == tuple(CR.weight_set("C", 3))[:8]
     assert not hasattr(training_config_parser().parse_args([]), "class_weights")       # an attribute without a flag
 
@@ -172,6 +172,48 @@ def test_criterion_of_reads_missing_attributes_as_defaults_and_is_immutable():
     assert not one.is_default and one.eos_coef == 0.25 and one != crit
     # all-one class weights are still the run-time path: the default record has none
     assert not criterion_of(SimpleNamespace(class_weights=[1.0, 1.0])).is_default
+
+
+DISPATCH_FAMILIES = {"default": (SimpleNamespace(), ""), "crit": (SimpleNamespace(eos_coef=0.25), "_crit"),
+                     "crit_class_weights": (SimpleNamespace(class_weights=[1.0, 2.0, 0.5]), "_crit"),
+                     "focal": (SimpleNamespace(class_criterion="focal"), "_focal")}
+# the arguments of a kind that are not the criterion's: (descriptor | sums, levels), then the operands
+DISPATCH_KINDS = {"match_cost": 2, "set_loss_sums": 3, "set_loss_finalize": 4, "set_loss_grad": 6}
+
+
+@pytest.mark.parametrize("kind", DISPATCH_KINDS)
+@pytest.mark.parametrize("family", DISPATCH_FAMILIES)
+def test_one_dispatch_names_a_declared_entry_point_with_its_blocks(family, kind):
+    from detr_tf import _hip
+    from detr_tf.loss.loss import ENTRY_LEAD, criterion_of
+    config, suffix = DISPATCH_FAMILIES[family]
+    crit = criterion_of(config)
+    weights = ctypes.c_void_p(64) if crit.class_weights is not None else None
+    name, blocks = crit.entry(kind, weights)
+    assert name == f"detr_hip_{kind}{suffix}_f32" and name in _hip._SIGNATURES
+    sig = _hip._SIGNATURES[name]
+    assert len(blocks) + DISPATCH_KINDS[kind] + 1 == len(sig)                  # + the stream
+    lead = ENTRY_LEAD[kind]
+    want = {"default": [], "focal": [crit.floats(), crit.focal_floats()]}.get(family, [crit.floats()])
+    for k, block in enumerate(want):                                           # host blocks of floats, in the order of the C signature
+        assert sig[lead + k] is ctypes.POINTER(ctypes.c_float) and list(blocks[k]) == list(block)
+    if suffix == "_crit" and kind in ("set_loss_sums", "set_loss_grad"):       # class weights: a device pointer (or None) behind the block
+        assert len(blocks) == 2 and blocks[1] is weights and sig[lead + 1] is _hip.f32p
+    else:
+        assert len(blocks) == len(want)
+    assert all(t is not ctypes.POINTER(ctypes.c_float) for t in sig[:lead] + sig[lead + len(want):])
+
+
+def test_criterion_is_a_plain_record_and_the_matcher_has_no_global_hook():
+    from detr_tf.loss import hungarian_matching
+    from detr_tf.loss.loss import CLASS_TERM_DEFAULTS, CRITERION_DEFAULTS, DEFAULT_CRITERION, Criterion
+    assert not hasattr(DEFAULT_CRITERION, "__dict__") and not hasattr(DEFAULT_CRITERION, "_class_term")
+    assert tuple(DEFAULT_CRITERION) == CRITERION_DEFAULTS + (None,) + CLASS_TERM_DEFAULTS
+    for name in ("__new__", "__eq__", "__ne__", "__hash__", "__repr__", "_replace", "__setattr__"):
+        assert name not in vars(Criterion), name
+    focal = DEFAULT_CRITERION._replace(class_criterion="focal")
+    assert focal.is_focal and focal != DEFAULT_CRITERION and hash(focal) != hash(DEFAULT_CRITERION) and "focal" in repr(focal)
+    assert not hasattr(hungarian_matching, "before_assign")
 
 
 @pytest.mark.parametrize("name", ["set_cost_class", "set_cost_bbox", "set_cost_giou", "class_loss_coef", "bbox_loss_coef", "giou_loss_coef",

@@ -374,6 +374,58 @@ def test_get_losses_follows_a_changing_config_and_rebuilds_the_class_weights(hip
     assert abs(totals[3] - totals[0]) <= 1e-5 * abs(totals[0])
 
 
+def _tiny_problem():
+    """Lv = 1, B = 1, Q = 4, C = 3, R = 3 with one target: the smallest shape with a matched and an unmatched query."""
+    rng = np.random.default_rng(11)
+    logits = rng.normal(size=(1, 1, 4, 3)).astype(np.float32)
+    boxes = np.concatenate([rng.uniform(0.3, 0.7, (1, 1, 4, 2)), rng.uniform(0.1, 0.3, (1, 1, 4, 2))], -1).astype(np.float32)
+    t_bbox = np.zeros((1, 3, 4), np.float32)
+    t_bbox[0, 0, 0] = 1.0                                       # the header row: one target
+    t_bbox[0, 1] = (0.5, 0.5, 0.2, 0.2)
+    t_class = np.array([[0, 1, 0]], np.int64)
+    return g(torch.from_numpy(logits)), g(torch.from_numpy(boxes)), g(torch.from_numpy(t_bbox)), g(torch.from_numpy(t_class))
+
+
+def test_get_losses_calls_before_assign_once_between_cost_and_assignment(hip):
+    from detr_tf.loss.loss import SetLoss, get_losses
+    lg, bx, tb, tc = _tiny_problem()
+    m_out = {"pred_logits": lg[0], "pred_boxes": bx[0]}
+    cfg = SimpleNamespace(background_class=2)
+    sl = SetLoss.get(1, 1, 4, 3, 3, lg.device)
+    seen = []
+
+    def hook():
+        torch.cuda.synchronize()
+        seen.append((bool(torch.isfinite(sl.matcher.cost[0, :, 0]).all()), sl.matcher.tgt_for_pred.cpu().tolist()))
+
+    totals = []
+    for k in range(2):
+        sl.matcher.cost.fill_(float("nan"))
+        sl.matcher.tgt_for_pred.fill_(SENTINEL)
+        totals.append(float(get_losses(m_out, tb, tc, cfg, before_assign=hook)[0]))
+        assert len(seen) == k + 1                               # exactly once per call
+        assert seen[k] == (True, [[SENTINEL] * 4])              # the cost matrix is there, the assignment has not run
+        assert sorted(sl.matcher.tgt_for_pred.cpu().tolist()[0]) == [-1, -1, -1, 0]
+    assert float(get_losses(m_out, tb, tc, cfg)[0]) == totals[0] == totals[1] and len(seen) == 2      # omitted: not called
+
+
+def test_two_set_losses_do_not_see_each_others_hook(hip):
+    """A second SetLoss runs a whole forward without a hook INSIDE the hook of the first: a hook kept anywhere but in the call's own
+    arguments would fire for it too."""
+    from detr_tf.loss.loss import SetLoss
+    lg, bx, tb, tc = _tiny_problem()
+    a, b = SetLoss(1, 1, 4, 3, 3, lg.device), SetLoss(1, 1, 4, 3, 3, lg.device)
+    calls, inner = [], []
+
+    def hook():
+        calls.append("a")
+        inner.append(float(b.forward(lg, bx, tb, tc, 2)[0]))
+
+    total_a = float(a.forward(lg, bx, tb, tc, 2, before_assign=hook)[0])
+    assert calls == ["a"] and inner == [total_a]
+    assert float(b.forward(lg, bx, tb, tc, 2)[0]) == total_a and calls == ["a"]
+
+
 def test_hungarian_matching_with_other_cost_weights(hip):
     from scipy.optimize import linear_sum_assignment
     from detr_tf.loss.hungarian_matching import hungarian_matching
