@@ -337,6 +337,9 @@ _SIGNATURES = {
     "detr_hip_fuse_views": [POINTER(TileMergeDesc), c_void_p, POINTER(ctypes.c_double * FUSE_PARAMS), c_void_p, c_void_p],
     "detr_hip_postprocess_scored": [POINTER(PostprocessDesc), c_int32, c_void_p],
     "detr_hip_detect_scored": [POINTER(DetectDesc), c_int32, c_void_p],
+    # the K best (query, class) pairs under sigmoid scoring: the descriptors of detect / postprocess, unchanged
+    "detr_hip_detect_multilabel": [POINTER(DetectDesc), c_void_p],
+    "detr_hip_postprocess_multilabel": [POINTER(PostprocessDesc), c_int32, c_float, c_void_p],
 }
 # scratch sizing queries (return int64 bytes)
 _SIGNATURES_I64 = {
@@ -361,6 +364,7 @@ ABI_VERSION = 9
 CRITERION_FLOATS = 8                                                           # DETR_CRITERION_FLOATS
 FOCAL_FLOATS = 2                                                               # DETR_FOCAL_FLOATS: alpha, gamma
 SCORINGS = {"softmax": 0, "sigmoid": 1}                                        # the `scoring` argument of the *_scored entry points
+MULTILABEL_MAX = 1024                                                          # max_detections of the *_multilabel entry points: 1..1024
 # detr_hip_struct_layout's `which` -> mirror, every descriptor struct of include/detr_hip.h (the table above the entry point there)
 LAYOUT_STRUCTS = {0: ReduceDesc, 1: GemmDesc, 2: Conv3x3Desc, 3: StemDesc, 4: LayerNormDesc, 5: AttnDesc, 6: SetLossDesc, 7: InputDesc,
                   8: PostprocessDesc, 9: MapMatchDesc, 100: DetectDesc, 200: TileMergeDesc, 300: OverlayDesc, 400: TrackDesc,

@@ -12,13 +12,22 @@ import numpy as np
 import torch
 
 from . import bbox
-from .inference import _scoring, get_model_inference_batched, scoring_of
+from .inference import _multilabel, _post_multilabel, _scoring, get_model_inference_batched, scoring_of
 from .loss.coco_eval import COCOAccumulator, DeviceCOCOAccumulator, check_meta
 from .loss.compute_map import APAccumulator, DeviceAPAccumulator
 
 
-def _add_batch_host(acc, model, m_outputs, target_bbox, target_class, background_class, scoring="softmax"):
-    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx", scoring=scoring)
+def _detections_host(m_outputs, background_class, scoring, multilabel):
+    """[(boxes, labels, scores)] per image in "yxyx": get_model_inference_batched's, or with multilabel = K the K best (query, class)
+    pairs of every image (detr_hip_postprocess_multilabel), best first."""
+    if not multilabel:
+        return get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx", scoring=scoring)
+    out_b, out_l, out_s, counts = _post_multilabel(m_outputs["pred_logits"], m_outputs["pred_boxes"], background_class, "yxyx", multilabel)
+    return [(out_b[b, :k], out_l[b, :k], out_s[b, :k]) for b, k in enumerate(counts.tolist())]
+
+
+def _add_batch_host(acc, model, m_outputs, target_bbox, target_class, background_class, scoring="softmax", multilabel=None):
+    dets = _detections_host(m_outputs, background_class, scoring, multilabel)
     if getattr(model, "engine", None) is not None:
         model.engine.check_mask_status()      # (padded batches with a device mask; the detections are read on the host anyway)
     tb = torch.as_tensor(np.asarray(target_bbox) if not torch.is_tensor(target_bbox) else target_bbox).float().cpu()
@@ -34,8 +43,8 @@ def _host(x):
     return (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).cpu()
 
 
-def _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, background_class, scoring="softmax"):
-    dets = get_model_inference_batched(m_outputs, background_class, bbox_format="yxyx", scoring=scoring)
+def _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, background_class, scoring="softmax", multilabel=None):
+    dets = _detections_host(m_outputs, background_class, scoring, multilabel)
     if getattr(model, "engine", None) is not None:
         model.engine.check_mask_status()
     tb, tc = _host(target_bbox).float(), _host(target_class)
@@ -47,7 +56,7 @@ def _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta,
                       crowd[b, 1:1 + n], area[b, 1:1 + n], size[b])
 
 
-def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate, scoring="softmax"):
+def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate, scoring="softmax", multilabel=None):
     acc = COCOAccumulator(len(class_names))
     for it, batch in enumerate(valid_dt):
         if not isinstance(batch, (tuple, list)) or len(batch) != 4:
@@ -59,11 +68,11 @@ def _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_re
         if accumulate == "device":
             if it == 0:
                 acc = DeviceCOCOAccumulator(len(class_names), device=m_outputs["pred_logits"].device)
-            acc.add_batch(m_outputs, target_bbox, target_class, meta, config.background_class, scoring)
+            acc.add_batch(m_outputs, target_bbox, target_class, meta, config.background_class, scoring, multilabel)
             if getattr(model, "engine", None) is not None:
                 model.engine.check_mask_status()
         else:
-            _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, config.background_class, scoring)
+            _add_batch_host_coco(acc, model, m_outputs, target_bbox, target_class, meta, config.background_class, scoring, multilabel)
         if max_batches is not None and it + 1 >= max_batches:
             break
     return acc.result(class_names, print_result=print_result)
@@ -74,11 +83,16 @@ def eval_model(model, config, class_names, valid_dt, max_batches=None, print_res
     """options: weights="model" (default) | "ema", keyword-only.  "ema" evaluates the averaged weights kept by config.ema_decay:
     the whole evaluation runs inside optimizers.ema_weights(model), and the trained weights are back, bit for bit, when it
     returns.  scoring="softmax" | "sigmoid" (get_model_inference_batched's), keyword-only; None (default) takes it from
-    config.class_criterion: "focal" -> "sigmoid"."""
+    config.class_criterion: "focal" -> "sigmoid".  multilabel=True (keyword-only, sigmoid scoring only; ValueError otherwise):
+    every image is evaluated on the max_detections (default 100, 1..1024) best (query, class) pairs instead of one detection per
+    query -- the rule the detectors trained with a sigmoid focal loss are evaluated under; both protocols, both accumulate modes."""
     weights = options.pop("weights", "model")
     scoring = options.pop("scoring", None)
     scoring = scoring_of(config) if scoring is None else scoring
     _scoring(scoring)
+    max_detections = options.pop("max_detections", 100)
+    # the row capacity K of the multi-label rows, None without them: the defaults launch what they always did
+    multilabel = int(max_detections) if _multilabel("eval_model", scoring, options.pop("multilabel", False)) else None
     if options:
         raise TypeError(f"eval_model() got an unexpected keyword argument {sorted(options)[0]!r}")
     if accumulate not in ("host", "device"):
@@ -90,20 +104,21 @@ def eval_model(model, config, class_names, valid_dt, max_batches=None, print_res
     if weights == "ema":
         from .optimizers import ema_weights
         with ema_weights(model):
-            return eval_model(model, config, class_names, valid_dt, max_batches, print_result, accumulate, protocol=protocol, scoring=scoring)
+            return eval_model(model, config, class_names, valid_dt, max_batches, print_result, accumulate, protocol=protocol, scoring=scoring,
+                              multilabel=multilabel is not None, max_detections=max_detections)
     if protocol == "coco":
-        return _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate, scoring)
+        return _eval_model_coco(model, config, class_names, valid_dt, max_batches, print_result, accumulate, scoring, multilabel)
     acc = APAccumulator(len(class_names))
     for it, (images, target_bbox, target_class) in enumerate(valid_dt):
         m_outputs = model(images, training=False)
         if accumulate == "device":
             if it == 0:
                 acc = DeviceAPAccumulator(len(class_names), device=m_outputs["pred_logits"].device)
-            acc.add_batch(m_outputs, target_bbox, target_class, config.background_class, scoring)
+            acc.add_batch(m_outputs, target_bbox, target_class, config.background_class, scoring, multilabel)
             if getattr(model, "engine", None) is not None:
                 model.engine.check_mask_status()  # (reads the mask status words of a padded batch; a no-op for an unpadded one)
         else:
-            _add_batch_host(acc, model, m_outputs, target_bbox, target_class, config.background_class, scoring)
+            _add_batch_host(acc, model, m_outputs, target_bbox, target_class, config.background_class, scoring, multilabel)
         if max_batches is not None and it + 1 >= max_batches:
             break
     return acc.result(class_names, print_result=print_result)

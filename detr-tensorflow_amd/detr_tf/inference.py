@@ -8,7 +8,9 @@ eager fallback; tensors on the CPU are moved to the model's device first by the 
 
 `detect_batched` goes the rest of the way to what a user draws (webcam_inference.py:26-34, eval.py:41-55), in one launch of
 `detr_hip_detect` (csrc/detect.hip): score threshold, detections sorted by score with a top-k cap, boxes in PIXELS of each image's
-own original size.  `Detector` wraps the whole chain: raw uint8 images -> input stage -> model -> `detect_batched`.
+own original size.  `Detector` wraps the whole chain: raw uint8 images -> input stage -> model -> `detect_batched`.  With
+`scoring="sigmoid", multilabel=True` the launch is `detr_hip_detect_multilabel` (csrc/detect_multilabel.hip): the K best (query,
+class) pairs of every image, so one query may give several detections.
 
 `merge_tiles` is the last step of SLICED inference (the model run on overlapping windows of a large image, plus the whole image):
 one launch of `detr_hip_tile_merge` (csrc/tile_merge.hip) maps every window's boxes back to image pixels and removes the duplicates
@@ -70,6 +72,17 @@ def _scoring(scoring):
     return hip.SCORINGS[scoring]
 
 
+MULTILABEL_DEFAULT_K = 100        # max_detections=None with multilabel: the K of the detectors that introduced the rule
+
+
+def _multilabel(who, scoring, multilabel):
+    """The `multilabel` keyword: whether a query may emit several classes (the K best (query, class) pairs of an image).  It
+    needs scoring="sigmoid": a softmax row has one class by construction."""
+    if multilabel and scoring != "sigmoid":
+        raise ValueError(f"{who}: multilabel=True needs scoring='sigmoid', got {scoring!r}: a softmax row has one class by construction")
+    return bool(multilabel)
+
+
 def scoring_of(config):
     """The scoring that goes with a config's class criterion: "sigmoid" for class_criterion = "focal", else "softmax"."""
     return "sigmoid" if getattr(config, "class_criterion", "softmax") == "focal" else "softmax"
@@ -94,6 +107,26 @@ def _post(logits, boxes, background_class, bbox_format, scoring="softmax"):
         hip._check(hip.load().detr_hip_postprocess(byref(d), hip._stream()), "detr_hip_postprocess")
     else:
         hip._check(hip.load().detr_hip_postprocess_scored(byref(d), mode, hip._stream()), "detr_hip_postprocess_scored")
+    return out_b, out_l, out_s, counts
+
+
+def _post_multilabel(logits, boxes, background_class, bbox_format, max_detections=MULTILABEL_DEFAULT_K, score_threshold=0.0):
+    """_post's rows under the multi-label rule: the max_detections best (query, class) pairs of every image, best first, as
+    [B, K] rows (detr_hip_postprocess_multilabel) -- what the evaluation matchers read with K as their row capacity."""
+    if bbox_format not in BBOX_FORMATS:
+        raise NotImplementedError()
+    K = int(max_detections)
+    if not 1 <= K <= hip.MULTILABEL_MAX:
+        raise ValueError(f"multilabel: max_detections={max_detections} must be in 1..{hip.MULTILABEL_MAX}")
+    logits, boxes = _model_outputs("get_model_inference", "post-processing", logits, boxes)
+    B, dev = logits.shape[0], logits.device
+    out_b, out_l, out_s = _ranked_rows(B, K, dev, 0)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    d = hip.PostprocessDesc()
+    _fill_model_outputs(d, logits, boxes, background_class)
+    d.B, d.bbox_format = B, BBOX_FORMATS[bbox_format]
+    d.out_boxes, d.out_labels, d.out_scores, d.counts = out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), counts.data_ptr()
+    hip._check(hip.load().detr_hip_postprocess_multilabel(byref(d), K, float(score_threshold), hip._stream()), "detr_hip_postprocess_multilabel")
     return out_b, out_l, out_s, counts
 
 
@@ -146,11 +179,15 @@ class Detections(NamedTuple):
     query: torch.Tensor
 
 
-def _check_detect_args(bbox_format, score_threshold, max_detections, Q=None):
+def _check_detect_args(bbox_format, score_threshold, max_detections, Q=None, multilabel=False):
     if bbox_format not in DETECT_FORMATS:
         raise RuntimeError(f"detect: unknown bbox_format {bbox_format!r}, expected one of {tuple(DETECT_FORMATS)}")
     if not math.isfinite(float(score_threshold)):
         raise RuntimeError(f"detect: score_threshold={score_threshold} is not finite")
+    if multilabel:                                   # K bounds the (query, class) pairs, not the queries
+        if max_detections is not None and not 1 <= int(max_detections) <= hip.MULTILABEL_MAX:
+            raise RuntimeError(f"detect: max_detections={max_detections} must be in 1..{hip.MULTILABEL_MAX} with multilabel")
+        return
     if max_detections is not None and (int(max_detections) < 1 or (Q is not None and int(max_detections) > Q)):
         raise RuntimeError(f"detect: max_detections={max_detections} must be in 1..Q" + ("" if Q is None else f"={Q} (the number of queries)"))
 
@@ -161,13 +198,14 @@ def _ranked_rows(B, K, dev, n_index):
             torch.empty(B, K, dtype=torch.float32, device=dev), *(torch.empty(B, K, dtype=torch.int32, device=dev) for _ in range(n_index)))
 
 
-def _detect(logits, boxes, sizes, background_class, score_threshold, max_detections, bbox_format, clip, scoring="softmax"):
+def _detect(logits, boxes, sizes, background_class, score_threshold, max_detections, bbox_format, clip, scoring="softmax", multilabel=False):
     mode = _scoring(scoring)
+    multilabel = _multilabel("detect", scoring, multilabel)
     _check_model_outputs("detect", "B", logits, boxes)
     B, Q, _ = logits.shape
-    _check_detect_args(bbox_format, score_threshold, max_detections, Q)
+    _check_detect_args(bbox_format, score_threshold, max_detections, Q, multilabel)
     logits, boxes = _model_outputs("detect_batched", "post-processing", logits, boxes)
-    K = Q if max_detections is None else int(max_detections)
+    K = (MULTILABEL_DEFAULT_K if multilabel else Q) if max_detections is None else int(max_detections)
     dev = logits.device
     sizes = torch.as_tensor(sizes).to(device=dev, dtype=torch.int32).contiguous()
     if tuple(sizes.shape) != (B, 2):
@@ -180,7 +218,9 @@ def _detect(logits, boxes, sizes, background_class, score_threshold, max_detecti
     d.max_detections, d.bbox_format, d.clip = K, DETECT_FORMATS[bbox_format], int(bool(clip))
     d.out_boxes, d.out_labels, d.out_scores, d.out_query, d.counts = (out_b.data_ptr(), out_l.data_ptr(), out_s.data_ptr(), out_q.data_ptr(),
                                                                       counts.data_ptr())
-    if mode == 0:
+    if multilabel:
+        hip._check(hip.load().detr_hip_detect_multilabel(byref(d), hip._stream()), "detr_hip_detect_multilabel")
+    elif mode == 0:
         hip._check(hip.load().detr_hip_detect(byref(d), hip._stream()), "detr_hip_detect")
     else:
         hip._check(hip.load().detr_hip_detect_scored(byref(d), mode, hip._stream()), "detr_hip_detect_scored")
@@ -188,7 +228,7 @@ def _detect(logits, boxes, sizes, background_class, score_threshold, max_detecti
 
 
 def detect_batched(m_outputs: dict, sizes, background_class, *, score_threshold=0.0, max_detections=None, bbox_format="xyxy", clip=True,
-                   scoring="softmax"):
+                   scoring="softmax", multilabel=False):
     """[Detections] for every image of the batch, in pixels.  `sizes` [B, 2] = (height, width) of every ORIGINAL image (host
     array or device tensor): the model's boxes are normalised to the image's own extent -- in a padded batch too, where the canvas
     is larger --, so that is what they are scaled by.  A query is kept when its label is not `background_class` and its score
@@ -197,9 +237,14 @@ def detect_batched(m_outputs: dict, sizes, background_class, *, score_threshold=
     "yxyx" or "xywh" (top-left + width / height); clip clamps the corners of the last three to the image.  One launch of
     detr_hip_detect and ONE host synchronisation (the per-image counts).  CUDA inputs only.
     scoring="sigmoid" (a model trained with class_criterion = "focal"): the score is the sigmoid of the best non-background logit, the
-    label its first arg-max, and every query is a candidate: the threshold alone decides (detr_hip_detect_scored)."""
+    label its first arg-max, and every query is a candidate: the threshold alone decides (detr_hip_detect_scored).
+    multilabel=True (scoring="sigmoid" only; "softmax" raises ValueError): a query may emit several classes.  The candidates are all
+    Q x (C - 1) (query, non-background class) pairs with sigmoid(logit) >= score_threshold; the max_detections best are returned (None:
+    100; 1..1024, independent of Q), descending score, ties by lower query, then lower class -- the rule Deformable DETR, DINO and
+    RT-DETR are evaluated under.  `query` repeats where a query emits several classes; every row carries its query's box.  One
+    launch of detr_hip_detect_multilabel."""
     out_b, out_l, out_s, out_q, counts = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, background_class,
-                                                 score_threshold, max_detections, bbox_format, clip, scoring)
+                                                 score_threshold, max_detections, bbox_format, clip, scoring, multilabel)
     return [Detections(out_b[b, :k], out_l[b, :k], out_s[b, :k], out_q[b, :k]) for b, k in enumerate(counts.tolist())]
 
 
@@ -742,26 +787,33 @@ class Detector:
     flip=False, scales=None and merge="nms" (the defaults) nothing of this runs.
 
     scoring: "softmax" or "sigmoid" (detect_batched's); None takes it from config.class_criterion ("focal" -> "sigmoid").  The
-    plain path and track() score that way; tiles, nms_threshold, flip, scales and merge with "sigmoid" raise NotImplementedError."""
+    plain path and track() score that way; tiles, nms_threshold, flip, scales and merge with "sigmoid" raise NotImplementedError.
+
+    multilabel=True (sigmoid scoring only; ValueError otherwise): the plain path and track() return the max_detections best (query,
+    class) pairs of every image instead of one detection per query (detect_batched's multilabel; max_detections up to 1024).  The
+    rows have the same layout, so track(), draw() and to_coco_results() take them unchanged; `query` repeats where a query emits
+    several classes.  What "sigmoid" rejects stays rejected."""
 
     RESIZE_MODES = ("shortest_side", "fixed")
 
     def __init__(self, model, config, *, background_class=None, score_threshold=0.7, max_detections=100, bbox_format="xyxy",
                  resize="shortest_side", shortest_side=800, max_size=1333, canvas=None, interpolation="cubic",
                  tiles=None, overlap=0.2, include_full=True, tile_batch=None, nms_threshold=None, match="iou", class_agnostic=False,
-                 edge_margin=0.0, flip=False, scales=None, merge="nms", sigma=0.5, score_min=0.001, min_members=1, scoring=None):
+                 edge_margin=0.0, flip=False, scales=None, merge="nms", sigma=0.5, score_min=0.001, min_members=1, scoring=None,
+                 multilabel=False):
         from .data import processing, transformation
         self.scoring = scoring_of(config) if scoring is None else scoring
         _scoring(self.scoring)
         if self.scoring != "softmax" and (tiles is not None or nms_threshold is not None or flip or scales is not None or merge != "nms"):
             raise NotImplementedError(f"Detector: scoring={self.scoring!r} with tiles / nms_threshold / flip / scales / merge: merge_tiles and "
                                       "fuse_views score from the logits themselves, by softmax only; use the plain path")
+        self.multilabel = _multilabel("Detector", self.scoring, multilabel)
         if resize not in self.RESIZE_MODES:
             raise ValueError(f"Detector: resize must be one of {self.RESIZE_MODES}, got {resize!r}")
         names = transformation.INTERP_NAMES if resize == "shortest_side" else tuple(processing.INTERPOLATIONS)
         if interpolation not in names:
             raise ValueError(f"Detector: interpolation must be one of {names} with resize={resize!r}, got {interpolation!r}")
-        _check_detect_args(bbox_format, score_threshold, max_detections)
+        _check_detect_args(bbox_format, score_threshold, max_detections, multilabel=self.multilabel)
         if background_class is None:
             background_class = getattr(config, "background_class", None)
         if background_class is None:
@@ -918,7 +970,8 @@ class Detector:
             detections = self._merge(m_outputs, np.arange(len(srcs) + 1, dtype=np.int32), windows, sizes)
         else:
             detections = detect_batched(m_outputs, sizes, self.background_class, score_threshold=self.score_threshold,
-                                        max_detections=self.max_detections, bbox_format=self.bbox_format, scoring=self.scoring)
+                                        max_detections=self.max_detections, bbox_format=self.bbox_format, scoring=self.scoring,
+                                        multilabel=self.multilabel)
         detections = detections[0] if single else detections
         if "attn" in m_outputs:
             return detections, _feature_maps(self.model, shape, m_outputs["attn"])
@@ -959,7 +1012,7 @@ class Detector:
             sizes = np.array([s.shape[:2] for s in srcs], np.int32)
             m_outputs, _ = self._forward(srcs, sizes, return_embeddings=appearance)
             rows = _detect(m_outputs["pred_logits"], m_outputs["pred_boxes"], sizes, self.background_class, self.score_threshold,
-                           self.max_detections, self.bbox_format, True, self.scoring)
+                           self.max_detections, self.bbox_format, True, self.scoring, self.multilabel)
             tracked = tracker.update_rows(*rows, active, m_outputs["embed"] if appearance else None,
                                           self._last_frames if tracker.motion else None)
         return tracked[0] if single else tracked

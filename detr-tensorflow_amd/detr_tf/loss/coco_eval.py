@@ -277,12 +277,16 @@ class DeviceCOCOAccumulator(_DeviceAccumulator):
         hip._check(hip.load().detr_hip_coco_match(byref(d), hip._stream()), "detr_hip_coco_match")
         self._records.append(rec)
 
-    def add_batch(self, m_outputs, t_bbox, t_class, meta, background_class, scoring="softmax"):
+    def add_batch(self, m_outputs, t_bbox, t_class, meta, background_class, scoring="softmax", multilabel=None):
         """The post-processing launch plus the match launch for one batch of model outputs; host / NumPy targets and metadata are
-        uploaded asynchronously.  No host synchronisation.  scoring: get_model_inference_batched's."""
-        from ..inference import _post
+        uploaded asynchronously.  No host synchronisation.  scoring: get_model_inference_batched's.  multilabel = K: the rows are
+        the K best (query, class) pairs of every image (detr_hip_postprocess_multilabel, sigmoid scoring) and K is the matcher's row capacity."""
+        from ..inference import _post, _post_multilabel
         meta = check_meta(meta, "DeviceCOCOAccumulator.add_batch")
-        out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"], m_outputs["pred_boxes"], background_class, "yxyx", scoring)
+        if multilabel is None:
+            out_b, out_l, out_s, counts = _post(m_outputs["pred_logits"], m_outputs["pred_boxes"], background_class, "yxyx", scoring)
+        else:
+            out_b, out_l, out_s, counts = _post_multilabel(m_outputs["pred_logits"], m_outputs["pred_boxes"], background_class, "yxyx", multilabel)
         self.add_detections(out_b, out_l, out_s, counts, self._device(t_bbox, torch.float32), self._device(t_class, torch.int64),
                             self._device(meta["crowd"], torch.uint8), self._device(meta["area"], torch.float32),
                             self._device(meta["size"], torch.int32))

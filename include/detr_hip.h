@@ -824,6 +824,37 @@ int detr_hip_detect(const detr_detect_desc *d, void *stream);
 int detr_hip_detect_scored(const detr_detect_desc *d, int32_t scoring, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multi-label detections under sigmoid scoring, appended (the ABI version is unchanged; no struct, no layout id): the K best of
+ * an image's Q x (C - 1) (query, class) pairs, the rule of the detectors trained with a sigmoid focal class loss (Deformable
+ * DETR's PostProcess and its successors).  One query may emit several classes; the number of detections is bounded by
+ * max_detections, not by Q.
+ *   replaces: sigmoid -> flatten -> topk -> gather over [B, Q * C] on the framework's side.
+ * One launch per batch, one workgroup per image (csrc/detect_multilabel.hip), Q <= 1024.  Per image b:
+ *   candidates: every pair (q, c), 0 <= q < Q, 0 <= c < C, c != background_class, with
+ *     s = 1 / (1 + expf(-logits[b, q, c])) >= score_threshold -- the sigmoid of detr_hip_detect_scored (scoring 1): an element
+ *     both score gets the same bits.  A NaN logit is never a candidate; -inf gives 0.0f, a candidate at score_threshold 0; +inf
+ *     and every logit above about 17 give exactly 1.0f.
+ *   order: descending s, exact ties by ascending flat index q * C + c: np.argsort(-s, kind="stable") over the flattened
+ *     row-major [Q, C] scores with the non-candidates removed.  An exact radix select on the bits of s, then a sort of the
+ *     survivors; no float atomics, a rerun is bit-identical.
+ *   output: the first K = max_detections of that order; K is independent of Q and may exceed it.  out_labels = c, out_scores = s,
+ *     out_query = q (it repeats where a query emits several classes), out_boxes = the box of query q; counts[b] =
+ *     min(K, candidates); rows [counts[b], K) of every output are zero.
+ * detr_hip_detect_multilabel: detr_detect_desc, UNCHANGED, every field with its meaning there except max_detections, which is
+ *   1..1024 here, not 1..Q.  Boxes in pixels of the image's own size exactly as detr_hip_detect writes them for that query
+ *   (bbox_format 0..3, clip).  Rejected before any launch: what detr_hip_detect_scored rejects with scoring 1 (null operands, bad
+ *   shapes, strides, formats, clip, a non-finite threshold, an unaligned out_boxes, C < 2, background_class outside [0, C)), and
+ *   max_detections outside 1..1024.
+ * detr_hip_postprocess_multilabel: the same selection on detr_postprocess_desc, UNCHANGED, with out_boxes / out_labels /
+ *   out_scores [B, max_detections(, 4)] and the boxes NORMALISED in detr_hip_postprocess's formats (0..2) and arithmetic -- the
+ *   rows detr_hip_map_match and detr_hip_coco_match read, with Q = max_detections as their row capacity.  There is no out_query.
+ *   Rejected: as above, on the fields this descriptor has; sL_q < C or other strides too small; an out_boxes that is not 16-byte
+ *   aligned.
+ * ------------------------------------------------------------------------------------------- */
+int detr_hip_detect_multilabel(const detr_detect_desc *d, void *stream);
+int detr_hip_postprocess_multilabel(const detr_postprocess_desc *d, int32_t max_detections, float score_threshold, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * COCO-protocol evaluation, per-image half, appended (the ABI version is unchanged):
  *   restates COCOeval's bbIou / evaluateImg for boxes (crowd regions, area ranges, ignore flags); the accumulate / summarize half
  *   is detr_tf/loss/coco_eval.py: COCOAccumulator.result.  One launch per batch, one workgroup per image (csrc/coco_match.hip).
